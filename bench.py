@@ -14,9 +14,12 @@ zero-copy delivery at the sink, drop token back.  The timed region is K back-to-
 closed by the sink's ack of the last one, bracketed by barrier + device sync.
 
 value = total payload bytes delivered by all ranks / max-over-ranks time (GB/s).
-The JSON line also carries the per-size latency ladder (p50/p99, reference semantics: timestamp
-after the fill), the pack-kernel roofline (HIP events on the node stream) and the CPU baseline
+A plain run sets up, warms up, times the K steps and prints the line with the headline and the
+pack-kernel roofline of the timed region (the packs' own stamps).  With `--full` the line also
+carries the per-size latency ladder (p50/p99, reference semantics: timestamp after the fill), the
+throughput ladders, the box's copy rates, the synchronous sends, the C3 block and the CPU baseline
 (C++ restatement of the reference shm path, oracle/build/shm_baseline, rank 0 at N=1).
+`--dump-outputs DIR` writes the sample the sink received in the last timed step to DIR/sample.npy.
 """
 from __future__ import annotations
 
@@ -44,6 +47,8 @@ LADDER_HOST = [8, 512, 2048, 4096, 65536, 4 << 20, 6220800, 40960000]
 # <= 1 MiB are packed by the producer straight into shared memory, larger ones staged to host
 # memory on receipt
 LADDER_D2H = [8, 4096, 65536, 1 << 20, 6220800, 40960000]
+# --dump-outputs: float32 elements of sample.npy at most (32 MB of the 64 MB a dump may take)
+DUMP_MAX_ELEMS = 8 << 20
 
 
 def host_lat_n(size, lat_n):
@@ -89,7 +94,36 @@ def parse():
                     help="N>1: skip the C4 fan-out / C5 chain runs after the timed region")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="skip the per-launch kernel stamps (roofline then unmeasured)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: CPU baseline, latency and throughput ladders, "
+                         "the box's copy rates, synchronous sends, the C3 block and (N>1) the "
+                         "cross-GPU runs; a plain run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the sample the sink received in the last "
+                         "one to DIR/sample.npy (float32, one element per byte; above "
+                         f"{DUMP_MAX_ELEMS:,} B a fixed seeded selection of that many)")
+    args = ap.parse_args()
+    if not args.full:  # everything but the headline's own run
+        args.no_ladder = args.no_cpu_baseline = args.no_c3 = args.no_cross_gpu = True
+        args.sync_n = 0
+    return args
+
+
+def dump_outputs(out_dir: str, raw_path: str, size: int):
+    """DIR/sample.npy from the bytes the sink wrote for the last timed step (bench_sink.cpp,
+    DORA_BENCH_DUMP): the delivered sample as float32, whole up to DUMP_MAX_ELEMS bytes, else
+    the bytes at DUMP_MAX_ELEMS ascending offsets drawn once from a fixed seed (the same
+    offsets for every run of one size)."""
+    import numpy as np
+    raw = np.fromfile(raw_path, dtype=np.uint8)
+    if raw.size != size:
+        raise RuntimeError(f"--dump-outputs: the sink wrote {raw.size} B, the sample has {size}")
+    if size > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0xD05A).integers(0, size, DUMP_MAX_ELEMS))
+        raw = raw[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sample.npy"), raw.astype(np.float32))
 
 
 class Ranks:
@@ -763,6 +797,12 @@ def main():
     from dora_amd.dataflow import Dataflow
     result_path = os.path.join(tempfile.mkdtemp(prefix="dora-bench-"), "sink.json")
     host_result_path = os.path.join(os.path.dirname(result_path), "hostsink.json")
+    # --dump-outputs (rank 0): the sink writes the last timed step's sample here, byte for byte
+    dump_raw = (os.path.join(os.path.dirname(result_path), "last_sample.bin")
+                if args.dump_outputs and rank == 0 else None)
+    sink_env = dict({"DORA_BENCH_RESULT": result_path}, **SINK_ENV)
+    if dump_raw:
+        sink_env["DORA_BENCH_DUMP"] = dump_raw
     desc = {"nodes": [
         {"id": "node", "path": "dynamic",
          "outputs": ["latency", "latency_host", "throughput", "to_host", "to_host_warm"],
@@ -777,7 +817,7 @@ def main():
          "inputs": {"latency": {"source": "node/latency", "queue_size": 10},
                     "latency_host": {"source": "node/latency_host", "queue_size": 10},
                     "throughput": {"source": "node/throughput", "queue_size": 10}},
-         "env": dict({"DORA_BENCH_RESULT": result_path}, **SINK_ENV),
+         "env": sink_env,
          "_unstable_deploy": {"gpu": local_rank}},
     ]}
     df = Dataflow(desc).start()
@@ -861,7 +901,7 @@ def main():
     import gc as _gc
     _gc.collect()
     _gc.disable()
-    copy_cal = box_copy_rate(S, stream)
+    copy_cal = box_copy_rate(S, stream) if args.full else None
     h2d_cal = box_h2d_rate(40960000, stream) if not args.no_ladder else None
     # the same at the mid sizes, where per-message dispatch rather than HBM binds
     copy_mid = {str(z): box_copy_rate(z, stream) for z in (4 << 20, 16 << 20)
@@ -1130,6 +1170,8 @@ def main():
             meta.update({"csum": to_i64(csum), "verify_late": True})
         if k == args.steps - 1:
             meta["ack"] = True  # the sink acks the region's last message on receipt
+            if dump_raw:
+                meta["dump"] = True  # ... and writes its bytes out after the ack
         send(k, meta)
         if k == 0:
             t_first = time.perf_counter()
@@ -1228,6 +1270,8 @@ def main():
 
     if rank != 0:
         return
+    if dump_raw:
+        dump_outputs(args.dump_outputs, dump_raw, S)
     traffic = pmc_traffic(S)
     lat = {}
     for s in sink.get("series", []):

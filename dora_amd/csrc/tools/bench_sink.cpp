@@ -6,9 +6,12 @@
 // `ack` parameter are acknowledged on the `ack` output (used by the bench to close a timed burst).
 // With `verify_late` the input is held (its token not returned) and checksummed right after the
 // next ack has gone out: the bench marks the last messages of its timed region so, and their
-// bytes are verified without putting a checksum kernel inside the timed region.
+// bytes are verified without putting a checksum kernel inside the timed region.  A held input
+// with a `dump` parameter is also copied to the host then and written, byte for byte, to the file
+// DORA_BENCH_DUMP names (bench.py --dump-outputs: the sample its last timed step delivered).
 // At the end of the stream it writes one JSON document with per-(input, size) statistics.
-//   env: DORA_GPU_DATAFLOW, DORA_NODE_ID, DORA_GPU_DEVICE, DORA_BENCH_RESULT (path)
+//   env: DORA_GPU_DATAFLOW, DORA_NODE_ID, DORA_GPU_DEVICE, DORA_BENCH_RESULT (path),
+//        DORA_BENCH_DUMP (path, optional)
 #include <algorithm>
 #include <array>
 #include <cstdio>
@@ -121,6 +124,7 @@ int main() {
     size_t len;
     uint64_t csum;
     Series* s;
+    bool dump;
   };
   std::vector<Held> held;  // verify_late inputs, checksummed after the next ack
   // (seq, receipt ns, ack sent ns) of inputs that asked for an ack: the bench splits its
@@ -135,6 +139,18 @@ int main() {
     } else {
       ++errors;
     }
+  };
+  const char* dump_path = std::getenv("DORA_BENCH_DUMP");
+  auto dump = [&](const void* p, size_t len) {
+    std::vector<uint8_t> host(len);
+    FILE* df = nullptr;
+    if ((len && (dora_gpu_memcpy_async(host.data(), p, len, st) != 0 ||
+                 dora_gpu_stream_sync(st) != 0)) ||
+        !(df = std::fopen(dump_path, "wb")) || std::fwrite(host.data(), 1, len, df) != len) {
+      std::fprintf(stderr, "sink: dump to %s failed\n", dump_path);
+      ++errors;
+    }
+    if (df) std::fclose(df);
   };
   // busy = wall - idle between the first and the last input (diagnostics)
   uint64_t w_first = 0, w_last = 0, idle_first = 0, idle_last = 0, fill_first = 0, fill_last = 0;
@@ -218,7 +234,8 @@ int main() {
       }
       const bool ack = params.count("ack") != 0;
       if (params.count("csum") && params.count("verify_late") && dev) {
-        held.push_back({ev, p, len, static_cast<uint64_t>(params["csum"].i), &s});
+        held.push_back({ev, p, len, static_cast<uint64_t>(params["csum"].i), &s,
+                        dump_path && params.count("dump")});
       } else {
         const uint64_t tf0 = mono();
         dora_event_free(ev);  // zero-copy consumer done: token goes back to the sender
@@ -230,6 +247,7 @@ int main() {
       if (ack) {
         for (Held& h : held) {
           verify(h.p, h.len, h.csum, *h.s);
+          if (h.dump) dump(h.p, h.len);
           dora_event_free(h.ev);
         }
         held.clear();
@@ -246,6 +264,7 @@ int main() {
   }
   for (Held& h : held) {  // no ack followed them
     verify(h.p, h.len, h.csum, *h.s);
+    if (h.dump) dump(h.p, h.len);
     dora_event_free(h.ev);
   }
   held.clear();

@@ -9,7 +9,7 @@ start -> last end) per pack â€” bench.py's figure, from the packs' own stamps â€
 packs' intervals per pack, with the fraction of 8 TB/s each gives for 2 x S bytes per pack.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/c3p -o run -- \\
-        python bench.py --no-ladder --no-cpu-baseline --steps 20 --warmup 5 > line.json
+        python bench.py --full --no-ladder --no-cpu-baseline --steps 20 --warmup 5 > line.json
     python scripts/c3_region.py gpurun_out/c3p --line line.json
 """
 import argparse

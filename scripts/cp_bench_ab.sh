@@ -7,7 +7,7 @@ mkdir -p "$out"
 for r in $(seq 1 $rounds); do
   for cfg in "$@"; do
     name=${cfg%%=*}; kv=${cfg#*=}
-    env $kv timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_${name}_$r.json" 2> "$out/bench_${name}_$r.err" || { echo BENCH FAILED; exit 1; }
+    env $kv timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_${name}_$r.json" 2> "$out/bench_${name}_$r.err" || { echo BENCH FAILED; exit 1; }
   done
 done
 echo ok

@@ -8,7 +8,7 @@ out=${1:?out dir}
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p "$out"
-B="python bench.py --no-ladder --no-cpu-baseline --no-c3"
+B="python bench.py --full --no-ladder --no-cpu-baseline --no-c3"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/c2_trace" -o run -- \
   $B --steps 200 --warmup 20 > "$out/c2_trace_bench.json" 2> "$out/c2_trace_bench.err"
 # the default (synchronous) send: every timed step waits for its own pack (a lone pack)
@@ -25,5 +25,5 @@ timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/c3_f
   $B --workload c3 --steps 50 --warmup 5 > "$out/c3_fetch_bench.json" 2> "$out/c3_fetch.err"
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/c3_write" -o run -- \
   $B --workload c3 --steps 50 --warmup 5 > "$out/c3_write_bench.json" 2> "$out/c3_write.err"
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
 echo done

@@ -10,7 +10,7 @@ root=$(pwd)
 for r in 1 2 3; do
   (cd "$root/wt04" && timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline \
     --lat-n 300 --detail "$out/d_r04_$r.json" > "$out/b_r04_$r.json" 2> "$out/b_r04_$r.err")
-  timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --lat-n 300 \
+  timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --lat-n 300 \
     --detail "$out/d_r05_$r.json" > "$out/b_r05_$r.json" 2> "$out/b_r05_$r.err"
 done
 echo done

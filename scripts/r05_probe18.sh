@@ -12,7 +12,7 @@ timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 for r in 0 1 2; do
   for tag in off on; do
     if [ $tag = off ]; then w=0; else w=25; fi
-    timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --keep-awake-us $w \
+    timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --keep-awake-us $w \
       --detail "$out/d_${tag}_$r.json" > "$out/b_${tag}_$r.json" 2> "$out/e_${tag}_$r.log"
     timeout -k 10 120 python -u scripts/small_lat_probe.py --n 300 --keep-awake-us $w \
       >> "$out/small_lat.jsonl" 2>> "$out/small_lat.err"

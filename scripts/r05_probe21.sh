@@ -8,7 +8,7 @@ out=${1:?out dir}
 mkdir -p "$out"
 export TMPDIR=/tmp
 for r in 1 2 3; do
-  DORA_BENCH_FIRST_PHASES=1 timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --no-ladder \
+  DORA_BENCH_FIRST_PHASES=1 timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --no-ladder \
     --no-c3 --no-cpu-baseline --detail "$out/d_$r.json" > "$out/b_$r.json" 2> "$out/e_$r.log"
 done
 echo done

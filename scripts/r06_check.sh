@@ -12,7 +12,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/s
 rc=$?
 echo "smoke rc=$rc"; tail -3 $out/smoke.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 --detail $out/bench_detail.json \
+timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 --detail $out/bench_detail.json \
   > $out/bench.json 2> $out/bench.err
 rc=$?
 echo "bench rc=$rc"; tail -c 2200 $out/bench.json

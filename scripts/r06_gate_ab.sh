@@ -11,8 +11,8 @@ timeout -k 10 400 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 tail -1 $out/tests.log
 for r in 1 2 3; do
   for t in base gate; do
-    if [ $t = base ]; then d=ab_base; else d=.; fi
-    (cd $d && timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > /tmp/b_$t.json 2>/dev/null) || exit 1
+    if [ $t = base ]; then d=ab_base; full=; else d=.; full=--full; fi  # the base tree predates --full
+    (cd $d && timeout -k 10 300 python -u bench.py $full --steps 20 --warmup 5 > /tmp/b_$t.json 2>/dev/null) || exit 1
     python - "$t" "$r" /tmp/b_$t.json >> $out/ab.jsonl <<'PY'
 import json, sys
 d = [json.loads(l) for l in open(sys.argv[3]) if l.startswith("{")][-1]

@@ -6,7 +6,7 @@ mkdir -p $out
 timeout -k 10 400 python -u -m pytest -x -v -s --timeout 300 --timeout-method thread -m gpu \
   tests/test_gpu_host_edges.py > $out/test.log 2>&1 || { tail -40 $out/test.log; exit 1; }
 grep -E "PASS|FAIL|host-only receiver" $out/test.log | tail -12
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --detail $out/detail.json \
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 --detail $out/detail.json \
   > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 python - <<PY
 import json

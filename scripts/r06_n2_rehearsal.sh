@@ -7,9 +7,9 @@ out=gpurun_out/${1:-r6n2}
 N2_ENV=${N2_ENV-GPU_MAX_HW_QUEUES=1}
 mkdir -p $out
 env DORA_BENCH_GPUS=1 ${N2_ENV} timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 20 --warmup 5 \
+  --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 20 --warmup 5 \
   --detail $out/detail_n2.json > $out/bench_n2.json 2> $out/bench_n2.err || exit 1
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --detail $out/detail_n1.json \
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 --detail $out/detail_n1.json \
   > $out/bench_n1.json 2> $out/bench_n1.err || exit 1
 for n in n2 n1; do python3 -c "
 import json

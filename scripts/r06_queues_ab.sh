@@ -5,7 +5,7 @@ out=gpurun_out/${1:-r6q}
 mkdir -p $out
 for r in 1 2; do
   for m in 4 3; do
-    DORA_GPU_AQL_QUEUES=$m timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 \
+    DORA_GPU_AQL_QUEUES=$m timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 \
       --detail $out/detail_${m}_$r.json > $out/bench_${m}_$r.json 2> $out/bench_${m}_$r.err || exit 1
     python3 -c "
 import json

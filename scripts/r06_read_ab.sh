@@ -8,7 +8,7 @@ timeout -k 10 400 python -u -m pytest -x -v -s --timeout 300 --timeout-method th
   tests/test_gpu_dataflow.py -k "rewritten_on_unrelated" > $out/test.log 2>&1 || { tail -40 $out/test.log; exit 1; }
 grep -E "PASS|FAIL|corrupted" $out/test.log | tail -8
 for r in 1 2; do
-  timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --detail $out/detail_$r.json \
+  timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 --detail $out/detail_$r.json \
     > $out/bench_$r.json 2> $out/bench_$r.err || exit 1
   python -c "
 import json

@@ -5,7 +5,7 @@ out=gpurun_out/${1:-r6rg}
 mkdir -p $out
 for r in 1 2; do
   for m in 1 4 8; do
-    DORA_GPU_READ_LANE_MIN=$m timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --no-ladder \
+    DORA_GPU_READ_LANE_MIN=$m timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 --no-ladder \
       --no-c3 --detail $out/detail_${m}_$r.json > $out/bench_${m}_$r.json 2> $out/bench_${m}_$r.err || exit 1
     python3 -c "
 import json

@@ -7,7 +7,7 @@ out=${1:?out dir}
 export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p "$out"
-B="python bench.py --no-ladder --no-cpu-baseline --no-c3 --sync-n 0"
+B="python bench.py --full --no-ladder --no-cpu-baseline --no-c3 --sync-n 0"
 export DORA_BENCH_SYNC_SENDS=1
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/sync_trace" -o run -- \
   $B --steps 200 --warmup 20 > "$out/sync_trace_bench.json" 2> "$out/sync_trace_bench.err"

@@ -178,6 +178,45 @@ def test_compact_line_fits_the_driver_tail():
     assert c["c3"]["frac"] == full["c3"]["roofline"]["frac"]
 
 
+def test_plain_run_is_the_headline_alone(monkeypatch):
+    """Without --full every leg beside the headline is off (CPU baseline, ladders, synchronous
+    sends, C3, cross-GPU runs); with it the defaults are what a run did before the option."""
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    assert a.no_ladder and a.no_cpu_baseline and a.no_c3 and a.no_cross_gpu and a.sync_n == 0
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not (a.no_ladder or a.no_cpu_baseline or a.no_c3 or a.no_cross_gpu)
+    assert a.sync_n == 20 and a.c3_steps == 20 and a.tp_n == 200 and a.lat_n == 1000
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--no-c3", "--sync-n", "0"])
+    a = bench.parse()
+    assert a.no_c3 and a.sync_n == 0 and not a.no_ladder
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """sample.npy: float32, one element per byte, whole up to DUMP_MAX_ELEMS bytes and the same
+    ascending seeded offsets on every run above; a sample of the wrong length is an error."""
+    import numpy as np
+
+    import bench
+    raw = (np.arange(5003, dtype=np.uint64) * 37 % 251).astype(np.uint8)
+    raw.tofile(tmp_path / "raw.bin")
+    bench.dump_outputs(str(tmp_path / "a"), str(tmp_path / "raw.bin"), 5003)
+    whole = np.load(tmp_path / "a" / "sample.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, raw.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    bench.dump_outputs(str(tmp_path / "b"), str(tmp_path / "raw.bin"), 5003)
+    bench.dump_outputs(str(tmp_path / "c"), str(tmp_path / "raw.bin"), 5003)
+    part = np.load(tmp_path / "b" / "sample.npy")
+    assert part.dtype == np.float32 and part.shape == (1000,)
+    assert np.array_equal(part, np.load(tmp_path / "c" / "sample.npy"))
+    assert set(part) <= set(whole) and not np.array_equal(part, whole[:1000])
+    with pytest.raises(RuntimeError, match="5003"):
+        bench.dump_outputs(str(tmp_path / "d"), str(tmp_path / "raw.bin"), 5004)
+
+
 def test_compact_line_with_cross_gpu_block():
     """N > 1: the compact line carries one short entry per cross-GPU configuration (link GB/s,
     xGMI fraction, RCCL groups and the ranks RCCL formed) and still fits the driver's tail."""
