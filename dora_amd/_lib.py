@@ -46,6 +46,17 @@ class DoraResult(ctypes.Structure):
     _fields_ = [("error", POINTER(VecU8))]
 
 
+FILL_WRITE_THROUGH = 0  # DORA_FILL_WRITE_THROUGH (include/dora_fill_ticket.h)
+FILL_PLAIN = 1          # DORA_FILL_PLAIN
+
+
+class FillTicket(ctypes.Structure):
+    """dora_fill_ticket of include/dora_fill_ticket.h (32 bytes): what dora_sample_fill_ticket
+    issues and a publishing kernel takes by value."""
+    _fields_ = [("flag", c_uint64), ("done", c_uint64), ("epoch", c_uint64),
+                ("workgroups", c_uint32), ("mode", c_uint32)]
+
+
 # name -> (restype, argtypes); `int` restype means a status code that is checked.
 _SIGS = {
     "dora_gpu_last_error": (c_char_p, []),
@@ -101,6 +112,8 @@ _SIGS = {
     "dora_gpu_csum64": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     "dora_gpu_csum64_sync": (c_int, [c_void_p, c_size_t, c_void_p, POINTER(c_uint64)]),
     "dora_gpu_fill_splitmix": (c_int, [c_void_p, c_size_t, c_uint64, c_void_p]),
+    "dora_gpu_fill_splitmix_ticket": (c_int, [c_void_p, c_size_t, c_uint64, POINTER(FillTicket),
+                                              c_void_p]),
     # node API
     "dora_node_init": (c_int, [c_char_p, c_char_p, c_int, POINTER(c_void_p)]),
     "dora_node_init_from_env": (c_int, [POINTER(c_void_p)]),
@@ -143,6 +156,9 @@ _SIGS = {
     "dora_node_set_profiling": (c_int, [c_void_p, c_int]),
     "dora_node_set_timing_period": (c_int, [c_void_p, c_uint64]),
     "dora_node_fill_paths": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "dora_node_sample_paths": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "dora_sample_fill_ticket": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32,
+                                        POINTER(FillTicket)]),
     "dora_node_host_bound_outputs": (c_int, [c_void_p, c_char_p, c_uint64, POINTER(c_uint64)]),
     "dora_node_host_paths": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64),
                                      POINTER(c_uint64), POINTER(c_uint64)]),
@@ -200,6 +216,8 @@ _TEST_SIGS = {
     "dora_gpu_test_d2h_copy_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_uint64, c_void_p]),
     "dora_gpu_test_stream_order_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_void_p]),
     "dora_gpu_test_abandoned_slots": (c_int, [c_int, POINTER(c_uint32)]),
+    "dora_gpu_test_publish_kernel": (c_int, [c_void_p, c_size_t, c_uint64, POINTER(FillTicket),
+                                             c_uint32, c_uint32, c_void_p]),
     "dora_gpu_test_keep_awake_stats": (c_int, [c_int, POINTER(c_uint64), POINTER(c_int)]),
     "dora_gpu_test_aql_ring_wc": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "dora_gpu_test_bcast_group": (c_int, [c_int, c_void_p, c_uint64, POINTER(c_int),

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "pack_device.h"
 #include "plan.h"
+#include "splitmix_device.h"
 
 namespace dora {
 namespace {
@@ -186,6 +187,14 @@ __global__ __launch_bounds__(kThreads) void fill_kernel(uint8_t* __restrict__ p,
       for (uint64_t k = 0; k < 8 && 8 * i + k < n; ++k) p[8 * i + k] = uint8_t(w >> (8 * k));
     }
   }
+}
+
+// The same payload written into a sample in place with write-through stores and published by the
+// launch itself through the public device header (include/dora_gpu_device.h): the grid is the
+// ticket's workgroup count, striding over the payload's 16-byte units.
+__global__ __launch_bounds__(kThreads) void fill_ticket_kernel(uint8_t* p, uint64_t n,
+                                                               uint64_t seed, dora_fill_ticket t) {
+  splitmix::fill_and_publish<true>(p, n, seed, t);
 }
 
 // Test tool (the acquire-fence negative control, tests/test_gpu_fence.py): every workgroup reads
@@ -663,6 +672,14 @@ int launch_fill(void* dst, size_t len, uint64_t seed, hipStream_t stream) {
   return DORA_OK;
 }
 
+int launch_fill_ticket(void* dst, size_t len, uint64_t seed, const dora_fill_ticket& t,
+                       hipStream_t stream) {
+  hipLaunchKernelGGL(fill_ticket_kernel, dim3(t.workgroups), dim3(kThreads), 0, stream,
+                     static_cast<uint8_t*>(dst), uint64_t(len), seed, t);
+  DORA_HIP(hipGetLastError());
+  return DORA_OK;
+}
+
 }  // namespace dora
 
 extern "C" {
@@ -704,6 +721,17 @@ int dora_gpu_csum64_sync(const void* data, size_t len, dora_stream_t stream, uin
 int dora_gpu_fill_splitmix(void* dst, size_t len, uint64_t seed, dora_stream_t stream) {
   if (!dst && len) return dora::fail(DORA_ERR_INVALID, "dst is NULL");
   return dora::launch_fill(dst, len, seed, static_cast<hipStream_t>(stream));
+}
+
+int dora_gpu_fill_splitmix_ticket(void* dst, size_t len, uint64_t seed,
+                                  const dora_fill_ticket* ticket, dora_stream_t stream) {
+  if (!dst || !ticket) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  if (reinterpret_cast<uintptr_t>(dst) & 15)
+    return dora::fail(DORA_ERR_INVALID, "dst must be 16-byte aligned (a sample's data is)");
+  if (!ticket->flag || !ticket->workgroups || ticket->workgroups > dora::kMaxSignalWgs ||
+      (ticket->workgroups > 1 && !ticket->done))
+    return dora::fail(DORA_ERR_INVALID, "not a ticket of dora_sample_fill_ticket");
+  return dora::launch_fill_ticket(dst, len, seed, *ticket, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

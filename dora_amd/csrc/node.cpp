@@ -762,6 +762,9 @@ struct dora_sample {
   uint64_t epoch = 0;
   bool stamped = false;  // the pack kernel stamps its start / signal time into the flag line
   bool read_signalled = false;  // its pack raises the flag line's read word (aql.h aql_pack)
+  // dora_sample_fill_ticket: the caller's own kernel raises the flag to `epoch`; the send queues
+  // no stream operation for it
+  bool self_published = false;
 };
 
 namespace dora {
@@ -900,6 +903,9 @@ struct dora_node {
   std::unordered_map<dora::DropToken, std::shared_ptr<dora::InputData>, dora::DropTokenHash>
       forwarded;
   uint64_t zero_copy_forwards = 0;
+  // in-place samples (dora_node_send_output_sample) by ordering: a stream operation of the send
+  // after the node stream, or the caller's own kernel (dora_sample_fill_ticket)
+  uint64_t samples_stream_ordered = 0, samples_self_published = 0;
 };
 
 namespace dora {
@@ -2082,9 +2088,32 @@ dora_sample* host_bound_sample(dora_node* n, uint64_t len, uint64_t ext_len) {
   return s;
 }
 
+// A ticketed sample (dora_sample_fill_ticket) that will not be sent, or whose send failed: its
+// kernel may have been launched or not, and nobody else will raise the flag.  Drain the node
+// stream (a kernel queued there has then stored the epoch itself), then raise the flag to the
+// ticket's epoch from the host if it is still below it — epochs only grow, so the store of a
+// kernel that runs late is harmless — so that no later allocation, dora_node_sync or free_slot
+// waits on an epoch nobody will store.
+void settle_ticket(dora_node* n, dora_sample* s) {
+  if (!s->self_published || !s->slot || s->slot->flag < 0) return;
+  NodeCore* c = n->core.get();
+  {
+    DeviceScope ds(c->device);
+    if (c->stream && hipStreamQuery(c->stream) == hipErrorNotReady)
+      (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+  }
+  auto& f = c->region->hdr()->nodes[c->idx].fill[s->slot->flag].epoch;
+  uint64_t cur = f.load(std::memory_order_acquire);
+  while (cur < s->epoch && !f.compare_exchange_weak(cur, s->epoch, std::memory_order_acq_rel)) {
+  }
+  s->self_published = false;
+}
+
 // An unsent sample back to the node: its slot to the cache (an inline Vec is just freed).
 void discard_sample(dora_node* n, dora_sample* s) {
   if (!s) return;
+  settle_ticket(n, s);
   if (s->slot) add_to_cache(n, s->slot);
   delete s;
 }
@@ -2900,7 +2929,24 @@ int dora_node_send_output_sample(dora_node* n, const char* output_id, const uint
     return dora::fail(DORA_ERR_INVALID,
                       "sample was already sent or discarded (or belongs to another node)");
   DORA_GUARD_BEGIN
-  if (sample && sample->slot && !sample->slot->host && sample->len &&
+  if (sample && sample->self_published) {
+    // the caller's kernel raises the slot's fill flag itself (dora_sample_fill_ticket set the
+    // sample up as order_fill would): no stream operation, on whichever stream the kernel runs
+    ++n->samples_self_published;
+    if (n->bcast_out.count(output_id)) {
+      // a broadcast-group output reads the slot on its own stream, which nothing orders after
+      // the caller's kernel: wait for the flag here
+      const std::atomic<uint64_t>* f = n->core->flag_host(sample->slot->flag);
+      const uint64_t t0 = dora::mono_ns();
+      while (!dora::fill_reached(f, sample->epoch)) {
+        if (dora::mono_ns() - t0 > 10000000000ull) {
+          dora::discard_sample(n, sample);
+          return dora::fail(DORA_ERR_TIMEOUT, "the sample's kernel did not publish it within 10 s");
+        }
+        __builtin_ia32_pause();
+      }
+    }
+  } else if (sample && sample->slot && !sample->slot->host && sample->len &&
       n->core->stream_used.load(std::memory_order_relaxed)) {
     // a sample written by kernels on the node stream (dora_node_stream): receivers wait for
     // that work through the slot's fill flag, the sender does not (no host synchronisation)
@@ -2912,9 +2958,55 @@ int dora_node_send_output_sample(dora_node* n, const char* output_id, const uint
       return dora::fail(DORA_ERR_HIP, "ordering the sample after the node stream: %s",
                         hipGetErrorString(e));
     }
+    ++n->samples_stream_ordered;
   }
   std::vector<uint8_t> ti(type_info, type_info + type_info_len);
   return dora::send_sample(n, output_id, ti, params, params_len, sample);
+  DORA_GUARD_END
+}
+
+int dora_sample_fill_ticket(dora_node* n, dora_sample* s, uint32_t workgroups, uint32_t mode,
+                            dora_fill_ticket* out) {
+  if (!n || !s || !out) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  if (!n->samples_live.count(s))
+    return dora::fail(DORA_ERR_INVALID,
+                      "fill ticket: the sample is not live on this node (already sent or "
+                      "discarded, or another node's)");
+  if (workgroups == 0 || workgroups > dora::kMaxSignalWgs)
+    return dora::fail(DORA_ERR_INVALID, "fill ticket: %u workgroups (1..%u: a fill flag owns %u "
+                      "done words)", workgroups, dora::kMaxSignalWgs, dora::kMaxSignalWgs);
+  if (mode != DORA_FILL_WRITE_THROUGH && mode != DORA_FILL_PLAIN)
+    return dora::fail(DORA_ERR_INVALID, "fill ticket: unknown mode %u", mode);
+  if (s->self_published)
+    return dora::fail(DORA_ERR_INVALID, "fill ticket: the sample already has a ticket");
+  if (!s->slot)
+    return dora::fail(DORA_ERR_UNSUPPORTED,
+                      "fill ticket: an inline sample (no device slot: below 4096 B on a node "
+                      "without a GPU, or empty) is written by the host");
+  if (s->slot->host)
+    return dora::fail(DORA_ERR_UNSUPPORTED,
+                      "fill ticket: a shared-memory sample is written by the host");
+  dora::NodeCore* c = n->core.get();
+  if (c->device < 0) return dora::fail(DORA_ERR_UNSUPPORTED, "fill ticket: the node has no GPU");
+  if (s->slot->flag < 0 || !c->region_dev)
+    return dora::fail(DORA_ERR_UNSUPPORTED,
+                      "fill ticket: the sample's slot has no fill flag (send it stream-ordered)");
+  if (!c->fill_done)
+    return dora::fail(DORA_ERR_UNSUPPORTED,
+                      "fill ticket: the node has no done words (send the sample stream-ordered)");
+  // as order_fill for FILL_FLAG, with the kernel in the place of the stream write
+  s->epoch = ++c->epoch;
+  s->fill = dora::FILL_FLAG;
+  s->slot->fill_epoch = s->epoch;
+  s->self_published = true;
+  dora::NodeCore::note(c->flag_pending, c->flag_host(s->slot->flag), s->epoch);
+  out->flag = reinterpret_cast<uint64_t>(c->flag_dev(s->slot->flag));
+  out->done = reinterpret_cast<uint64_t>(c->fill_done + size_t(s->slot->flag) * dora::kMaxSignalWgs);
+  out->epoch = s->epoch;
+  out->workgroups = workgroups;
+  out->mode = mode;
+  return DORA_OK;
   DORA_GUARD_END
 }
 
@@ -3435,6 +3527,13 @@ int dora_node_pack_intervals(dora_node* n, double* out_ms, size_t cap, size_t* c
   const size_t pairs = n->intervals.size() / 2;
   *count = pairs;
   for (size_t i = 0; i < 2 * std::min(cap, pairs); ++i) out_ms[i] = n->intervals[i];
+  return DORA_OK;
+}
+
+int dora_node_sample_paths(dora_node* n, uint64_t* stream_ordered, uint64_t* self_published) {
+  if (!n) return dora::fail(DORA_ERR_INVALID, "NULL node");
+  if (stream_ordered) *stream_ordered = n->samples_stream_ordered;
+  if (self_published) *self_published = n->samples_self_published;
   return DORA_OK;
 }
 

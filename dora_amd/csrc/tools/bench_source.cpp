@@ -13,6 +13,9 @@
 // (examples/benchmark/node/src/main.rs via allocate_data_sample + send_output_sample,
 // apis/rust/node/src/node/mod.rs:246-346): a slot is allocated, a kernel on the node stream
 // writes the payload into it in place, and the sample is sent — no pack, no source buffer.
+// DORA_BENCH_SAMPLE_PATH=2: the same, and the kernel publishes the sample itself
+// (dora_sample_fill_ticket + dora_gpu_fill_splitmix_ticket, on a stream that is not the node
+// stream): one launch per message and no stream operation of the send.
 // Outputs `latency` and `throughput` (warmup and ack requests go on `throughput`, like the
 // reference node's two outputs); every input is an ack channel from a receiver.
 //   env: DORA_GPU_DATAFLOW, DORA_NODE_ID, DORA_GPU_DEVICE, DORA_BENCH_RESULT (path)
@@ -127,8 +130,10 @@ int main() {
   dora_gpu_stream_sync(st);
 
   // sample path: the node stream the payload kernels run on, and byte_array type infos by size
-  const bool sample_path = env_long("DORA_BENCH_SAMPLE_PATH", 0) != 0;
-  dora_stream_t nst = sample_path ? dora_node_stream(node) : nullptr;
+  const long sample_mode = env_long("DORA_BENCH_SAMPLE_PATH", 0);
+  const bool sample_path = sample_mode != 0;
+  const bool self_publish = sample_mode == 2;
+  dora_stream_t nst = sample_path && !self_publish ? dora_node_stream(node) : nullptr;
   std::map<uint64_t, std::vector<uint8_t>> tis;
   auto type_info = [&](const void* data, uint64_t size) -> const std::vector<uint8_t>& {
     auto it = tis.find(size);
@@ -149,7 +154,16 @@ int main() {
                            size_t params_len) -> int {
     dora_sample* smp = nullptr;
     if (dora_node_allocate_data_sample(node, size, &smp) != 0) return -1;
-    if (size && dora_gpu_fill_splitmix(dora_sample_data(smp), size, 0xD05A + size, nst) != 0) {
+    if (size && self_publish) {
+      // four 16-byte units per lane, at most the pack's signalling grid (1024 workgroups)
+      const uint64_t wgs = std::min<uint64_t>(std::max<uint64_t>((size + 16383) / 16384, 1), 1024);
+      dora_fill_ticket ticket;
+      if (dora_sample_fill_ticket(node, smp, uint32_t(wgs), DORA_FILL_WRITE_THROUGH, &ticket) != 0 ||
+          dora_gpu_fill_splitmix_ticket(dora_sample_data(smp), size, 0xD05A + size, &ticket, st) != 0) {
+        dora_sample_discard(node, smp);
+        return -1;
+      }
+    } else if (size && dora_gpu_fill_splitmix(dora_sample_data(smp), size, 0xD05A + size, nst) != 0) {
       dora_sample_discard(node, smp);
       return -1;
     }
@@ -269,6 +283,8 @@ int main() {
   dora_node_bcast_stats(node, &bgroups, nullptr, &bsent, nullptr, nullptr, &berr);
   uint64_t branks = 0;
   dora_node_bcast_ranks(node, &branks);
+  uint64_t stream_ordered = 0, self_published = 0;
+  dora_node_sample_paths(node, &stream_ordered, &self_published);
   FILE* f = out_path ? std::fopen(out_path, "w") : stdout;
   const double delivered = double(tp_size) * double(tp_n) * double(acks);
   std::fprintf(f,
@@ -277,14 +293,16 @@ int main() {
                "\"send_phase_us\": {\"alloc_us\": %.2f, \"launch_us\": %.2f, \"fill_us\": %.2f, "
                "\"send_us\": %.2f}, \"slots_created\": %llu, \"cache_hits\": %llu, "
                "\"bcast_groups\": %llu, \"bcast_ranks\": %llu, \"bcast_sent\": %llu, "
-               "\"bcast_error\": \"%s\", "
+               "\"bcast_error\": \"%s\", \"samples_stream_ordered\": %llu, "
+               "\"samples_self_published\": %llu, "
                "\"tp_busy_us_per_msg\": %.3f, \"aql_batches\": %llu, \"aql_batched_msgs\": %llu}\n",
                errors, ok ? "true" : "false", acks, (unsigned long long)tp_size, tp_n, tp_s,
                tp_s > 0 ? delivered / tp_s / 1e9 : 0.0,
                tp_s > 0 ? double(tp_size) * double(tp_n) / tp_s / 1e9 : 0.0, phase[0], phase[1],
                phase[2], phase[3], (unsigned long long)slots, (unsigned long long)hits,
                (unsigned long long)bgroups, (unsigned long long)branks, (unsigned long long)bsent,
-               json_safe(berr).c_str(),
+               json_safe(berr).c_str(), (unsigned long long)stream_ordered,
+               (unsigned long long)self_published,
                tp_n > 0 ? (tp_s * 1e9 - double(idle1 - idle0)) / 1e3 / double(tp_n) : 0.0,
                (unsigned long long)batches, (unsigned long long)batched);
   if (f != stdout) std::fclose(f);

@@ -220,6 +220,15 @@ class Node:
         if rc:
             _lib.check(rc)
 
+    def sample_fill_ticket(self, sample_ptr, workgroups: int,
+                           mode: int = _lib.FILL_WRITE_THROUGH) -> "_lib.FillTicket":
+        """dora_sample_fill_ticket: the ticket with which one kernel launch of `workgroups`
+        workgroups publishes the sample `sample_ptr` (of dora_node_allocate_data_sample) it
+        writes in place; the send then queues no stream operation for it."""
+        t = _lib.FillTicket()
+        call("dora_sample_fill_ticket", self.handle, sample_ptr, workgroups, mode, byref(t))
+        return t
+
     def set_compact(self, enable: bool = True):
         """Send device arrays with compacting plans (slices move only their own bytes)."""
         call("dora_node_set_compact", self.handle, int(enable))

@@ -16,6 +16,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dora_fill_ticket.h" /* dora_fill_ticket, DORA_FILL_* (dora_sample_fill_ticket below) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -222,6 +224,12 @@ int dora_gpu_csum64(const void* data, size_t len, uint64_t* out_dev, dora_stream
 int dora_gpu_csum64_sync(const void* data, size_t len, dora_stream_t stream, uint64_t* out);
 /* Fill `len` device bytes with the splitmix64 stream of `seed` (BASELINE.md §2 payloads). */
 int dora_gpu_fill_splitmix(void* dst, size_t len, uint64_t seed, dora_stream_t stream);
+/* The same payload written into a sample in place and published by the kernel itself: `ticket`
+ * from dora_sample_fill_ticket for that sample (the kernel stores write-through:
+ * DORA_FILL_WRITE_THROUGH is the mode to ask for), `dst` the sample's data (16-byte aligned), one launch of the ticket's workgroup count on `stream`.  The in-tree
+ * user of include/dora_gpu_device.h; the kernel to copy from is examples/publish_kernel.hip. */
+int dora_gpu_fill_splitmix_ticket(void* dst, size_t len, uint64_t seed,
+                                  const dora_fill_ticket* ticket, dora_stream_t stream);
 /* ------------------------------------------------------------------------------------------ */
 /* Node API — replaces DoraNode / EventStream (apis/rust/node/src/node/mod.rs:42-503,         */
 /* apis/rust/node/src/event_stream/mod.rs:27-235) and the C node API (apis/c/node/node_api.h) */
@@ -272,12 +280,31 @@ void dora_sample_discard(dora_node* node, dora_sample* sample);
  * was already sent or discarded is refused with DORA_ERR_INVALID (the reference moves its
  * DataSample into the call).  The sample must be written before the call: on the host, or by
  * work queued on dora_node_stream() — receivers then wait for that work through the slot's fill
- * signal, the call does not — or on another stream the caller synchronized.  `params` is the encoded
- * MetadataParameters (u32 n, then per entry: u64 klen, key, u8 tag 0=bool 1=int 2=string,
+ * signal, the call does not — or on another stream the caller synchronized, or by a kernel that
+ * publishes it itself (dora_sample_fill_ticket below: no stream operation at all).  `params` is
+ * the encoded MetadataParameters (u32 n, then per entry: u64 klen, key, u8 tag 0=bool 1=int 2=string,
  * value: u8 | i64 | u64 len + bytes). */
 int dora_node_send_output_sample(dora_node* node, const char* output_id, const uint8_t* type_info,
                                  size_t type_info_len, const uint8_t* params, size_t params_len,
                                  dora_sample* sample);
+/* Publishing a sample from the caller's own kernel (new; no reference counterpart).  Takes the
+ * sample's send epoch and fills `out` for ONE launch of `workgroups` workgroups (1..4096) that
+ * writes the sample and calls dora_fill_publish (include/dora_gpu_device.h); `mode` says how it
+ * stores (DORA_FILL_WRITE_THROUGH / DORA_FILL_PLAIN).  dora_node_send_output_sample then queues
+ * no stream operation for the sample: receivers wait on the slot's fill flag, which the kernel
+ * raises.  The kernel may run on any stream and be launched before or after the send.  A ticket
+ * whose kernel never runs (or runs with another workgroup count) delivers a sample that fails at
+ * its receivers after DORA_GPU_TRANSIT_LIMIT_MS, like any fill that never completes, and
+ * dora_node_sync then times out.  Discarding a ticketed sample (dora_sample_discard,
+ * dora_node_free) drains the node stream and raises the flag from the host, so the slot is
+ * reusable; a kernel launched for it on another stream must have completed before the discard.
+ * Refused with DORA_ERR_UNSUPPORTED (the stream-ordered path of dora_node_send_output_sample
+ * remains): an inline sample (no slot: below 4096 B on a host-only node, or empty), a
+ * shared-memory slot, a node without a GPU, a slot without a fill flag or a node without done
+ * words.  DORA_ERR_INVALID: workgroups 0 or > 4096, an unknown mode, a sample not live on this
+ * node, a second ticket for one sample. */
+int dora_sample_fill_ticket(dora_node* node, dora_sample* sample, uint32_t workgroups,
+                            uint32_t mode, dora_fill_ticket* out);
 /* send_output (mod.rs:198-215): plan + allocate + HIP pack + send.  `device_type` as in
  * dora_gpu_plan; a host-resident array whose sample is < 4096 B travels inline as the
  * reference's DataMessage::Vec (mod.rs:40,303-319: no slot, no GPU work).  Like the reference,
@@ -380,6 +407,10 @@ int dora_node_dataflow_counters(dora_node* node, const char* node_id, uint64_t* 
  * sources of <= 8 segments) or hipLaunchKernel on
  * the node's fill streams (larger, host sources, compacting transforms, relays). */
 int dora_node_fill_paths(dora_node* node, uint64_t* aql_packs, uint64_t* hip_packs);
+/* In-place samples (dora_node_send_output_sample) sent by each ordering: after the node stream by
+ * a stream operation of the send, or published by the caller's own kernel
+ * (dora_sample_fill_ticket).  Either pointer may be NULL. */
+int dora_node_sample_paths(dora_node* node, uint64_t* stream_ordered, uint64_t* self_published);
 /* The host side of the data plane (new; diagnostics): host-resident sources of 4096 B..2 MiB a
  * device node wrote into its slot with the CPU through the large BAR (the reference's memcpy
  * into its shared-memory sample, arrow_utils.rs:48: no GPU dispatch), and device samples a node

@@ -43,6 +43,13 @@ int dora_gpu_test_d2h_copy_probe(int device, int mode, uint64_t bytes, uint32_t 
 int dora_gpu_test_stream_order_probe(int device, int mode, uint64_t bytes, uint32_t n,
                                      uint64_t* out_ns);
 int dora_gpu_test_abandoned_slots(int device, uint32_t* slots);
+/* Test hook of the self-published sample path (include/dora_gpu_device.h): as
+ * dora_gpu_fill_splitmix_ticket, with `threads_per_wg` threads per workgroup (a multiple of 64 up
+ * to 1024) and, with `store_mode` 1, ordinary stores (the ticket must then be DORA_FILL_PLAIN);
+ * 0 stores write-through.  One launch of the ticket's workgroup count on `stream`. */
+int dora_gpu_test_publish_kernel(void* dst, size_t len, uint64_t seed,
+                                 const dora_fill_ticket* ticket, uint32_t threads_per_wg,
+                                 uint32_t store_mode, dora_stream_t stream);
 /* Test tool: empty packets the keep-awake thread of `device` has published in this process
  * (dora_gpu_set_keep_awake), and whether it is parked (no send for 100 ms). */
 int dora_gpu_test_keep_awake_stats(int device, uint64_t* heartbeats, int* parked);

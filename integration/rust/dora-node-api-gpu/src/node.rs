@@ -418,8 +418,24 @@ impl GpuNode {
         Ok(DataSample { raw, node: self.node.clone() })
     }
 
+    /// The ticket with which one kernel launch of `workgroups` workgroups publishes `sample`
+    /// itself (`dora_fill_publish`, include/dora_gpu_device.h): pass it to the kernel by value;
+    /// `send_output_sample` then queues no stream operation for the sample.  `mode`:
+    /// `sys::DORA_FILL_WRITE_THROUGH` or `sys::DORA_FILL_PLAIN`.
+    pub fn sample_fill_ticket(
+        &mut self,
+        sample: &mut DataSample,
+        workgroups: u32,
+        mode: u32,
+    ) -> Result<sys::dora_fill_ticket> {
+        let mut t = sys::dora_fill_ticket::default();
+        let g = lock(&self.node);
+        check(unsafe { sys::dora_sample_fill_ticket(g.raw, sample.raw, workgroups, mode, &mut t) })?;
+        Ok(t)
+    }
+
     /// send_output_sample (mod.rs:246-275).  The sample must be fully written (its stream
-    /// synchronised) before the call.
+    /// synchronised) before the call, or published by its own kernel (`sample_fill_ticket`).
     pub fn send_output_sample(
         &mut self,
         output_id: &str,
