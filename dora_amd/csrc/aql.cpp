@@ -1418,7 +1418,7 @@ int aql_stamp_reduce(int device, const uint64_t* base, uint32_t area_words,
                                 HSA_WAIT_STATE_ACTIVE) != 0) {
     // A diagnostic: the data-path queues stay in use.  The packet is still queued and may yet
     // run: its signal is abandoned (a later reduction makes its own), the caller must not free
-    // or reuse `areas` / `out` (node.cpp leaks them and reads the areas through the BAR), and
+    // or reuse `areas` / `out` (node_measure.cpp dora_node_region_end leaks them and reads the areas through the BAR), and
     // its argument slot is never written again — a later pack's arguments there would be the
     // reduction's if it ran after them.  Queues that lose several stop dispatching.
     a->reduce_sig.handle = 0;

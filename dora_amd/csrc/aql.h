@@ -38,11 +38,11 @@ bool aql_usable(const AqlQueue* q);
 // the workgroups k that map there (s_memrealtime, atomic max).
 //
 // `sync`: the caller waits for this pack before it does anything else (a synchronous send,
-// node.cpp wait_source_read).  A single-segment pack that is sent synchronously, or that finds
+// node_send.cpp wait_source_read).  A single-segment pack that is sent synchronously, or that finds
 // every queue idle, runs alone on the GPU: its arguments go to the device ring and it reads
 // without the acquire fence; a synchronous one is also signalled by the command processor at any
 // size >= 1 MiB, with a grid of up to 3584 workgroups (no done words to poll, so no
-// 1024-workgroup signalling cap).  A synchronous one of 1-256 MiB of 16-byte-aligned bytes is
+// 1024-workgroup signalling cap).  A synchronous one of 1-192 MiB (kReadMaxUnits) of 16-byte-aligned bytes is
 // read-signalled (*read_signalled): the pack raises the flag line's read word (FillFlag
 // read_epoch) once every source byte is in its workgroups' registers, before its stores drain,
 // and the caller may return then.
@@ -94,7 +94,7 @@ int bar_alloc(int device, size_t bytes, void** out);
 int bar_write(int device, void* dst, const void* src, size_t bytes);
 void bar_free(void* p);
 
-// Host-resident sources written straight into a device slot by the CPU (node.cpp
+// Host-resident sources written straight into a device slot by the CPU (node_send.cpp
 // host_bar_fill): bar_map makes a hipMalloc'd slot host-accessible through the large BAR (once
 // per slot; its IPC export is unaffected), bar_copy writes bytes with streaming stores, and
 // bar_publish (sfence + HDP flush + one read-back of `last`) returns once every byte written so
@@ -103,7 +103,7 @@ int bar_map(AqlQueue* q, void* p);
 void bar_copy(void* dst, const void* src, size_t n);
 void bar_publish(AqlQueue* q, const void* last);
 
-// Region-end reduction of stamp areas (node.cpp): one dispatch of dora_aql_stamp_reduce over
+// Region-end reduction of stamp areas (node_measure.cpp dora_node_region_end): one dispatch of dora_aql_stamp_reduce over
 // `n` areas of `area_words` words each at `base` (device memory), area indices in `areas`, writing
 // (start, latest end) pairs to `out` (host memory the GPU can write); waits for it (bounded).
 int aql_stamp_reduce(int device, const uint64_t* base, uint32_t area_words,

@@ -174,7 +174,7 @@ void dora_aql_pack1r_u4(
   }
 }
 
-// Region-end reduction of CP-signalled packs' stamp areas (aql.cpp aql_stamp_reduce, node.cpp
+// Region-end reduction of CP-signalled packs' stamp areas (aql.cpp aql_stamp_reduce, node_measure.cpp
 // dora_node_region_end): workgroup i reads area `areas[i]` of `base` (area_words words: [0] the
 // first workgroup's start, then the end stamps of pack_body's CP branch) and writes (start,
 // latest end) to out[2i], out[2i + 1] in host memory.  The words were written by system-scope

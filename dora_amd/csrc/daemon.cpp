@@ -637,7 +637,7 @@ class Daemon {
 
   // EV_READY's payload for node i: its outputs whose every receiver is a running local node
   // without a GPU (DORA_GPU_DEVICE < 0) — such samples are wanted in host memory only, so the
-  // producer packs them straight into shared memory (node.cpp pack_and_send) instead of into
+  // producer packs them straight into shared memory (node_send.cpp pack_and_send) instead of into
   // an HBM slot each receiver would copy out.  [u32 n][str output] x n.
   std::vector<uint8_t> ready_payload(int i) {
     std::vector<const std::string*> outs;

@@ -22,14 +22,9 @@
 #include "common.h"
 #include "device_array.h"
 #include "dora_gpu.h"
+#include "node_internal.h"  // proxy_send, vec_sample
 
 namespace dora {
-
-// node.cpp: send a sample with the producer's original timestamp (the remote message's).
-int proxy_send(dora_node* n, const char* output_id, const uint8_t* ti, size_t ti_len,
-               const uint8_t* params, size_t params_len, dora_sample* sample, uint64_t ts);
-dora_sample* vec_sample(const uint8_t* p, size_t len);
-
 namespace {
 
 bool send_all(int fd, const uint8_t* p, size_t n) {

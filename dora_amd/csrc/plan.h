@@ -127,7 +127,7 @@ uint64_t metadata_len(const char* meta);
 // Everything a plan of (array, schema) depends on when it reads no array bytes, as words: per
 // node in walk order the schema's identity and strings (hashed), flags, and the array's length,
 // offset, null count, buffer addresses and child counts.  Equal keys give equal plans (a node's
-// plan cache, node.cpp).  False when the tree is too large to key.
+// plan cache, node_internal.h PlanCache).  False when the tree is too large to key.
 bool plan_key(const ArrowArray* array, const ArrowSchema* schema, std::vector<uint64_t>& out);
 
 Layout layout_of(const char* format);

@@ -101,7 +101,7 @@ int main() {
   uint64_t* csum_dev = nullptr;
   dora_gpu_malloc(reinterpret_cast<void**>(&csum_dev), 8);
   // a stream of its own: every checksum below is synchronised before its input is released, so
-  // the node stream stays unused and no release has to query it (node.cpp stream_used)
+  // the node stream stays unused and no release has to query it (node_internal.h NodeCore::stream_used)
   dora_stream_t st = nullptr;
   const bool own_stream = dora_gpu_stream_create(&st) == 0;
   if (!own_stream) st = dora_node_stream(node);

@@ -97,7 +97,7 @@ int main() {
   const long acks = env_long("DORA_BENCH_ACKS", 1);
   const long verify_n = env_long("DORA_BENCH_VERIFY", 2);
   // the payloads are made (and synchronised) on a stream of its own before any send: the node
-  // stream stays unused, so sends need not query it (node.cpp stream_used)
+  // stream stays unused, so sends need not query it (node_internal.h NodeCore::stream_used)
   dora_stream_t st = nullptr;
   const bool own_stream = dora_gpu_stream_create(&st) == 0;
   if (!own_stream) st = dora_node_stream(node);

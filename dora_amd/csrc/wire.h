@@ -92,7 +92,7 @@ struct Metadata {
   uint16_t version = 0;
   uint64_t timestamp_ns = 0;
   std::vector<uint8_t> type_info;
-  std::vector<uint8_t> parameters;  // BTreeMap<String, Parameter> encoding (node.cpp)
+  std::vector<uint8_t> parameters;  // BTreeMap<String, Parameter> encoding (node_send.cpp put_metadata)
 };
 
 // Encoder.  Tracks its own length over storage that only grows: a send encodes ~25 fields, and

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A D2H copy of a small sample into pinned host memory, HIP against the HSA copy call
 (dora_gpu_test_d2h_copy_probe): p50 / p99 of call -> complete per size, 1 ms apart like the
-latency ladder, two interleaved rounds.  The staging of a receiver without a GPU (node.cpp
+latency ladder, two interleaved rounds.  The staging of a receiver without a GPU (node_recv.cpp
 stage_to_host) pays the HIP figure at every small size.
 
     python scripts/d2h_copy_probe.py --n 300

@@ -1,4 +1,4 @@
-// Host cost of hipGetDevice / hipSetDevice (same device) per call: what node.cpp's DeviceScope
+// Host cost of hipGetDevice / hipSetDevice (same device) per call: what node_internal.h's DeviceScope
 // adds to every entry point.   hipcc -O2 scripts/get_device_probe.cpp -o build/get_device_probe
 #include <hip/hip_runtime.h>
 

@@ -141,7 +141,7 @@ def test_slots_recycle_through_drop_tokens(launcher, tmp_path):
 
 
 def test_slot_cache_keeps_many_sizes(launcher, tmp_path):
-    """r04: a sender whose message sizes change keeps its slots (up to 64 within 4 GiB, node.cpp
+    """r04: a sender whose message sizes change keeps its slots (up to 64 within 4 GiB, node_slots.cpp
     slot_cache_bytes) instead of the reference's 20, so cycling through 30 sizes (30 slot
     capacities) a second and a third time creates no slot (the 20-entry cache evicted and
     re-created them on every pass: hipFree inside a send), and every delivered payload is still
@@ -670,7 +670,7 @@ def test_slow_receiver_drop_oldest_returns_tokens(launcher, tmp_path):
 
 def test_default_queue_keeps_up_with_async_burst(launcher, tmp_path):
     """A receiver with the reference's default queue_size (10) that keeps up with a back-to-back
-    burst drops nothing: the sender keeps at most 10 samples in flight below 8 MiB (node.cpp
+    burst drops nothing: the sender keeps at most 10 samples in flight below 8 MiB (node_send.cpp
     max_in_flight), and inputs whose fill is still running are not yet queued for the drop
     policy (the reference fills before the message leaves the sender).  Every 50th input is
     checksummed against its source."""
@@ -1383,7 +1383,7 @@ def test_full_size_samples_byte_identical_to_the_oracle(launcher, mode):
 def test_events_consumed_on_another_thread_bit_exact(event_thread):
     """The node is made on this thread; its events are taken, mapped and checksummed on a
     worker thread that never selected a HIP device — as a Rust EventStream moved to another
-    thread, or the facade's async pump (node.cpp DeviceScope: every entry point makes the node's
+    thread, or the facade's async pump (node_internal.h DeviceScope: every entry point makes the node's
     GPU current for the call).  With `event_thread` the node also drains on its event-stream
     thread.  One GPU cannot tell devices apart; this keeps the hand-over itself exact."""
     import ctypes

@@ -80,7 +80,7 @@ def test_host_small_payloads_go_inline_bit_exact(launcher):
             del ev
         paths1 = tx.fill_paths()
         # nothing was packed: the 4096-B message went into its slot by CPU stores through the
-        # BAR (node.cpp host_bar_fill), the rest inline
+        # BAR (node_send.cpp host_bar_fill), the rest inline
         assert paths1 == paths0, paths1
         assert tx.host_paths()["bar_fills"] - bar0 == 1, tx.host_paths()
         # host pyarrow arrays whose sample is < 4096 B (the reference's own KATs and fixtures)

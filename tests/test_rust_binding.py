@@ -53,6 +53,17 @@ def test_safe_crate_uses_only_declared_symbols():
     assert used and used <= declared, sorted(used - declared)
 
 
+def test_sys_crate_compiles_the_library_sources():
+    """dora-gpu-sys/build.rs builds the library from the same sources as dora_amd/build.py."""
+    from dora_amd.build import LIB_SOURCES
+    rs = open(os.path.join(RUST, "dora-gpu-sys", "build.rs")).read()
+    body = rs[rs.index("const LIB_SOURCES"):]
+    body = body[body.index("=") + 1:body.index("];")]  # past the `&[&str]` of the type
+    got = re.findall(r'"([^"]+)"', body)
+    assert len(got) == len(set(got)), got
+    assert sorted(got) == sorted(LIB_SOURCES), sorted(set(got) ^ set(LIB_SOURCES))
+
+
 def test_device_ipc_wire_order_matches_wire_h():
     """DeviceIpc::encode writes the fields in WBuf::data's order (dora_amd/csrc/wire.h)."""
     wire = open(os.path.join(ROOT, "dora_amd", "csrc", "wire.h")).read()
