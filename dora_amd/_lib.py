@@ -50,6 +50,13 @@ FILL_WRITE_THROUGH = 0  # DORA_FILL_WRITE_THROUGH (include/dora_fill_ticket.h)
 FILL_PLAIN = 1          # DORA_FILL_PLAIN
 
 
+class Tensor(ctypes.Structure):
+    """dora_tensor of include/dora_gpu.h: a strided view, the fields of DLPack's DLTensor."""
+    _fields_ = [("data", c_void_p), ("byte_offset", c_uint64), ("dtype_code", c_uint8),
+                ("dtype_bits", c_uint8), ("dtype_lanes", ctypes.c_uint16), ("ndim", c_int32),
+                ("shape", POINTER(c_int64)), ("strides", POINTER(c_int64))]
+
+
 class FillTicket(ctypes.Structure):
     """dora_fill_ticket of include/dora_fill_ticket.h (32 bytes): what dora_sample_fill_ticket
     issues and a publishing kernel takes by value."""
@@ -89,6 +96,9 @@ _SIGS = {
     "dora_gpu_plan": (c_int, [POINTER(ArrowArray), POINTER(ArrowSchema), c_int32,
                               POINTER(c_void_p)]),
     "dora_gpu_plan_bytes": (c_int, [c_void_p, c_size_t, c_int32, POINTER(c_void_p)]),
+    "dora_gpu_plan_tensor": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
+    "dora_node_send_output_tensor": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
+                                             c_size_t, c_uint32]),
     "dora_gpu_plan_compact": (c_int, [POINTER(ArrowArray), POINTER(ArrowSchema), c_int32,
                                       POINTER(c_void_p)]),
     "dora_node_set_compact": (c_int, [c_void_p, c_int]),

@@ -18,7 +18,7 @@ INCLUDE = os.path.join(ROOT, "include")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = "gfx950"
 
-LIB_SOURCES = ["runtime.cpp", "plan.cpp", "device_array.cpp", "kernels.hip", "shm.cpp", "bcast.cpp", "operator_api.cpp", "stdout_capture.cpp",
+LIB_SOURCES = ["runtime.cpp", "plan.cpp", "tensor_plan.cpp", "device_array.cpp", "kernels.hip", "shm.cpp", "bcast.cpp", "operator_api.cpp", "stdout_capture.cpp",
                "wire.cpp", "trace.cpp", "daemon.cpp", "node.cpp", "node_slots.cpp", "node_send.cpp",
                "node_recv.cpp", "node_measure.cpp", "aql.cpp", "interdaemon.cpp", "bincode.cpp"]
 AQL_KERNELS = "aql_kernels.hip"  # standalone gfx950 code object embedded in the library

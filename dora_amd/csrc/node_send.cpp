@@ -953,6 +953,24 @@ int dora_node_send_output_bytes_ex(dora_node* n, const char* output_id, const vo
   DORA_GUARD_END
 }
 
+int dora_node_send_output_tensor(dora_node* n, const char* output_id, const dora_tensor* tensor,
+                                 ArrowDeviceType device_type, const uint8_t* params,
+                                 size_t params_len, uint32_t flags) {
+  if (!n || !output_id || !tensor) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  dora_plan* plan = nullptr;
+  {
+    dora::SubSpan sp(dora::SP_SEND_PLAN);
+    const int rc = dora::build_tensor_plan(tensor, device_type, &plan);
+    if (rc != DORA_OK) return rc;
+  }
+  // a dense view is one copy segment over the caller's memory, a strided one over the plan's
+  // staging buffer: either way a host source, which the send has read when it returns
+  std::unique_ptr<dora_plan> owner(plan);
+  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
+  DORA_GUARD_END
+}
+
 int dora_node_send_output_bytes(dora_node* n, const char* output_id, const void* data, size_t len,
                                 ArrowDeviceType device_type, const uint8_t* params,
                                 size_t params_len) {

@@ -134,6 +134,8 @@ Layout layout_of(const char* format);
 inline Layout layout_of(const std::string& format) { return layout_of(format.c_str()); }
 int build_plan(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                dora_plan** out, bool validity_in_sample = false);
+// A tensor view in host memory (dora_gpu_plan_tensor, tensor_plan.cpp).
+int build_tensor_plan(const dora_tensor* tensor, ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -147,5 +149,8 @@ struct dora_plan {
   bool read_device = false;  // planning read bytes of the array (last offsets, bitmaps)
   std::vector<dora::Segment> segs;
   dora::TypeInfoNode root;
+  // tensor plans (tensor_plan.cpp): the row-major copy of a strided host view, which the plan's
+  // one segment then reads
+  std::vector<uint8_t> staged;
   uint64_t fill_size() const { return ext_size > size ? ext_size : size; }
 };

@@ -232,6 +232,74 @@ PyObject* py_send_array(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   return PyLong_FromLong(rc);
 }
 
+// The layout of DLPack's DLManagedTensor (dlpack.h, unversioned capsules named "dltensor");
+// restated, not vendored.
+struct DlTensor {
+  void* data;
+  int32_t device_type, device_id;
+  int32_t ndim;
+  uint8_t code, bits;
+  uint16_t lanes;
+  int64_t* shape;
+  int64_t* strides;
+  uint64_t byte_offset;
+};
+struct DlManaged {
+  DlTensor t;
+  void* ctx;
+  void (*deleter)(DlManaged*);
+};
+
+// send_tensor(handle, output_id, capsule, device_type, metadata, flags) -> status: the tensor of
+// a "dltensor" capsule (an object's __dlpack__()) as dora_node_send_output_tensor.  The capsule
+// is consumed as DLPack prescribes: renamed "used_dltensor", its deleter called once the call
+// has returned (a host source has then been read).
+PyObject* py_send_tensor(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  if (nargs != 6) {
+    PyErr_SetString(PyExc_TypeError,
+                    "send_tensor(handle, output_id, capsule, device_type, metadata, flags)");
+    return nullptr;
+  }
+  void* h = nullptr;
+  if (!as_ptr(args[0], &h)) return nullptr;
+  const char* oid = as_cstr(args[1]);
+  if (!oid) return nullptr;
+  if (!PyCapsule_IsValid(args[2], "dltensor")) {
+    PyErr_SetString(PyExc_TypeError, "expected a DLPack capsule named \"dltensor\" (an unused, "
+                                     "unversioned one)");
+    return nullptr;
+  }
+  const long dev = PyLong_AsLong(args[3]);
+  if (dev == -1 && PyErr_Occurred()) return nullptr;
+  const unsigned long flags = PyLong_AsUnsignedLong(args[5]);
+  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
+  std::string& params = t_params;
+  if (!encode(args[4], params)) return nullptr;
+  auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(args[2], "dltensor"));
+  if (!m || PyCapsule_SetName(args[2], "used_dltensor") != 0) return nullptr;
+  dora_tensor t{};
+  t.data = m->t.data;
+  t.byte_offset = m->t.byte_offset;
+  t.dtype_code = m->t.code;
+  t.dtype_bits = m->t.bits;
+  t.dtype_lanes = m->t.lanes;
+  t.ndim = m->t.ndim;
+  t.shape = m->t.shape;
+  t.strides = m->t.strides;
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor(static_cast<dora_node*>(h), oid, &t,
+                                    static_cast<ArrowDeviceType>(dev),
+                                    reinterpret_cast<const uint8_t*>(params.data()), params.size(),
+                                    static_cast<uint32_t>(flags));
+  Py_END_ALLOW_THREADS
+  // the deleter may run Python code (numpy's, torch's drop a reference): under the GIL, and
+  // after the status has been taken (it must not disturb the thread's error message either:
+  // the caller reads dora_gpu_last_error only when rc != 0, and deleters do not call the library)
+  if (m->deleter) m->deleter(m);
+  return PyLong_FromLong(rc);
+}
+
 // MetadataParameters bytes -> dict (the inverse of encode; dora_amd.node.decode_parameters).
 PyObject* decode(const uint8_t* p, size_t n) {
   PyObject* out = PyDict_New();
@@ -685,6 +753,8 @@ PyMethodDef methods[] = {
      METH_FASTCALL, "dora_node_send_output_bytes with parameters encoded from a dict."},
     {"send_buffer", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_buffer)),
      METH_FASTCALL, "dora_node_send_output_bytes of host bytes read in place (buffer protocol)."},
+    {"send_tensor", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor)),
+     METH_FASTCALL, "dora_node_send_output_tensor of a DLPack capsule, which it consumes."},
     {"send_array", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_array)),
      METH_FASTCALL, "dora_node_send_output with parameters encoded from a dict."},
     {nullptr, nullptr, 0, nullptr}};

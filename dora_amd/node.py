@@ -9,6 +9,7 @@
     node.send_output("out", pa.array([...]), {"k": 1})   # host pyarrow: inline < 4096 B, else DMA
     node.send_output("out", device_array)                 # HBM array -> HIP pack kernel
     node.send_output("out", b"raw bytes")                 # ArrowTypeInfo::byte_array
+    node.send_output("out", frame.transpose(2, 0, 1))     # a host tensor view (dora_amd.tensor)
 """
 from __future__ import annotations
 
@@ -21,10 +22,14 @@ from ctypes import byref, c_double, c_size_t, c_uint8, c_uint64, c_void_p
 from typing import Optional
 
 from . import _lib
-from ._lib import ARROW_DEVICE_CPU, ARROW_DEVICE_ROCM, DoraGpuError, call, load
+from ._lib import (ARROW_DEVICE_CPU, ARROW_DEVICE_ROCM, ARROW_DEVICE_ROCM_HOST, DoraGpuError,
+                   call, load)
 from .arrow_c import ArrowArray, ArrowSchema, CArray
 
 SEND_ASYNC = 1  # DORA_SEND_ASYNC (include/dora_gpu.h)
+_DL_ROCM = 10          # DLPack device types: kDLROCM
+_DL_CPU = 1
+_DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinned)
 from .device import DeviceArray, DeviceBuffer
 from .type_info import decode
 
@@ -192,10 +197,43 @@ class Node:
             with CArray.from_pyarrow(data) as c:
                 rc = _fast.send_array(self.handle, output_id, ctypes.addressof(c.array),
                                       ctypes.addressof(c.schema), ARROW_DEVICE_CPU, metadata)
+        elif hasattr(data, "__dlpack__") and hasattr(data, "__dlpack_device__"):
+            rc = self._send_tensor(output_id, data, metadata, f)
         else:
-            raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray or a DeviceBuffer")
+            raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer or "
+                            "a host tensor with __dlpack__ (numpy, torch)")
         if rc:
             _lib.check(rc)
+
+    def _send_tensor(self, output_id: str, data, metadata, flags: int) -> int:
+        """A DLPack producer (numpy.ndarray, a CPU or pinned torch.Tensor), strided views
+        included, as the nested FixedSizeList array of its shape (dora_node_send_output_tensor;
+        dora_amd.tensor).  The tensor has been read on return: pinned memory, which the GPU reads
+        asynchronously to the host, is declared as such and copied inside the call."""
+        dev_type = int(data.__dlpack_device__()[0])
+        if dev_type == _DL_ROCM:
+            raise TypeError("sending a tensor in device memory is not implemented: send a "
+                            "contiguous one with send_output_device_bytes(output_id, "
+                            "t.data_ptr(), nbytes)")
+        if dev_type not in _DL_HOST:
+            raise TypeError(f"tensors of DLPack device type {dev_type} cannot be sent")
+        dev = ARROW_DEVICE_CPU if dev_type == _DL_CPU else ARROW_DEVICE_ROCM_HOST
+        try:
+            cap = data.__dlpack__()
+        except BufferError:
+            # numpy refuses to export a read-only array (np.broadcast_to, an array over a received
+            # pyarrow buffer) as an unversioned capsule, which cannot say "read-only"; the send
+            # only reads, so its array interface serves
+            if not hasattr(data, "__array_interface__"):
+                raise
+            from .tensor import _describe_array
+            t, keep = _describe_array(data)
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor(self.handle, output_id.encode(), byref(t),
+                                                        dev, params, len(params), flags)
+            del keep
+            return rc
+        return _fast.send_tensor(self.handle, output_id, cap, dev, metadata, flags)
 
     def send_output_async(self, output_id: str, data, metadata: Optional[dict] = None):
         """send_output(..., asynchronous=True)."""

@@ -1,0 +1,94 @@
+"""Tensors as messages.
+
+A tensor of shape `(d0, d1, .., dk)` and dtype `T` travels as the Arrow array of length `d0` and
+type `FixedSizeList<..FixedSizeList<T>[dk]..>[d1]` built from its row-major values (child fields
+named `item`, nullable, as pyarrow creates them); a 1-D tensor is the plain primitive array.  Its
+sample is one buffer, the row-major bytes, so the shape travels in the type and a node of the
+reference can send or receive the same message.
+
+    node.send_output("image", frame.transpose(2, 0, 1))   # numpy or CPU torch: any host DLPack tensor
+    chw = tensor.to_numpy(event["value"])                  # host receiver: the nested pyarrow array
+    chw = tensor.to_numpy(event["value"].to_pyarrow())     # device receiver: downloaded first
+
+A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
+is copied once, so every source has been read when `send_output` returns.
+"""
+from __future__ import annotations
+
+from ctypes import c_int64
+
+from ._lib import Tensor
+
+_DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
+
+
+def tensor_type(dtype, shape):
+    """The pyarrow type of a tensor message of numpy `dtype` and `shape`."""
+    import numpy as np
+    import pyarrow as pa
+    t = pa.from_numpy_dtype(np.dtype(dtype))
+    for d in reversed(tuple(shape)[1:]):
+        t = pa.list_(t, int(d))
+    return t
+
+
+def from_numpy(x):
+    """The nested pyarrow array of a numpy array (copied to row-major order if it is a view)."""
+    import numpy as np
+    import pyarrow as pa
+    x = np.asarray(x)
+    if x.ndim < 1:
+        raise ValueError("a tensor message has at least one dimension")
+    arr = pa.array(np.ascontiguousarray(x).reshape(-1))
+    for d in reversed(x.shape[1:]):
+        arr = pa.FixedSizeListArray.from_arrays(arr, int(d))
+    return arr
+
+
+def to_numpy(arr):
+    """The numpy array of a nested pyarrow array (a host receiver's `event["value"]`): shape
+    `(len, s1, .., sk)`.  Nulls at any level are refused."""
+    import pyarrow as pa
+    shape = [len(arr)]
+    while pa.types.is_fixed_size_list(arr.type):
+        if arr.null_count:
+            raise TypeError("a tensor message has no nulls")
+        shape.append(arr.type.list_size)
+        arr = arr.flatten()  # the values of this array's own slice
+    if arr.null_count:
+        raise TypeError("a tensor message has no nulls")
+    return arr.to_numpy(zero_copy_only=False).reshape(shape)
+
+
+def _describe(ptr: int, shape, strides, dtype, byte_offset: int = 0) -> tuple:
+    """A `dora_tensor` over `ptr` (strides in elements, or None for row-major) and the ctypes
+    arrays it points at, which the caller keeps alive with it."""
+    import numpy as np
+    dt = np.dtype(dtype)
+    t = Tensor()
+    t.data = ptr
+    t.byte_offset = byte_offset
+    t.dtype_code = _DL_CODES.get(dt.kind, 255)
+    t.dtype_bits = dt.itemsize * 8
+    t.dtype_lanes = 1
+    t.ndim = len(shape)
+    sh = (c_int64 * max(len(shape), 1))(*shape)
+    t.shape = sh
+    st = None
+    if strides is not None:
+        st = (c_int64 * max(len(strides), 1))(*strides)
+        t.strides = st
+    return t, (sh, st)
+
+
+def _describe_array(x) -> tuple:
+    """`_describe` of an object with `__array_interface__` (a numpy array, read-only ones
+    included, which numpy's own `__dlpack__` refuses to export)."""
+    import numpy as np
+    x = np.asarray(x)
+    strides = [s // x.dtype.itemsize for s in x.strides]
+    t, keep = _describe(x.__array_interface__["data"][0], x.shape, strides, x.dtype)
+    return t, (x, keep)
+
+
+__all__ = ["tensor_type", "from_numpy", "to_numpy"]

@@ -167,6 +167,52 @@ int dora_gpu_plan_compact(const struct ArrowArray* array, const struct ArrowSche
  * what `send_output_raw`'s copy closure writes (node/mod.rs:180-196). */
 int dora_gpu_plan_bytes(const void* src, size_t len, ArrowDeviceType device_type,
                         dora_plan** out);
+/*
+ * Tensors (new; no reference counterpart).  A strided n-dimensional view,
+ * described by the fields of DLPack's DLTensor (nothing is vendored): element `i0, .., ik` lives
+ * at `data + byte_offset + (i0 * strides[0] + .. + ik * strides[k]) * (dtype_bits / 8)`.
+ * On the wire a tensor of shape (d0, d1, .., dk) and dtype T is the Arrow array of length d0 of
+ * type FixedSizeList<..FixedSizeList<T>[dk]..>[d1] (child fields named `item`, nullable, as
+ * pyarrow creates them; a 1-D tensor is the plain primitive array), whose sample is one buffer:
+ * the row-major values.  The shape travels in the type, so a reference node can send or receive
+ * the same message.
+ *
+ * dora_gpu_plan_tensor canonicalises the view (extents of 1 dropped, neighbours merged when
+ * strides[i] == shape[i+1] * strides[i+1], an innermost unit stride folded into a row of bytes).
+ * `device_type` says where the view lives, as in dora_gpu_plan:
+ *   ARROW_DEVICE_CPU        a view that is dense after canonicalisation plans exactly as
+ *                           dora_gpu_plan_bytes over `data + offset`, with the nested type info;
+ *                           any other view is gathered by the CPU, inside this call, into a
+ *                           row-major staging buffer the plan owns, and planned as a dense copy
+ *                           of that buffer (what the caller's own copy to contiguous memory
+ *                           would have done);
+ *   ARROW_DEVICE_ROCM_HOST  pinned host memory: always copied into the staging buffer, dense or
+ *                           not (a DMA or kernel reading pinned memory runs asynchronously to
+ *                           the host; the copy keeps "read on return" true);
+ *   ARROW_DEVICE_ROCM       HBM: not implemented in this version, DORA_ERR_UNSUPPORTED.
+ *
+ * Accepted dtypes: int and uint of 8/16/32/64 bits, float of 16/32/64 bits, lanes == 1.
+ * DORA_ERR_UNSUPPORTED, with a message naming the dtype: bool (Arrow's is a bitmap), bfloat16 and
+ * complex (Arrow has neither: send a view as uint16 or as pairs of floats), lanes != 1, and a
+ * view of more than 8 dimensions after merging.  DORA_ERR_INVALID: ndim < 1, a negative extent,
+ * an extent of 0 in any dimension but the first, a byte count that overflows 64 bits, a NULL
+ * `data` with a non-zero element count.  d0 == 0 plans an empty message.
+ * A dense ARROW_DEVICE_CPU view is borrowed until the pack completes; any other has been read
+ * on return.  Shape and strides are trusted, as a DLPack producer's are: beyond the checks
+ * above, the bytes a view reaches are not bounded against any allocation, and strides whose
+ * products with the extents do not fit 64 bits are the caller's error.
+ */
+typedef struct dora_tensor {
+  const void* data;
+  uint64_t byte_offset;
+  uint8_t dtype_code; /* DLPack: 0 int, 1 uint, 2 float, 4 bfloat, 5 complex, 6 bool */
+  uint8_t dtype_bits;
+  uint16_t dtype_lanes;
+  int32_t ndim;
+  const int64_t* shape;
+  const int64_t* strides; /* in elements, signed, 0 allowed; NULL = row-major */
+} dora_tensor;
+int dora_gpu_plan_tensor(const dora_tensor* tensor, ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -341,6 +387,16 @@ int dora_node_send_output_ex(dora_node* node, const char* output_id, const struc
 int dora_node_send_output_bytes_ex(dora_node* node, const char* output_id, const void* data,
                                    size_t len, ArrowDeviceType device_type, const uint8_t* params,
                                    size_t params_len, uint32_t flags);
+/* Send a tensor view (dora_gpu_plan_tensor: its wire type, `device_type`, accepted dtypes and
+ * refusals).  A host or pinned source takes the paths of any host source: inline below 4096 B,
+ * shared memory on a node without a GPU or for receivers that all lack one, else the BAR fill or
+ * the DMA into a device slot; it has been read when the call returns (pageable memory declared
+ * ARROW_DEVICE_CPU: as dora_node_send_output_bytes; memory that is in fact pinned must be
+ * declared ARROW_DEVICE_ROCM_HOST).  `flags`: DORA_SEND_ASYNC as for the _ex sends; it changes
+ * nothing for this version's sources, which are host memory and safe to reuse on return. */
+int dora_node_send_output_tensor(dora_node* node, const char* output_id, const dora_tensor* tensor,
+                                 ArrowDeviceType device_type, const uint8_t* params,
+                                 size_t params_len, uint32_t flags);
 /* Make DORA_SEND_ASYNC the default of every send of this node (also DORA_GPU_SEND_ASYNC=1). */
 int dora_node_set_async_sends(dora_node* node, int enable);
 /* Event-stream thread (the reference's event_stream_loop, apis/rust/node/src/event_stream/

@@ -12,7 +12,7 @@ use std::process::Command;
 
 const ARCH: &str = "gfx950";
 const LIB_SOURCES: &[&str] = &[
-    "runtime.cpp", "plan.cpp", "device_array.cpp", "kernels.hip", "shm.cpp", "bcast.cpp",
+    "runtime.cpp", "plan.cpp", "tensor_plan.cpp", "device_array.cpp", "kernels.hip", "shm.cpp", "bcast.cpp",
     "operator_api.cpp", "stdout_capture.cpp", "wire.cpp", "trace.cpp", "daemon.cpp", "node.cpp",
     "node_slots.cpp", "node_send.cpp", "node_recv.cpp", "node_measure.cpp", "aql.cpp",
     "interdaemon.cpp", "bincode.cpp",

@@ -18,7 +18,9 @@ OPAQUE = {"dora_plan", "dora_node", "dora_sample", "dora_event", "dora_daemon"}
 # structs passed by pointer that the caller allocates: declared here as opaque #[repr(C)] blocks
 # of the size their header states (dora_fill_ticket.h: DORA_FILL_TICKET_SIZE)
 SIZED = {"dora_fill_ticket"}
-SCALAR = {"int": "c_int", "int64_t": "i64", "uint64_t": "u64", "uint32_t": "u32",
+# plain structs the caller fills in, declared field by field from the header (struct_decl)
+STRUCTS = {"dora_tensor"}
+SCALAR = {"uint16_t": "u16", "int": "c_int", "int64_t": "i64", "uint64_t": "u64", "uint32_t": "u32",
           "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64",
           "uint8_t": "u8", "char": "c_char", "void": "c_void", "ArrowDeviceType": "ArrowDeviceType",
           "dora_stream_t": "dora_stream_t", "dora_event_t": "dora_event_t",
@@ -42,7 +44,7 @@ def rust_type(c):
     consts = [i for i, w in enumerate(c.replace("*", " * ").split()) if w == "const"]
     words = [w for w in base if w != "const"]
     name = " ".join(words)
-    if name in OPAQUE or name in SIZED:
+    if name in OPAQUE or name in SIZED or name in STRUCTS:
         t = name
     elif name in SCALAR:
         t = SCALAR[name]
@@ -98,12 +100,33 @@ def ticket_decl():
     return out
 
 
+def struct_decl(name, text):
+    """A plain struct of the header as a #[repr(C)] Rust struct with the same fields in the same
+    order, each type mapped as a parameter's would be (tests/test_rust_binding.py holds ffi.rs to
+    this generator's output, so a header edit that is not regenerated fails there)."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), text, flags=re.S)
+    if not m:
+        raise SystemExit(f"struct {name} not found in the header")
+    out = [f"/// `{name}` (include/dora_gpu.h), field for field.",
+           "#[repr(C)]", "#[derive(Clone, Copy)]", f"pub struct {name} {{"]
+    for decl in m.group(1).split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        fm = re.match(r"(.*?)(\b\w+)$", decl)
+        out.append(f"    pub {fm.group(2)}: {rust_type(fm.group(1))},")
+    out.append("}")
+    return out
+
+
 def main():
     lines = ["// Generated by integration/rust/gen_ffi.py from include/dora_gpu.h -- do not edit.",
              "// tests/test_rust_binding.py checks that every function of the header is declared",
              "// here with the same parameter count.",
              "use crate::*;", "use std::os::raw::{c_char, c_int, c_void};", "",
              *ticket_decl(), "",
+             *[ln for n in sorted(STRUCTS) for ln in struct_decl(n, open(HEADER).read())], "",
              'extern "C" {']
     for ret, name, args in prototypes(open(HEADER).read()):
         ps = ", ".join(f"{n}: {t}" for n, t in param_list(args))
