@@ -221,6 +221,11 @@ _TEST_SIGS = {
     "dora_gpu_test_bar_alloc": (c_int, [c_int, c_size_t, POINTER(c_void_p)]),
     "dora_gpu_test_bar_write": (c_int, [c_int, c_void_p, c_void_p, c_size_t]),
     "dora_gpu_test_bar_free": (None, [c_void_p]),
+    "dora_gpu_test_gather_kernel": (c_int, [c_int]),
+    "dora_gpu_test_plan_gather": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
+                                          POINTER(c_int), POINTER(c_uint64), POINTER(c_uint32),
+                                          POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
+                                          POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
     "dora_gpu_test_aql_hold": (c_int, [c_int, c_int]),
     "dora_gpu_test_reduce_timeout": (c_int, [c_uint64]),
     "dora_gpu_test_d2h_copy_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_uint64, c_void_p]),

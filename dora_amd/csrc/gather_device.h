@@ -1,0 +1,378 @@
+// Device code of the strided gather (a device tensor view that is not dense, tensor_plan.cpp):
+// the row-major bytes of the view written into a sample, read once and written once.
+//
+// Everything that computes an address — output unit -> (row, byte in row), the odometer -> source
+// offset, which load reaches which bytes, which store writes which — is plain C++ in functions that
+// compile for host and device alike, and all memory goes through a policy object `M`.  The kernel
+// (kernels.hip) passes a policy of real loads and stores; the host emulation of
+// tests/test_gather_index_host.py passes one that runs the same functions lane by lane over the
+// whole grid with every offset checked.  Nothing here uses an intrinsic.
+//
+// Addressing is 64-bit throughout.  The output is cut into 16-byte units on absolute 16-byte
+// boundaries of the destination; the up to 15 bytes before the first and after the last whole
+// unit are written one by one, so nothing is ever written at or past dst + total.
+#pragma once
+
+#include <cstdint>
+
+#include "plan.h"
+
+#if defined(__HIPCC__)
+#define DORA_HD __host__ __device__ inline
+#else
+#define DORA_HD inline
+#endif
+
+namespace dora {
+namespace gather {
+
+constexpr int kDims = kMaxTensorDims;
+constexpr int kThreads = 256;
+// Workgroups at most: 32 per CU of an MI355X, every lane then walks its units a grid apart.
+constexpr uint64_t kMaxGrid = 8192;
+
+struct U16 {
+  uint32_t w[4];
+};
+
+// Kernel arguments (by value).  The view's dimensions are right-aligned in shape[] / stride[]
+// and padded on the left with extent 1, so every walk is over kDims dimensions.
+struct Args {
+  const uint8_t* src;  // element (0, .., 0)
+  uint8_t* dst;
+  uint64_t total;   // output bytes
+  uint64_t row;     // contiguous source bytes per row (a multiple of `piece`)
+  uint64_t head;    // output bytes before the first whole unit (< 16, <= total)
+  uint64_t nunits;  // whole units: output bytes [head + 16 u, +16), u < nunits
+  int64_t lo, hi;   // closed interval of offsets from `src` that may be read
+  uint32_t piece;   // bytes per load where a unit is put together from several rows: the element
+                    // size when units start on an element, else 1
+  uint32_t pad;
+  int64_t shape[kDims];
+  int64_t stride[kDims];
+};
+
+// Arguments of the gather of `g` into `dst`.
+DORA_HD Args make_args(const GatherDesc& g, uint8_t* dst) {
+  Args a{};
+  a.src = g.view.src;
+  a.dst = dst;
+  a.total = g.view.total;
+  a.row = g.view.row;
+  const uint64_t mis = (16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15;
+  a.head = mis < a.total ? mis : a.total;
+  a.nunits = (a.total - a.head) / 16;
+  a.lo = g.lo;
+  a.hi = g.hi;
+  a.piece = (g.elem && a.head % g.elem == 0 && a.row % g.elem == 0) ? g.elem : 1;
+  a.pad = 0;
+  for (int k = 0; k < kDims; ++k) {
+    const int i = k - (kDims - g.view.nd);
+    a.shape[k] = i >= 0 ? g.view.shape[i] : 1;
+    a.stride[k] = i >= 0 ? g.view.stride[i] : 0;
+  }
+  return a;
+}
+
+DORA_HD uint64_t grid_for(const Args& a) {
+  const uint64_t g = (a.nunits + kThreads - 1) / kThreads;
+  return g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g;
+}
+
+// A row of the view: its index in every dimension and the offset of its first byte from `src`.
+struct RowPos {
+  int64_t off;
+  int64_t idx[kDims];
+};
+
+// Row `r` (row-major over shape[]) -> RowPos.  Every partial sum of idx * stride lies inside
+// [lo, hi], which the plan computed without overflow.
+DORA_HD void row_pos(const Args& a, uint64_t r, RowPos& p) {
+  p.off = 0;
+#pragma unroll
+  for (int k = kDims - 1; k >= 0; --k) {
+    const uint64_t n = static_cast<uint64_t>(a.shape[k]);
+    uint64_t i = 0;
+    if (n != 1) {
+      if ((r | n) >> 32) {
+        i = r % n;
+        r = r / n;
+      } else {  // the common case: a 32-bit division
+        const uint32_t r32 = static_cast<uint32_t>(r), n32 = static_cast<uint32_t>(n);
+        i = r32 % n32;
+        r = r32 / n32;
+      }
+    }
+    p.idx[k] = static_cast<int64_t>(i);
+    p.off += static_cast<int64_t>(i) * a.stride[k];
+  }
+}
+
+// The odometer: RowPos of the next row (the row after the last one is row 0).
+DORA_HD void next_row(const Args& a, RowPos& p) {
+  bool carry = true;
+#pragma unroll
+  for (int k = kDims - 1; k >= 0; --k) {
+    if (!carry) continue;
+    if (p.idx[k] + 1 < a.shape[k]) {
+      ++p.idx[k];
+      p.off += a.stride[k];
+      carry = false;
+    } else {
+      p.off -= p.idx[k] * a.stride[k];
+      p.idx[k] = 0;
+    }
+  }
+}
+
+// Output byte `o` -> its row and byte in the row.
+DORA_HD void out_pos(const Args& a, uint64_t o, uint64_t* r, uint64_t* b) {
+  if ((o | a.row) >> 32) {
+    *r = o / a.row;
+  } else {
+    *r = static_cast<uint32_t>(o) / static_cast<uint32_t>(a.row);
+  }
+  *b = o - *r * a.row;
+}
+
+// 16 output bytes put together from loads of G bytes (G divides the row and the unit's offset in
+// its row, so no load straddles two rows), walking the odometer as rows end.
+template <int G, class M>
+DORA_HD U16 gather_pieces(const Args& a, RowPos& p, uint64_t b, M& m) {
+  U16 v = {{0, 0, 0, 0}};
+#pragma unroll
+  for (int j = 0; j < 16 / G; ++j) {
+    const uint64_t x = m.template load_piece<G>(p.off + static_cast<int64_t>(b));
+    constexpr int kPerWord = G >= 4 ? 1 : 4 / G;
+    if constexpr (G == 8) {
+      v.w[2 * j] = static_cast<uint32_t>(x);
+      v.w[2 * j + 1] = static_cast<uint32_t>(x >> 32);
+    } else {
+      v.w[j / kPerWord] |= static_cast<uint32_t>(x) << (8 * G * (j % kPerWord));
+    }
+    b += G;
+    if (b >= a.row) {
+      b = 0;
+      next_row(a, p);
+    }
+  }
+  return v;
+}
+
+// Whole unit `u` of the output.  A unit inside one row is one 16-byte load when the source
+// address is a whole number of dwords, else two aligned 16-byte loads funnel-shifted — where
+// both lie inside [lo, hi]; every other unit is put together piece by piece.
+template <class M>
+DORA_HD void gather_unit(const Args& a, uint64_t u, M& m) {
+  const uint64_t o = a.head + 16 * u;
+  uint64_t r, b;
+  out_pos(a, o, &r, &b);
+  RowPos p;
+  row_pos(a, r, p);
+  if (b + 16 <= a.row) {
+    const int64_t s = p.off + static_cast<int64_t>(b);
+    const uint32_t mis = static_cast<uint32_t>(
+        (reinterpret_cast<uintptr_t>(a.src) + static_cast<uint64_t>(s)) & 15);
+    if ((mis & 3) == 0) {
+      m.store16(o, m.load16(s));
+      return;
+    }
+    // (hi - 31 cannot overflow: hi >= row - 1 >= 15 here)
+    if (s - a.lo >= static_cast<int64_t>(mis) && s - static_cast<int64_t>(mis) <= a.hi - 31) {
+      const int64_t w = s - static_cast<int64_t>(mis);
+      m.store16(o, m.funnel(m.load16(w), m.load16(w + 16), mis));
+      return;
+    }
+  }
+  U16 v;
+  switch (a.piece) {
+    case 8: v = gather_pieces<8>(a, p, b, m); break;
+    case 4: v = gather_pieces<4>(a, p, b, m); break;
+    case 2: v = gather_pieces<2>(a, p, b, m); break;
+    default: v = gather_pieces<1>(a, p, b, m); break;
+  }
+  m.store16(o, v);
+}
+
+// Output byte `o` on its own (the bytes before the first and after the last whole unit).
+template <class M>
+DORA_HD void gather_byte(const Args& a, uint64_t o, M& m) {
+  uint64_t r, b;
+  out_pos(a, o, &r, &b);
+  RowPos p;
+  row_pos(a, r, p);
+  m.store1(o, static_cast<uint8_t>(m.template load_piece<1>(p.off + static_cast<int64_t>(b))));
+}
+
+// Everything lane `lane` of `lanes` does: lanes 0..15 a head byte each, lanes 16..31 a tail
+// byte each, and every lane the whole units lane, lane + lanes, ..
+template <class M>
+DORA_HD void gather_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+  if (lane < 16) {
+    if (lane < a.head) gather_byte(a, lane, m);
+  } else if (lane < 32) {
+    const uint64_t t0 = a.head + 16 * a.nunits;  // <= total
+    if (lane - 16 < a.total - t0) gather_byte(a, t0 + (lane - 16), m);
+  }
+  for (uint64_t u = lane; u < a.nunits; u += lanes) gather_unit(a, u, m);
+}
+
+
+// ------------------------------------------------------------------------------------------
+// The tiled transpose (gather_tile_kernel): for a view whose source-contiguous dimension `c`
+// (byte stride == element size) is not the output's innermost one `j` (the last canonical
+// dimension; row == elem).  One workgroup moves a kT x kT tile of the (c, j) plane through LDS:
+// it loads along c (coalesced in the source), stores along j (coalesced in the output); the other
+// dimensions are an outer odometer over tiles.  Every address — tile -> origin, (thread, step)
+// -> source offset / LDS index / output element, and the partial-tile predicates — is computed
+// here, in host/device code the emulation runs thread by thread, phase by phase.
+// ------------------------------------------------------------------------------------------
+namespace tile {
+
+constexpr int kT = 32;           // tile edge in elements
+constexpr int kPitch = kT + 1;   // LDS row pitch in elements: a column read hits kT different banks
+constexpr int kLds = kT * kPitch;
+constexpr int kSteps = kT * kT / kThreads;  // elements per thread and phase
+constexpr uint64_t kMaxGrid = 1u << 20;
+
+struct Args {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t total;
+  int64_t lo, hi;
+  uint32_t elem;
+  uint32_t c;               // the source-contiguous dimension (right-aligned index; j = kDims - 1)
+  uint64_t ntc, ntj, ntiles;  // tiles along c, along j, in all
+  int64_t shape[kDims];
+  int64_t stride[kDims];    // bytes
+  uint64_t ostride[kDims];  // elements of the row-major output per step of each dimension
+};
+
+// The source-contiguous dimension of `g` the tile kernel would transpose against (index into
+// g.view), or -1 when the kernel does not apply: the innermost dimension is itself contiguous,
+// or source, strides or destination are not element-aligned.
+DORA_HD int contiguous_dim(const GatherDesc& g, const uint8_t* dst) {
+  const uint64_t e = g.elem;
+  if (g.view.nd < 2 || g.view.row != e || (e != 1 && e != 2 && e != 4 && e != 8)) return -1;
+  if ((reinterpret_cast<uintptr_t>(g.view.src) | reinterpret_cast<uintptr_t>(dst)) & (e - 1)) return -1;
+  int c = -1;
+  for (int k = 0; k < g.view.nd; ++k) {
+    if (g.view.stride[k] & static_cast<int64_t>(e - 1)) return -1;
+    if (k < g.view.nd - 1 && g.view.stride[k] == static_cast<int64_t>(e)) c = k;
+  }
+  return c;
+}
+
+DORA_HD Args make_args(const GatherDesc& g, uint8_t* dst, int c) {
+  Args a{};
+  a.src = g.view.src;
+  a.dst = dst;
+  a.total = g.view.total;
+  a.lo = g.lo;
+  a.hi = g.hi;
+  a.elem = g.elem;
+  const int shift = kDims - g.view.nd;
+  a.c = static_cast<uint32_t>(c + shift);
+  for (int k = 0; k < kDims; ++k) {
+    const int i = k - shift;
+    a.shape[k] = i >= 0 ? g.view.shape[i] : 1;
+    a.stride[k] = i >= 0 ? g.view.stride[i] : 0;
+  }
+  a.ostride[kDims - 1] = 1;
+  for (int k = kDims - 2; k >= 0; --k)
+    a.ostride[k] = a.ostride[k + 1] * static_cast<uint64_t>(a.shape[k + 1]);
+  a.ntc = (static_cast<uint64_t>(a.shape[a.c]) + kT - 1) / kT;
+  a.ntj = (static_cast<uint64_t>(a.shape[kDims - 1]) + kT - 1) / kT;
+  uint64_t outer = 1;
+  for (int k = 0; k < kDims - 1; ++k)
+    if (static_cast<uint32_t>(k) != a.c) outer *= static_cast<uint64_t>(a.shape[k]);
+  a.ntiles = outer * a.ntc * a.ntj;  // <= the element count, which fits 64 bits
+  return a;
+}
+
+DORA_HD uint64_t grid_for(const Args& a) { return a.ntiles < kMaxGrid ? a.ntiles : kMaxGrid; }
+
+// Where tile `t` starts: first element along c and j, and the outer dimensions' share of the
+// source offset (bytes) and of the output position (elements).
+struct Origin {
+  int64_t src_off;
+  uint64_t out_elem;
+  uint64_t c0, j0;
+};
+
+DORA_HD Origin origin(const Args& a, uint64_t t) {
+  Origin o;
+  o.j0 = (t % a.ntj) * kT;
+  t /= a.ntj;
+  o.c0 = (t % a.ntc) * kT;
+  t /= a.ntc;
+  o.src_off = 0;
+  o.out_elem = 0;
+#pragma unroll
+  for (int k = kDims - 2; k >= 0; --k) {
+    if (static_cast<uint32_t>(k) == a.c) continue;
+    const uint64_t n = static_cast<uint64_t>(a.shape[k]);
+    if (n == 1) continue;
+    const uint64_t i = t % n;
+    t /= n;
+    o.src_off += static_cast<int64_t>(i) * a.stride[k];
+    o.out_elem += i * a.ostride[k];
+  }
+  return o;
+}
+
+// One element a thread moves in one step of a phase; `on` false outside a partial tile.
+struct Slot {
+  bool on;
+  int64_t src_off;    // load phase: bytes from src
+  uint32_t lds;       // element index into the tile
+  uint64_t out_elem;  // store phase: element of the output
+};
+
+// Load phase: consecutive threads walk c (contiguous in the source); tile[lj][lc].
+DORA_HD Slot load_slot(const Args& a, const Origin& o, uint32_t thread, int step) {
+  const uint32_t lc = thread % kT, lj = thread / kT + static_cast<uint32_t>(step) * (kThreads / kT);
+  Slot s{};
+  s.on = o.c0 + lc < static_cast<uint64_t>(a.shape[a.c]) &&
+         o.j0 + lj < static_cast<uint64_t>(a.shape[kDims - 1]);
+  if (!s.on) return s;
+  s.src_off = o.src_off + static_cast<int64_t>(o.c0 + lc) * a.stride[a.c] +
+              static_cast<int64_t>(o.j0 + lj) * a.stride[kDims - 1];
+  s.lds = lj * kPitch + lc;
+  return s;
+}
+
+// Store phase: consecutive threads walk j (contiguous in the output); reads tile[oj][oc].
+DORA_HD Slot store_slot(const Args& a, const Origin& o, uint32_t thread, int step) {
+  const uint32_t oj = thread % kT, oc = thread / kT + static_cast<uint32_t>(step) * (kThreads / kT);
+  Slot s{};
+  s.on = o.c0 + oc < static_cast<uint64_t>(a.shape[a.c]) &&
+         o.j0 + oj < static_cast<uint64_t>(a.shape[kDims - 1]);
+  if (!s.on) return s;
+  s.lds = oj * kPitch + oc;
+  s.out_elem = o.out_elem + (o.c0 + oc) * a.ostride[a.c] + (o.j0 + oj);
+  return s;
+}
+
+template <class M>
+DORA_HD void load_phase(const Args& a, const Origin& o, uint32_t thread, M& m) {
+#pragma unroll
+  for (int step = 0; step < kSteps; ++step) {
+    const Slot s = load_slot(a, o, thread, step);
+    if (s.on) m.lds_write(s.lds, m.load_elem(s.src_off));
+  }
+}
+
+template <class M>
+DORA_HD void store_phase(const Args& a, const Origin& o, uint32_t thread, M& m) {
+#pragma unroll
+  for (int step = 0; step < kSteps; ++step) {
+    const Slot s = store_slot(a, o, thread, step);
+    if (s.on) m.store_elem(s.out_elem, m.lds_read(s.lds));
+  }
+}
+
+}  // namespace tile
+
+}  // namespace gather
+}  // namespace dora

@@ -16,6 +16,7 @@
 
 #include "aql.h"
 #include "common.h"
+#include "gather_device.h"
 #include "pack_device.h"
 #include "plan.h"
 #include "splitmix_device.h"
@@ -248,6 +249,89 @@ __global__ __launch_bounds__(64) void l1_stale_kernel(const uint32_t* src, uint3
   second[b * 64 + t] = probe_load<MODE>(src + t);
 }
 
+// ------------------------------------------------------------------------------------------
+// gather_rows_kernel: a strided device tensor view into row-major order (gather_device.h holds
+// every address computation; this is its memory policy).  Rows are read with the pack's 16-byte
+// non-temporal loads, elements of rows shorter than a unit with plain cached loads (a transposed
+// source line is touched by many units), the sample is written with the pack's write-through
+// stores.
+// ------------------------------------------------------------------------------------------
+struct GatherMem {
+  const uint8_t* src;
+  uint8_t* dst;
+  typedef uint16_t u16_u __attribute__((aligned(1)));
+  typedef uint32_t u32_u __attribute__((aligned(1)));
+  typedef uint64_t u64_u __attribute__((aligned(1)));
+
+  __device__ __forceinline__ gather::U16 load16(int64_t s) const {  // src + s: whole dwords
+    const u32x4 v = ld16<1, true>(src + s);
+    return {{v.x, v.y, v.z, v.w}};
+  }
+  template <int G>
+  __device__ __forceinline__ uint64_t load_piece(int64_t s) const {
+    const uint8_t* p = src + s;
+    if constexpr (G == 8) return *reinterpret_cast<const u64_u*>(p);
+    if constexpr (G == 4) return *reinterpret_cast<const u32_u*>(p);
+    if constexpr (G == 2) return *reinterpret_cast<const u16_u*>(p);
+    return *p;
+  }
+  // bytes [mis, mis + 16) of lo | hi
+  __device__ __forceinline__ gather::U16 funnel(gather::U16 lo, gather::U16 hi,
+                                                uint32_t mis) const {
+    const u32x4 l = {lo.w[0], lo.w[1], lo.w[2], lo.w[3]}, h = {hi.w[0], hi.w[1], hi.w[2], hi.w[3]};
+    u32x4 o;
+    switch (mis >> 2) {
+      case 0: o = pack::funnel<0>(l, h, mis & 3); break;
+      case 1: o = pack::funnel<1>(l, h, mis & 3); break;
+      case 2: o = pack::funnel<2>(l, h, mis & 3); break;
+      default: o = pack::funnel<3>(l, h, mis & 3); break;
+    }
+    return {{o.x, o.y, o.z, o.w}};
+  }
+  __device__ __forceinline__ void store16(uint64_t o, gather::U16 v) const {
+    st16<2>(dst + o, u32x4{v.w[0], v.w[1], v.w[2], v.w[3]});
+  }
+  __device__ __forceinline__ void store1(uint64_t o, uint8_t v) const { st1<2>(dst + o, v); }
+};
+
+__global__ __launch_bounds__(gather::kThreads) void gather_rows_kernel(gather::Args a) {
+  GatherMem m{a.src, a.dst};
+  gather::gather_lane(a, uint64_t(blockIdx.x) * gather::kThreads + threadIdx.x,
+                      uint64_t(gridDim.x) * gather::kThreads, m);
+}
+
+// gather_tile_kernel: the (c, j) plane of a permuted view through a padded LDS tile
+// (gather_device.h tile::): loads coalesced along the source-contiguous dimension, stores
+// coalesced along the output's innermost one.  Source, strides and destination are
+// element-aligned (tile::contiguous_dim), so every access is a natural one of T.
+template <typename T>
+struct TileMem {
+  const uint8_t* src;
+  uint8_t* dst;
+  T* lds;
+  __device__ __forceinline__ T load_elem(int64_t s) const {
+    return *reinterpret_cast<const T*>(src + s);
+  }
+  __device__ __forceinline__ void lds_write(uint32_t i, T v) const { lds[i] = v; }
+  __device__ __forceinline__ T lds_read(uint32_t i) const { return lds[i]; }
+  __device__ __forceinline__ void store_elem(uint64_t e, T v) const {
+    __builtin_nontemporal_store(v, reinterpret_cast<T*>(dst) + e);
+  }
+};
+
+template <typename T>
+__global__ __launch_bounds__(gather::kThreads) void gather_tile_kernel(gather::tile::Args a) {
+  __shared__ T lds[gather::tile::kLds];
+  TileMem<T> m{a.src, a.dst, lds};
+  for (uint64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+    const gather::tile::Origin o = gather::tile::origin(a, t);
+    gather::tile::load_phase(a, o, threadIdx.x, m);
+    __syncthreads();
+    gather::tile::store_phase(a, o, threadIdx.x, m);
+    __syncthreads();  // the tile is reused by this workgroup's next one
+  }
+}
+
 unsigned grid_for(uint64_t items) {
   uint64_t g = (items + kThreads - 1) / kThreads;
   return static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>(g, 4096)));
@@ -375,6 +459,101 @@ int launch_pack(const Segment* segs_in, size_t n_in, ArrowDeviceType dev, uint8_
     DORA_HIP(hipGetLastError());
     ++launch;
   }
+  return DORA_OK;
+}
+
+// A device tensor view is read only after the runtime has named the allocation that holds it:
+// the strides come from the caller, and a read outside mapped memory faults the whole GPU.
+int check_device_range(const GatherDesc& g, int device) {
+  const uintptr_t base = reinterpret_cast<uintptr_t>(g.view.src);
+  // the first and last byte read, as addresses (no wrap-around)
+  uintptr_t first, last;
+  const uintptr_t below = uintptr_t(0) - static_cast<uintptr_t>(g.lo);  // -lo, lo <= 0
+  if (g.lo > 0 || g.hi < 0 || __builtin_sub_overflow(base, below, &first) ||
+      __builtin_add_overflow(base, static_cast<uintptr_t>(g.hi), &last))
+    return fail(DORA_ERR_INVALID, "tensor view [%lld, %lld] from %p wraps the address space",
+                (long long)g.lo, (long long)g.hi, (const void*)g.view.src);
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof(at));
+  hipError_t e = hipPointerGetAttributes(&at, g.view.src);
+  if (e != hipSuccess || at.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    return fail(DORA_ERR_INVALID, "tensor data %p was declared device memory but the runtime "
+                "knows it as %s", (const void*)g.view.src,
+                e != hipSuccess ? "no allocation of its own"
+                                : at.type == hipMemoryTypeHost ? "host memory" : "another kind");
+  }
+  if (device >= 0 && at.device != device)
+    return fail(DORA_ERR_INVALID, "tensor data %p is on GPU %d, not on this node's GPU %d",
+                (const void*)g.view.src, at.device, device);
+  hipDeviceptr_t ab = nullptr;
+  size_t asz = 0;
+  e = hipMemGetAddressRange(&ab, &asz, const_cast<uint8_t*>(g.view.src));
+  if (e != hipSuccess || !asz) {
+    (void)hipGetLastError();
+    return fail(DORA_ERR_INVALID, "the runtime cannot name the allocation that holds tensor "
+                "data %p (%s)", (const void*)g.view.src, hipGetErrorString(e));
+  }
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(ab), a1 = a0 + (asz - 1);  // closed
+  if (first < a0 || last > a1)
+    return fail(DORA_ERR_INVALID, "tensor view reaches bytes [%p, %p], outside its allocation "
+                "[%p, %p]: nothing was launched", (const void*)first, (const void*)last,
+                (const void*)a0, (const void*)a1);
+  return DORA_OK;
+}
+
+// Which kernel gathers `g` into `dst`, stated once.  The tiled transpose, where it applies
+// (tile::contiguous_dim: a source-contiguous dimension c that is not the output's innermost
+// dimension j, everything element-aligned), when c is at least kTileMinC elements long and a row
+// of the output along j at least kTileMinRowBytes; gather_rows_kernel for everything else:
+// crops, slices, broadcasts, unaligned views, C = 3 of HWC->CHW (a 32-wide tile of it is nine
+// tenths empty: 85 us against 8.7) and short output rows (NCHW->NHWC float16 with C = 64, 128-byte
+// rows: 14.4 us against 10.7).  Measured rows against tile, five interleaved rounds
+// (profiles/tensor_gather_kernels.jsonl): the tile wins at every other point tried,
+// element sizes 1, 2, 4 and 8, c of 16 and 32 elements and 256-byte rows included.
+constexpr int64_t kTileMinC = 16;
+constexpr int64_t kTileMinRowBytes = 256;
+std::atomic<int> g_gather_force{0};  // test hook: 1 rows, 2 tile wherever it applies
+
+int select_tile_dim(const GatherDesc& g, const uint8_t* dst) {
+  const int force = g_gather_force.load(std::memory_order_relaxed);
+  if (force == 1) return -1;
+  const int c = gather::tile::contiguous_dim(g, dst);
+  if (c < 0 || force == 2) return c;
+  const int64_t row_bytes = g.view.shape[g.view.nd - 1] * static_cast<int64_t>(g.elem);
+  return g.view.shape[c] >= kTileMinC && row_bytes >= kTileMinRowBytes ? c : -1;
+}
+
+void gather_force(int mode) { g_gather_force.store(mode, std::memory_order_relaxed); }
+
+int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEvent_t ev_start,
+                  hipEvent_t ev_stop) {
+  if (!g.view.total) return DORA_OK;
+  const int c = select_tile_dim(g, dst);
+  if (c >= 0) {
+    const gather::tile::Args a = gather::tile::make_args(g, dst, c);
+    void (*kern)(gather::tile::Args) = g.elem == 1   ? gather_tile_kernel<uint8_t>
+                                       : g.elem == 2 ? gather_tile_kernel<uint16_t>
+                                       : g.elem == 4 ? gather_tile_kernel<uint32_t>
+                                                     : gather_tile_kernel<uint64_t>;
+    const dim3 grid(static_cast<unsigned>(gather::tile::grid_for(a)));
+    if (ev_start || ev_stop) {
+      hipExtLaunchKernelGGL(kern, grid, dim3(gather::kThreads), 0, stream, ev_start, ev_stop, 0, a);
+    } else {
+      hipLaunchKernelGGL(kern, grid, dim3(gather::kThreads), 0, stream, a);
+    }
+    DORA_HIP(hipGetLastError());
+    return DORA_OK;
+  }
+  const gather::Args a = gather::make_args(g, dst);
+  const dim3 grid(static_cast<unsigned>(gather::grid_for(a)));
+  if (ev_start || ev_stop) {
+    hipExtLaunchKernelGGL(gather_rows_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
+                          ev_stop, 0, a);
+  } else {
+    hipLaunchKernelGGL(gather_rows_kernel, grid, dim3(gather::kThreads), 0, stream, a);
+  }
+  DORA_HIP(hipGetLastError());
   return DORA_OK;
 }
 
@@ -691,8 +870,18 @@ int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_
     return dora::fail(DORA_ERR_TOO_SMALL,
                       "target buffer too small (total_len: %zu, required_len: %llu)", dst_len,
                       static_cast<unsigned long long>(plan->size));
-  if (plan->segs.empty()) return DORA_OK;
+  if (plan->segs.empty() && !plan->gather) return DORA_OK;
   if (!dst) return dora::fail(DORA_ERR_INVALID, "dst is NULL");
+  if (plan->dev_tensor) {
+    // a device tensor view: inside one allocation of the current GPU before anything reads it
+    int device = 0;
+    DORA_HIP(hipGetDevice(&device));
+    const int rc = dora::check_device_range(plan->gd, device);
+    if (rc != DORA_OK) return rc;
+    if (plan->gather)
+      return dora::launch_gather(plan->gd, static_cast<uint8_t*>(dst),
+                                 static_cast<hipStream_t>(stream));
+  }
   return dora::launch_pack(plan->segs.data(), plan->segs.size(), plan->dev,
                            static_cast<uint8_t*>(dst), static_cast<hipStream_t>(stream), nullptr,
                            nullptr, nullptr, nullptr, dst_len);

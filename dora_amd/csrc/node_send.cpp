@@ -408,6 +408,23 @@ int fill_sample(dora_node* n, dora_sample* s, const Segment* segs, size_t nseg,
   return DORA_OK;
 }
 
+// Launch the gather of a strided device tensor view (a gather plan, tensor_plan.cpp) into sample
+// `s` on stream `st` (null: the next fill stream, ordered after the node stream) and let the
+// stream write the fill epoch behind it (order_fill): no AQL packet, no in-kernel signal.
+int gather_sample(dora_node* n, dora_sample* s, const GatherDesc& g, hipStream_t st,
+                  hipEvent_t t_start, hipEvent_t t_stop, bool signal) {
+  DeviceScope ds(n->core->device);
+  if (!st) st = n->core->next_fill_stream();
+  ++n->hip_packs;
+  int rc = launch_gather(g, static_cast<uint8_t*>(s->slot->ptr), st, t_start, t_stop);
+  if (rc != DORA_OK || !signal) return rc;  // (a broadcast-group send orders what follows itself)
+  for (size_t i = 0; i < n->core->fill_streams.size(); ++i)
+    if (n->core->fill_streams[i] == st) n->core->fill_unsignalled[i] = 1;
+  hipError_t e = order_fill(n, s, st);
+  if (e != hipSuccess) return fail(DORA_ERR_HIP, "fill signal: %s", hipGetErrorString(e));
+  return DORA_OK;
+}
+
 // A same-GPU device input re-sent in place: the descriptor points at the producer's slot (its
 // fill is complete: the input was handed out), under a token of this node; the input — and with
 // it the producer's token — is held until that token returns.  No copy, no new slot.
@@ -578,6 +595,13 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
   const uint64_t t0 = mono_ns();
   // a host-resident array below the zero-copy threshold goes inline, as in the reference
   const bool host_src = plan->dev != ARROW_DEVICE_ROCM;
+  if (plan->dev_tensor && plan->size && n->core->device >= 0) {
+    // a device tensor view: its strides are the caller's, so the runtime names the allocation
+    // it must lie in before anything is allocated or launched
+    DeviceScope ds(n->core->device);
+    const int rc = check_device_range(plan->gd, n->core->device);
+    if (rc != DORA_OK) return rc;
+  }
   // a device array for receivers that all lack a GPU: packed into shared memory
   // (host_bound_sample; not inside a timed region, whose stamps live in HBM slots' flags, and
   // not a plan whose validity bitmaps travel in a tail past the sample: a SharedMemory message
@@ -585,7 +609,8 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
   const bool host_bound = plan->size && plan->fill_size() == plan->size && !n->host_bound.empty() &&
                           !n->timed.armed && n->core->device >= 0 &&
                           n->host_bound.count(output_id) && !n->bcast_out.count(output_id);
-  if (host_bound && !host_src && plan->size <= kHostPackMax) {
+  if (host_bound && !host_src && !plan->gather && plan->size <= kHostPackMax) {
+    // (a gather plan takes the HBM slot, which such receivers stage as usual)
     s = host_bound_sample(n, plan->size, plan->size);
   } else if (host_bound && host_src && plan->size >= kZeroCopyThreshold) {
     // a host source for them: the CPU copies it into shared memory, as a node without a GPU
@@ -628,7 +653,8 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
     hipEvent_t t_start = tp ? tp->start : nullptr, t_stop = tp ? tp->stop : nullptr;
     // Timed region: packs that signal their own fill stamp their device time into the flag
     // line; only packs that cannot (kernel signal off, transforms) need timing events
-    const bool stampable = n->core->fill_done && !plan->compact;
+    // (nor can a gather: the stream raises its flag)
+    const bool stampable = n->core->fill_done && !plan->compact && !plan->gather;
     if (n->timed.armed && plan->dev != ARROW_DEVICE_CPU) {
       if (!stampable && !n->timed.started && !tp) {  // its start is the fallback's origin
         t_start = n->timed.start;
@@ -643,8 +669,11 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
     if (bcast) n->core->order_after_node_stream(bo->second.stream);
     const bool sync = plan->dev == ARROW_DEVICE_ROCM &&
                       !((flags & DORA_SEND_ASYNC) || n->async_default);
-    rc = fill_sample(n, s, plan->segs.data(), plan->segs.size(), plan->dev,
-                     bcast ? bo->second.stream : nullptr, t_start, t_stop, !bcast, sync);
+    rc = plan->gather
+             ? gather_sample(n, s, plan->gd, bcast ? bo->second.stream : nullptr, t_start, t_stop,
+                             !bcast)
+             : fill_sample(n, s, plan->segs.data(), plan->segs.size(), plan->dev,
+                           bcast ? bo->second.stream : nullptr, t_start, t_stop, !bcast, sync);
     if (rc != DORA_OK) {
       if (tp) tp->pending = false;
       add_to_cache(n, s->slot);
@@ -964,8 +993,10 @@ int dora_node_send_output_tensor(dora_node* n, const char* output_id, const dora
     const int rc = dora::build_tensor_plan(tensor, device_type, &plan);
     if (rc != DORA_OK) return rc;
   }
-  // a dense view is one copy segment over the caller's memory, a strided one over the plan's
-  // staging buffer: either way a host source, which the send has read when it returns
+  // a host view is one copy segment, over the caller's memory when dense and over the plan's
+  // staging buffer when strided: a host source, which the send has read when it returns.  A
+  // device view is one copy segment when dense and a gather when strided; the synchronous send
+  // waits until the kernel has read it
   std::unique_ptr<dora_plan> owner(plan);
   return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
   DORA_GUARD_END

@@ -74,6 +74,30 @@ struct Segment {
   uint64_t src_len = 0;
 };
 
+// A strided tensor view after canonicalisation (tensor_plan.cpp), in bytes: `nd` dimensions of
+// `shape[i]` steps of `stride[i]` bytes (signed, 0 allowed), each addressing a contiguous row of
+// `row` bytes (an innermost unit stride folded in; else one element).
+constexpr int kMaxTensorDims = 8;
+struct StridedView {
+  const uint8_t* src;  // element (0, .., 0)
+  uint64_t total;      // output bytes
+  uint64_t row;
+  int nd;              // 0..kMaxTensorDims (0: dense)
+  int64_t shape[kMaxTensorDims];
+  int64_t stride[kMaxTensorDims];
+};
+
+// What a device tensor plan reads (ARROW_DEVICE_ROCM): the view, its element size and the closed
+// interval [lo, hi] of byte offsets from `view.src` that any element of it can reach, computed
+// without overflow.  A dense view (nd == 0) is read by the plan's one segment, a strided one by
+// the gather kernel (gather_device.h); either way the interval is checked against the
+// allocation that holds `view.src` before anything is launched (check_device_range).
+struct GatherDesc {
+  StridedView view;
+  uint32_t elem;
+  int64_t lo, hi;
+};
+
 // Fill signal written by a pack launch itself (kernels.hip): once every workgroup's stores are
 // complete, a system-scope store of `epoch` into `flag` (device view of a host-registered fill
 // flag), preceded by the launch's start / signal times into flag[1], flag[2] (the flag must own
@@ -113,6 +137,15 @@ int launch_pack(const Segment* segs, size_t n, ArrowDeviceType dev, uint8_t* dst
                 const FillSignal* signal = nullptr, bool* signalled = nullptr,
                 uint64_t dst_cap = 0);
 
+// The allocation holding `g.view.src` must be device memory of `device` and contain
+// [src + lo, src + hi]; DORA_ERR_INVALID naming both otherwise (kernels.hip).
+int check_device_range(const GatherDesc& g, int device);
+// Launch the gather of a strided device view into `dst` (16-byte units of the row-major output,
+// write-through stores; nothing at or past dst + g.view.total) on `stream` (kernels.hip); with
+// timing events, the dispatch stamps its begin into `ev_start` and its end into `ev_stop`.
+int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream,
+                  hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+
 // Pack device segments into `dst` (device or mapped host memory) and return once complete,
 // waiting on the launch's own fill signal instead of a blocking stream synchronise.
 int launch_pack_wait(const Segment* segs, size_t n, uint8_t* dst, hipStream_t stream);
@@ -134,7 +167,7 @@ Layout layout_of(const char* format);
 inline Layout layout_of(const std::string& format) { return layout_of(format.c_str()); }
 int build_plan(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                dora_plan** out, bool validity_in_sample = false);
-// A tensor view in host memory (dora_gpu_plan_tensor, tensor_plan.cpp).
+// A tensor view in host or device memory (dora_gpu_plan_tensor, tensor_plan.cpp).
 int build_tensor_plan(const dora_tensor* tensor, ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
@@ -152,5 +185,10 @@ struct dora_plan {
   // tensor plans (tensor_plan.cpp): the row-major copy of a strided host view, which the plan's
   // one segment then reads
   std::vector<uint8_t> staged;
+  // device tensor plans: what the plan reads (dev_tensor), and whether a gather kernel rather
+  // than `segs` (then empty) reads it
+  bool dev_tensor = false;
+  bool gather = false;
+  dora::GatherDesc gd{};
   uint64_t fill_size() const { return ext_size > size ? ext_size : size; }
 };

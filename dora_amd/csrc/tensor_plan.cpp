@@ -1,6 +1,7 @@
 // Planning of a tensor send (dora_gpu_plan_tensor, include/dora_gpu.h): validation of a strided
-// view in host memory, its canonical form, the nested FixedSizeList type info, and the CPU gather
-// of views that are not dense.
+// view, its canonical form, the nested FixedSizeList type info, the CPU gather of host views
+// that are not dense, and for views in device memory — which are never read here — the gather
+// descriptor with the interval of offsets the view reaches.
 //
 // Wire form (no reference counterpart for tensors; the layout is the reference's for the
 // equivalent array): shape (d0, .., dk) of T is FixedSizeList<..FixedSizeList<T>[dk]..>[d1] of
@@ -18,19 +19,6 @@
 namespace dora {
 
 namespace {
-
-// A strided view after canonicalisation, in bytes: `nd` dimensions of `shape[i]` steps of
-// `stride[i]` bytes (signed, 0 allowed), each addressing a contiguous row of `row` bytes (an
-// innermost unit stride folded in; else one element).
-constexpr int kMaxTensorDims = 8;
-struct StridedView {
-  const uint8_t* src;  // element (0, .., 0)
-  uint64_t total;      // output bytes
-  uint64_t row;
-  int nd;              // 1..kMaxTensorDims
-  int64_t shape[kMaxTensorDims];
-  int64_t stride[kMaxTensorDims];
-};
 
 // Row-major walk of the view: one memcpy per row, an odometer over the dimensions.  The source
 // position is kept as an offset from `src` (a negative stride steps below it and back).
@@ -133,16 +121,34 @@ struct Dim {
   int64_t n, s;  // extent, stride in bytes
 };
 
+// The closed interval [lo, hi] of byte offsets from element (0, .., 0) that the view reaches: lo
+// the sum of the negative (n - 1) * stride terms, hi the positive ones plus the row's last byte.
+// False when a product or a sum leaves int64: a device view's strides are not trusted, since an
+// out-of-range read on the GPU is a machine-wide event.
+bool reach(const StridedView& g, int64_t* lo, int64_t* hi) {
+  int64_t l = 0, h = 0;
+  if (g.row == 0 || g.row - 1 > uint64_t(INT64_MAX)) return false;
+  h = static_cast<int64_t>(g.row - 1);
+  for (int i = 0; i < g.nd; ++i) {
+    int64_t span;
+    if (__builtin_mul_overflow(g.shape[i] - 1, g.stride[i], &span)) return false;
+    if (__builtin_add_overflow(span < 0 ? l : h, span, span < 0 ? &l : &h)) return false;
+  }
+  // every offset in between must be representable from either end
+  int64_t width;
+  if (__builtin_sub_overflow(h, l, &width)) return false;
+  *lo = l;
+  *hi = h;
+  return true;
+}
+
 }  // namespace
 
 int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out) {
   if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!t) return fail(DORA_ERR_INVALID, "tensor is NULL");
-  if (dev == ARROW_DEVICE_ROCM)
-    return fail(DORA_ERR_UNSUPPORTED, "tensors in device memory are not implemented yet (host "
-                "and pinned memory are): send a contiguous one with dora_node_send_output_bytes");
-  if (dev != ARROW_DEVICE_CPU && dev != ARROW_DEVICE_ROCM_HOST)
+  if (dev != ARROW_DEVICE_CPU && dev != ARROW_DEVICE_ROCM_HOST && dev != ARROW_DEVICE_ROCM)
     return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
   const char* leaf = leaf_format(*t);
   if (!leaf) return DORA_ERR_UNSUPPORTED;
@@ -228,6 +234,21 @@ int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out
   for (size_t i = 0; i < dims.size(); ++i) {
     g.shape[i] = dims[i].n;
     g.stride[i] = dims[i].s;
+  }
+  if (dev == ARROW_DEVICE_ROCM) {
+    // device memory is never dereferenced here: a dense view is dora_gpu_plan_bytes' plan with
+    // the nested type info (every device path unchanged), a strided one the gather kernel's
+    // descriptor and no segments
+    p->dev_tensor = true;
+    p->gd.view = g;
+    p->gd.elem = static_cast<uint32_t>(elem);
+    if (!reach(g, &p->gd.lo, &p->gd.hi))
+      return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
+                  "stride, summed over its dimensions)");
+    if (dims.empty()) p->segs.push_back({base, 0, bytes});
+    else p->gather = true;
+    *out = p.release();
+    return DORA_OK;
   }
   // what the caller's own copy to contiguous memory would have done: every host path (inline
   // Vec, shared memory, BAR fill, DMA) then sees a dense pageable source

@@ -32,6 +32,7 @@ int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t 
                          uint32_t* grid);
 int launch_l2_touch(const void* p, size_t len, hipStream_t stream);
 int l1_stale_probe(int device, int mode, uint32_t* bad_first, uint32_t* stale, uint32_t* blocks);
+void gather_force(int mode);
 }  // namespace dora
 
 namespace dora {
@@ -308,6 +309,32 @@ int dora_gpu_test_bar_write(int device, void* dst, const void* src, size_t bytes
 }
 
 void dora_gpu_test_bar_free(void* ptr) { dora::bar_free(ptr); }
+
+int dora_gpu_test_gather_kernel(int mode) {
+  if (mode < 0 || mode > 2) return dora::fail(DORA_ERR_INVALID, "gather kernel mode %d", mode);
+  dora::gather_force(mode);
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_gather(const dora_plan* plan, int* gather, const void** src, int* nd,
+                              uint64_t* row, uint32_t* elem, int64_t* shape, int64_t* stride,
+                              int64_t* lo, int64_t* hi) {
+  if (!plan || !plan->dev_tensor)
+    return dora::fail(DORA_ERR_INVALID, "not a device tensor plan");
+  const dora::GatherDesc& g = plan->gd;
+  if (gather) *gather = plan->gather;
+  if (src) *src = g.view.src;
+  if (nd) *nd = g.view.nd;
+  if (row) *row = g.view.row;
+  if (elem) *elem = g.elem;
+  for (int i = 0; i < dora::kMaxTensorDims; ++i) {
+    if (shape) shape[i] = i < g.view.nd ? g.view.shape[i] : 0;
+    if (stride) stride[i] = i < g.view.nd ? g.view.stride[i] : 0;
+  }
+  if (lo) *lo = g.lo;
+  if (hi) *hi = g.hi;
+  return DORA_OK;
+}
 
 int dora_gpu_test_ide_output(const char* dataflow_id, const char* node_id,
                                         const char* output_id, const uint8_t* type_info,

@@ -192,7 +192,8 @@ class DeviceArray:
     def length(self) -> int:
         return self.array.length
 
-    # DLPack (kDLROCM): zero-copy hand-off of fixed-width device samples to torch & co.
+    # DLPack (kDLROCM): zero-copy hand-off of fixed-width device samples to torch & co.; a
+    # tensor message (nested FixedSizeList without nulls) as one tensor of its shape
     def __dlpack__(self, stream=None, **kwargs):
         from .dlpack import to_dlpack_capsule, values_view
         ptr, n, fmt = values_view(self)

@@ -54,16 +54,18 @@ _PyCapsule_New.restype = ctypes.py_object
 _PyCapsule_New.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p]
 
 
-def to_dlpack_capsule(ptr: int, length: int, fmt: str, device_id: int, owner):
-    """A 'dltensor' PyCapsule over `length` elements of Arrow format `fmt` at device `ptr`."""
+def to_dlpack_capsule(ptr: int, length, fmt: str, device_id: int, owner):
+    """A 'dltensor' PyCapsule over elements of Arrow format `fmt` at device `ptr`: `length` of
+    them, or a row-major tensor of shape `length` (a tuple)."""
     if fmt not in _DTYPES:
         raise TypeError(f"DLPack export supports fixed-width numeric arrays, not {fmt!r}")
     code, bits = _DTYPES[fmt]
-    shape = (ctypes.c_int64 * 1)(length)
+    dims = tuple(length) if isinstance(length, (tuple, list)) else (length,)
+    shape = (ctypes.c_int64 * len(dims))(*dims)
     m = DLManagedTensor()
     m.dl_tensor.data = ptr
     m.dl_tensor.device = DLDevice(kDLROCM, device_id)
-    m.dl_tensor.ndim = 1
+    m.dl_tensor.ndim = len(dims)
     m.dl_tensor.dtype = DLDataType(code, bits, 1)
     m.dl_tensor.shape = shape
     m.dl_tensor.strides = None
@@ -75,10 +77,32 @@ def to_dlpack_capsule(ptr: int, length: int, fmt: str, device_id: int, owner):
     return _PyCapsule_New(ctypes.addressof(m), b"dltensor", None)
 
 
+def _no_nulls(a, t):
+    # (a null count of -1 is "not computed": a validity bitmap then counts as nulls)
+    if a.null_count > 0 or (a.null_count < 0 and a.n_buffers > 0 and a.buffers[0]):
+        raise TypeError(f"DLPack export of a tensor message needs an array without nulls ({t})")
+
+
 def values_view(device_array):
-    """(pointer, length, format) of the values buffer of a fixed-width DeviceArray."""
+    """(pointer, shape, format) of the values of a DeviceArray that is a fixed-width numeric
+    array (shape: its length) or a tensor message, FixedSizeList<..<T>[sk]..>[s1] without nulls
+    at any level (shape (length, s1, .., sk), the row-major values of this array's own slice)."""
     import pyarrow as pa
-    t = device_array.type
+    t, a = device_array.type, device_array.array
+    if pa.types.is_fixed_size_list(t):
+        dims, off = [a.length], a.offset
+        while pa.types.is_fixed_size_list(t):
+            _no_nulls(a, t)
+            if a.n_children != 1:
+                raise TypeError(f"malformed fixed-size list array ({t})")
+            dims.append(t.list_size)
+            child = a.children[0].contents
+            off = off * t.list_size + child.offset
+            a, t = child, t.value_type
+        _no_nulls(a, t)
+        leaf = DeviceLeaf(a, t, off)
+        ptr, _, fmt = values_view(leaf)
+        return ptr, tuple(dims), fmt
     if pa.types.is_dictionary(t) or not (pa.types.is_integer(t) or pa.types.is_floating(t)):
         raise TypeError(f"DLPack export needs a fixed-width numeric array, got {t}")
     fmt = {pa.int8(): "c", pa.uint8(): "C", pa.int16(): "s", pa.uint16(): "S",
@@ -89,5 +113,13 @@ def values_view(device_array):
     if a.n_buffers < 2 or not a.buffers[1]:
         ptr = 0
     else:
-        ptr = a.buffers[1] + a.offset * width
+        ptr = a.buffers[1] + getattr(device_array, "offset", a.offset) * width
     return ptr, a.length, fmt
+
+
+class DeviceLeaf:
+    """The leaf values of a tensor message for values_view: a child array, its type and the
+    element offset of the parent's slice within it."""
+
+    def __init__(self, array, arrow_type, offset):
+        self.array, self.type, self.offset = array, arrow_type, offset

@@ -10,6 +10,7 @@
     node.send_output("out", device_array)                 # HBM array -> HIP pack kernel
     node.send_output("out", b"raw bytes")                 # ArrowTypeInfo::byte_array
     node.send_output("out", frame.transpose(2, 0, 1))     # a host tensor view (dora_amd.tensor)
+    node.send_output("out", frame_cuda.permute(2, 0, 1))  # a torch view in HBM: gathered by a kernel
 """
 from __future__ import annotations
 
@@ -150,6 +151,35 @@ class _Event(dict):
         return ti
 
 
+_hip_runtime_checked = False
+
+
+def _require_one_hip_runtime():
+    """A device tensor's producer and this library must share one HIP runtime: a stream or an
+    allocation of one runtime means nothing to another.  torch's ROCm wheels carry their own
+    libamdhip64; when torch is imported before dora_amd the library binds to it, the other way
+    round the process holds two.  Checked once, at the first device tensor send (the producer's
+    library is loaded by then)."""
+    global _hip_runtime_checked
+    if _hip_runtime_checked:
+        return
+    libs = set()
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                path = line.rsplit(None, 1)[-1]
+                if os.path.basename(path).startswith("libamdhip64"):
+                    libs.add(os.path.realpath(path))
+    except OSError:
+        pass
+    if len(libs) > 1:
+        raise RuntimeError("two HIP runtimes are loaded in this process (" + ", ".join(sorted(libs))
+                           + "): a device tensor of one cannot be read through the other. "
+                           "Import the tensor's library (torch) before dora_amd, so that both "
+                           "use the same one")
+    _hip_runtime_checked = True
+
+
 class Node:
     """The reference's `Node` pyclass (apis/python/node/src/lib.rs:29-209): `Node(node_id=None)`,
     `next(timeout=None)`, iteration (`__iter__` / `__next__`), `send_output(output_id, data,
@@ -171,6 +201,9 @@ class Node:
         self.id = self._lib.dora_node_id(self.handle).decode()
         self.device = device if device is not None else int(os.environ.get("DORA_GPU_DEVICE", "0"))
         self._region = dataflow or os.environ.get("DORA_GPU_DATAFLOW", "")
+        self._async_tensors = []  # device tensors of asynchronous sends, held until sync()
+        # the node's own default (dora_node_init reads the same variable; set_async_sends)
+        self._async_default = os.environ.get("DORA_GPU_SEND_ASYNC", "")[:1] == "1"
 
     # -------------------------------------------------------------------------------- sending
     def send_output(self, output_id: str, data, metadata: Optional[dict] = None, *,
@@ -201,20 +234,45 @@ class Node:
             rc = self._send_tensor(output_id, data, metadata, f)
         else:
             raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer or "
-                            "a host tensor with __dlpack__ (numpy, torch)")
+                            "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU)")
         if rc:
             _lib.check(rc)
 
+    # asynchronous device tensor sends whose source is held until the next sync(): past this
+    # many, the send syncs first (each entry pins a tensor's storage)
+    _ASYNC_TENSORS_MAX = 64
+
     def _send_tensor(self, output_id: str, data, metadata, flags: int) -> int:
-        """A DLPack producer (numpy.ndarray, a CPU or pinned torch.Tensor), strided views
+        """A DLPack producer (numpy.ndarray, a CPU, pinned or device torch.Tensor), strided views
         included, as the nested FixedSizeList array of its shape (dora_node_send_output_tensor;
-        dora_amd.tensor).  The tensor has been read on return: pinned memory, which the GPU reads
-        asynchronously to the host, is declared as such and copied inside the call."""
-        dev_type = int(data.__dlpack_device__()[0])
+        dora_amd.tensor).  A host tensor has been read on return: pinned memory, which the GPU
+        reads asynchronously to the host, is declared as such and copied inside the call.
+
+        A device tensor (kDLROCM, on this node's GPU) is read by a kernel: in place when it is
+        dense, gathered into row-major order when it is a strided view.  The producer is asked
+        for the capsule with `__dlpack__(stream=<the node stream>)`, DLPack's own handshake: it
+        orders the node stream after its current stream, and the kernel runs after the node
+        stream.  Without `asynchronous` the call returns once the kernel has read the tensor;
+        with it, once the kernel is queued, and the node holds the tensor until the next
+        `sync()` or `close()` (at most `_ASYNC_TENSORS_MAX` of them: the send then syncs first).
+        The caller must not overwrite it before that `sync()`."""
+        dl_dev = data.__dlpack_device__()
+        dev_type = int(dl_dev[0])
         if dev_type == _DL_ROCM:
-            raise TypeError("sending a tensor in device memory is not implemented: send a "
-                            "contiguous one with send_output_device_bytes(output_id, "
-                            "t.data_ptr(), nbytes)")
+            ordinal = int(dl_dev[1])
+            if ordinal != self.device:
+                raise TypeError(f"the tensor is on GPU {ordinal}, this node on GPU {self.device}: "
+                                "a node sends tensors of its own GPU")
+            _require_one_hip_runtime()
+            held = bool(flags & SEND_ASYNC) or self._async_default
+            if held and len(self._async_tensors) >= self._ASYNC_TENSORS_MAX:
+                self.sync()
+            # (dora_node_stream: the node then knows its stream is in use, and fills wait on it)
+            cap = data.__dlpack__(stream=int(self._lib.dora_node_stream(self.handle)))
+            rc = _fast.send_tensor(self.handle, output_id, cap, ARROW_DEVICE_ROCM, metadata, flags)
+            if held and not rc:
+                self._async_tensors.append(data)
+            return rc
         if dev_type not in _DL_HOST:
             raise TypeError(f"tensors of DLPack device type {dev_type} cannot be sent")
         dev = ARROW_DEVICE_CPU if dev_type == _DL_CPU else ARROW_DEVICE_ROCM_HOST
@@ -242,6 +300,7 @@ class Node:
     def set_async_sends(self, enable: bool = True):
         """Make every send of this node asynchronous (dora_node_set_async_sends)."""
         call("dora_node_set_async_sends", self.handle, int(enable))
+        self._async_default = bool(enable)
 
     def set_event_thread(self, enable: bool = True):
         """Drain the daemon's events on a background thread (the reference's event-stream thread;
@@ -471,8 +530,10 @@ class Node:
         call("dora_node_region_begin", self.handle)
 
     def sync(self):
-        """Wait for every fill of this node and its node stream (dora_node_sync)."""
+        """Wait for every fill of this node and its node stream (dora_node_sync); device tensors
+        sent asynchronously since the last call have then been read and are let go."""
         call("dora_node_sync", self.handle)
+        self._async_tensors.clear()
 
     def region_mark(self):
         """Record the region's stop events after the last send, without waiting on them."""
@@ -497,8 +558,11 @@ class Node:
 
     def close(self):
         if self.handle:
+            if self._async_tensors:
+                self._lib.dora_node_sync(self.handle)  # their gathers read them until then
             self._lib.dora_node_free(self.handle)
             self.handle = None
+            self._async_tensors.clear()
 
     def __enter__(self):
         return self

@@ -7,11 +7,16 @@ sample is one buffer, the row-major bytes, so the shape travels in the type and 
 reference can send or receive the same message.
 
     node.send_output("image", frame.transpose(2, 0, 1))   # numpy or CPU torch: any host DLPack tensor
+    node.send_output("image", frame_cuda.permute(2, 0, 1))  # a torch tensor in this node's HBM
+    chw = tensor.to_torch(event["value"])                  # device receiver: zero-copy, in HBM
     chw = tensor.to_numpy(event["value"])                  # host receiver: the nested pyarrow array
     chw = tensor.to_numpy(event["value"].to_pyarrow())     # device receiver: downloaded first
 
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
-is copied once, so every source has been read when `send_output` returns.
+is copied once, so every source has been read when `send_output` returns.  A tensor in device
+memory is read by a kernel: in place when dense, gathered by the gfx950 gather kernel when it is a
+strided view (one read and one write of HBM, no `.contiguous()` first).  The producer must share
+the HIP runtime of this library: import torch before dora_amd (Node._send_tensor).
 """
 from __future__ import annotations
 
@@ -60,6 +65,17 @@ def to_numpy(arr):
     return arr.to_numpy(zero_copy_only=False).reshape(shape)
 
 
+def to_torch(value):
+    """The torch tensor of a received tensor message: zero-copy over the HBM sample for a device
+    receiver's `event["value"]` (DLPack, kDLROCM; the tensor keeps the input alive), a copy of
+    the nested pyarrow array for a host receiver's.  Nulls at any level are refused."""
+    import torch
+    if hasattr(value, "__dlpack__"):
+        return torch.from_dlpack(value)
+    import numpy as np
+    return torch.from_numpy(np.array(to_numpy(value)))
+
+
 def _describe(ptr: int, shape, strides, dtype, byte_offset: int = 0) -> tuple:
     """A `dora_tensor` over `ptr` (strides in elements, or None for row-major) and the ctypes
     arrays it points at, which the caller keeps alive with it."""
@@ -91,4 +107,4 @@ def _describe_array(x) -> tuple:
     return t, (x, keep)
 
 
-__all__ = ["tensor_type", "from_numpy", "to_numpy"]
+__all__ = ["tensor_type", "from_numpy", "to_numpy", "to_torch"]

@@ -189,7 +189,26 @@ int dora_gpu_plan_bytes(const void* src, size_t len, ArrowDeviceType device_type
  *   ARROW_DEVICE_ROCM_HOST  pinned host memory: always copied into the staging buffer, dense or
  *                           not (a DMA or kernel reading pinned memory runs asynchronously to
  *                           the host; the copy keeps "read on return" true);
- *   ARROW_DEVICE_ROCM       HBM: not implemented in this version, DORA_ERR_UNSUPPORTED.
+ *   ARROW_DEVICE_ROCM       HBM.  Planning reads nothing and calls nothing in HIP.  A view that is
+ *                           dense after canonicalisation plans exactly as dora_gpu_plan_bytes
+ *                           over `data + offset`, with the nested type info, and takes every
+ *                           device path unchanged.  Any other view plans a gather: no segments,
+ *                           and a kernel (gather_rows_kernel, gfx950) that reads the view once and
+ *                           writes the row-major sample once.  Device strides are NOT trusted (a
+ *                           read outside mapped memory faults the whole GPU): the closed interval
+ *                           of byte offsets the view reaches — the negative (extent - 1) * stride
+ *                           terms below element 0, the positive ones plus a row above — is
+ *                           computed with overflow checks (DORA_ERR_INVALID if it leaves 64 bits),
+ *                           and before anything is launched (dora_gpu_pack, a node's send) the
+ *                           runtime must name one device allocation, on the current / the node's
+ *                           GPU, that contains it: DORA_ERR_INVALID naming both otherwise, and
+ *                           nothing is launched.  (A caching allocator's segment counts as the
+ *                           allocation: the check keeps reads inside mapped memory.)  Stream
+ *                           contract: the kernel runs on a stream ordered after the node stream
+ *                           (dora_node_stream), so a producer orders its writes by queueing them
+ *                           on, or making them precede, the node stream.  The view is borrowed
+ *                           until the kernel has read it: a synchronous send returns after that
+ *                           ("read on return"), see dora_node_send_output_tensor.
  *
  * Accepted dtypes: int and uint of 8/16/32/64 bits, float of 16/32/64 bits, lanes == 1.
  * DORA_ERR_UNSUPPORTED, with a message naming the dtype: bool (Arrow's is a bitmap), bfloat16 and
@@ -197,10 +216,10 @@ int dora_gpu_plan_bytes(const void* src, size_t len, ArrowDeviceType device_type
  * view of more than 8 dimensions after merging.  DORA_ERR_INVALID: ndim < 1, a negative extent,
  * an extent of 0 in any dimension but the first, a byte count that overflows 64 bits, a NULL
  * `data` with a non-zero element count.  d0 == 0 plans an empty message.
- * A dense ARROW_DEVICE_CPU view is borrowed until the pack completes; any other has been read
- * on return.  Shape and strides are trusted, as a DLPack producer's are: beyond the checks
- * above, the bytes a view reaches are not bounded against any allocation, and strides whose
- * products with the extents do not fit 64 bits are the caller's error.
+ * A dense ARROW_DEVICE_CPU view is borrowed until the pack completes; any other host view has
+ * been read on return.  Shape and strides of a host view are trusted, as a DLPack producer's
+ * are: beyond the checks above, the bytes it reaches are not bounded against any allocation, and
+ * strides whose products with the extents do not fit 64 bits are the caller's error.
  */
 typedef struct dora_tensor {
   const void* data;
@@ -392,8 +411,14 @@ int dora_node_send_output_bytes_ex(dora_node* node, const char* output_id, const
  * shared memory on a node without a GPU or for receivers that all lack one, else the BAR fill or
  * the DMA into a device slot; it has been read when the call returns (pageable memory declared
  * ARROW_DEVICE_CPU: as dora_node_send_output_bytes; memory that is in fact pinned must be
- * declared ARROW_DEVICE_ROCM_HOST).  `flags`: DORA_SEND_ASYNC as for the _ex sends; it changes
- * nothing for this version's sources, which are host memory and safe to reuse on return. */
+ * declared ARROW_DEVICE_ROCM_HOST).  A device source (ARROW_DEVICE_ROCM) must lie inside one
+ * allocation of the node's GPU (DORA_ERR_INVALID otherwise, nothing sent); dense, it is packed as
+ * dora_node_send_output_bytes packs device bytes; strided, it is gathered into an HBM slot on a
+ * fill stream ordered after the node stream, and the stream raises the sample's fill flag.  The
+ * call returns once the kernel has read the source.  `flags`: DORA_SEND_ASYNC changes nothing
+ * for host sources; a device source's send then returns once the kernel is queued, and the
+ * caller keeps the source alive and unwritten until dora_node_sync (or writes it only through
+ * work queued on dora_node_stream fetched after the send). */
 int dora_node_send_output_tensor(dora_node* node, const char* output_id, const dora_tensor* tensor,
                                  ArrowDeviceType device_type, const uint8_t* params,
                                  size_t params_len, uint32_t flags);

@@ -65,6 +65,19 @@ int dora_gpu_test_batch_args(size_t n_msgs, const size_t* seg_counts, const uint
                              const uint64_t* dsts, const uint64_t* dst_caps,
                              const uint64_t* flags, const uint64_t* epochs, uint8_t* out,
                              size_t cap, uint32_t* grid);
+/* Test tool (host only): what a device tensor plan (dora_gpu_plan_tensor with ARROW_DEVICE_ROCM)
+ * reads.  *gather 1 if a gather kernel reads it (the plan then has no segments), 0 if it is
+ * dense; *src element (0, .., 0); the canonical view as *nd (<= 8) extents and byte strides in
+ * shape[8] / stride[8], each addressing *row contiguous bytes of *elem-byte elements; [*lo, *hi]
+ * the closed interval of byte offsets from *src the view reaches.  DORA_ERR_INVALID for any
+ * other plan. */
+int dora_gpu_test_plan_gather(const dora_plan* plan, int* gather, const void** src, int* nd,
+                              uint64_t* row, uint32_t* elem, int64_t* shape, int64_t* stride,
+                              int64_t* lo, int64_t* hi);
+/* Test and probe tool: which kernel gathers strided device tensor views of this process from now
+ * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
+ * it applies (short contiguous extents included). */
+int dora_gpu_test_gather_kernel(int mode);
 int dora_gpu_test_bar_write(int device, void* dst, const void* src, size_t bytes);
 /* Test tools (host only) of the fill-flag protocol (FillFlag, 128 bytes, 64-byte aligned): the
  * completion test of epoch `epoch` (1: complete) and the sender's set-up of a fill the command
