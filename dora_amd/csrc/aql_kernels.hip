@@ -24,26 +24,24 @@ extern "C" __global__ __launch_bounds__(kThreads) void dora_aql_packb_u4(
 // processor once per dispatch (gfx950 kernarg preload, built with
 // -mllvm -amdgpu-kernarg-preload-count=14), so they can sit in host memory — no BAR writes and
 // no HDP flush per send (aql.cpp; profiles/r01_aql_preload_probe.jsonl: 0.15 vs 1.6 us host
-// time per dispatch at the same device time).  The chunk count is derived here as
-// build_aql_args derives it for one segment.
+// time per dispatch at the same device time).  The chunk layout is derived here by the function
+// the host's builders use (pack_device.h chunk_layout).
 template <int U, int NT = 2>
 __device__ __forceinline__ void pack1(uint8_t* dst, const uint8_t* src, uint64_t len,
                                       uint64_t* flag, uint32_t* done, uint64_t epoch,
                                       uint32_t chunk_bytes, uint32_t grid) {
-  const uint64_t nc =
-      dora::pack::segment_chunks(reinterpret_cast<uintptr_t>(dst), 0, len, chunk_bytes);
   dora::pack::PackArgsT<1> a;
   a.dst = dst;
   a.flag = flag;
   a.done = done;
   a.epoch = epoch;
-  a.n_chunks = static_cast<uint32_t>(nc);
   a.nseg = 1;
   a.chunk_bytes = chunk_bytes;
   a.grid = grid;
   a.edge_mask = 0;  // a tail unit past `len` may lie outside the destination: bytes one by one
-  a.chunk_end[0] = static_cast<uint32_t>(nc);
   a.seg[0] = {src, 0, len};
+  a.n_chunks = dora::pack::chunk_layout(reinterpret_cast<uintptr_t>(dst), a.seg, 1, chunk_bytes,
+                                        a.chunk_end);
   dora::pack::pack_body<U, NT>(a, __builtin_amdgcn_workgroup_id_x(), grid);
 }
 
@@ -104,45 +102,19 @@ void dora_aql_pack1r_u4(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every load of this workgroup has returned
   __syncthreads();
   const uint32_t e = static_cast<uint32_t>(epoch);
-  if (t == 0) __hip_atomic_store(done + blk, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  dora_gu32* const gdone = (dora_gu32*)done;
+  dora_fill_arrive(gdone, blk, e, t);
   // workgroup 0's go for the stores: the flag's last done word, free below kMaxSignalWgs.  Only
   // for grids an idle GPU holds at once (<= 1024 of these 63-VGPR workgroups, a 50 MB pack): a
   // larger one would hold its resident workgroups for the whole bound while the rest wait
   uint32_t* const go = grid <= 1024 ? done + (kMaxSignalWgs - 1) : nullptr;
   if (blk == 0) {
-    // as signal_fill: every done word at once per round, bounded (a lost workgroup leaves the
-    // read word unset; the send then waits for the fill instead)
-    constexpr int kPer = kMaxSignalWgs / kThreads;
-    __shared__ uint32_t missing;
-    for (uint32_t round = 0; round < (1u << 22); ++round) {
-      if (t == 0) missing = 0;
-      __syncthreads();
-      // four loads in flight per lane at a time: this workgroup's source bytes stay in VGPRs
-      // meanwhile, and few registers keep every workgroup of the grid resident
-      bool all_mine = true;
-#pragma unroll 1
-      for (int k0 = 0; k0 < kPer; k0 += 4) {
-        uint32_t w[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint32_t i = t + (k0 + j) * kThreads;
-          w[j] = i < grid ? __hip_atomic_load(done + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : e;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) all_mine &= w[j] == e;
-      }
-      if (!all_mine) missing = 1;
-      __syncthreads();
-      const bool all = missing == 0;
-      __syncthreads();
-      if (all) {
-        if (t == 0) {
-          __hip_atomic_store(rflag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          if (go) __hip_atomic_store(go, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
+    // four loads in flight per lane at a time: this workgroup's source bytes stay in VGPRs
+    // meanwhile, and few registers keep every workgroup of the grid resident.  A lost workgroup
+    // leaves the read word unset; the send then waits for the fill instead
+    if (dora_fill_wait_all<4>(gdone, grid, e, t, kThreads) && t == 0) {
+      __hip_atomic_store(rflag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (go) __hip_atomic_store(go, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   } else if (go) {
     // the stores wait for every workgroup's loads (the go word, raised with the read word), so
@@ -164,14 +136,7 @@ void dora_aql_pack1r_u4(
       __builtin_amdgcn_raw_buffer_store_b128(v[k], rd, off, 16 * kThreads * k, kCoherentPolicy);
   if (tail_lane) st1<kCoherent>(dst + 16 * uint64_t(units) + t, tb);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the fill: complete before the waves end
-  if (stamps) {
-    __syncthreads();
-    if (t == 0) {
-      __hip_atomic_fetch_max(stamps + 1 + (blk % kCpStampWgs), __builtin_amdgcn_s_memrealtime(),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      if (blk == 0) __hip_atomic_store(stamps, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  if (stamps) stamp_cp(stamps, blk, t_start);
 }
 
 // Region-end reduction of CP-signalled packs' stamp areas (aql.cpp aql_stamp_reduce, node_measure.cpp

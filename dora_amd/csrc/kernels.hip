@@ -198,57 +198,6 @@ __global__ __launch_bounds__(kThreads) void fill_ticket_kernel(uint8_t* p, uint6
   splitmix::fill_and_publish<true>(p, n, seed, t);
 }
 
-// Test tool (the acquire-fence negative control, tests/test_gpu_fence.py): every workgroup reads
-// all of [p, p + n) with plain cached loads, so that each XCD's L2 ends up holding the lines
-// (one workgroup per CU: 32 per XCD, dispatched round robin over the XCDs).  The reduction is
-// stored only under a condition the data never meets, so the loads cannot be elided.
-__global__ __launch_bounds__(kThreads) void l2_touch_kernel(const uint8_t* __restrict__ p,
-                                                            uint64_t n, uint32_t* __restrict__ sink) {
-  const uint64_t nu = n / 16;
-  uint32_t x = 0;
-  for (uint64_t i = threadIdx.x; i < nu; i += kThreads) {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(p + 16 * i);
-    x ^= w[0] ^ w[1] ^ w[2] ^ w[3];
-  }
-  if (x == 0x5EEDF00Du && n == 1) sink[blockIdx.x] = x;
-}
-
-// Test tool (the fence probe's failing control, tests/test_gpu_fence.py): can a CU's cache hand
-// a wave stale source bytes inside ONE dispatch?  One 64-lane workgroup per CU reads 64 words of
-// `src` (coarse-grained device memory the host then rewrites through the BAR) into `first`,
-// reports its arrival on a host counter, waits (bounded) for the host's `go` — given after the
-// rewrite — and reads the same words again into `second`.  `mode` picks the loads: 0 plain
-// (L1-cached), 1 non-temporal (the pack's default loads), 2 agent-coherent sc1 (the coherent
-// pack's).  A plain load served by the CU's L1 returns the old words; a load that bypasses L1
-// cannot.  The arrival counter is a vector atomic, the poll a system-scope load; every wave
-// leaves after at most ~2^22 sleeps, so a host that never answers cannot hang the device.
-template <int MODE>
-__device__ __forceinline__ uint32_t probe_load(const uint32_t* p) {
-  if constexpr (MODE == 0) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-  if constexpr (MODE == 1) return __builtin_nontemporal_load(p);
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(64) void l1_stale_kernel(const uint32_t* src, uint32_t* first,
-                                                      uint32_t* second, uint32_t* arrived,
-                                                      const uint32_t* go) {
-  const uint32_t t = threadIdx.x, b = blockIdx.x;
-  asm volatile("" ::: "memory");
-  first[b * 64 + t] = probe_load<MODE>(src + t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (t == 0) {
-    __hip_atomic_fetch_add(arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (uint32_t i = 0; i < (1u << 22); ++i) {
-      if (__hip_atomic_load(go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) break;
-      __builtin_amdgcn_s_sleep(2);
-    }
-  }
-  __syncthreads();
-  asm volatile("" ::: "memory");
-  second[b * 64 + t] = probe_load<MODE>(src + t);
-}
-
 // ------------------------------------------------------------------------------------------
 // gather_rows_kernel: a strided device tensor view into row-major order (gather_device.h holds
 // every address computation; this is its memory policy).  Rows are read with the pack's 16-byte
@@ -361,6 +310,57 @@ uint64_t edge_mask(const Segment* segs, size_t n, const uint8_t* dst, uint64_t c
   return mask;
 }
 
+// The chunk size a message's pack would use on its own (a batch holds messages of one size).
+uint32_t aql_chunk_bytes(const Segment* segs, size_t n) {
+  uint64_t body = 0;
+  for (size_t k = 0; k < n; ++k) body += segs[k].len;
+  return choose_chunk_bytes(body);  // the AQL kernels keep 4 loads in flight per lane
+}
+
+namespace {
+
+// Who reports a launch's fill: nobody (a pack that is not its plan's last launch), the kernel
+// (fill flag and done words) or the command processor (the dispatch's completion signal).
+enum class Signal { kNone, kInKernel, kCp };
+
+// Workgroups of a pack of `chunks` chunks: the grid policy, here alone.  Unsignalled: one per
+// chunk.  In-kernel signals: the signalling grid (kSignalGrid).  Signalled by the command
+// processor: nothing to poll, so up to kCpGrid workgroups for the single-segment kernels — a lone
+// 40.96 MB pack capped at 1024 keeps 8 MiB in flight, half of what HBM needs — and
+// kCpGridMulti for the multi-segment kernel.
+uint32_t pack_grid(uint32_t chunks, Signal how, bool single) {
+  const uint32_t cap = how == Signal::kInKernel ? kSignalGrid
+                       : how == Signal::kCp     ? (single ? kCpGrid : kCpGridMulti)
+                                                : chunks;
+  return std::min(chunks, cap);
+}
+
+void set_segs(PackSeg* out, const Segment* segs, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    out[k] = {static_cast<const uint8_t*>(segs[k].src), segs[k].dst_off, segs[k].len};
+}
+
+// The head every pack's arguments share (PackArgsT<N>, AqlBatchArgs), filled here alone from
+// a.seg[0 .. nseg): destination, signal, chunk layout (pack_device.h chunk_layout) and grid.
+template <class A>
+int finish_args(A& a, uint8_t* dst, const FillSignal& sig, size_t nseg, uint32_t chunk_bytes,
+                uint64_t edge, Signal how, bool single) {
+  a.dst = dst;
+  a.flag = sig.flag;
+  a.done = sig.done;
+  a.epoch = sig.epoch;
+  a.nseg = static_cast<uint32_t>(nseg);
+  a.chunk_bytes = chunk_bytes;
+  a.edge_mask = edge;
+  a.n_chunks = chunk_layout(reinterpret_cast<uintptr_t>(dst), a.seg, a.nseg, chunk_bytes,
+                            a.chunk_end);
+  if (!a.n_chunks) return fail(DORA_ERR_INVALID, "pack: too many chunks");
+  a.grid = pack_grid(a.n_chunks, how, single);
+  return DORA_OK;
+}
+
+}  // namespace
+
 // Launch the pack of `n` segments into `dst` (device).  Copy segments with device sources go
 // to pack_kernel in batches of kMaxSegs, transform segments (compacting plans) to
 // transform_kernel; host sources are DMA'd with hipMemcpyAsync.  With timing events the
@@ -394,40 +394,23 @@ int launch_pack(const Segment* segs_in, size_t n_in, ArrowDeviceType dev, uint8_
   while (i < n) {
     PackArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.dst = dst;
-    uint64_t body = 0;
     const size_t m = std::min<size_t>(kMaxSegs, n - i);
-    for (size_t k = 0; k < m; ++k) body += segs[i + k].len;
-    a.chunk_bytes = choose_chunk_bytes(body);
-    uint64_t chunks = 0;
-    for (size_t k = 0; k < m; ++k) {
-      const Segment& s = segs[i + k];
-      a.seg[k] = {static_cast<const uint8_t*>(s.src), s.dst_off, s.len};
-      chunks += segment_chunks(reinterpret_cast<uintptr_t>(dst), s.dst_off, s.len, a.chunk_bytes);
-      if (chunks > 0x7fffffffull) return fail(DORA_ERR_INVALID, "pack: too many chunks");
-      a.chunk_end[k] = static_cast<uint32_t>(chunks);
-    }
-    a.nseg = static_cast<uint32_t>(m);
-    // one launch holding the whole plan: its boundary units may be written whole
-    if (!any_x && m == n) a.edge_mask = edge_mask(segs, n, dst, dst_cap);
     const bool first = launch == 0, last = launch + 1 == n_launch;
-    a.n_chunks = static_cast<uint32_t>(chunks);
-    uint64_t grid = chunks;
-    void (*kern)(PackArgs) = pack_kernel<kUnroll, 1>;
-    if (last && signal) {
-      // signalling launch: write-through stores, at most kSignalGrid workgroups
-      a.flag = signal->flag;
-      a.done = signal->done;
-      a.epoch = signal->epoch;
-      if (grid > kSignalGrid) grid = kSignalGrid;
-      kern = pack_kernel<kUnroll, 2>;
-    }
-    a.grid = static_cast<uint32_t>(grid);
+    // the signalling launch: write-through stores, the signalling grid
+    const bool signals = last && signal;
+    // one launch holding the whole plan: its boundary units may be written whole
+    const uint64_t edge = !any_x && m == n ? edge_mask(segs, n, dst, dst_cap) : 0;
+    set_segs(a.seg, segs + i, m);
+    const int rc = finish_args(a, dst, signals ? *signal : FillSignal{}, m,
+                               aql_chunk_bytes(segs + i, m), edge,
+                               signals ? Signal::kInKernel : Signal::kNone, m == 1);
+    if (rc != DORA_OK) return rc;
+    void (*kern)(PackArgs) = signals ? pack_kernel<kUnroll, 2> : pack_kernel<kUnroll, 1>;
     if (ev_start || ev_stop) {
-      hipExtLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, stream,
+      hipExtLaunchKernelGGL(kern, dim3(a.grid), dim3(kThreads), 0, stream,
                             first ? ev_start : nullptr, last ? ev_stop : nullptr, 0, a);
     } else {
-      hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, stream, a);
+      hipLaunchKernelGGL(kern, dim3(a.grid), dim3(kThreads), 0, stream, a);
     }
     DORA_HIP(hipGetLastError());
     if (a.flag && signalled) *signalled = true;
@@ -613,13 +596,6 @@ int launch_pack_wait(const Segment* segs, size_t n, uint8_t* dst, hipStream_t st
 size_t aql_args_size() { return sizeof(AqlPackArgs); }
 size_t aql_batch_args_size() { return sizeof(dora::pack::AqlBatchArgs); }
 
-// The chunk size a message's pack would use on its own (a batch holds messages of one size).
-uint32_t aql_chunk_bytes(const Segment* segs, size_t n) {
-  uint64_t body = 0;
-  for (size_t k = 0; k < n; ++k) body += segs[k].len;
-  return choose_chunk_bytes(body);  // the AQL kernels keep 4 loads in flight per lane
-}
-
 // Arguments of dora_aql_packb_u4: the segments of `n` messages with absolute destinations,
 // sorted by address, each message's stitched-edge bits carried over from its own edge_mask.
 int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t cap,
@@ -654,21 +630,14 @@ int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t 
   std::sort(all, all + ns, [](const S& a, const S& b) { return a.dst < b.dst; });
   AqlBatchArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.chunk_bytes = chunk;
-  uint64_t chunks = 0;
+  uint64_t edge = 0;
   for (size_t k = 0; k < ns; ++k) {
     a.seg[k] = {all[k].src, all[k].dst, all[k].len};
-    chunks += segment_chunks(0, all[k].dst, all[k].len, chunk);
-    if (chunks > 0x7fffffffull) return fail(DORA_ERR_INVALID, "pack: too many chunks");
-    a.chunk_end[k] = static_cast<uint32_t>(chunks);
-    a.edge_mask |= uint64_t(all[k].edge) << (2 * k);
+    edge |= uint64_t(all[k].edge) << (2 * k);
   }
-  a.nseg = static_cast<uint32_t>(ns);
-  a.n_chunks = static_cast<uint32_t>(chunks);
-  a.grid = static_cast<uint32_t>(std::min<uint64_t>(chunks, kSignalGrid));
-  a.flag = items[0].sig.flag;
-  a.done = items[0].sig.done;
-  a.epoch = items[0].sig.epoch;
+  // a null destination: the segments' offsets are addresses; the first message's signal
+  const int rc = finish_args(a, nullptr, items[0].sig, ns, chunk, edge, Signal::kInKernel, false);
+  if (rc != DORA_OK) return rc;
   a.nmsg = static_cast<uint32_t>(n);
   for (size_t m = 0; m < n; ++m) a.msg[m] = {items[m].sig.flag, items[m].sig.epoch};
   std::memcpy(out, &a, sizeof(a));
@@ -676,70 +645,47 @@ int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t 
   return DORA_OK;
 }
 
-// Workgroups of an AQL pack signalled as `sig` says.  In-kernel signals (a flag): the signalling
-// grid (kSignalGrid).  Signalled by the command processor (no flag): nothing to poll, so up to
-// kCpGrid workgroups — a lone 40.96 MB pack capped at 1024 keeps 8 MiB in flight, half of what
-// HBM needs.
-uint64_t signal_grid_cap(const FillSignal& sig) { return sig.flag ? kSignalGrid : kCpGrid; }
-
 // Arguments of one AQL-dispatched signalling pack (aql.cpp): the same chunking and signalling
-// grid as launch_pack's last launch.
+// grid as launch_pack's last launch; without a flag the command processor signals it.
 int build_aql_args(const Segment* segs, size_t n, uint8_t* dst, const FillSignal& sig,
                    uint8_t* out, size_t cap, uint32_t* grid_out, uint64_t dst_cap) {
   if (n == 0 || n > size_t(kMaxAqlSegs)) return fail(DORA_ERR_INVALID, "AQL pack: %zu segments", n);
   if (cap < sizeof(AqlPackArgs)) return fail(DORA_ERR_INVALID, "AQL pack: argument buffer");
+  for (size_t k = 0; k < n; ++k)
+    if (segs[k].op != SEG_COPY) return fail(DORA_ERR_INVALID, "AQL pack: transform segment");
   AqlPackArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.dst = dst;
-  uint64_t body = 0;
-  for (size_t k = 0; k < n; ++k) {
-    if (segs[k].op != SEG_COPY) return fail(DORA_ERR_INVALID, "AQL pack: transform segment");
-    body += segs[k].len;
-  }
-  a.chunk_bytes = choose_chunk_bytes(body);
-  const uint64_t base = reinterpret_cast<uintptr_t>(dst);
-  uint64_t chunks = 0;
-  for (size_t k = 0; k < n; ++k) {
-    const Segment& s = segs[k];
-    a.seg[k] = {static_cast<const uint8_t*>(s.src), s.dst_off, s.len};
-    chunks += segment_chunks(base, s.dst_off, s.len, a.chunk_bytes);
-    if (chunks > 0x7fffffffull) return fail(DORA_ERR_INVALID, "pack: too many chunks");
-    a.chunk_end[k] = static_cast<uint32_t>(chunks);
-  }
-  a.nseg = static_cast<uint32_t>(n);
-  a.edge_mask = edge_mask(segs, n, dst, dst_cap);
-  a.n_chunks = static_cast<uint32_t>(chunks);
-  const uint64_t grid_cap = sig.flag ? kSignalGrid : kCpGridMulti;
-  a.grid = static_cast<uint32_t>(std::min<uint64_t>(chunks, grid_cap));
-  a.flag = sig.flag;
-  a.done = sig.done;
-  a.epoch = sig.epoch;
+  set_segs(a.seg, segs, n);
+  const int rc = finish_args(a, dst, sig, n, aql_chunk_bytes(segs, n),
+                             edge_mask(segs, n, dst, dst_cap),
+                             sig.flag ? Signal::kInKernel : Signal::kCp, false);
+  if (rc != DORA_OK) return rc;
   std::memcpy(out, &a, sizeof(a));
   *grid_out = a.grid;
   return DORA_OK;
 }
 
 // Arguments of the preloaded single-segment AQL kernels (aql_kernels.hip dora_aql_pack1_*):
-// dst, src, len, flag, done, epoch, chunk_bytes, grid — 56 bytes, the same chunk shape and grid
-// build_aql_args chooses for one segment at sample offset 0.
+// dst, src, len, flag, done, epoch, chunk_bytes, grid — 56 bytes, the head of a one-segment pack
+// at sample offset 0; the kernel derives the chunk layout itself.
 int build_aql_args1(const Segment& sg, uint8_t* dst, const FillSignal& sig, uint8_t* out,
                     uint32_t* grid_out) {
   if (sg.op != SEG_COPY || sg.dst_off != 0)
     return fail(DORA_ERR_INVALID, "AQL single-segment pack: segment at offset %llu",
                 (unsigned long long)sg.dst_off);
-  const uint64_t base = reinterpret_cast<uintptr_t>(dst);
-  const uint64_t cap = signal_grid_cap(sig);
-  const uint32_t chunk_bytes = choose_chunk_bytes(sg.len);
-  const uint64_t chunks = segment_chunks(base, 0, sg.len, chunk_bytes);
-  if (chunks > 0x7fffffffull) return fail(DORA_ERR_INVALID, "pack: too many chunks");
-  const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(chunks, cap));
+  PackArgsT<1> a;
+  std::memset(&a, 0, sizeof(a));
+  set_segs(a.seg, &sg, 1);
+  const int rc = finish_args(a, dst, sig, 1, aql_chunk_bytes(&sg, 1), 0,
+                             sig.flag ? Signal::kInKernel : Signal::kCp, true);
+  if (rc != DORA_OK) return rc;
   const uint64_t words[6] = {reinterpret_cast<uintptr_t>(dst), reinterpret_cast<uintptr_t>(sg.src),
                              sg.len, reinterpret_cast<uintptr_t>(sig.flag),
                              reinterpret_cast<uintptr_t>(sig.done), sig.epoch};
   std::memcpy(out, words, sizeof(words));
-  std::memcpy(out + 48, &chunk_bytes, 4);
-  std::memcpy(out + 52, &grid, 4);
-  *grid_out = grid;
+  std::memcpy(out + 48, &a.chunk_bytes, 4);
+  std::memcpy(out + 52, &a.grid, 4);
+  *grid_out = a.grid;
   return DORA_OK;
 }
 
@@ -754,92 +700,6 @@ int launch_csum(const void* data, size_t len, uint64_t* out_dev, hipStream_t str
   hipLaunchKernelGGL(csum_finalize, dim3(1), dim3(1), 0, stream,
                      reinterpret_cast<unsigned long long*>(out_dev), uint64_t(len));
   DORA_HIP(hipGetLastError());
-  return DORA_OK;
-}
-
-int launch_l2_touch(const void* p, size_t len, hipStream_t stream) {
-  if (len < 16) return DORA_OK;
-  int cus = 0, dev = 0;
-  DORA_HIP(hipGetDevice(&dev));
-  DORA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  hipLaunchKernelGGL(l2_touch_kernel, dim3(std::max(cus, 1)), dim3(kThreads), 0, stream,
-                     static_cast<const uint8_t*>(p), uint64_t(len), nullptr);
-  DORA_HIP(hipGetLastError());
-  return DORA_OK;
-}
-
-// One run of l1_stale_kernel (see there): `src` holds 64 words of pattern A, the host rewrites
-// them to pattern B once every workgroup has read them.  Out: workgroups whose first read was
-// not A (setup failures), whose second read still held A words (stale), and the workgroups.
-int l1_stale_probe(int device, int mode, uint32_t* bad_first, uint32_t* stale, uint32_t* blocks) {
-  *bad_first = *stale = *blocks = 0;
-  DORA_HIP(hipSetDevice(device));
-  int cus = 0;
-  DORA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-  const uint32_t nb = uint32_t(std::max(cus, 1));
-  void* bar = nullptr;
-  int rc = bar_alloc(device, 4096, &bar);
-  if (rc != DORA_OK) return rc;
-  uint32_t A[64], B[64];
-  for (uint32_t i = 0; i < 64; ++i) {
-    A[i] = 0xA0000000u | i;
-    B[i] = 0xB0000000u | i;
-  }
-  uint32_t *first = nullptr, *second = nullptr, *ctl = nullptr;
-  auto cleanup = [&] {
-    if (first) (void)hipFree(first);
-    if (second) (void)hipFree(second);
-    if (ctl) (void)hipHostFree(ctl);
-    bar_free(bar);
-  };
-  if (bar_write(device, bar, A, sizeof(A)) != DORA_OK ||
-      hipMalloc(&first, size_t(nb) * 256) != hipSuccess ||
-      hipMalloc(&second, size_t(nb) * 256) != hipSuccess ||
-      hipHostMalloc(&ctl, 128, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-    cleanup();
-    return fail(DORA_ERR_HIP, "l1 stale probe: setup");
-  }
-  volatile uint32_t* arrived = ctl;
-  volatile uint32_t* go = ctl + 16;  // its own cache line
-  *arrived = 0;
-  *go = 0;
-  uint32_t *d_arr = nullptr, *d_go = nullptr;
-  (void)hipHostGetDevicePointer(reinterpret_cast<void**>(&d_arr), ctl, 0);
-  d_go = d_arr + 16;
-  hipStream_t st = nullptr;
-  DORA_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  auto kern = mode == 0 ? l1_stale_kernel<0> : mode == 1 ? l1_stale_kernel<1> : l1_stale_kernel<2>;
-  hipLaunchKernelGGL(kern, dim3(nb), dim3(64), 0, st, static_cast<const uint32_t*>(bar), first,
-                     second, d_arr, d_go);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
-    // every workgroup has read A (bounded: a workgroup that never got a CU is just not counted)
-    const auto t0 = std::chrono::steady_clock::now();
-    while (*arrived < nb && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(2)) {
-    }
-    (void)bar_write(device, bar, B, sizeof(B));
-    __atomic_store_n(const_cast<uint32_t*>(go), 1u, __ATOMIC_SEQ_CST);
-    e = hipStreamSynchronize(st);
-  }
-  (void)hipStreamDestroy(st);
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(DORA_ERR_HIP, "l1 stale probe: %s", hipGetErrorString(e));
-  }
-  std::vector<uint32_t> f(size_t(nb) * 64), g(size_t(nb) * 64);
-  DORA_HIP(hipMemcpy(f.data(), first, f.size() * 4, hipMemcpyDeviceToHost));
-  DORA_HIP(hipMemcpy(g.data(), second, g.size() * 4, hipMemcpyDeviceToHost));
-  for (uint32_t b = 0; b < nb; ++b) {
-    bool bf = false, bs = false;
-    for (uint32_t i = 0; i < 64; ++i) {
-      bf |= f[b * 64 + i] != A[i];
-      bs |= g[b * 64 + i] == A[i];
-    }
-    *bad_first += bf;
-    *stale += bs;
-  }
-  *blocks = nb;
-  cleanup();
   return DORA_OK;
 }
 

@@ -18,6 +18,7 @@
 
 #include <cstdint>
 
+#include "dora_gpu_device.h"
 #include "plan.h"
 
 namespace dora {
@@ -28,7 +29,7 @@ constexpr int kMaxSegs = 32;       // segments of a HIP-launched pack
 constexpr int kMaxAqlSegs = 8;     // segments of an AQL-dispatched pack (smaller kernargs)
 // Workgroups of a signalling pack (r01 sweep, profiles/r01_signal_sweep.jsonl: 1024 beats 512
 // and 2048-4096 at 16-40 MB, flat at 4 MB).  Packs signalled by the command processor have no
-// done words to poll and take up to cp_grid() workgroups instead (aql.cpp).
+// done words to poll and take more workgroups instead (kernels.hip pack_grid).
 constexpr uint32_t kSignalGrid = 1024;
 // Chunk windows start on a cache line: a segment's body is cut into chunks from the 128-byte
 // line holding its first aligned unit, so every wave's 1 KiB store covers whole lines (64-byte
@@ -53,6 +54,20 @@ struct PackSeg {
   uint64_t dst_off;
   uint64_t len;
 };
+
+// The chunk layout of a launch, computed here alone for the host's argument builders and for the
+// kernels that derive it themselves: chunk_end[k] = chunks of segments 0..k of a destination at
+// `base`.  Returns the launch's chunk count; 0: more than a chunk index holds (0x7fffffff).
+__host__ __device__ inline uint32_t chunk_layout(uint64_t base, const PackSeg* seg, uint32_t nseg,
+                                                 uint32_t chunk_bytes, uint32_t* chunk_end) {
+  uint64_t chunks = 0;
+  for (uint32_t k = 0; k < nseg; ++k) {
+    chunks += segment_chunks(base, seg[k].dst_off, seg[k].len, chunk_bytes);
+    if (chunks > 0x7fffffffull) return 0;
+    chunk_end[k] = static_cast<uint32_t>(chunks);
+  }
+  return static_cast<uint32_t>(chunks);
+}
 
 template <int MAXSEG>
 struct PackArgsT {
@@ -329,124 +344,43 @@ __device__ __forceinline__ void pack_chunk(const A& args, uint32_t chunk) {
   }
 }
 
-// In-kernel fill signal.  A signalling launch writes the sample through to device scope (sc1:
-// no dirty lines left in the per-XCD L2s, so no cache write-back is needed), every workgroup
-// waits for its stores to complete and publishes the epoch in its own done word, and
-// workgroup 0 — dispatched first — polls all done words and then stores the epoch into the
-// host fill flag with a system-scope release.  No same-address atomics (those serialise at
-// ~0.1 us each across XCDs) and no L2 write-back per workgroup (~0.1 us each, serial per
-// XCD): this replaces the stream write-value packet, a ~4 us blit kernel plus a kernel
-// boundary per message on ROCm 7.
+// In-kernel fill signal of a pack launch: the protocol of include/dora_gpu_device.h (arrive, wait
+// for all, raise; the reasoning is there).  A signalling launch writes the sample through to
+// device scope, every wave waits for its own stores before the workgroup's barrier, every
+// workgroup arrives on its own done word, and workgroup 0 — dispatched first — polls them all
+// (up to kMaxSignalWgs / kThreads = 16 loads in flight per lane) and then runs `raise`, which
+// the caller supplies: a single pack stamps and raises its flag, a batch every message's.  A lost
+// workgroup: nothing is raised, receivers report the failure.
 // `blk`/`nblk`: this workgroup and the launch's workgroup count, passed in so that the AQL
 // kernels need no hidden kernel arguments.
-// Workgroup 0 also stamps the launch (s_memrealtime, 100 MHz) into the flag's line: its own
-// start, taken on entry, and the time it signals — the fill's device time without a profiled
-// queue or timing events.
-__device__ __forceinline__ void stamp_fill(uint64_t* flag, uint64_t t_start) {
-  __hip_atomic_store(flag + 1, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(flag + 2, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-template <class A>
-__device__ __forceinline__ void signal_fill(const A& a, uint32_t blk, uint32_t nblk,
-                                            uint64_t t_start) {
-  const uint32_t e = static_cast<uint32_t>(a.epoch);
+template <class Raise>
+__device__ __forceinline__ void signal_fill(uint32_t* done, uint64_t epoch, uint32_t blk,
+                                            uint32_t nblk, Raise raise) {
+  const uint32_t e = static_cast<uint32_t>(epoch);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's sample stores are complete
   __syncthreads();
-  if (nblk == 1) {  // nothing to wait for but this workgroup's own stores
-    if (threadIdx.x == 0) {
-      stamp_fill(a.flag, t_start);
-      __hip_atomic_store(a.flag, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    return;
+  if (nblk > 1) {  // else nothing to wait for but this workgroup's own stores
+    dora_gu32* const gdone = (dora_gu32*)done;
+    dora_fill_arrive(gdone, blk, e, threadIdx.x);
+    if (blk != 0 || !dora_fill_wait_all<kMaxSignalWgs / kThreads>(gdone, nblk, e, threadIdx.x,
+                                                                  kThreads))
+      return;
   }
-  if (threadIdx.x == 0) __hip_atomic_store(a.done + blk, e, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-  if (blk != 0) return;
-  // Poll every done word at once per round (up to kMaxSignalWgs / kThreads = 16 independent
-  // loads in flight per lane), so completion is seen one load round trip after the last
-  // workgroup.  Bounded (~seconds): a lost workgroup must not hang the device; the flag then
-  // stays unset and the receiver reports the fill as failed.  The workgroup vote goes through
-  // one LDS word (__syncthreads_and would read the workgroup size from hidden arguments).
-  constexpr int kPer = kMaxSignalWgs / kThreads;
-  __shared__ uint32_t missing;
-  bool ok = false;
-  for (uint32_t round = 0; round < (1u << 22); ++round) {
-    if (threadIdx.x == 0) missing = 0;
-    __syncthreads();
-    uint32_t v[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const uint32_t i = threadIdx.x + k * kThreads;
-      v[k] = i < nblk ? __hip_atomic_load(a.done + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                      : e;
-    }
-    bool mine = true;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) mine &= v[k] == e;
-    if (!mine) missing = 1;
-    __syncthreads();
-    const bool all = missing == 0;
-    __syncthreads();
-    if (all) {
-      ok = true;
-      break;
-    }
-    __builtin_amdgcn_s_sleep(1);
-  }
-  // Relaxed: everything this store publishes is already written through (sample stores and done
-  // words are device-scope write-through and complete), and it issues only after every done
-  // word was observed; a release would write back this XCD's whole L2 for nothing.
-  if (threadIdx.x == 0 && ok) {
-    stamp_fill(a.flag, t_start);
-    __hip_atomic_store(a.flag, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  raise();
 }
 
-// A batch's signal: as signal_fill, and workgroup 0's lanes k < nmsg then stamp and signal
-// message k's flag (every message completes with the whole batch).
-__device__ __forceinline__ void signal_batch(const AqlBatchArgs& a, uint32_t blk, uint32_t nblk,
-                                             uint64_t t_start) {
-  const uint32_t e = static_cast<uint32_t>(a.epoch);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+// The stamps of a pack the command processor signals inside a timed region.  `st` is its stamp
+// area (device memory, zeroed by the host, read once the region's packs have all completed):
+// [0] the first workgroup's start, [1 + blk mod kCpStampWgs] the latest time a workgroup mapping
+// there had all its stores complete (system-scope atomic max: performed past the L2s, where the
+// host's BAR read finds it; a grid of any size fits the area).  Every wave has waited for its
+// stores before the call.
+__device__ __forceinline__ void stamp_cp(uint64_t* st, uint32_t blk, uint64_t t_start) {
   __syncthreads();
-  if (nblk > 1) {
-    if (threadIdx.x == 0)
-      __hip_atomic_store(a.done + blk, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (blk != 0) return;
-    constexpr int kPer = kMaxSignalWgs / kThreads;
-    __shared__ uint32_t missing;
-    bool ok = false;
-    for (uint32_t round = 0; round < (1u << 22); ++round) {
-      if (threadIdx.x == 0) missing = 0;
-      __syncthreads();
-      uint32_t v[kPer];
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) {
-        const uint32_t i = threadIdx.x + k * kThreads;
-        v[k] = i < nblk ? __hip_atomic_load(a.done + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                        : e;
-      }
-      bool mine = true;
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) mine &= v[k] == e;
-      if (!mine) missing = 1;
-      __syncthreads();
-      const bool all = missing == 0;
-      __syncthreads();
-      if (all) {
-        ok = true;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (!ok) return;  // a lost workgroup: the flags stay unset, receivers report the failure
-  }
-  if (threadIdx.x < a.nmsg) {
-    const BatchMsg m = a.msg[threadIdx.x];
-    stamp_fill(m.flag, t_start);
-    __hip_atomic_store(m.flag, m.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x == 0) {
+    __hip_atomic_fetch_max(st + 1 + (blk % kCpStampWgs), __builtin_amdgcn_s_memrealtime(),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (blk == 0) __hip_atomic_store(st, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -461,30 +395,24 @@ __device__ __forceinline__ void pack_body(const A& args, uint32_t blk, uint32_t 
   for (uint32_t c = blk; c < args.n_chunks; c += nblk) pack_chunk<U, NT>(args, c);
   if constexpr (NT >= 2) {
     if (args.flag) {  // all-zero arguments are a no-op
-      if constexpr (__is_same(A, AqlBatchArgs)) {
-        signal_batch(args, blk, nblk, t_start);
-      } else {
-        signal_fill(args, blk, nblk, t_start);
-      }
+      signal_fill(args.done, args.epoch, blk, nblk, [&]() __attribute__((always_inline)) {
+        if constexpr (__is_same(A, AqlBatchArgs)) {
+          // lanes k < nmsg raise message k's flag (every message completes with the whole batch)
+          if (threadIdx.x < args.nmsg) {
+            const BatchMsg m = args.msg[threadIdx.x];
+            dora_fill_raise((dora_gu64*)m.flag, m.epoch, t_start);
+          }
+        } else {
+          if (threadIdx.x == 0) dora_fill_raise((dora_gu64*)args.flag, args.epoch, t_start);
+        }
+      });
     } else if (args.done) {
       // done words but no flag: the dispatch's completion signal reports the fill (the command
       // processor's, aql.cpp aql_cp_candidate); every wave's stores are complete before it ends
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (args.epoch) {
-        // a pack inside a timed region: `epoch` is its stamp area (device memory, zeroed by the
-        // host, read once the region's packs have all completed) — [0] the first workgroup's
-        // start, [1 + blk mod kCpStampWgs] the latest time a workgroup mapping there had all its
-        // stores complete (system-scope atomic max: performed past the L2s, where the host's BAR
-        // read finds it; a grid of any size fits the area)
-        uint64_t* st = reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(args.epoch));
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          __hip_atomic_fetch_max(st + 1 + (blk % kCpStampWgs), __builtin_amdgcn_s_memrealtime(),
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          if (blk == 0)
-            __hip_atomic_store(st, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
+      // a pack inside a timed region: `epoch` is its stamp area
+      if (args.epoch)
+        stamp_cp(reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(args.epoch)), blk, t_start);
     }
   }
 }

@@ -2,7 +2,7 @@
 // the shipped library (dora_amd/build.py build_testing) and linked against it — the product's
 // ABI (include/dora_gpu.h) carries none of them.  Declared in include/dora_gpu_testing.h; used by
 // tests/ and scripts/ only.  Each hook calls into the library's internals (aql.cpp, kernels.hip,
-// bincode.cpp, bcast.cpp, shm.h).
+// bincode.cpp, bcast.cpp, shm.h) or into this library's own kernels (fence_probes.hip).
 #include <hip/hip_runtime_api.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -23,6 +23,7 @@
 #include "common.h"
 #include "dora_gpu.h"
 #include "dora_gpu_testing.h"
+#include "fence_probes.h"
 #include "plan.h"
 #include "shm.h"
 
@@ -30,8 +31,6 @@ namespace dora {
 // kernels.hip
 int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t cap,
                          uint32_t* grid);
-int launch_l2_touch(const void* p, size_t len, hipStream_t stream);
-int l1_stale_probe(int device, int mode, uint32_t* bad_first, uint32_t* stale, uint32_t* blocks);
 void gather_force(int mode);
 }  // namespace dora
 

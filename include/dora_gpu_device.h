@@ -63,14 +63,80 @@ __device__ __forceinline__ void (dora_st1)(void* p, uint8_t v) {
  * it to dora_fill_publish as `t_start` to have the stamps span the whole kernel. */
 __device__ __forceinline__ uint64_t (dora_fill_clock)() { return __builtin_amdgcn_s_memrealtime(); }
 
-/* Stamp the flag line (start, signal time) and raise the flag: one lane of workgroup 0. */
-__device__ __forceinline__ void (dora_fill_raise)(const dora_fill_ticket& t, uint64_t t_start) {
-  dora_gu64* const flag = reinterpret_cast<dora_gu64*>(static_cast<uintptr_t>(t.flag));
+/* ------------------------------------------------------------------------------------------ */
+/* The fill signal, in three steps.  This is its one home: dora_fill_publish below and the      */
+/* library's own pack kernels are all built from these.  `wg` / `nwg`: the workgroup and the    */
+/* launch's workgroup count; `tid` / `nthreads`: the lane's linear index in its workgroup and   */
+/* the workgroup's size.  All passed in: nothing here reads blockDim or gridDim, so a kernel    */
+/* dispatched without hidden arguments can call them.                                           */
+/*                                                                                              */
+/* Before the first step every wave waits for its own stores (s_waitcnt vmcnt(0)) and the       */
+/* workgroup passes a barrier: the caller's part, because what is waited for differs (a pack's  */
+/* stores, a read-signalled pack's loads, a plain-store kernel's write-back).  With the sample  */
+/* written through to device scope (sc1) no dirty line is left in the per-XCD L2s, so nothing   */
+/* below needs a release: no same-address atomics (those serialise at ~0.1 us each across XCDs) */
+/* and no L2 write-back per workgroup (~0.1 us each, serial per XCD).  For the packs this       */
+/* replaces the stream write-value packet, a ~4 us blit kernel plus a kernel boundary per       */
+/* message on ROCm 7.                                                                           */
+/* ------------------------------------------------------------------------------------------ */
+
+/* Arrive: lane 0 stores the epoch's low word into the workgroup's own done word. */
+__device__ __forceinline__ void (dora_fill_arrive)(dora_gu32* done, uint32_t wg, uint32_t e,
+                                                   uint32_t tid) {
+  if (tid == 0) __hip_atomic_store(done + wg, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+/*
+ * Wait for all: workgroup 0 only, every thread of it in uniform control flow.  Polls every done
+ * word once per round, LOADS independent loads in flight per lane, so completion is seen one
+ * load round trip after the last workgroup arrived.  True once every word holds `e`.  Bounded,
+ * 2^22 rounds (seconds): a lost workgroup must not hang the device; the caller then leaves the
+ * flag unset and the receiver reports the fill as failed.  The workgroup's vote goes through one
+ * LDS word (__syncthreads_and would read the workgroup size from hidden arguments): 16 bytes of
+ * static LDS, 16-byte aligned, so that a dynamic LDS base stays 16-byte aligned.
+ */
+template <int LOADS>
+__device__ __forceinline__ bool (dora_fill_wait_all)(const dora_gu32* done, uint32_t nwg,
+                                                     uint32_t e, uint32_t tid,
+                                                     uint32_t nthreads) {
+  __shared__ __attribute__((aligned(16))) uint32_t missing[4];
+  for (uint32_t round = 0; round < (1u << 22); ++round) {
+    if (tid == 0) missing[0] = 0;
+    __syncthreads();
+    bool mine = true;
+    for (uint32_t base = tid; base < nwg; base += LOADS * nthreads) {
+      uint32_t v[LOADS];
+#pragma unroll
+      for (int k = 0; k < LOADS; ++k) {
+        const uint32_t i = base + k * nthreads;
+        v[k] = i < nwg ? __hip_atomic_load(done + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                       : e;
+      }
+#pragma unroll
+      for (int k = 0; k < LOADS; ++k) mine &= v[k] == e;
+    }
+    if (!mine) missing[0] = 1;
+    __syncthreads();
+    const bool all = missing[0] == 0;
+    __syncthreads();
+    if (all) return true;
+    __builtin_amdgcn_s_sleep(1);
+  }
+  return false;
+}
+
+/* Raise: stamp the flag line (the launch's start, taken on entry, and the time it signals,
+ * s_memrealtime: the fill's device time without a profiled queue or timing events) and store the
+ * epoch into the flag.  One lane of workgroup 0. */
+__device__ __forceinline__ void (dora_fill_raise)(dora_gu64* flag, uint64_t epoch,
+                                                  uint64_t t_start) {
   __hip_atomic_store(flag + 1, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   __hip_atomic_store(flag + 2, (dora_fill_clock)(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  /* relaxed: everything this store publishes is complete and written through or written back,
-   * and it issues only after every done word was observed */
-  __hip_atomic_store(flag, t.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  /* Relaxed: everything this store publishes is already complete and written through (sample
+   * stores and done words are device-scope write-through) or written back, and it issues only
+   * after every done word was observed; a release would write back this XCD's whole L2 for
+   * nothing. */
+  __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 /*
@@ -80,9 +146,9 @@ __device__ __forceinline__ void (dora_fill_raise)(const dora_fill_ticket& t, uin
  * Any workgroup size and shape.  `t_start`: the start stamp (0: now).
  *
  * Each workgroup raises its done word once its stores are complete; workgroup 0 polls all of
- * them and then raises the flag.  The poll is bounded (~2 s): a lost workgroup leaves the flag
- * unset and never hangs the device.  Uses 16 bytes of static LDS (a 16-byte-aligned vote word:
- * a dynamic LDS base stays 16-byte aligned).
+ * them, eight loads in flight per lane, and then raises the flag.  The poll is bounded (2^22
+ * rounds, seconds): a lost workgroup leaves the flag unset and never hangs the device.  Uses the
+ * 16 bytes of static LDS of dora_fill_wait_all.
  */
 __device__ __forceinline__ void (dora_fill_publish)(const dora_fill_ticket t, uint32_t wg,
                                                     uint32_t nwg, uint64_t t_start = 0) {
@@ -100,50 +166,15 @@ __device__ __forceinline__ void (dora_fill_publish)(const dora_fill_ticket t, ui
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  if (nwg == 1) { /* nothing to wait for but this workgroup's own stores */
-    if (tid == 0) (dora_fill_raise)(t, t_start);
-    return;
+  if (nwg > 1) { /* else nothing to wait for but this workgroup's own stores */
+    const uint32_t e = static_cast<uint32_t>(t.epoch);
+    dora_gu32* const done = reinterpret_cast<dora_gu32*>(static_cast<uintptr_t>(t.done));
+    (dora_fill_arrive)(done, wg, e, tid);
+    if (wg != 0 || !(dora_fill_wait_all<8>)(done, nwg, e, tid, nthreads)) return;
   }
-  const uint32_t e = static_cast<uint32_t>(t.epoch);
-  dora_gu32* const done = reinterpret_cast<dora_gu32*>(static_cast<uintptr_t>(t.done));
-  if (tid == 0) __hip_atomic_store(done + wg, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (wg != 0) return;
-  /* vote[0]: some lane saw a done word below the epoch this round; vote[1]: give up */
-  __shared__ __attribute__((aligned(16))) uint32_t vote[4];
-  const uint64_t t0 = (dora_fill_clock)();
-  bool ok = false;
-  for (;;) {
-    if (tid == 0) {
-      vote[0] = 0;
-      vote[1] = (dora_fill_clock)() - t0 > 200000000ull ? 1u : 0u;
-    }
-    __syncthreads();
-    /* every done word once per round, eight independent loads in flight per lane */
-    bool mine = true;
-    for (uint32_t base = tid; base < nwg; base += 8 * nthreads) {
-      uint32_t v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { /* past the end: word 0 again, so the loads stay unconditional */
-        const uint32_t i = base + k * nthreads;
-        v[k] = __hip_atomic_load(done + (i < nwg ? i : 0u), __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) mine &= v[k] == e;
-    }
-    if (!mine) vote[0] = 1;
-    const bool give_up = vote[1] != 0;
-    __syncthreads();
-    const bool all = vote[0] == 0;
-    __syncthreads();
-    if (all) {
-      ok = true;
-      break;
-    }
-    if (give_up) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  if (tid == 0 && ok) (dora_fill_raise)(t, t_start);
+  if (tid == 0)
+    (dora_fill_raise)(reinterpret_cast<dora_gu64*>(static_cast<uintptr_t>(t.flag)), t.epoch,
+                      t_start);
 }
 
 /* The same for a launch whose workgroups are all of its grid: linearises blockIdx / gridDim. */

@@ -66,6 +66,10 @@ def test_test_hooks_live_in_their_own_library(lib):
     exported = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
                               text=True, check=True).stdout
     assert "dora_gpu_test_" not in exported
+    # nor the test tools' kernels and launchers (the fence probes, csrc/testing/fence_probes.hip)
+    demangled = subprocess.run(["nm", "-D", "-C", _lib.LIB_PATH], capture_output=True, text=True,
+                               check=True).stdout
+    assert "l1_stale" not in demangled and "l2_touch" not in demangled
 
 
 def test_product_library_has_no_tuning_entry_point(lib):
