@@ -57,6 +57,11 @@ class Tensor(ctypes.Structure):
                 ("shape", POINTER(c_int64)), ("strides", POINTER(c_int64))]
 
 
+class TensorField(ctypes.Structure):
+    """dora_tensor_field of include/dora_gpu.h: a named tensor of a struct-of-tensors message."""
+    _fields_ = [("name", c_char_p), ("tensor", Tensor)]
+
+
 class FillTicket(ctypes.Structure):
     """dora_fill_ticket of include/dora_fill_ticket.h (32 bytes): what dora_sample_fill_ticket
     issues and a publishing kernel takes by value."""
@@ -97,6 +102,9 @@ _SIGS = {
                               POINTER(c_void_p)]),
     "dora_gpu_plan_bytes": (c_int, [c_void_p, c_size_t, c_int32, POINTER(c_void_p)]),
     "dora_gpu_plan_tensor": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
+    "dora_gpu_plan_tensor_struct": (c_int, [c_void_p, c_size_t, c_int32, POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_struct": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
+                                                    c_int32, c_char_p, c_size_t, c_uint32]),
     "dora_node_send_output_tensor": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                              c_size_t, c_uint32]),
     "dora_gpu_plan_compact": (c_int, [POINTER(ArrowArray), POINTER(ArrowSchema), c_int32,
@@ -226,6 +234,12 @@ _TEST_SIGS = {
                                           POINTER(c_int), POINTER(c_uint64), POINTER(c_uint32),
                                           POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
                                           POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
+    "dora_gpu_test_plan_field": (c_int, [c_void_p, c_size_t, c_void_p, POINTER(c_size_t),
+                                         POINTER(c_int), POINTER(c_uint64), POINTER(c_uint64),
+                                         POINTER(c_int), POINTER(c_void_p), POINTER(c_int),
+                                         POINTER(c_uint64), POINTER(c_uint32),
+                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
+                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
     "dora_gpu_test_aql_hold": (c_int, [c_int, c_int]),
     "dora_gpu_test_reduce_timeout": (c_int, [c_uint64]),
     "dora_gpu_test_d2h_copy_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_uint64, c_void_p]),

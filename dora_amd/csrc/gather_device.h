@@ -374,5 +374,73 @@ DORA_HD void store_phase(const Args& a, const Origin& o, uint32_t thread, M& m) 
 
 }  // namespace tile
 
+// ------------------------------------------------------------------------------------------
+// Several views in one launch (gather_struct_kernel): the fields of a struct-of-tensors plan,
+// each written to its own byte range of one sample.  Every field keeps the arguments and the body
+// it would have on its own (rows: gather_lane over the field's lanes; tile: the tile loop over
+// the field's workgroups); the launch's workgroups are dealt to the fields in order, each field
+// getting the grid its own kernel would have used, and a workgroup finds its field by scanning
+// the table of first workgroups.  A field's writes stay inside [dst, dst + total) of its own
+// arguments — the head / tail bytes and the tile predicates see to that — so the padding between
+// fields and the neighbours' bytes are never touched.
+// ------------------------------------------------------------------------------------------
+namespace multi {
+
+constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
+enum Kind : uint32_t { kRows = 0, kTile = 1 };
+
+struct Field {
+  uint32_t kind;
+  uint32_t pad;
+  union {
+    gather::Args rows;
+    tile::Args tile;
+  };
+};
+
+struct Args {
+  uint32_t n;
+  uint32_t wg_begin[kMaxFields + 1];  // field k runs workgroups [wg_begin[k], wg_begin[k + 1])
+  Field f[kMaxFields];
+};
+static_assert(sizeof(Args) <= 4096, "multi::Args is passed by value: the kernel-argument limit");
+
+// Arguments of the gather of g[0..n) into dst + off[k]; tile_c[k] is the source-contiguous
+// dimension the tile body transposes field k against, or negative for the rows body (the
+// launcher's selection).  The grid is wg_begin[n]: at most 8 * 2^20 workgroups.
+DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile_c, int n,
+                       uint8_t* dst) {
+  Args a{};
+  a.n = static_cast<uint32_t>(n);
+  uint32_t wg = 0;
+  for (int k = 0; k < n; ++k) {
+    a.wg_begin[k] = wg;
+    Field& f = a.f[k];
+    if (tile_c[k] >= 0) {
+      f.kind = kTile;
+      f.tile = tile::make_args(g[k], dst + off[k], tile_c[k]);
+      wg += static_cast<uint32_t>(tile::grid_for(f.tile));
+    } else {
+      f.kind = kRows;
+      f.rows = gather::make_args(g[k], dst + off[k]);
+      wg += static_cast<uint32_t>(gather::grid_for(f.rows));
+    }
+  }
+  for (int k = n; k <= kMaxFields; ++k) a.wg_begin[k] = wg;
+  return a;
+}
+
+DORA_HD uint32_t grid_for(const Args& a) { return a.wg_begin[a.n]; }
+
+// The field workgroup `w` (< grid_for) belongs to: uniform over the workgroup, at most
+// kMaxFields - 1 steps.
+DORA_HD int field_of(const Args& a, uint32_t w) {
+  int k = 0;
+  while (k + 1 < static_cast<int>(a.n) && w >= a.wg_begin[k + 1]) ++k;
+  return k;
+}
+
+}  // namespace multi
+
 }  // namespace gather
 }  // namespace dora

@@ -268,16 +268,49 @@ struct TileMem {
   }
 };
 
+// Tiles first, first + step, .. of `a` through the workgroup's tile `lds`.
 template <typename T>
-__global__ __launch_bounds__(gather::kThreads) void gather_tile_kernel(gather::tile::Args a) {
-  __shared__ T lds[gather::tile::kLds];
+__device__ __forceinline__ void tile_loop(const gather::tile::Args& a, uint64_t first,
+                                          uint64_t step, T* lds) {
   TileMem<T> m{a.src, a.dst, lds};
-  for (uint64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+  for (uint64_t t = first; t < a.ntiles; t += step) {
     const gather::tile::Origin o = gather::tile::origin(a, t);
     gather::tile::load_phase(a, o, threadIdx.x, m);
     __syncthreads();
     gather::tile::store_phase(a, o, threadIdx.x, m);
     __syncthreads();  // the tile is reused by this workgroup's next one
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(gather::kThreads) void gather_tile_kernel(gather::tile::Args a) {
+  __shared__ T lds[gather::tile::kLds];
+  tile_loop<T>(a, blockIdx.x, gridDim.x, lds);
+}
+
+// gather_struct_kernel: the fields of a struct-of-tensors plan in one launch (gather_device.h
+// multi::).  A workgroup finds its field in the table (a uniform scan of at most 7 steps) and
+// runs that field's own body over the field's share of the grid: gather_lane with the lane
+// numbered inside the share, or the tile loop over one LDS buffer of 8-byte words that serves
+// every element size (8.25 KiB a workgroup: the four workgroups a CU holds at the rows body's
+// register count take 33 of its 160 KiB, so the buffer costs the rows fields no occupancy,
+// DESIGN §4).
+__global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  const uint32_t w = blockIdx.x;
+  const int k = gather::multi::field_of(a, w);
+  const gather::multi::Field& f = a.f[k];
+  const uint64_t local = w - a.wg_begin[k], share = a.wg_begin[k + 1] - a.wg_begin[k];
+  if (f.kind == gather::multi::kRows) {
+    GatherMem m{f.rows.src, f.rows.dst};
+    gather::gather_lane(f.rows, local * gather::kThreads + threadIdx.x, share * gather::kThreads, m);
+    return;
+  }
+  switch (f.tile.elem) {
+    case 1: tile_loop(f.tile, local, share, reinterpret_cast<uint8_t*>(lds)); break;
+    case 2: tile_loop(f.tile, local, share, reinterpret_cast<uint16_t*>(lds)); break;
+    case 4: tile_loop(f.tile, local, share, reinterpret_cast<uint32_t*>(lds)); break;
+    default: tile_loop(f.tile, local, share, lds); break;
   }
 }
 
@@ -485,6 +518,17 @@ int check_device_range(const GatherDesc& g, int device) {
   return DORA_OK;
 }
 
+int check_plan_range(const dora_plan& plan, int device) {
+  if (plan.fields.empty()) return check_device_range(plan.gd, device);
+  for (size_t k = 0; k < plan.fields.size(); ++k) {
+    const int rc = check_device_range(plan.fields[k].gd, device);
+    if (rc == DORA_OK) continue;
+    const std::string why = dora_gpu_last_error();
+    return fail(rc, "field %zu `%s`: %s", k, plan.fields[k].name.c_str(), why.c_str());
+  }
+  return DORA_OK;
+}
+
 // Which kernel gathers `g` into `dst`, stated once.  The tiled transpose, where it applies
 // (tile::contiguous_dim: a source-contiguous dimension c that is not the output's innermost
 // dimension j, everything element-aligned), when c is at least kTileMinC elements long and a row
@@ -538,6 +582,39 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEven
   }
   DORA_HIP(hipGetLastError());
   return DORA_OK;
+}
+
+int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
+                         hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (n == 0 || n > size_t(gather::multi::kMaxFields))
+    return fail(DORA_ERR_INVALID, "gather of %zu struct fields", n);
+  GatherDesc g[gather::multi::kMaxFields];
+  uint64_t off[gather::multi::kMaxFields];
+  int tile_c[gather::multi::kMaxFields];
+  for (size_t k = 0; k < n; ++k) {
+    if (!fields[k].bytes) return fail(DORA_ERR_INVALID, "gather of an empty struct field");
+    g[k] = fields[k].gd;
+    off[k] = fields[k].dst_off;
+    tile_c[k] = select_tile_dim(g[k], dst + off[k]);  // each field as it would go on its own
+  }
+  const gather::multi::Args a = gather::multi::make_args(g, off, tile_c, static_cast<int>(n), dst);
+  const dim3 grid(gather::multi::grid_for(a));
+  if (ev_start || ev_stop) {
+    hipExtLaunchKernelGGL(gather_struct_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
+                          ev_stop, 0, a);
+  } else {
+    hipLaunchKernelGGL(gather_struct_kernel, grid, dim3(gather::kThreads), 0, stream, a);
+  }
+  DORA_HIP(hipGetLastError());
+  return DORA_OK;
+}
+
+int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
+                       hipEvent_t ev_start, hipEvent_t ev_stop) {
+  return plan.fields.empty()
+             ? launch_gather(plan.gd, dst, stream, ev_start, ev_stop)
+             : launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
+                                    ev_stop);
 }
 
 // Launch a pack and wait for it by spinning on a host flag the launch writes itself (a
@@ -736,11 +813,11 @@ int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_
     // a device tensor view: inside one allocation of the current GPU before anything reads it
     int device = 0;
     DORA_HIP(hipGetDevice(&device));
-    const int rc = dora::check_device_range(plan->gd, device);
+    const int rc = dora::check_plan_range(*plan, device);
     if (rc != DORA_OK) return rc;
     if (plan->gather)
-      return dora::launch_gather(plan->gd, static_cast<uint8_t*>(dst),
-                                 static_cast<hipStream_t>(stream));
+      return dora::launch_plan_gather(*plan, static_cast<uint8_t*>(dst),
+                                      static_cast<hipStream_t>(stream));
   }
   return dora::launch_pack(plan->segs.data(), plan->segs.size(), plan->dev,
                            static_cast<uint8_t*>(dst), static_cast<hipStream_t>(stream), nullptr,

@@ -408,15 +408,16 @@ int fill_sample(dora_node* n, dora_sample* s, const Segment* segs, size_t nseg,
   return DORA_OK;
 }
 
-// Launch the gather of a strided device tensor view (a gather plan, tensor_plan.cpp) into sample
+// Launch the gather of a gather plan (tensor_plan.cpp: one strided device tensor view, or the
+// fields of a struct of device tensors of which any is strided, in one launch) into sample
 // `s` on stream `st` (null: the next fill stream, ordered after the node stream) and let the
 // stream write the fill epoch behind it (order_fill): no AQL packet, no in-kernel signal.
-int gather_sample(dora_node* n, dora_sample* s, const GatherDesc& g, hipStream_t st,
+int gather_sample(dora_node* n, dora_sample* s, const dora_plan& plan, hipStream_t st,
                   hipEvent_t t_start, hipEvent_t t_stop, bool signal) {
   DeviceScope ds(n->core->device);
   if (!st) st = n->core->next_fill_stream();
   ++n->hip_packs;
-  int rc = launch_gather(g, static_cast<uint8_t*>(s->slot->ptr), st, t_start, t_stop);
+  int rc = launch_plan_gather(plan, static_cast<uint8_t*>(s->slot->ptr), st, t_start, t_stop);
   if (rc != DORA_OK || !signal) return rc;  // (a broadcast-group send orders what follows itself)
   for (size_t i = 0; i < n->core->fill_streams.size(); ++i)
     if (n->core->fill_streams[i] == st) n->core->fill_unsignalled[i] = 1;
@@ -599,7 +600,7 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
     // a device tensor view: its strides are the caller's, so the runtime names the allocation
     // it must lie in before anything is allocated or launched
     DeviceScope ds(n->core->device);
-    const int rc = check_device_range(plan->gd, n->core->device);
+    const int rc = check_plan_range(*plan, n->core->device);
     if (rc != DORA_OK) return rc;
   }
   // a device array for receivers that all lack a GPU: packed into shared memory
@@ -670,7 +671,7 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
     const bool sync = plan->dev == ARROW_DEVICE_ROCM &&
                       !((flags & DORA_SEND_ASYNC) || n->async_default);
     rc = plan->gather
-             ? gather_sample(n, s, plan->gd, bcast ? bo->second.stream : nullptr, t_start, t_stop,
+             ? gather_sample(n, s, *plan, bcast ? bo->second.stream : nullptr, t_start, t_stop,
                              !bcast)
              : fill_sample(n, s, plan->segs.data(), plan->segs.size(), plan->dev,
                            bcast ? bo->second.stream : nullptr, t_start, t_stop, !bcast, sync);
@@ -997,6 +998,25 @@ int dora_node_send_output_tensor(dora_node* n, const char* output_id, const dora
   // staging buffer when strided: a host source, which the send has read when it returns.  A
   // device view is one copy segment when dense and a gather when strided; the synchronous send
   // waits until the kernel has read it
+  std::unique_ptr<dora_plan> owner(plan);
+  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
+  DORA_GUARD_END
+}
+
+int dora_node_send_output_tensor_struct(dora_node* n, const char* output_id,
+                                        const dora_tensor_field* fields, size_t count,
+                                        ArrowDeviceType device_type, const uint8_t* params,
+                                        size_t params_len, uint32_t flags) {
+  if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  dora_plan* plan = nullptr;
+  {
+    dora::SubSpan sp(dora::SP_SEND_PLAN);
+    const int rc = dora::build_tensor_struct_plan(fields, count, device_type, &plan);
+    if (rc != DORA_OK) return rc;
+  }
+  // host fields and all-dense device fields: a multi-segment plan like any other; device fields
+  // of which any is strided: a gather plan, which goes where a single strided tensor's goes
   std::unique_ptr<dora_plan> owner(plan);
   return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
   DORA_GUARD_END

@@ -98,6 +98,17 @@ struct GatherDesc {
   int64_t lo, hi;
 };
 
+// One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
+// own tensor plan would describe it (dense: nd == 0), where its row-major values start in the
+// sample and how many bytes they are.  Fields follow one another in destination order.
+constexpr size_t kMaxStructFields = 8;
+struct PlanField {
+  std::string name;
+  GatherDesc gd;
+  uint64_t dst_off;
+  uint64_t bytes;
+};
+
 // Fill signal written by a pack launch itself (kernels.hip): once every workgroup's stores are
 // complete, a system-scope store of `epoch` into `flag` (device view of a host-registered fill
 // flag), preceded by the launch's start / signal times into flag[1], flag[2] (the flag must own
@@ -140,11 +151,23 @@ int launch_pack(const Segment* segs, size_t n, ArrowDeviceType dev, uint8_t* dst
 // The allocation holding `g.view.src` must be device memory of `device` and contain
 // [src + lo, src + hi]; DORA_ERR_INVALID naming both otherwise (kernels.hip).
 int check_device_range(const GatherDesc& g, int device);
+// The same for everything a device tensor plan reads: its one view, or every field of a struct
+// plan (each may sit in an allocation of its own; a refusal names the field).
+int check_plan_range(const dora_plan& plan, int device);
 // Launch the gather of a strided device view into `dst` (16-byte units of the row-major output,
 // write-through stores; nothing at or past dst + g.view.total) on `stream` (kernels.hip); with
 // timing events, the dispatch stamps its begin into `ev_start` and its end into `ev_stop`.
 int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream,
                   hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// Launch the gather of every field of a multi-gather struct plan into `dst + dst_off` in one
+// launch of gather_struct_kernel (kernels.hip): each field's bytes as launch_gather writes them,
+// nothing between fields and nothing at or past the last field's end.
+int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
+                         hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+// The gather a gather plan asks for: launch_gather of its view, or launch_gather_struct of its
+// fields.
+int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
+                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
 // Pack device segments into `dst` (device or mapped host memory) and return once complete,
 // waiting on the launch's own fill signal instead of a blocking stream synchronise.
@@ -169,6 +192,9 @@ int build_plan(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceTy
                dora_plan** out, bool validity_in_sample = false);
 // A tensor view in host or device memory (dora_gpu_plan_tensor, tensor_plan.cpp).
 int build_tensor_plan(const dora_tensor* tensor, ArrowDeviceType dev, dora_plan** out);
+// Named tensors of one leading extent as one Struct message (dora_gpu_plan_tensor_struct).
+int build_tensor_struct_plan(const dora_tensor_field* fields, size_t n, ArrowDeviceType dev,
+                             dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -190,5 +216,8 @@ struct dora_plan {
   bool dev_tensor = false;
   bool gather = false;
   dora::GatherDesc gd{};
+  // struct-of-tensors plans (dev_tensor): one entry per field instead of `gd`; with `gather`,
+  // gather_struct_kernel reads all of them in one launch (a multi-gather plan), else `segs` does
+  std::vector<dora::PlanField> fields;
   uint64_t fill_size() const { return ext_size > size ? ext_size : size; }
 };

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "dora_gpu.h"
 
@@ -297,6 +298,81 @@ PyObject* py_send_tensor(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   // after the status has been taken (it must not disturb the thread's error message either:
   // the caller reads dora_gpu_last_error only when rc != 0, and deleters do not call the library)
   if (m->deleter) m->deleter(m);
+  return PyLong_FromLong(rc);
+}
+
+// send_tensor_struct(handle, output_id, names, capsules, device_type, metadata, flags) -> status:
+// the tensors of a tuple of "dltensor" capsules under a tuple of names as
+// dora_node_send_output_tensor_struct.  Every capsule is consumed the way send_tensor consumes
+// its one: all are checked first (a refused argument leaves them untouched), then renamed, and
+// their deleters run once the call has returned.
+PyObject* py_send_tensor_struct(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  if (nargs != 7 || !PyTuple_Check(args[2]) || !PyTuple_Check(args[3]) ||
+      PyTuple_GET_SIZE(args[2]) != PyTuple_GET_SIZE(args[3])) {
+    PyErr_SetString(PyExc_TypeError, "send_tensor_struct(handle, output_id, names, capsules, "
+                                     "device_type, metadata, flags): names and capsules are "
+                                     "tuples of one length");
+    return nullptr;
+  }
+  void* h = nullptr;
+  if (!as_ptr(args[0], &h)) return nullptr;
+  const char* oid = as_cstr(args[1]);
+  if (!oid) return nullptr;
+  const Py_ssize_t n = PyTuple_GET_SIZE(args[2]);
+  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
+  std::vector<DlManaged*> managed(static_cast<size_t>(n));
+  for (Py_ssize_t k = 0; k < n; ++k) {
+    fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
+    if (!fields[size_t(k)].name) return nullptr;
+    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
+    if (!PyCapsule_IsValid(cap, "dltensor")) {
+      PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
+                                    "unused, unversioned one)", k);
+      return nullptr;
+    }
+    for (Py_ssize_t j = 0; j < k; ++j)
+      if (PyTuple_GET_ITEM(args[3], j) == cap) {
+        PyErr_Format(PyExc_TypeError, "fields %zd and %zd share one capsule", j, k);
+        return nullptr;
+      }
+  }
+  const long dev = PyLong_AsLong(args[4]);
+  if (dev == -1 && PyErr_Occurred()) return nullptr;
+  const unsigned long flags = PyLong_AsUnsignedLong(args[6]);
+  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
+  std::string& params = t_params;
+  if (!encode(args[5], params)) return nullptr;
+  for (Py_ssize_t k = 0; k < n; ++k) {
+    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
+    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
+    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
+      // (cannot happen after the checks above; the capsules renamed so far are released)
+      for (Py_ssize_t j = 0; j < k; ++j)
+        if (managed[size_t(j)]->deleter) managed[size_t(j)]->deleter(managed[size_t(j)]);
+      return nullptr;
+    }
+    managed[size_t(k)] = m;
+    dora_tensor& t = fields[size_t(k)].tensor;
+    t = dora_tensor{};
+    t.data = m->t.data;
+    t.byte_offset = m->t.byte_offset;
+    t.dtype_code = m->t.code;
+    t.dtype_bits = m->t.bits;
+    t.dtype_lanes = m->t.lanes;
+    t.ndim = m->t.ndim;
+    t.shape = m->t.shape;
+    t.strides = m->t.strides;
+  }
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor_struct(static_cast<dora_node*>(h), oid, fields.data(),
+                                           fields.size(), static_cast<ArrowDeviceType>(dev),
+                                           reinterpret_cast<const uint8_t*>(params.data()),
+                                           params.size(), static_cast<uint32_t>(flags));
+  Py_END_ALLOW_THREADS
+  // (deleters under the GIL and after the status has been taken, as in send_tensor)
+  for (DlManaged* m : managed)
+    if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 
@@ -755,6 +831,9 @@ PyMethodDef methods[] = {
      METH_FASTCALL, "dora_node_send_output_bytes of host bytes read in place (buffer protocol)."},
     {"send_tensor", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor)),
      METH_FASTCALL, "dora_node_send_output_tensor of a DLPack capsule, which it consumes."},
+    {"send_tensor_struct",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_struct)),
+     METH_FASTCALL, "dora_node_send_output_tensor_struct of named DLPack capsules, which it consumes."},
     {"send_array", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_array)),
      METH_FASTCALL, "dora_node_send_output with parameters encoded from a dict."},
     {nullptr, nullptr, 0, nullptr}};

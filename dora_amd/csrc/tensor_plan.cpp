@@ -8,6 +8,11 @@
 // length d0, child fields `item`, nullable.  `copy_array_into_sample` packs such an array as one
 // buffer, the row-major values at offset 0, so the plan is one segment of `count * sizeof(T)`
 // bytes and the type info a chain of nodes without buffers down to the leaf.
+//
+// A record of tensors (dora_gpu_plan_tensor_struct) is the Struct array of those columns: the
+// same per-tensor work once per field, each leaf at the running offset padded to its element
+// size, the struct node without a buffer; host fields as copy segments, device fields as copy
+// segments when all are dense and as one multi-gather when any is strided.
 #include <cstring>
 #include <memory>
 #include <string>
@@ -82,41 +87,6 @@ const char* leaf_format(const dora_tensor& t) {
   return nullptr;
 }
 
-// The type info chain of shape[0..ndim) over a leaf of `bytes` bytes, as build_plan's walk
-// serialises the equivalent array: every node carries its own type as a top-level schema.
-void tensor_type_info(const char* leaf, const int64_t* shape, int ndim, uint64_t bytes,
-                      TypeInfoNode& root) {
-  std::vector<ArrowSchema> sch(static_cast<size_t>(ndim));
-  std::vector<ArrowSchema*> child(static_cast<size_t>(ndim), nullptr);
-  std::vector<std::string> fmt(static_cast<size_t>(ndim));
-  for (int i = 0; i < ndim; ++i) {
-    ArrowSchema& s = sch[size_t(i)];
-    std::memset(&s, 0, sizeof(s));
-    fmt[size_t(i)] = i + 1 < ndim ? "+w:" + std::to_string(shape[i + 1]) : std::string(leaf);
-    s.format = fmt[size_t(i)].c_str();
-    s.name = i ? "item" : "";
-    s.flags = i ? ARROW_FLAG_NULLABLE : 0;
-    if (i + 1 < ndim) {
-      child[size_t(i)] = &sch[size_t(i) + 1];
-      s.children = &child[size_t(i)];
-      s.n_children = 1;
-    }
-  }
-  TypeInfoNode* node = &root;
-  uint64_t len = 1;
-  for (int i = 0; i < ndim; ++i) {
-    len *= static_cast<uint64_t>(shape[i]);
-    serialize_schema(&sch[size_t(i)], true, node->schema);
-    node->len = len;
-    if (i + 1 < ndim) {
-      node->children.emplace_back();
-      node = &node->children.back();
-    } else {
-      node->bufs.push_back({0, bytes});
-    }
-  }
-}
-
 struct Dim {
   int64_t n, s;  // extent, stride in bytes
 };
@@ -142,14 +112,66 @@ bool reach(const StridedView& g, int64_t* lo, int64_t* hi) {
   return true;
 }
 
-}  // namespace
+// The Arrow C schema of a tensor of `leaf` and shape[0..ndim): the chain of fixed-size lists
+// down to the leaf, child fields `item`, nullable; the head carries `name` (a struct's field) or
+// none.  The nodes point into the vectors, which are sized once.
+struct TypeChain {
+  std::vector<ArrowSchema> sch;
+  std::vector<ArrowSchema*> child;
+  std::vector<std::string> fmt;
+  TypeChain(const char* leaf, const int64_t* shape, int ndim, const char* name)
+      : sch(static_cast<size_t>(ndim)), child(static_cast<size_t>(ndim), nullptr),
+        fmt(static_cast<size_t>(ndim)) {
+    for (int i = 0; i < ndim; ++i) {
+      ArrowSchema& s = sch[size_t(i)];
+      std::memset(&s, 0, sizeof(s));
+      fmt[size_t(i)] = i + 1 < ndim ? "+w:" + std::to_string(shape[i + 1]) : std::string(leaf);
+      s.format = fmt[size_t(i)].c_str();
+      s.name = i ? "item" : name;
+      s.flags = i || name[0] ? ARROW_FLAG_NULLABLE : 0;
+      if (i + 1 < ndim) {
+        child[size_t(i)] = &sch[size_t(i) + 1];
+        s.children = &child[size_t(i)];
+        s.n_children = 1;
+      }
+    }
+  }
+  TypeChain(const TypeChain&) = delete;
+  TypeChain& operator=(const TypeChain&) = delete;
+};
 
-int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out) {
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
+// The type info chain of shape[0..ndim) over a leaf of `bytes` bytes at sample offset `off`, as
+// build_plan's walk serialises the equivalent array: every node carries its own type as a
+// top-level schema.
+void tensor_type_info(const TypeChain& c, const int64_t* shape, int ndim, uint64_t off,
+                      uint64_t bytes, TypeInfoNode& root) {
+  TypeInfoNode* node = &root;
+  uint64_t len = 1;
+  for (int i = 0; i < ndim; ++i) {
+    len *= static_cast<uint64_t>(shape[i]);
+    serialize_schema(&c.sch[size_t(i)], true, node->schema);
+    node->len = len;
+    if (i + 1 < ndim) {
+      node->children.emplace_back();
+      node = &node->children.back();
+    } else {
+      node->bufs.push_back({off, bytes});
+    }
+  }
+}
+
+// What planning one tensor yields, for a message of its own and for a field of a struct alike:
+// the accepted leaf format, the byte count, and — unless it is empty — the canonical view over
+// `data + byte_offset` (nd == 0: dense) with, for device memory, the interval it reaches.
+struct TensorView {
+  const char* leaf = nullptr;
+  uint64_t bytes = 0;
+  GatherDesc gd{};
+};
+
+// Validation, canonical view and reach of `t`; the failure recorded otherwise.
+int describe_tensor(const dora_tensor* t, ArrowDeviceType dev, TensorView& out) {
   if (!t) return fail(DORA_ERR_INVALID, "tensor is NULL");
-  if (dev != ARROW_DEVICE_CPU && dev != ARROW_DEVICE_ROCM_HOST && dev != ARROW_DEVICE_ROCM)
-    return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
   const char* leaf = leaf_format(*t);
   if (!leaf) return DORA_ERR_UNSUPPORTED;
   const int64_t elem = t->dtype_bits / 8;
@@ -173,89 +195,214 @@ int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out
   if (!t->data && count) return fail(DORA_ERR_INVALID, "tensor data is NULL");
 
   // canonical view: no extents of 1, mergeable neighbours merged
-  std::vector<Dim> dims;
+  Dim dims[kMaxTensorDims];
+  size_t nd = 0;
   {
     int64_t rm = elem;  // row-major stride when strides is NULL
-    std::vector<int64_t> sb(static_cast<size_t>(t->ndim));
-    for (int i = t->ndim - 1; i >= 0; --i) {
+    for (int i = t->ndim - 1; i >= 0; --i) {  // innermost first: merged into dims[0]
+      int64_t sb;
       if (t->strides) {
-        if (__builtin_mul_overflow(t->strides[i], elem, &sb[size_t(i)]))
+        if (__builtin_mul_overflow(t->strides[i], elem, &sb))
           return fail(DORA_ERR_INVALID, "tensor stride %d overflows 64 bits", i);
       } else {
-        sb[size_t(i)] = rm;
+        sb = rm;
         rm *= t->shape[i] ? t->shape[i] : 1;
       }
-    }
-    for (int i = 0; i < t->ndim && count; ++i) {
-      if (t->shape[i] == 1) continue;
-      const Dim d{t->shape[i], sb[size_t(i)]};
-      int64_t span;  // bytes one step of the previous dimension must cover to merge
-      if (!dims.empty() && !__builtin_mul_overflow(d.n, d.s, &span) && dims.back().s == span) {
-        dims.back().n *= d.n;
-        dims.back().s = d.s;
+      if (t->shape[i] == 1 || !count) continue;
+      const Dim d{t->shape[i], sb};
+      int64_t span;  // bytes one step of this dimension must cover to merge with the next inner
+      if (nd && !__builtin_mul_overflow(dims[0].n, dims[0].s, &span) && d.s == span) {
+        dims[0].n *= d.n;
       } else {
-        dims.push_back(d);
+        if (nd == size_t(kMaxTensorDims))
+          return fail(DORA_ERR_UNSUPPORTED,
+                      "tensor view has more than %d dimensions after merging", kMaxTensorDims);
+        for (size_t k = nd; k > 0; --k) dims[k] = dims[k - 1];
+        dims[0] = d;
+        ++nd;
       }
     }
   }
-  if (dims.size() > size_t(kMaxTensorDims))
-    return fail(DORA_ERR_UNSUPPORTED, "tensor view has %zu dimensions after merging (at most %d)",
-                dims.size(), kMaxTensorDims);
+  out.leaf = leaf;
+  out.bytes = bytes;
+  if (bytes == 0) return DORA_OK;
+  // an innermost unit stride folds into a row of bytes
+  uint64_t row = static_cast<uint64_t>(elem);
+  if (nd && dims[nd - 1].s == elem) {
+    row = static_cast<uint64_t>(dims[nd - 1].n) * static_cast<uint64_t>(elem);
+    --nd;
+  }
+  StridedView& g = out.gd.view;
+  g.src = static_cast<const uint8_t*>(t->data) + t->byte_offset;
+  g.total = bytes;
+  g.row = row;
+  g.nd = static_cast<int>(nd);
+  for (size_t i = 0; i < nd; ++i) {
+    g.shape[i] = dims[i].n;
+    g.stride[i] = dims[i].s;
+  }
+  out.gd.elem = static_cast<uint32_t>(elem);
+  // device strides are not trusted; a host view's reach is its producer's word
+  if (dev == ARROW_DEVICE_ROCM && !reach(g, &out.gd.lo, &out.gd.hi))
+    return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
+                "stride, summed over its dimensions)");
+  return DORA_OK;
+}
 
+bool known_device(ArrowDeviceType dev) {
+  return dev == ARROW_DEVICE_CPU || dev == ARROW_DEVICE_ROCM_HOST || dev == ARROW_DEVICE_ROCM;
+}
+
+// The recorded failure again, with the field it belongs to in front.
+int field_fail(int rc, size_t k, const char* name) {
+  const std::string why = dora_gpu_last_error();
+  return fail(rc, "field %zu `%s`: %s", k, name ? name : "(null)", why.c_str());
+}
+
+}  // namespace
+
+int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!t) return fail(DORA_ERR_INVALID, "tensor is NULL");
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
   DORA_GUARD_BEGIN
+  TensorView v;
+  const int rc = describe_tensor(t, dev, v);
+  if (rc != DORA_OK) return rc;
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev;
-  p->size = bytes;
-  tensor_type_info(leaf, t->shape, t->ndim, bytes, p->root);
-  if (bytes == 0) {
+  p->size = v.bytes;
+  tensor_type_info(TypeChain(v.leaf, t->shape, t->ndim, ""), t->shape, t->ndim, 0, v.bytes,
+                   p->root);
+  if (v.bytes == 0) {
     *out = p.release();
     return DORA_OK;
   }
-  const uint8_t* base = static_cast<const uint8_t*>(t->data) + t->byte_offset;
-  // an innermost unit stride folds into a row of bytes
-  uint64_t row = static_cast<uint64_t>(elem);
-  if (!dims.empty() && dims.back().s == elem) {
-    row = static_cast<uint64_t>(dims.back().n) * static_cast<uint64_t>(elem);
-    dims.pop_back();
-  }
+  const StridedView& g = v.gd.view;
   // dense pageable memory: exactly dora_gpu_plan_bytes' plan, with the nested type info.  Pinned
   // memory is staged even when dense: copies and kernels reading it are asynchronous to the
   // host, and the send promises that the source has been read when it returns.
-  if (dims.empty() && dev == ARROW_DEVICE_CPU) {
-    p->segs.push_back({base, 0, bytes});
+  if (g.nd == 0 && dev == ARROW_DEVICE_CPU) {
+    p->segs.push_back({g.src, 0, v.bytes});
     *out = p.release();
     return DORA_OK;
-  }
-  StridedView g{};
-  g.src = base;
-  g.total = bytes;
-  g.row = row;
-  g.nd = static_cast<int>(dims.size());
-  for (size_t i = 0; i < dims.size(); ++i) {
-    g.shape[i] = dims[i].n;
-    g.stride[i] = dims[i].s;
   }
   if (dev == ARROW_DEVICE_ROCM) {
     // device memory is never dereferenced here: a dense view is dora_gpu_plan_bytes' plan with
     // the nested type info (every device path unchanged), a strided one the gather kernel's
     // descriptor and no segments
     p->dev_tensor = true;
-    p->gd.view = g;
-    p->gd.elem = static_cast<uint32_t>(elem);
-    if (!reach(g, &p->gd.lo, &p->gd.hi))
-      return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
-                  "stride, summed over its dimensions)");
-    if (dims.empty()) p->segs.push_back({base, 0, bytes});
+    p->gd = v.gd;
+    if (g.nd == 0) p->segs.push_back({g.src, 0, v.bytes});
     else p->gather = true;
     *out = p.release();
     return DORA_OK;
   }
   // what the caller's own copy to contiguous memory would have done: every host path (inline
   // Vec, shared memory, BAR fill, DMA) then sees a dense pageable source
-  p->staged.resize(bytes);
+  p->staged.resize(v.bytes);
   gather_host(g, p->staged.data());
   p->dev = ARROW_DEVICE_CPU;  // pageable memory, whatever the view's was
-  p->segs.push_back({p->staged.data(), 0, bytes});
+  p->segs.push_back({p->staged.data(), 0, v.bytes});
+  *out = p.release();
+  return DORA_OK;
+  DORA_GUARD_END
+}
+
+int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceType dev,
+                             dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a struct of tensors has at least one field");
+  if (n > kMaxStructFields)
+    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
+                kMaxStructFields, n);
+  DORA_GUARD_BEGIN
+  std::unique_ptr<dora_plan> p(new dora_plan());
+  p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
+  p->fields.resize(n);
+  std::vector<std::unique_ptr<TypeChain>> chains(n);
+  std::vector<ArrowSchema*> kids(n);
+  p->root.children.resize(n);
+  uint64_t off = 0, staged = 0;
+  bool strided = false;
+  for (size_t k = 0; k < n; ++k) {
+    const char* name = f[k].name;
+    if (!name || !name[0])
+      return fail(DORA_ERR_INVALID, "field %zu has %s name", k, name ? "an empty" : "a NULL");
+    for (size_t j = 0; j < k; ++j)
+      if (std::strcmp(f[j].name, name) == 0)
+        return fail(DORA_ERR_INVALID, "field %zu `%s` repeats the name of field %zu", k, name, j);
+    const dora_tensor& t = f[k].tensor;
+    TensorView v;
+    const int rc = describe_tensor(&t, dev, v);
+    if (rc != DORA_OK) return field_fail(rc, k, name);
+    if (t.shape[0] != f[0].tensor.shape[0])
+      return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
+                  "%lld: the fields of a struct share shape[0] (give tensors of unrelated shapes "
+                  "a leading extent of 1)", k, name, static_cast<long long>(t.shape[0]),
+                  f[0].name, static_cast<long long>(f[0].tensor.shape[0]));
+    // the running offset padded to the leaf's element size (a power of two)
+    const uint64_t elem = t.dtype_bits / 8;
+    uint64_t padded, end;
+    if (__builtin_add_overflow(off, elem - 1, &padded) ||
+        __builtin_add_overflow(padded & ~(elem - 1), v.bytes, &end) || end >> 63)
+      return fail(DORA_ERR_INVALID, "field %zu `%s`: the message's size overflows 64 bits", k, name);
+    off = padded & ~(elem - 1);
+    PlanField& pf = p->fields[k];
+    pf.name = name;
+    pf.gd = v.gd;
+    pf.dst_off = off;
+    pf.bytes = v.bytes;
+    chains[k].reset(new TypeChain(v.leaf, t.shape, t.ndim, name));
+    kids[k] = &chains[k]->sch[0];
+    tensor_type_info(*chains[k], t.shape, t.ndim, off, v.bytes, p->root.children[k]);
+    off = end;
+    const bool stage = dev == ARROW_DEVICE_ROCM_HOST || (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
+    if (stage) staged += v.bytes;  // (<= off)
+    strided |= v.gd.view.nd != 0;
+  }
+  ArrowSchema top;
+  std::memset(&top, 0, sizeof(top));
+  top.format = "+s";
+  top.name = "";
+  top.children = kids.data();
+  top.n_children = static_cast<int64_t>(n);
+  serialize_schema(&top, true, p->root.schema);
+  p->root.len = static_cast<uint64_t>(f[0].tensor.shape[0]);
+  p->size = off;
+  if (off == 0) {  // d0 == 0: an empty message, nothing to read
+    p->fields.clear();
+    *out = p.release();
+    return DORA_OK;
+  }
+  if (dev == ARROW_DEVICE_ROCM) {
+    // never dereferenced here.  All dense: the copy segments of any device plan (every device
+    // path, the AQL multi-segment packs included); any strided: no segments, one launch of
+    // gather_struct_kernel over every field.  Either way each field's reach is checked first.
+    p->dev_tensor = true;
+    p->gather = strided;
+    if (!strided)
+      for (const PlanField& pf : p->fields) p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
+    *out = p.release();
+    return DORA_OK;
+  }
+  // host fields: dense pageable ones read in place, the others gathered now into one staging
+  // buffer — an ordinary multi-segment host plan
+  p->staged.resize(staged);
+  uint64_t at = 0;
+  for (const PlanField& pf : p->fields) {
+    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0) {
+      p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
+      continue;
+    }
+    gather_host(pf.gd.view, p->staged.data() + at);
+    p->segs.push_back({p->staged.data() + at, pf.dst_off, pf.bytes});
+    at += pf.bytes;
+  }
+  p->fields.clear();  // (device plans keep them for the range check and the gather)
   *out = p.release();
   return DORA_OK;
   DORA_GUARD_END
@@ -268,6 +415,11 @@ extern "C" {
 int dora_gpu_plan_tensor(const dora_tensor* tensor, ArrowDeviceType device_type,
                          dora_plan** out) {
   return dora::build_tensor_plan(tensor, device_type, out);
+}
+
+int dora_gpu_plan_tensor_struct(const dora_tensor_field* fields, size_t n,
+                                ArrowDeviceType device_type, dora_plan** out) {
+  return dora::build_tensor_struct_plan(fields, n, device_type, out);
 }
 
 }  // extern "C"

@@ -32,6 +32,7 @@ namespace dora {
 int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t cap,
                          uint32_t* grid);
 void gather_force(int mode);
+int select_tile_dim(const GatherDesc& g, const uint8_t* dst);
 }  // namespace dora
 
 namespace dora {
@@ -318,7 +319,7 @@ int dora_gpu_test_gather_kernel(int mode) {
 int dora_gpu_test_plan_gather(const dora_plan* plan, int* gather, const void** src, int* nd,
                               uint64_t* row, uint32_t* elem, int64_t* shape, int64_t* stride,
                               int64_t* lo, int64_t* hi) {
-  if (!plan || !plan->dev_tensor)
+  if (!plan || !plan->dev_tensor || !plan->fields.empty())
     return dora::fail(DORA_ERR_INVALID, "not a device tensor plan");
   const dora::GatherDesc& g = plan->gd;
   if (gather) *gather = plan->gather;
@@ -329,6 +330,32 @@ int dora_gpu_test_plan_gather(const dora_plan* plan, int* gather, const void** s
   for (int i = 0; i < dora::kMaxTensorDims; ++i) {
     if (shape) shape[i] = i < g.view.nd ? g.view.shape[i] : 0;
     if (stride) stride[i] = i < g.view.nd ? g.view.stride[i] : 0;
+  }
+  if (lo) *lo = g.lo;
+  if (hi) *hi = g.hi;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, size_t* n_fields,
+                             int* gather, uint64_t* dst_off, uint64_t* bytes, int* kind,
+                             const void** src, int* nd, uint64_t* row, uint32_t* elem,
+                             int64_t* shape, int64_t* stride, int64_t* lo, int64_t* hi) {
+  if (!plan || !plan->dev_tensor || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a device struct-of-tensors plan with a field %zu", i);
+  const dora::PlanField& f = plan->fields[i];
+  const dora::GatherDesc& g = f.gd;
+  if (n_fields) *n_fields = plan->fields.size();
+  if (gather) *gather = plan->gather;
+  if (dst_off) *dst_off = f.dst_off;
+  if (bytes) *bytes = f.bytes;
+  if (kind) *kind = dora::select_tile_dim(g, static_cast<const uint8_t*>(dst) + f.dst_off);
+  if (src) *src = g.view.src;
+  if (nd) *nd = g.view.nd;
+  if (row) *row = g.view.row;
+  if (elem) *elem = g.elem;
+  for (int k = 0; k < dora::kMaxTensorDims; ++k) {
+    if (shape) shape[k] = k < g.view.nd ? g.view.shape[k] : 0;
+    if (stride) stride[k] = k < g.view.nd ? g.view.stride[k] : 0;
   }
   if (lo) *lo = g.lo;
   if (hi) *hi = g.hi;

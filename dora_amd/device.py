@@ -207,6 +207,16 @@ class DeviceArray:
     def device_id(self) -> int:
         return getattr(self, "_device_id", 0)
 
+    def field(self, name_or_index):
+        """Field `name_or_index` of a struct array as a child view (this array's own slice of
+        the child): it shares this array's lifetime and exports DLPack as a DeviceArray does."""
+        return DeviceArrayView(self, self, name_or_index)
+
+    def field_views(self) -> dict:
+        """`{name: field(name)}` of a struct of tensor columns without nulls (a received
+        struct-of-tensors message; dora_amd.tensor.to_torch)."""
+        return _field_views(self, self)
+
     def close(self):
         release_array(self.array)
         if self._schema is not None:
@@ -226,6 +236,62 @@ class DeviceArray:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class DeviceArrayView:
+    """A field of a device struct array: a copy of the child's ArrowArray header narrowed to the
+    parent's slice (nothing is released through it), the field's type, and the DeviceArray that
+    owns the memory, which every DLPack export of the view keeps alive."""
+
+    def __init__(self, owner: DeviceArray, parent, name_or_index):
+        import pyarrow as pa
+        t, a = parent.type, parent.array
+        if not pa.types.is_struct(t):
+            raise TypeError(f"field() needs a struct array, got {t}")
+        i = t.get_field_index(name_or_index) if isinstance(name_or_index, str) else int(name_or_index)
+        if not 0 <= i < t.num_fields or i >= a.n_children:
+            raise KeyError(f"no field {name_or_index!r} in {t}")
+        child = a.children[i].contents
+        c = ArrowArray.from_buffer_copy(child)
+        c.offset = child.offset + a.offset
+        c.length = a.length
+        if child.null_count and (a.offset or a.length != child.length):
+            c.null_count = -1  # not computed for the slice
+        c.release = None  # a borrowed header: the owner releases the array
+        self.array, self.type, self._owner = c, t.field(i).type, owner
+
+    @property
+    def length(self) -> int:
+        return self.array.length
+
+    @property
+    def device_id(self) -> int:
+        return self._owner.device_id
+
+    def field(self, name_or_index):
+        return DeviceArrayView(self._owner, self, name_or_index)
+
+    def field_views(self) -> dict:
+        return _field_views(self._owner, self)
+
+    def __dlpack__(self, stream=None, **kwargs):
+        from .dlpack import to_dlpack_capsule, values_view
+        ptr, n, fmt = values_view(self)
+        return to_dlpack_capsule(ptr, n, fmt, self.device_id, self._owner)
+
+    def __dlpack_device__(self):
+        from .dlpack import kDLROCM
+        return (kDLROCM, self.device_id)
+
+
+def _field_views(owner, parent) -> dict:
+    import pyarrow as pa
+    from .dlpack import _no_nulls
+    if not pa.types.is_struct(parent.type):
+        raise TypeError(f"not a struct of tensor columns: {parent.type}")
+    _no_nulls(parent.array, parent.type)
+    return {parent.type.field(i).name: DeviceArrayView(owner, parent, i)
+            for i in range(parent.type.num_fields)}
 
 
 __all__ = ["Stream", "Event", "DeviceBuffer", "DeviceArray", "device_count", "set_device",

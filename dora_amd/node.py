@@ -232,9 +232,12 @@ class Node:
                                       ctypes.addressof(c.schema), ARROW_DEVICE_CPU, metadata)
         elif hasattr(data, "__dlpack__") and hasattr(data, "__dlpack_device__"):
             rc = self._send_tensor(output_id, data, metadata, f)
+        elif isinstance(data, dict):
+            rc = self._send_tensor_struct(output_id, data, metadata, f)
         else:
-            raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer or "
-                            "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU)")
+            raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer, "
+                            "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU) "
+                            "or a dict of such tensors")
         if rc:
             _lib.check(rc)
 
@@ -292,6 +295,72 @@ class Node:
             del keep
             return rc
         return _fast.send_tensor(self.handle, output_id, cap, dev, metadata, flags)
+
+    def _send_tensor_struct(self, output_id: str, data: dict, metadata, flags: int) -> int:
+        """A dict of DLPack producers as one Struct message with a field per entry, in the dict's
+        order (dora_node_send_output_tensor_struct; dora_amd.tensor): every tensor shares
+        shape[0], and all are host tensors or all are on this node's GPU.  Host fields have been
+        read on return.  Device fields do the `__dlpack__(stream=<the node stream>)` handshake
+        each and are read by one kernel launch; an asynchronous send holds every one of them until
+        the next `sync()`, as `_send_tensor` holds its one."""
+        if not data:
+            raise TypeError("a struct of tensors has at least one field")
+        kinds = {}
+        for name, v in data.items():
+            if not isinstance(name, str):
+                raise TypeError(f"field names are str, not {type(name).__name__}")
+            if not (hasattr(v, "__dlpack__") and hasattr(v, "__dlpack_device__")):
+                raise TypeError(f"field `{name}` is not a tensor with __dlpack__")
+            dl_dev = v.__dlpack_device__()
+            dev_type = int(dl_dev[0])
+            if dev_type == _DL_ROCM:
+                if int(dl_dev[1]) != self.device:
+                    raise TypeError(f"field `{name}` is on GPU {int(dl_dev[1])}, this node on GPU "
+                                    f"{self.device}: a node sends tensors of its own GPU")
+                kinds[name] = "device"
+            elif dev_type in _DL_HOST:
+                kinds[name] = "host"
+            else:
+                raise TypeError(f"field `{name}`: tensors of DLPack device type {dev_type} "
+                                "cannot be sent")
+        first = next(iter(kinds))
+        for name, kind in kinds.items():
+            if kind != kinds[first]:
+                raise TypeError(f"field `{first}` is a {kinds[first]} tensor and field `{name}` a "
+                                f"{kind} tensor: the fields of one message are all host tensors "
+                                "or all on this node's GPU")
+        names = tuple(data)
+        if kinds[first] == "device":
+            _require_one_hip_runtime()
+            held = bool(flags & SEND_ASYNC) or self._async_default
+            if held and len(self._async_tensors) + len(names) > self._ASYNC_TENSORS_MAX:
+                self.sync()
+            stream = int(self._lib.dora_node_stream(self.handle))
+            caps = tuple(v.__dlpack__(stream=stream) for v in data.values())
+            rc = _fast.send_tensor_struct(self.handle, output_id, names, caps, ARROW_DEVICE_ROCM,
+                                          metadata, flags)
+            if held and not rc:
+                self._async_tensors.extend(data.values())
+            return rc
+        # host fields: pinned memory in any of them makes the whole record pinned (copied inside
+        # the call); a read-only numpy array cannot export a capsule, so then every field goes
+        # through its array interface
+        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in data.values())
+        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
+        try:
+            caps = tuple(v.__dlpack__() for v in data.values())
+        except BufferError:
+            if not all(hasattr(v, "__array_interface__") for v in data.values()):
+                raise
+            from .tensor import _describe_array, _describe_fields
+            described = [_describe_array(v) for v in data.values()]
+            fields, keep = _describe_fields(names, [t for t, _ in described])
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_struct(
+                self.handle, output_id.encode(), fields, len(names), dev, params, len(params), flags)
+            del keep, described
+            return rc
+        return _fast.send_tensor_struct(self.handle, output_id, names, caps, dev, metadata, flags)
 
     def send_output_async(self, output_id: str, data, metadata: Optional[dict] = None):
         """send_output(..., asynchronous=True)."""

@@ -232,6 +232,37 @@ typedef struct dora_tensor {
   const int64_t* strides; /* in elements, signed, 0 allowed; NULL = row-major */
 } dora_tensor;
 int dora_gpu_plan_tensor(const dora_tensor* tensor, ArrowDeviceType device_type, dora_plan** out);
+/*
+ * A record of tensors as one message: `n` named tensors, 1 <= n <= 8, that share shape[0] = d0
+ * and live in the same place (`device_type`, as above, for all of them).  On the wire it is the
+ * Arrow array of length d0 and type Struct<name_0: T_0, .., name_{n-1}: T_{n-1}>, T_k exactly the
+ * type dora_gpu_plan_tensor gives field k alone, fields nullable (as
+ * pyarrow.StructArray.from_arrays makes them).  The sample is the reference layout of that array:
+ * the struct node and the list nodes carry no buffer, each leaf's row-major values sit at the
+ * running offset padded to the leaf's element size, in field order; padding bytes are not
+ * written.  d0 == 0 plans an empty message.  A reference node reads it as a StructArray.
+ * Tensors of unrelated shapes travel as a struct of length 1: give each a leading extent of 1.
+ *
+ * Host fields: a dense pageable one is a copy segment over the caller's memory (borrowed until the
+ * pack completes), a strided or pinned one has been gathered into the plan's staging buffer on
+ * return; the plan is an ordinary multi-segment host plan.  Device fields are never dereferenced
+ * here: when every field is dense the plan is n copy segments; when any is strided it carries no
+ * segments and one launch of gather_struct_kernel (gfx950) reads every field, dense ones
+ * included, and writes each into its own byte range.  Either way every field's reach is checked
+ * against the allocation that holds it — fields may sit in different allocations — before
+ * anything is launched; a refusal names the field.
+ *
+ * DORA_ERR_INVALID, naming the field: n == 0, a NULL or empty name, a duplicate name, a field
+ * whose shape[0] differs from field 0's, a total size that overflows 64 bits.
+ * DORA_ERR_UNSUPPORTED: n > 8.  Each tensor's own refusals (dora_gpu_plan_tensor) pass through
+ * with the field's name prefixed.
+ */
+typedef struct dora_tensor_field {
+  const char* name;
+  dora_tensor tensor;
+} dora_tensor_field;
+int dora_gpu_plan_tensor_struct(const dora_tensor_field* fields, size_t n,
+                                ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -422,6 +453,18 @@ int dora_node_send_output_bytes_ex(dora_node* node, const char* output_id, const
 int dora_node_send_output_tensor(dora_node* node, const char* output_id, const dora_tensor* tensor,
                                  ArrowDeviceType device_type, const uint8_t* params,
                                  size_t params_len, uint32_t flags);
+/* Send a record of tensors as one Struct message (dora_gpu_plan_tensor_struct: wire type, layout
+ * and refusals).  Host fields and all-dense device fields take the paths of any multi-segment
+ * plan.  Device fields of which any is strided are gathered by one kernel launch into an HBM slot,
+ * as a single strided tensor is: on a fill stream ordered after the node stream (a
+ * broadcast-group output: on its own stream), the stream raises the fill flag, receivers without
+ * a GPU stage the slot as usual.  A synchronous send returns once the kernel has read every
+ * field; with DORA_SEND_ASYNC, once it is queued, and the caller keeps every field alive and
+ * unwritten until dora_node_sync. */
+int dora_node_send_output_tensor_struct(dora_node* node, const char* output_id,
+                                        const dora_tensor_field* fields, size_t n,
+                                        ArrowDeviceType device_type, const uint8_t* params,
+                                        size_t params_len, uint32_t flags);
 /* Make DORA_SEND_ASYNC the default of every send of this node (also DORA_GPU_SEND_ASYNC=1). */
 int dora_node_set_async_sends(dora_node* node, int enable);
 /* Event-stream thread (the reference's event_stream_loop, apis/rust/node/src/event_stream/

@@ -74,6 +74,18 @@ int dora_gpu_test_batch_args(size_t n_msgs, const size_t* seg_counts, const uint
 int dora_gpu_test_plan_gather(const dora_plan* plan, int* gather, const void** src, int* nd,
                               uint64_t* row, uint32_t* elem, int64_t* shape, int64_t* stride,
                               int64_t* lo, int64_t* hi);
+/* Test tool (host only): field `i` of a device struct-of-tensors plan
+ * (dora_gpu_plan_tensor_struct with ARROW_DEVICE_ROCM, d0 > 0).  *n_fields the plan's field count,
+ * *gather 1 if gather_struct_kernel reads the fields (no segments), 0 if all are dense;
+ * *dst_off / *bytes the field's byte range in the sample; *kind which body gathers it into a
+ * sample at address `dst` under the current selection (dora_gpu_test_gather_kernel): -1 the rows
+ * body, else the dimension of the view the tile body transposes against; the view, element size
+ * and reach as dora_gpu_test_plan_gather gives them (nd == 0: dense).  DORA_ERR_INVALID for any
+ * other plan or index. */
+int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, size_t* n_fields,
+                             int* gather, uint64_t* dst_off, uint64_t* bytes, int* kind,
+                             const void** src, int* nd, uint64_t* row, uint32_t* elem,
+                             int64_t* shape, int64_t* stride, int64_t* lo, int64_t* hi);
 /* Test and probe tool: which kernel gathers strided device tensor views of this process from now
  * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
  * it applies (short contiguous extents included). */
