@@ -62,6 +62,16 @@ class TensorField(ctypes.Structure):
     _fields_ = [("name", c_char_p), ("tensor", Tensor)]
 
 
+PARTITION_LENGTHS = 0  # DORA_PARTITION_LENGTHS (include/dora_gpu.h)
+PARTITION_OFFSETS = 1  # DORA_PARTITION_OFFSETS
+
+
+class TensorList(ctypes.Structure):
+    """dora_tensor_list of include/dora_gpu.h: the fields of a ragged batch and its partition."""
+    _fields_ = [("fields", POINTER(TensorField)), ("n", c_size_t), ("partition", Tensor),
+                ("partition_form", c_uint32), ("partition_device", c_int32)]
+
+
 class FillTicket(ctypes.Structure):
     """dora_fill_ticket of include/dora_fill_ticket.h (32 bytes): what dora_sample_fill_ticket
     issues and a publishing kernel takes by value."""
@@ -105,6 +115,9 @@ _SIGS = {
     "dora_gpu_plan_tensor_struct": (c_int, [c_void_p, c_size_t, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_struct": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
                                                     c_int32, c_char_p, c_size_t, c_uint32]),
+    "dora_gpu_plan_tensor_list": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_list": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
+                                                  c_size_t, c_uint32]),
     "dora_node_send_output_tensor": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                              c_size_t, c_uint32]),
     "dora_gpu_plan_compact": (c_int, [POINTER(ArrowArray), POINTER(ArrowSchema), c_int32,
@@ -240,6 +253,10 @@ _TEST_SIGS = {
                                          POINTER(c_uint64), POINTER(c_uint32),
                                          POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
                                          POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
+    "dora_gpu_test_plan_list": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
+                                        POINTER(c_uint64), POINTER(c_int), POINTER(c_int),
+                                        POINTER(c_uint64), POINTER(ctypes.c_int64),
+                                        POINTER(ctypes.c_int64), POINTER(c_uint64)]),
     "dora_gpu_test_aql_hold": (c_int, [c_int, c_int]),
     "dora_gpu_test_reduce_timeout": (c_int, [c_uint64]),
     "dora_gpu_test_d2h_copy_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_uint64, c_void_p]),

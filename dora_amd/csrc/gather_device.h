@@ -384,10 +384,122 @@ DORA_HD void store_phase(const Args& a, const Origin& o, uint32_t thread, M& m) 
 // arguments — the head / tail bytes and the tile predicates see to that — so the padding between
 // fields and the neighbours' bytes are never touched.
 // ------------------------------------------------------------------------------------------
+// ------------------------------------------------------------------------------------------
+// The offsets of a ragged batch whose partition lives in HBM (one more share of
+// gather_struct_kernel): one workgroup scans `count` words of 4 or 8 bytes into the sample's
+// int32 offsets, all `count + 1 - offsets` of them.  Lengths: o[0] = 0 and o[i + 1] = min(n,
+// sum_{j <= i} max(len_j, 0)), an inclusive sum written one word on.  Offsets: o[i] = min(n, max(0,
+// max_{j <= i} in_j)), an inclusive maximum written in place.  Either way every input is clamped
+// to [0, n] first and the running value saturates at n, so the words are monotone, inside [0, n]
+// and no sum leaves 64 bits whatever the input holds.
+//
+// The scan goes in tiles of kTile words with a carried total: each thread reads its kItems
+// consecutive words and scans them in registers (load_phase), the kThreads thread totals are
+// scanned through two LDS rows by doubling (step_phase, kSteps of them, a barrier after each), and
+// each thread combines carry, the totals before it and its own prefix into its output words
+// (store_phase, which also returns the next carry: the same in every thread).  Tile -> word
+// range, thread -> words, the LDS slots, the carry and the clamps are all here.
+// ------------------------------------------------------------------------------------------
+namespace scan {
+
+constexpr int kItems = 4;                   // words per thread and tile
+constexpr int kTile = kThreads * kItems;    // words per tile
+constexpr int kSteps = 8;                   // log2(kThreads)
+constexpr int kLds = 2 * kThreads;          // two rows of thread totals (8-byte words)
+static_assert((1 << kSteps) == kThreads, "the doubling scan covers the workgroup");
+
+struct Args {
+  const uint8_t* src;  // the partition's words (null: no scan share in this launch)
+  uint8_t* dst;        // the sample's offsets buffer
+  uint64_t count;      // input words
+  uint64_t n;          // the clamp: rows of the values
+  uint32_t wide;       // 0: int32 words, 1: int64
+  uint32_t offsets;    // 0: lengths (sum), 1: offsets (maximum)
+};
+
+DORA_HD Args make_args(const ScanDesc& s, uint8_t* dst) {
+  Args a{};
+  a.src = s.src;
+  a.dst = dst;
+  a.count = s.count;
+  a.n = s.n;
+  a.wide = s.wide;
+  a.offsets = s.offsets;
+  return a;
+}
+
+DORA_HD uint64_t tiles(const Args& a) { return (a.count + kTile - 1) / kTile; }
+// output words in all
+DORA_HD uint64_t out_words(const Args& a) { return a.count + (a.offsets ? 0 : 1); }
+
+DORA_HD uint64_t clamp_in(const Args& a, int64_t v) {
+  return v <= 0 ? 0 : static_cast<uint64_t>(v) > a.n ? a.n : static_cast<uint64_t>(v);
+}
+// the operator over clamped values, saturating at n (both operands <= n: no overflow)
+DORA_HD uint64_t combine(const Args& a, uint64_t x, uint64_t y) {
+  if (a.offsets) return x > y ? x : y;
+  const uint64_t s = x + y;
+  return s > a.n ? a.n : s;
+}
+
+// A thread's own words of a tile, scanned: pre[k] the inclusive prefix of its first k + 1 words.
+struct Local {
+  uint64_t pre[kItems];
+};
+
+// o[0] of the lengths form, which no input word produces.
+template <class M>
+DORA_HD void head(const Args& a, uint32_t thread, M& m) {
+  if (thread == 0 && !a.offsets) m.store_word(0, 0);
+}
+
+template <class M>
+DORA_HD void load_phase(const Args& a, uint64_t tile, uint32_t thread, Local& loc, M& m) {
+  const uint64_t first = tile * kTile + static_cast<uint64_t>(thread) * kItems;
+  uint64_t run = 0;  // the identity of both operators over [0, n]
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) {
+    const uint64_t i = first + static_cast<uint64_t>(k);
+    if (i < a.count) run = combine(a, run, clamp_in(a, m.load_word(i)));
+    loc.pre[k] = run;
+  }
+  m.lds_write(thread, run);
+}
+
+// Step `step` of the doubling scan over the thread totals: row (step & 1) -> the other row.
+template <class M>
+DORA_HD void step_phase(const Args& a, uint32_t thread, int step, M& m) {
+  const uint32_t from = static_cast<uint32_t>(step & 1) * kThreads, to = kThreads - from;
+  const uint32_t d = 1u << step;
+  uint64_t v = m.lds_read(from + thread);
+  if (thread >= d) v = combine(a, m.lds_read(from + thread - d), v);
+  m.lds_write(to + thread, v);
+}
+
+// After kSteps steps (an even number) the inclusive totals are back in row 0.  Writes the
+// thread's words of the tile; returns the carry into the next tile.
+template <class M>
+DORA_HD uint64_t store_phase(const Args& a, uint64_t tile, uint32_t thread, const Local& loc,
+                             uint64_t carry, M& m) {
+  static_assert(kSteps % 2 == 0, "the totals end in row 0");
+  const uint64_t before = thread ? combine(a, carry, m.lds_read(thread - 1)) : carry;
+  const uint64_t first = tile * kTile + static_cast<uint64_t>(thread) * kItems;
+  const uint64_t shift = a.offsets ? 0 : 1;
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) {
+    const uint64_t i = first + static_cast<uint64_t>(k);
+    if (i < a.count) m.store_word(i + shift, static_cast<uint32_t>(combine(a, before, loc.pre[k])));
+  }
+  return combine(a, carry, m.lds_read(kThreads - 1));
+}
+
+}  // namespace scan
+
 namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
-enum Kind : uint32_t { kRows = 0, kTile = 1 };
+// (a scan share, kScan, is no Field: it has no view; it runs workgroups [0, wg_begin[0]))
+enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2 };
 
 struct Field {
   uint32_t kind;
@@ -402,17 +514,24 @@ struct Args {
   uint32_t n;
   uint32_t wg_begin[kMaxFields + 1];  // field k runs workgroups [wg_begin[k], wg_begin[k + 1])
   Field f[kMaxFields];
+  scan::Args scan;  // src null: no scan share, wg_begin[0] == 0
 };
 static_assert(sizeof(Args) <= 4096, "multi::Args is passed by value: the kernel-argument limit");
 
 // Arguments of the gather of g[0..n) into dst + off[k]; tile_c[k] is the source-contiguous
 // dimension the tile body transposes field k against, or negative for the rows body (the
-// launcher's selection).  The grid is wg_begin[n]: at most 8 * 2^20 workgroups.
+// launcher's selection).  With `sc` the launch's first workgroup scans a ragged batch's partition
+// into the offsets at dst + 0 and the fields' workgroups follow it (n may then be 0).  The grid is
+// wg_begin[n]: at most 8 * 2^20 + 1 workgroups.
 DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile_c, int n,
-                       uint8_t* dst) {
+                       uint8_t* dst, const ScanDesc* sc = nullptr) {
   Args a{};
   a.n = static_cast<uint32_t>(n);
   uint32_t wg = 0;
+  if (sc) {
+    a.scan = scan::make_args(*sc, dst);
+    wg = 1;
+  }
   for (int k = 0; k < n; ++k) {
     a.wg_begin[k] = wg;
     Field& f = a.f[k];
@@ -432,7 +551,7 @@ DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile
 
 DORA_HD uint32_t grid_for(const Args& a) { return a.wg_begin[a.n]; }
 
-// The field workgroup `w` (< grid_for) belongs to: uniform over the workgroup, at most
+// The field workgroup `w` (wg_begin[0] <= w < grid_for) belongs to: uniform over the workgroup, at most
 // kMaxFields - 1 steps.
 DORA_HD int field_of(const Args& a, uint32_t w) {
   int k = 0;

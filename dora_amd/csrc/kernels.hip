@@ -288,16 +288,65 @@ __global__ __launch_bounds__(gather::kThreads) void gather_tile_kernel(gather::t
   tile_loop<T>(a, blockIdx.x, gridDim.x, lds);
 }
 
+// The scan share's memory: the partition's words with plain loads (each is read once, by one
+// thread), the thread totals in the workgroup's LDS buffer, the offsets with the pack's
+// write-through stores, one aligned dword each.
+struct ScanMem {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint64_t* lds;
+  uint32_t wide;
+  __device__ __forceinline__ int64_t load_word(uint64_t i) const {
+    return wide ? reinterpret_cast<const int64_t*>(src)[i]
+                : static_cast<int64_t>(reinterpret_cast<const int32_t*>(src)[i]);
+  }
+  __device__ __forceinline__ void lds_write(uint32_t i, uint64_t v) const { lds[i] = v; }
+  __device__ __forceinline__ uint64_t lds_read(uint32_t i) const { return lds[i]; }
+  __device__ __forceinline__ void store_word(uint64_t i, uint32_t v) const {
+    st4<2>(dst + 4 * i, v);
+  }
+};
+
+// The whole scan share, run by one workgroup: tile by tile with the carry in a register of every
+// thread (gather_device.h scan::).  The barrier that ends a tile keeps the next tile's totals out
+// of row 0 until every thread has read this tile's.
+__device__ __forceinline__ void scan_share(const gather::scan::Args& a, uint64_t* lds) {
+  namespace sc = gather::scan;
+  ScanMem m{a.src, a.dst, lds, a.wide};
+  sc::head(a, threadIdx.x, m);
+  uint64_t carry = 0;
+  const uint64_t nt = sc::tiles(a);
+  for (uint64_t t = 0; t < nt; ++t) {
+    sc::Local loc;
+    sc::load_phase(a, t, threadIdx.x, loc, m);
+    __syncthreads();
+#pragma unroll
+    for (int step = 0; step < sc::kSteps; ++step) {
+      sc::step_phase(a, threadIdx.x, step, m);
+      __syncthreads();
+    }
+    carry = sc::store_phase(a, t, threadIdx.x, loc, carry, m);
+    __syncthreads();
+  }
+}
+
 // gather_struct_kernel: the fields of a struct-of-tensors plan in one launch (gather_device.h
 // multi::).  A workgroup finds its field in the table (a uniform scan of at most 7 steps) and
 // runs that field's own body over the field's share of the grid: gather_lane with the lane
 // numbered inside the share, or the tile loop over one LDS buffer of 8-byte words that serves
 // every element size (8.25 KiB a workgroup: the four workgroups a CU holds at the rows body's
 // register count take 33 of its 160 KiB, so the buffer costs the rows fields no occupancy,
-// DESIGN §4).
+// DESIGN §4).  A ragged batch whose partition is in HBM adds one workgroup in front of the
+// fields' (w < wg_begin[0]): it scans the partition into the sample's offsets through the first
+// 4 KiB of the same buffer.
+static_assert(gather::scan::kLds <= gather::tile::kLds, "the scan's rows fit the tile buffer");
 __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather::multi::Args a) {
   __shared__ uint64_t lds[gather::tile::kLds];
   const uint32_t w = blockIdx.x;
+  if (w < a.wg_begin[0]) {
+    scan_share(a.scan, lds);
+    return;
+  }
   const int k = gather::multi::field_of(a, w);
   const gather::multi::Field& f = a.f[k];
   const uint64_t local = w - a.wg_begin[k], share = a.wg_begin[k + 1] - a.wg_begin[k];
@@ -519,7 +568,15 @@ int check_device_range(const GatherDesc& g, int device) {
 }
 
 int check_plan_range(const dora_plan& plan, int device) {
-  if (plan.fields.empty()) return check_device_range(plan.gd, device);
+  if (plan.scan_on && plan.scan.count) {
+    // a ragged batch's partition in HBM: its words like any field
+    const int rc = check_device_range(plan.scan.reach, device);
+    if (rc != DORA_OK) {
+      const std::string why = dora_gpu_last_error();
+      return fail(rc, "partition: %s", why.c_str());
+    }
+  }
+  if (plan.fields.empty()) return plan.list ? DORA_OK : check_device_range(plan.gd, device);
   for (size_t k = 0; k < plan.fields.size(); ++k) {
     const int rc = check_device_range(plan.fields[k].gd, device);
     if (rc == DORA_OK) continue;
@@ -585,9 +642,14 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEven
 }
 
 int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
-                         hipEvent_t ev_start, hipEvent_t ev_stop) {
-  if (n == 0 || n > size_t(gather::multi::kMaxFields))
+                         hipEvent_t ev_start, hipEvent_t ev_stop, const ScanDesc* scan) {
+  if ((n == 0 && !scan) || n > size_t(gather::multi::kMaxFields))
     return fail(DORA_ERR_INVALID, "gather of %zu struct fields", n);
+  if (scan && (scan->count > kMaxScanEntries || (reinterpret_cast<uintptr_t>(dst) & 3) ||
+               (scan->count && (reinterpret_cast<uintptr_t>(scan->src) & (scan->wide ? 7u : 3u)))))
+    return fail(DORA_ERR_INVALID, "scan of %llu words into %p: at most %llu words, offsets and "
+                "words aligned", static_cast<unsigned long long>(scan->count),
+                static_cast<void*>(dst), static_cast<unsigned long long>(kMaxScanEntries));
   GatherDesc g[gather::multi::kMaxFields];
   uint64_t off[gather::multi::kMaxFields];
   int tile_c[gather::multi::kMaxFields];
@@ -597,7 +659,8 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
     off[k] = fields[k].dst_off;
     tile_c[k] = select_tile_dim(g[k], dst + off[k]);  // each field as it would go on its own
   }
-  const gather::multi::Args a = gather::multi::make_args(g, off, tile_c, static_cast<int>(n), dst);
+  const gather::multi::Args a =
+      gather::multi::make_args(g, off, tile_c, static_cast<int>(n), dst, scan);
   const dim3 grid(gather::multi::grid_for(a));
   if (ev_start || ev_stop) {
     hipExtLaunchKernelGGL(gather_struct_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
@@ -611,10 +674,19 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
 
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (plan.list)
+    return launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
+                                ev_stop, plan.scan_on ? &plan.scan : nullptr);
   return plan.fields.empty()
              ? launch_gather(plan.gd, dst, stream, ev_start, ev_stop)
              : launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
                                     ev_stop);
+}
+
+int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream) {
+  for (const Segment& g : plan.prefix)
+    DORA_HIP(hipMemcpyAsync(dst + g.dst_off, g.src, g.len, hipMemcpyHostToDevice, stream));
+  return DORA_OK;
 }
 
 // Launch a pack and wait for it by spinning on a host flag the launch writes itself (a
@@ -813,7 +885,10 @@ int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_
     // a device tensor view: inside one allocation of the current GPU before anything reads it
     int device = 0;
     DORA_HIP(hipGetDevice(&device));
-    const int rc = dora::check_plan_range(*plan, device);
+    int rc = dora::check_plan_range(*plan, device);
+    if (rc != DORA_OK) return rc;
+    rc = dora::launch_plan_prefix(*plan, static_cast<uint8_t*>(dst),
+                                  static_cast<hipStream_t>(stream));
     if (rc != DORA_OK) return rc;
     if (plan->gather)
       return dora::launch_plan_gather(*plan, static_cast<uint8_t*>(dst),

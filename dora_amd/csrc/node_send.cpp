@@ -610,8 +610,10 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
   const bool host_bound = plan->size && plan->fill_size() == plan->size && !n->host_bound.empty() &&
                           !n->timed.armed && n->core->device >= 0 &&
                           n->host_bound.count(output_id) && !n->bcast_out.count(output_id);
-  if (host_bound && !host_src && !plan->gather && plan->size <= kHostPackMax) {
-    // (a gather plan takes the HBM slot, which such receivers stage as usual)
+  if (host_bound && !host_src && !plan->gather && plan->prefix.empty() &&
+      plan->size <= kHostPackMax) {
+    // (a gather plan, or one with a host prefix, takes the HBM slot, which such receivers stage
+    // as usual)
     s = host_bound_sample(n, plan->size, plan->size);
   } else if (host_bound && host_src && plan->size >= kZeroCopyThreshold) {
     // a host source for them: the CPU copies it into shared memory, as a node without a GPU
@@ -670,11 +672,21 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
     if (bcast) n->core->order_after_node_stream(bo->second.stream);
     const bool sync = plan->dev == ARROW_DEVICE_ROCM &&
                       !((flags & DORA_SEND_ASYNC) || n->async_default);
-    rc = plan->gather
-             ? gather_sample(n, s, *plan, bcast ? bo->second.stream : nullptr, t_start, t_stop,
-                             !bcast)
-             : fill_sample(n, s, plan->segs.data(), plan->segs.size(), plan->dev,
-                           bcast ? bo->second.stream : nullptr, t_start, t_stop, !bcast, sync);
+    hipStream_t st = bcast ? bo->second.stream : nullptr;
+    rc = DORA_OK;
+    if (!plan->prefix.empty()) {
+      // a ragged batch's host offsets beside device values: copied on the stream the pack or
+      // gather then takes (a given stream keeps the pack off the AQL queue), so the fill signal
+      // that follows covers them
+      DeviceScope ds(n->core->device);
+      if (!st) st = n->core->next_fill_stream();
+      rc = launch_plan_prefix(*plan, static_cast<uint8_t*>(s->slot->ptr), st);
+    }
+    if (rc == DORA_OK)
+      rc = plan->gather
+               ? gather_sample(n, s, *plan, st, t_start, t_stop, !bcast)
+               : fill_sample(n, s, plan->segs.data(), plan->segs.size(), plan->dev, st, t_start,
+                             t_stop, !bcast, sync);
     if (rc != DORA_OK) {
       if (tp) tp->pending = false;
       add_to_cache(n, s->slot);
@@ -1017,6 +1029,24 @@ int dora_node_send_output_tensor_struct(dora_node* n, const char* output_id,
   }
   // host fields and all-dense device fields: a multi-segment plan like any other; device fields
   // of which any is strided: a gather plan, which goes where a single strided tensor's goes
+  std::unique_ptr<dora_plan> owner(plan);
+  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
+  DORA_GUARD_END
+}
+
+int dora_node_send_output_tensor_list(dora_node* n, const char* output_id,
+                                      const dora_tensor_list* list, ArrowDeviceType device_type,
+                                      const uint8_t* params, size_t params_len, uint32_t flags) {
+  if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  dora_plan* plan = nullptr;
+  {
+    dora::SubSpan sp(dora::SP_SEND_PLAN);
+    const int rc = dora::build_tensor_list_plan(list, device_type, &plan);
+    if (rc != DORA_OK) return rc;
+  }
+  // host values: a multi-segment host plan whose first segment is the offsets; device values: the
+  // struct send's plan behind the offsets, which a prefix copy or the launch's scan share writes
   std::unique_ptr<dora_plan> owner(plan);
   return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
   DORA_GUARD_END

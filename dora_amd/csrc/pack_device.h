@@ -165,6 +165,15 @@ __device__ __forceinline__ void st16(uint8_t* p, u32x4 v) {
   }
 }
 
+// one aligned dword (the offsets a ragged batch's scan share writes)
+template <int NT>
+__device__ __forceinline__ void st4(uint8_t* p, uint32_t v) {
+  if constexpr (NT >= 2) {
+    asm volatile("global_store_dword %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
+  } else {
+    *reinterpret_cast<uint32_t*>(p) = v;
+  }
+}
 template <int NT>
 __device__ __forceinline__ void st1(uint8_t* p, uint8_t v) {
   if constexpr (NT >= 2) {

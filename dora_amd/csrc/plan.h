@@ -109,6 +109,21 @@ struct PlanField {
   uint64_t bytes;
 };
 
+// The partition of a ragged-batch plan (dora_gpu_plan_tensor_list) when it lives in HBM: `count`
+// dense words of 4 or 8 bytes at `src` (B lengths, or B + 1 offsets), never read on the host.  One
+// workgroup of the plan's launch scans them into the sample's B + 1 int32 offsets, every one
+// clamped to [0, n] (gather_device.h scan::).  `reach` is what check_plan_range holds against the
+// allocation of `src` before anything is launched.
+constexpr uint64_t kMaxScanEntries = 1u << 20;
+struct ScanDesc {
+  const uint8_t* src;
+  uint64_t count;   // input words
+  uint64_t n;       // rows of the values: the clamp
+  uint32_t wide;    // 0: int32 words, 1: int64
+  uint32_t offsets; // 0: the words are lengths (sum), 1: offsets (running maximum)
+  GatherDesc reach;
+};
+
 // Fill signal written by a pack launch itself (kernels.hip): once every workgroup's stores are
 // complete, a system-scope store of `epoch` into `flag` (device view of a host-registered fill
 // flag), preceded by the launch's start / signal times into flag[1], flag[2] (the flag must own
@@ -162,8 +177,16 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream,
 // Launch the gather of every field of a multi-gather struct plan into `dst + dst_off` in one
 // launch of gather_struct_kernel (kernels.hip): each field's bytes as launch_gather writes them,
 // nothing between fields and nothing at or past the last field's end.
+// With `scan` (a ragged-batch plan whose partition is in HBM; n may then be 0) one more workgroup
+// of the same launch writes the sample's offsets at dst + 0 (dst a whole number of dwords).
 int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
-                         hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                         hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
+                         const ScanDesc* scan = nullptr);
+// The host-source segments a device plan carries beside what its kernel reads (a ragged batch's
+// offsets computed in the plan): copied into `dst` on `stream`, ahead of the pack or gather that
+// follows on the same stream.  The bytes are pageable memory of the plan: the runtime has staged
+// them when the call returns.
+int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
 // The gather a gather plan asks for: launch_gather of its view, or launch_gather_struct of its
 // fields.
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
@@ -195,6 +218,8 @@ int build_tensor_plan(const dora_tensor* tensor, ArrowDeviceType dev, dora_plan*
 // Named tensors of one leading extent as one Struct message (dora_gpu_plan_tensor_struct).
 int build_tensor_struct_plan(const dora_tensor_field* fields, size_t n, ArrowDeviceType dev,
                              dora_plan** out);
+// A ragged batch: the fields' rows cut into lists by a partition (dora_gpu_plan_tensor_list).
+int build_tensor_list_plan(const dora_tensor_list* list, ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -219,5 +244,13 @@ struct dora_plan {
   // struct-of-tensors plans (dev_tensor): one entry per field instead of `gd`; with `gather`,
   // gather_struct_kernel reads all of them in one launch (a multi-gather plan), else `segs` does
   std::vector<dora::PlanField> fields;
+  // ragged-batch plans (tensor_plan.cpp): the int32 offsets computed from a host partition, read
+  // by a segment — of `segs` in a host plan, of `prefix` in a device plan, whose other bytes a
+  // kernel moves — or, for a partition in HBM, the scan the plan's one launch carries
+  bool list = false;
+  std::vector<int32_t> list_offsets;
+  std::vector<dora::Segment> prefix;
+  bool scan_on = false;
+  dora::ScanDesc scan{};
   uint64_t fill_size() const { return ext_size > size ? ext_size : size; }
 };

@@ -376,6 +376,104 @@ PyObject* py_send_tensor_struct(PyObject*, PyObject* const* args, Py_ssize_t nar
   return PyLong_FromLong(rc);
 }
 
+// send_tensor_list(handle, output_id, names, capsules, partition, form, partition_device,
+// device_type, metadata, flags) -> status: a ragged batch as dora_node_send_output_tensor_list.
+// `names` is a tuple of str over the tuple `capsules`, or None over a tuple of one capsule (a bare
+// tensor); `partition` a "dltensor" capsule of the 1-D lengths or offsets.  Every capsule, the
+// partition's included, is consumed as send_tensor_struct consumes its own: all checked first,
+// then renamed, their deleters run once the call has returned.
+PyObject* py_send_tensor_list(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  const char* usage = "send_tensor_list(handle, output_id, names, capsules, partition, form, "
+                      "partition_device, device_type, metadata, flags): names is None over one "
+                      "capsule or a tuple as long as the tuple of capsules";
+  if (nargs != 10 || !PyTuple_Check(args[3]) ||
+      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
+                           : PyTuple_Check(args[2]) &&
+                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+    PyErr_SetString(PyExc_TypeError, usage);
+    return nullptr;
+  }
+  void* h = nullptr;
+  if (!as_ptr(args[0], &h)) return nullptr;
+  const char* oid = as_cstr(args[1]);
+  if (!oid) return nullptr;
+  const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
+  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
+  std::vector<PyObject*> caps(static_cast<size_t>(n) + 1);
+  for (Py_ssize_t k = 0; k <= n; ++k) {
+    PyObject* cap = k < n ? PyTuple_GET_ITEM(args[3], k) : args[4];
+    if (k < n) {
+      fields[size_t(k)].name = nullptr;
+      if (args[2] != Py_None) {
+        fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
+        if (!fields[size_t(k)].name) return nullptr;
+      }
+    }
+    if (!PyCapsule_IsValid(cap, "dltensor")) {
+      if (k < n)
+        PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
+                                      "unused, unversioned one)", k);
+      else
+        PyErr_SetString(PyExc_TypeError, "partition: expected a DLPack capsule named \"dltensor\" "
+                                         "(an unused, unversioned one)");
+      return nullptr;
+    }
+    for (Py_ssize_t j = 0; j < k; ++j)
+      if (caps[size_t(j)] == cap) {
+        PyErr_Format(PyExc_TypeError, "capsules %zd and %zd are one capsule", j, k);
+        return nullptr;
+      }
+    caps[size_t(k)] = cap;
+  }
+  const long form = PyLong_AsLong(args[5]);
+  if (form == -1 && PyErr_Occurred()) return nullptr;
+  const long pdev = PyLong_AsLong(args[6]);
+  if (pdev == -1 && PyErr_Occurred()) return nullptr;
+  const long dev = PyLong_AsLong(args[7]);
+  if (dev == -1 && PyErr_Occurred()) return nullptr;
+  const unsigned long flags = PyLong_AsUnsignedLong(args[9]);
+  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
+  std::string& params = t_params;
+  if (!encode(args[8], params)) return nullptr;
+  dora_tensor_list list{};
+  std::vector<DlManaged*> managed(caps.size());
+  for (size_t k = 0; k < caps.size(); ++k) {
+    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(caps[k], "dltensor"));
+    if (!m || PyCapsule_SetName(caps[k], "used_dltensor") != 0) {
+      // (cannot happen after the checks above; the capsules renamed so far are released)
+      for (size_t j = 0; j < k; ++j)
+        if (managed[j]->deleter) managed[j]->deleter(managed[j]);
+      return nullptr;
+    }
+    managed[k] = m;
+    dora_tensor& t = k + 1 < caps.size() ? fields[k].tensor : list.partition;
+    t = dora_tensor{};
+    t.data = m->t.data;
+    t.byte_offset = m->t.byte_offset;
+    t.dtype_code = m->t.code;
+    t.dtype_bits = m->t.bits;
+    t.dtype_lanes = m->t.lanes;
+    t.ndim = m->t.ndim;
+    t.shape = m->t.shape;
+    t.strides = m->t.strides;
+  }
+  list.fields = fields.data();
+  list.n = fields.size();
+  list.partition_form = static_cast<uint32_t>(form);
+  list.partition_device = static_cast<ArrowDeviceType>(pdev);
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor_list(static_cast<dora_node*>(h), oid, &list,
+                                         static_cast<ArrowDeviceType>(dev),
+                                         reinterpret_cast<const uint8_t*>(params.data()),
+                                         params.size(), static_cast<uint32_t>(flags));
+  Py_END_ALLOW_THREADS
+  // (deleters under the GIL and after the status has been taken, as in send_tensor)
+  for (DlManaged* m : managed)
+    if (m->deleter) m->deleter(m);
+  return PyLong_FromLong(rc);
+}
+
 // MetadataParameters bytes -> dict (the inverse of encode; dora_amd.node.decode_parameters).
 PyObject* decode(const uint8_t* p, size_t n) {
   PyObject* out = PyDict_New();
@@ -834,6 +932,9 @@ PyMethodDef methods[] = {
     {"send_tensor_struct",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_struct)),
      METH_FASTCALL, "dora_node_send_output_tensor_struct of named DLPack capsules, which it consumes."},
+    {"send_tensor_list",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_list)),
+     METH_FASTCALL, "dora_node_send_output_tensor_list of DLPack capsules, which it consumes."},
     {"send_array", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_array)),
      METH_FASTCALL, "dora_node_send_output with parameters encoded from a dict."},
     {nullptr, nullptr, 0, nullptr}};

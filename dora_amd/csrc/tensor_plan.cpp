@@ -13,6 +13,10 @@
 // same per-tensor work once per field, each leaf at the running offset padded to its element
 // size, the struct node without a buffer; host fields as copy segments, device fields as copy
 // segments when all are dense and as one multi-gather when any is strided.
+//
+// A ragged batch (dora_gpu_plan_tensor_list) is the List array over such a tensor or record: the
+// int32 offsets first, then the same leaves behind them.  A host partition is checked and turned
+// into offsets here; one in HBM is never read, and the plan's one launch scans it.
 #include <cstring>
 #include <memory>
 #include <string>
@@ -310,6 +314,91 @@ int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out
   DORA_GUARD_END
 }
 
+namespace {
+
+// The fields of a record laid out from sample offset `off`: the schemas and what the loop over
+// them found, for the struct plan and the ragged-batch plan alike.
+struct FieldLayout {
+  std::vector<std::unique_ptr<TypeChain>> chains;
+  std::vector<ArrowSchema*> kids;
+  uint64_t off = 0;     // in: where the first leaf may start; out: the end of the last
+  uint64_t staged = 0;  // bytes of host fields that are gathered or copied now
+  bool strided = false;
+};
+
+// Validation, view and type info of every field of `f[0..n)`, each leaf at the running offset
+// padded to its element size: PlanFields into `p`, type info into nodes[k].  `bare`: the one
+// field is a tensor of its own (no name; its chain's head is called `head`).
+int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
+                  const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
+                  FieldLayout& lay) {
+  p.fields.resize(n);
+  lay.chains.resize(n);
+  lay.kids.resize(n);
+  nodes.resize(n);
+  uint64_t off = lay.off;
+  for (size_t k = 0; k < n; ++k) {
+    const char* name = bare ? head : f[k].name;
+    if (!bare) {
+      if (!name || !name[0])
+        return fail(DORA_ERR_INVALID, "field %zu has %s name", k, name ? "an empty" : "a NULL");
+      for (size_t j = 0; j < k; ++j)
+        if (std::strcmp(f[j].name, name) == 0)
+          return fail(DORA_ERR_INVALID, "field %zu `%s` repeats the name of field %zu", k, name, j);
+    }
+    const dora_tensor& t = f[k].tensor;
+    TensorView v;
+    const int rc = describe_tensor(&t, dev, v);
+    if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
+    if (t.shape[0] != f[0].tensor.shape[0])
+      return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
+                  "%lld: the fields of a struct share shape[0] (give tensors of unrelated shapes "
+                  "a leading extent of 1)", k, name, static_cast<long long>(t.shape[0]),
+                  f[0].name, static_cast<long long>(f[0].tensor.shape[0]));
+    // the running offset padded to the leaf's element size (a power of two)
+    const uint64_t elem = t.dtype_bits / 8;
+    uint64_t padded, end;
+    if (__builtin_add_overflow(off, elem - 1, &padded) ||
+        __builtin_add_overflow(padded & ~(elem - 1), v.bytes, &end) || end >> 63)
+      return fail(DORA_ERR_INVALID, "field %zu `%s`: the message's size overflows 64 bits", k,
+                  bare ? "" : name);
+    off = padded & ~(elem - 1);
+    PlanField& pf = p.fields[k];
+    pf.name = bare ? "" : name;
+    pf.gd = v.gd;
+    pf.dst_off = off;
+    pf.bytes = v.bytes;
+    lay.chains[k].reset(new TypeChain(v.leaf, t.shape, t.ndim, name));
+    lay.kids[k] = &lay.chains[k]->sch[0];
+    tensor_type_info(*lay.chains[k], t.shape, t.ndim, off, v.bytes, nodes[k]);
+    off = end;
+    const bool stage = dev == ARROW_DEVICE_ROCM_HOST || (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
+    if (stage) lay.staged += v.bytes;  // (<= off)
+    lay.strided |= v.gd.view.nd != 0;
+  }
+  lay.off = off;
+  return DORA_OK;
+}
+
+// Host fields (none of them empty): dense pageable ones read in place, the others gathered now
+// into one staging buffer — the segments of an ordinary multi-segment host plan.
+void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
+  p.staged.resize(staged);
+  uint64_t at = 0;
+  for (const PlanField& pf : p.fields) {
+    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0) {
+      p.segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
+      continue;
+    }
+    gather_host(pf.gd.view, p.staged.data() + at);
+    p.segs.push_back({p.staged.data() + at, pf.dst_off, pf.bytes});
+    at += pf.bytes;
+  }
+  p.fields.clear();  // (device plans keep them for the range check and the gather)
+}
+
+}  // namespace
+
 int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceType dev,
                              dora_plan** out) {
   if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
@@ -322,53 +411,15 @@ int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceTy
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
-  p->fields.resize(n);
-  std::vector<std::unique_ptr<TypeChain>> chains(n);
-  std::vector<ArrowSchema*> kids(n);
-  p->root.children.resize(n);
-  uint64_t off = 0, staged = 0;
-  bool strided = false;
-  for (size_t k = 0; k < n; ++k) {
-    const char* name = f[k].name;
-    if (!name || !name[0])
-      return fail(DORA_ERR_INVALID, "field %zu has %s name", k, name ? "an empty" : "a NULL");
-    for (size_t j = 0; j < k; ++j)
-      if (std::strcmp(f[j].name, name) == 0)
-        return fail(DORA_ERR_INVALID, "field %zu `%s` repeats the name of field %zu", k, name, j);
-    const dora_tensor& t = f[k].tensor;
-    TensorView v;
-    const int rc = describe_tensor(&t, dev, v);
-    if (rc != DORA_OK) return field_fail(rc, k, name);
-    if (t.shape[0] != f[0].tensor.shape[0])
-      return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
-                  "%lld: the fields of a struct share shape[0] (give tensors of unrelated shapes "
-                  "a leading extent of 1)", k, name, static_cast<long long>(t.shape[0]),
-                  f[0].name, static_cast<long long>(f[0].tensor.shape[0]));
-    // the running offset padded to the leaf's element size (a power of two)
-    const uint64_t elem = t.dtype_bits / 8;
-    uint64_t padded, end;
-    if (__builtin_add_overflow(off, elem - 1, &padded) ||
-        __builtin_add_overflow(padded & ~(elem - 1), v.bytes, &end) || end >> 63)
-      return fail(DORA_ERR_INVALID, "field %zu `%s`: the message's size overflows 64 bits", k, name);
-    off = padded & ~(elem - 1);
-    PlanField& pf = p->fields[k];
-    pf.name = name;
-    pf.gd = v.gd;
-    pf.dst_off = off;
-    pf.bytes = v.bytes;
-    chains[k].reset(new TypeChain(v.leaf, t.shape, t.ndim, name));
-    kids[k] = &chains[k]->sch[0];
-    tensor_type_info(*chains[k], t.shape, t.ndim, off, v.bytes, p->root.children[k]);
-    off = end;
-    const bool stage = dev == ARROW_DEVICE_ROCM_HOST || (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
-    if (stage) staged += v.bytes;  // (<= off)
-    strided |= v.gd.view.nd != 0;
-  }
+  FieldLayout lay;
+  const int rc = layout_fields(f, n, dev, false, nullptr, *p, p->root.children, lay);
+  if (rc != DORA_OK) return rc;
+  const uint64_t off = lay.off;
   ArrowSchema top;
   std::memset(&top, 0, sizeof(top));
   top.format = "+s";
   top.name = "";
-  top.children = kids.data();
+  top.children = lay.kids.data();
   top.n_children = static_cast<int64_t>(n);
   serialize_schema(&top, true, p->root.schema);
   p->root.len = static_cast<uint64_t>(f[0].tensor.shape[0]);
@@ -383,26 +434,238 @@ int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceTy
     // path, the AQL multi-segment packs included); any strided: no segments, one launch of
     // gather_struct_kernel over every field.  Either way each field's reach is checked first.
     p->dev_tensor = true;
-    p->gather = strided;
-    if (!strided)
+    p->gather = lay.strided;
+    if (!lay.strided)
       for (const PlanField& pf : p->fields) p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
     *out = p.release();
     return DORA_OK;
   }
-  // host fields: dense pageable ones read in place, the others gathered now into one staging
-  // buffer — an ordinary multi-segment host plan
-  p->staged.resize(staged);
-  uint64_t at = 0;
-  for (const PlanField& pf : p->fields) {
-    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0) {
-      p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
-      continue;
+  stage_host_fields(*p, dev, lay.staged);
+  *out = p.release();
+  return DORA_OK;
+  DORA_GUARD_END
+}
+
+namespace {
+
+// The partition of a ragged batch as words: a 1-D dense tensor of int32 or int64.
+struct Partition {
+  const uint8_t* src = nullptr;
+  uint64_t count = 0;
+  bool wide = false;
+};
+
+int describe_partition(const dora_tensor& t, Partition& out) {
+  if (t.dtype_code != DL_INT || t.dtype_lanes != 1 || (t.dtype_bits != 32 && t.dtype_bits != 64))
+    return fail(DORA_ERR_INVALID, "partition dtype (code %u, %u bits, %u lanes) is not int32 or "
+                "int64", unsigned(t.dtype_code), unsigned(t.dtype_bits), unsigned(t.dtype_lanes));
+  if (t.ndim != 1 || !t.shape)
+    return fail(DORA_ERR_INVALID, "partition has %d dimensions (a 1-D tensor of lengths or "
+                "offsets)", t.ndim);
+  if (t.shape[0] < 0)
+    return fail(DORA_ERR_INVALID, "partition extent %lld is negative",
+                static_cast<long long>(t.shape[0]));
+  if (t.strides && t.shape[0] > 1 && t.strides[0] != 1)
+    return fail(DORA_ERR_INVALID, "partition stride %lld: the partition is dense",
+                static_cast<long long>(t.strides[0]));
+  if (!t.data && t.shape[0]) return fail(DORA_ERR_INVALID, "partition data is NULL");
+  out.src = static_cast<const uint8_t*>(t.data) + t.byte_offset;
+  out.count = static_cast<uint64_t>(t.shape[0]);
+  out.wide = t.dtype_bits == 64;
+  if (out.count && (reinterpret_cast<uintptr_t>(out.src) & (out.wide ? 7u : 3u)))
+    return fail(DORA_ERR_INVALID, "partition data %p is not aligned to its %d-byte words",
+                static_cast<const void*>(out.src), out.wide ? 8 : 4);
+  return DORA_OK;
+}
+
+// The B + 1 offsets of a host partition over `rows` rows, checked: DORA_ERR_INVALID naming the
+// first word that breaks the rule.
+int host_offsets(const Partition& pt, bool offsets_form, uint64_t rows, std::vector<int32_t>& o) {
+  auto word = [&](uint64_t i) -> int64_t {
+    if (pt.wide) {
+      int64_t v;
+      std::memcpy(&v, pt.src + 8 * i, 8);
+      return v;
     }
-    gather_host(pf.gd.view, p->staged.data() + at);
-    p->segs.push_back({p->staged.data() + at, pf.dst_off, pf.bytes});
-    at += pf.bytes;
+    int32_t v;
+    std::memcpy(&v, pt.src + 4 * i, 4);
+    return v;
+  };
+  const int64_t n = static_cast<int64_t>(rows);
+  if (offsets_form) {
+    o.resize(pt.count);
+    int64_t prev = 0;
+    for (uint64_t i = 0; i < pt.count; ++i) {
+      const int64_t v = word(i);
+      if (i == 0 && v != 0)
+        return fail(DORA_ERR_INVALID, "partition: offset 0 is %lld: offsets start at 0",
+                    static_cast<long long>(v));
+      if (v < prev)
+        return fail(DORA_ERR_INVALID, "partition: offset %llu is %lld, below offset %llu (%lld): "
+                    "offsets never decrease", static_cast<unsigned long long>(i),
+                    static_cast<long long>(v), static_cast<unsigned long long>(i - 1),
+                    static_cast<long long>(prev));
+      if (v > n)
+        return fail(DORA_ERR_INVALID, "partition: offset %llu is %lld, past the %lld rows of the "
+                    "values", static_cast<unsigned long long>(i), static_cast<long long>(v),
+                    static_cast<long long>(n));
+      o[i] = static_cast<int32_t>(v);
+      prev = v;
+    }
+    if (prev != n)
+      return fail(DORA_ERR_INVALID, "partition: offset %llu, the last, is %lld: offsets end at "
+                  "the %lld rows of the values", static_cast<unsigned long long>(pt.count - 1),
+                  static_cast<long long>(prev), static_cast<long long>(n));
+    return DORA_OK;
   }
-  p->fields.clear();  // (device plans keep them for the range check and the gather)
+  o.resize(pt.count + 1);
+  int64_t sum = 0;
+  o[0] = 0;
+  for (uint64_t i = 0; i < pt.count; ++i) {
+    const int64_t v = word(i);
+    if (v < 0)
+      return fail(DORA_ERR_INVALID, "partition: length %llu is %lld: lengths are not negative",
+                  static_cast<unsigned long long>(i), static_cast<long long>(v));
+    if (v > n - sum)
+      return fail(DORA_ERR_INVALID, "partition: lengths 0..%llu sum past the %lld rows of the "
+                  "values (length %llu is %lld)", static_cast<unsigned long long>(i),
+                  static_cast<long long>(n), static_cast<unsigned long long>(i),
+                  static_cast<long long>(v));
+    sum += v;
+    o[i + 1] = static_cast<int32_t>(sum);
+  }
+  if (sum != n)
+    return fail(DORA_ERR_INVALID, "partition: the %llu lengths sum to %lld, the values have %lld "
+                "rows (index %llu is where they fall short)",
+                static_cast<unsigned long long>(pt.count), static_cast<long long>(sum),
+                static_cast<long long>(n), static_cast<unsigned long long>(pt.count));
+  return DORA_OK;
+}
+
+}  // namespace
+
+int build_tensor_list_plan(const dora_tensor_list* l, ArrowDeviceType dev, dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!l) return fail(DORA_ERR_INVALID, "list is NULL");
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (!known_device(l->partition_device))
+    return fail(DORA_ERR_INVALID, "unsupported partition_device %d", l->partition_device);
+  if (l->partition_form != DORA_PARTITION_LENGTHS && l->partition_form != DORA_PARTITION_OFFSETS)
+    return fail(DORA_ERR_INVALID, "partition_form %u is neither lengths nor offsets",
+                l->partition_form);
+  const size_t n = l->n;
+  const dora_tensor_field* f = l->fields;
+  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a ragged batch has values: at least one field");
+  if (n > kMaxStructFields)
+    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
+                kMaxStructFields, n);
+  const bool bare = n == 1 && !f[0].name;
+  const bool offsets_form = l->partition_form == DORA_PARTITION_OFFSETS;
+  const bool dev_part = l->partition_device == ARROW_DEVICE_ROCM;
+  if (dev_part && dev != ARROW_DEVICE_ROCM)
+    return fail(DORA_ERR_INVALID, "a partition in device memory needs values on this node's GPU: "
+                "with host values pass the partition as a host list (.tolist())");
+  DORA_GUARD_BEGIN
+  Partition pt;
+  int rc = describe_partition(l->partition, pt);
+  if (rc != DORA_OK) return rc;
+  if (offsets_form && pt.count == 0)
+    return fail(DORA_ERR_INVALID, "partition: offsets have at least one entry (B + 1 of them)");
+  if (pt.count >= (uint64_t(1) << 31) - (offsets_form ? 0 : 1))
+    return fail(DORA_ERR_UNSUPPORTED, "a ragged batch of %llu lists needs 64-bit offsets "
+                "(LargeList), which is not produced",
+                static_cast<unsigned long long>(pt.count - (offsets_form ? 1 : 0)));
+  if (dev_part && pt.count > kMaxScanEntries)
+    return fail(DORA_ERR_UNSUPPORTED, "a partition in device memory has at most %llu entries "
+                "(%llu given): one workgroup scans them",
+                static_cast<unsigned long long>(kMaxScanEntries),
+                static_cast<unsigned long long>(pt.count));
+  const uint64_t lists = pt.count - (offsets_form ? 1 : 0);
+  const uint64_t obytes = (lists + 1) * 4;
+
+  std::unique_ptr<dora_plan> p(new dora_plan());
+  p->list = true;
+  p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
+  // the type info: the list node with its offsets buffer, under it the values' node — the
+  // tensor's chain, or the struct node over the fields' chains
+  p->root.children.resize(1);
+  TypeInfoNode& child = p->root.children[0];
+  FieldLayout lay;
+  lay.off = obytes;
+  std::vector<TypeInfoNode> solo;
+  rc = layout_fields(f, n, dev, bare, "item", *p, bare ? solo : child.children, lay);
+  if (rc != DORA_OK) return rc;
+  const uint64_t rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
+  if (rows >> 31)
+    return fail(DORA_ERR_UNSUPPORTED, "a ragged batch over %llu rows needs 64-bit offsets "
+                "(LargeList), which is not produced", static_cast<unsigned long long>(rows));
+  ArrowSchema item;
+  std::memset(&item, 0, sizeof(item));
+  ArrowSchema* item_ptr = &item;
+  if (bare) {
+    child = std::move(solo[0]);
+    item_ptr = lay.kids[0];
+  } else {
+    item.format = "+s";
+    item.name = "item";
+    item.flags = ARROW_FLAG_NULLABLE;
+    item.children = lay.kids.data();
+    item.n_children = static_cast<int64_t>(n);
+    serialize_schema(&item, true, child.schema);
+    child.len = rows;
+  }
+  ArrowSchema top;
+  std::memset(&top, 0, sizeof(top));
+  top.format = "+l";
+  top.name = "";
+  top.children = &item_ptr;
+  top.n_children = 1;
+  serialize_schema(&top, true, p->root.schema);
+  p->root.len = lists;
+  p->root.bufs.push_back({0, obytes});
+  p->size = lay.off;
+  const bool empty = rows == 0;  // every field is then empty: only the offsets travel
+  if (empty) p->fields.clear();
+
+  if (!dev_part) {
+    rc = host_offsets(pt, offsets_form, rows, p->list_offsets);
+    if (rc != DORA_OK) return rc;
+    const Segment oseg{p->list_offsets.data(), 0, obytes};
+    if (dev != ARROW_DEVICE_ROCM || empty) {
+      // host values (or none): an ordinary multi-segment host plan, the offsets its first segment
+      p->dev = ARROW_DEVICE_CPU;
+      p->segs.push_back(oseg);
+      if (!empty) stage_host_fields(*p, dev, lay.staged);
+      *out = p.release();
+      return DORA_OK;
+    }
+    // device values: the offsets go ahead on the pack's stream, the fields as in the struct plan
+    p->prefix.push_back(oseg);
+    p->dev_tensor = true;
+    p->gather = lay.strided;
+    if (!lay.strided)
+      for (const PlanField& pf : p->fields) p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
+    *out = p.release();
+    return DORA_OK;
+  }
+  // a partition in HBM: never read here.  One launch scans it and gathers every field, dense
+  // ones included.
+  p->dev_tensor = true;
+  p->gather = true;
+  p->scan_on = true;
+  ScanDesc& sc = p->scan;
+  sc.src = pt.src;
+  sc.count = pt.count;
+  sc.n = rows;
+  sc.wide = pt.wide ? 1 : 0;
+  sc.offsets = offsets_form ? 1 : 0;
+  sc.reach.view.src = pt.src;
+  sc.reach.view.total = pt.count * (pt.wide ? 8 : 4);
+  sc.reach.view.row = sc.reach.view.total;
+  sc.reach.elem = pt.wide ? 8 : 4;
+  sc.reach.lo = 0;
+  sc.reach.hi = static_cast<int64_t>(sc.reach.view.total) - 1;
   *out = p.release();
   return DORA_OK;
   DORA_GUARD_END
@@ -420,6 +683,11 @@ int dora_gpu_plan_tensor(const dora_tensor* tensor, ArrowDeviceType device_type,
 int dora_gpu_plan_tensor_struct(const dora_tensor_field* fields, size_t n,
                                 ArrowDeviceType device_type, dora_plan** out) {
   return dora::build_tensor_struct_plan(fields, n, device_type, out);
+}
+
+int dora_gpu_plan_tensor_list(const dora_tensor_list* list, ArrowDeviceType device_type,
+                              dora_plan** out) {
+  return dora::build_tensor_list_plan(list, device_type, out);
 }
 
 }  // extern "C"

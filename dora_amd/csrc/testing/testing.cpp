@@ -362,6 +362,23 @@ int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, s
   return DORA_OK;
 }
 
+int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, uint64_t* count,
+                            int* wide, int* offsets_form, uint64_t* rows, int64_t* lo, int64_t* hi,
+                            uint64_t* prefix_bytes) {
+  if (!plan || !plan->list) return dora::fail(DORA_ERR_INVALID, "not a ragged-batch plan");
+  const dora::ScanDesc& s = plan->scan;
+  if (scan) *scan = plan->scan_on;
+  if (src) *src = s.src;
+  if (count) *count = s.count;
+  if (wide) *wide = static_cast<int>(s.wide);
+  if (offsets_form) *offsets_form = static_cast<int>(s.offsets);
+  if (rows) *rows = s.n;
+  if (lo) *lo = s.reach.lo;
+  if (hi) *hi = s.reach.hi;
+  if (prefix_bytes) *prefix_bytes = plan->prefix.empty() ? 0 : plan->prefix[0].len;
+  return DORA_OK;
+}
+
 int dora_gpu_test_ide_output(const char* dataflow_id, const char* node_id,
                                         const char* output_id, const uint8_t* type_info,
                                         size_t type_info_len, const uint8_t* params,

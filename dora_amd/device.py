@@ -217,6 +217,17 @@ class DeviceArray:
         struct-of-tensors message; dora_amd.tensor.to_torch)."""
         return _field_views(self, self)
 
+    def list_values(self):
+        """The child of a List array as a view narrowed by nothing: the offsets index it, as in
+        Arrow.  It shares this array's lifetime and exports DLPack (or `field_views`, for a struct
+        child) as a DeviceArray does."""
+        return DeviceListValues(self, self)
+
+    def list_offsets(self):
+        """The `length + 1` int32 offsets of this List array's own slice (the parent's `offset`
+        respected) as a zero-copy kDLROCM DLPack producer over the sample."""
+        return DeviceListOffsets(self, self)
+
     def close(self):
         release_array(self.array)
         if self._schema is not None:
@@ -282,6 +293,42 @@ class DeviceArrayView:
     def __dlpack_device__(self):
         from .dlpack import kDLROCM
         return (kDLROCM, self.device_id)
+
+
+class DeviceListValues(DeviceArrayView):
+    """The child of a device List array (DeviceArray.list_values): the child's own header, whole."""
+
+    def __init__(self, owner: DeviceArray, parent):
+        import pyarrow as pa
+        t, a = parent.type, parent.array
+        if not pa.types.is_list(t) or a.n_children != 1:
+            raise TypeError(f"list_values() needs a List array, got {t}")
+        c = ArrowArray.from_buffer_copy(a.children[0].contents)
+        c.release = None  # a borrowed header: the owner releases the array
+        self.array, self.type, self._owner = c, t.value_type, owner
+
+
+class DeviceListOffsets:
+    """The offsets of a device List array (DeviceArray.list_offsets) for DLPack consumers; every
+    export keeps the DeviceArray that owns the memory alive."""
+
+    def __init__(self, owner: DeviceArray, parent):
+        import pyarrow as pa
+        from .dlpack import _no_nulls
+        t, a = parent.type, parent.array
+        if not pa.types.is_list(t) or a.n_buffers < 2:
+            raise TypeError(f"list_offsets() needs a List array, got {t}")
+        _no_nulls(a, t)
+        self._owner, self.length = owner, a.length + 1
+        self._ptr = (a.buffers[1] or 0) + 4 * a.offset
+
+    def __dlpack__(self, stream=None, **kwargs):
+        from .dlpack import to_dlpack_capsule
+        return to_dlpack_capsule(self._ptr, self.length, "i", self._owner.device_id, self._owner)
+
+    def __dlpack_device__(self):
+        from .dlpack import kDLROCM
+        return (kDLROCM, self._owner.device_id)
 
 
 def _field_views(owner, parent) -> dict:

@@ -32,6 +32,7 @@ _DL_ROCM = 10          # DLPack device types: kDLROCM
 _DL_CPU = 1
 _DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinned)
 from .device import DeviceArray, DeviceBuffer
+from .tensor import Ragged as _Ragged
 from .type_info import decode
 
 try:
@@ -234,10 +235,13 @@ class Node:
             rc = self._send_tensor(output_id, data, metadata, f)
         elif isinstance(data, dict):
             rc = self._send_tensor_struct(output_id, data, metadata, f)
+        elif isinstance(data, _Ragged):
+            rc = self._send_ragged(output_id, data, metadata, f)
         else:
             raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer, "
-                            "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU) "
-                            "or a dict of such tensors")
+                            "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU), "
+                            "a dict of such tensors or a ragged batch of either "
+                            "(dora_amd.tensor.ragged)")
         if rc:
             _lib.check(rc)
 
@@ -361,6 +365,106 @@ class Node:
             del keep, described
             return rc
         return _fast.send_tensor_struct(self.handle, output_id, names, caps, dev, metadata, flags)
+
+    def _tensor_kind(self, v, what: str) -> str:
+        """"host" or "device" of a DLPack producer `v` (`what` names it in a refusal)."""
+        if not (hasattr(v, "__dlpack__") and hasattr(v, "__dlpack_device__")):
+            raise TypeError(f"{what} is not a tensor with __dlpack__")
+        dl_dev = v.__dlpack_device__()
+        dev_type = int(dl_dev[0])
+        if dev_type == _DL_ROCM:
+            if int(dl_dev[1]) != self.device:
+                raise TypeError(f"{what} is on GPU {int(dl_dev[1])}, this node on GPU "
+                                f"{self.device}: a node sends tensors of its own GPU")
+            return "device"
+        if dev_type in _DL_HOST:
+            return "host"
+        raise TypeError(f"{what}: tensors of DLPack device type {dev_type} cannot be sent")
+
+    def _send_ragged(self, output_id: str, data, metadata, flags: int) -> int:
+        """A ragged batch (dora_amd.tensor.ragged) as one List message
+        (dora_node_send_output_tensor_list): the values as `_send_tensor` or `_send_tensor_struct`
+        would take them, cut into lists by the partition.
+
+        A partition on the host — a Python sequence, a numpy array, a CPU tensor — goes with any
+        values and is checked inside the call: a refusal names the first offending index and
+        nothing is sent.  A partition on this node's GPU needs device values; it does the
+        `__dlpack__(stream=<the node stream>)` handshake like every field, is never read on the
+        host, and is held with the values until `sync()` by an asynchronous send.  Its words are
+        clamped into a well-formed List by the kernel, not checked (dora_amd.tensor)."""
+        import numpy as np
+        from ._lib import PARTITION_LENGTHS, PARTITION_OFFSETS
+        values = data.values
+        record = isinstance(values, dict)
+        if record:
+            if not values:
+                raise TypeError("a struct of tensors has at least one field")
+            for name in values:
+                if not isinstance(name, str):
+                    raise TypeError(f"field names are str, not {type(name).__name__}")
+            kinds = {name: self._tensor_kind(v, f"field `{name}`") for name, v in values.items()}
+            first = next(iter(kinds))
+            for name, kind in kinds.items():
+                if kind != kinds[first]:
+                    raise TypeError(f"field `{first}` is a {kinds[first]} tensor and field `{name}` "
+                                    f"a {kind} tensor: the fields of one message are all host "
+                                    "tensors or all on this node's GPU")
+            kind, tensors, names = kinds[first], list(values.values()), tuple(values)
+        else:
+            kind, tensors, names = self._tensor_kind(values, "the values"), [values], None
+        part = data.offsets if data.offsets is not None else data._lengths
+        form = PARTITION_OFFSETS if data.offsets is not None else PARTITION_LENGTHS
+        part_dev = ARROW_DEVICE_CPU
+        if hasattr(part, "__dlpack_device__") and int(part.__dlpack_device__()[0]) not in _DL_HOST:
+            if self._tensor_kind(part, "the partition") == "device" and kind != "device":
+                raise TypeError("a partition in device memory needs values on this node's GPU: "
+                                "with host values pass the partition as a host list (.tolist())")
+            part_dev = ARROW_DEVICE_ROCM
+        else:
+            # a fresh int32 or int64 array the call reads and drops
+            a = np.asarray(part)
+            if a.size == 0:
+                a = a.astype(np.int64)
+            if a.dtype.kind not in "iu":
+                raise TypeError(f"the partition holds {a.dtype}, not integers")
+            part = np.array(a.reshape(-1), dtype=a.dtype if a.dtype in (np.int32, np.int64)
+                            else np.int64, copy=True)
+        if kind == "device":
+            _require_one_hip_runtime()
+            held = bool(flags & SEND_ASYNC) or self._async_default
+            if held and len(self._async_tensors) + len(tensors) + 1 > self._ASYNC_TENSORS_MAX:
+                self.sync()
+            stream = int(self._lib.dora_node_stream(self.handle))
+            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
+            pcap = part.__dlpack__(stream=stream) if part_dev == ARROW_DEVICE_ROCM \
+                else part.__dlpack__()
+            rc = _fast.send_tensor_list(self.handle, output_id, names, caps, pcap, form, part_dev,
+                                        ARROW_DEVICE_ROCM, metadata, flags)
+            if held and not rc:
+                self._async_tensors.extend(tensors)
+                if part_dev == ARROW_DEVICE_ROCM:
+                    self._async_tensors.append(part)
+            return rc
+        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
+        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
+        try:
+            caps = tuple(v.__dlpack__() for v in tensors)
+        except BufferError:
+            # (read-only numpy arrays: every field through its array interface, as in
+            # _send_tensor_struct)
+            if not all(hasattr(v, "__array_interface__") for v in tensors):
+                raise
+            from .tensor import _describe_array, _describe_list
+            described = [_describe_array(v) for v in tensors]
+            pt, pkeep = _describe_array(part)
+            lst, keep = _describe_list(names, [t for t, _ in described], pt, form, part_dev)
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_list(
+                self.handle, output_id.encode(), byref(lst), dev, params, len(params), flags)
+            del keep, described, pkeep
+            return rc
+        return _fast.send_tensor_list(self.handle, output_id, names, caps, part.__dlpack__(), form,
+                                      part_dev, dev, metadata, flags)
 
     def send_output_async(self, output_id: str, data, metadata: Optional[dict] = None):
         """send_output(..., asynchronous=True)."""

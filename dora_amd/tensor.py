@@ -20,6 +20,21 @@ type `Struct<name: T, ..>` whose fields are those tensor columns (nullable, as
     node.send_output("det", {"bbox": out[:, :4], "conf": out[:, 4], "cls": out[:, 5]})
     det = tensor.to_torch(event["value"])                  # {"bbox": .., "conf": .., "cls": ..}
 
+A ragged batch — N rows of a tensor, or of a dict of tensors sharing N, cut into B lists of
+different lengths — travels as one message too, the Arrow array of length B and type
+`List<item: T>` (int32 offsets; `T` the tensor's or the record's type above):
+
+    node.send_output("clouds", tensor.ragged({"x": p[:, 0], "y": p[:, 1]}, lengths=counts))
+    node.send_output("dets", tensor.ragged(out[:, :4], offsets=nt.offsets()))  # offsets in HBM
+    r = tensor.to_torch(event["value"])                    # Ragged: r.values, r.offsets (int32)
+
+A partition on the host (a sequence, numpy, a CPU tensor) is checked inside the send: lengths are
+non-negative and sum to N, offsets start at 0, never decrease and end at N, else the send raises
+and nothing leaves.  A partition in this node's HBM (device values only) is never read on the
+host: the send's one kernel launch turns it into offsets, clamped so that the message is a
+well-formed List whatever the words hold — a partition that does not describe N rows is then the
+producer's bug and shows as other list boundaries, not as an error.
+
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
 is copied once, so every source has been read when `send_output` returns.  A tensor in device
 memory is read by a kernel: in place when dense, gathered by the gfx950 gather kernel when it is a
@@ -30,7 +45,7 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import Tensor, TensorField
+from ._lib import Tensor, TensorField, TensorList
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -76,11 +91,102 @@ def from_numpy_struct(fields):
     return pa.StructArray.from_arrays([from_numpy(v) for v in fields.values()], names=list(fields))
 
 
+class Ragged:
+    """A ragged batch: `values`, a tensor or a dict of tensors of leading extent N, and the
+    partition of those N rows into B lists, as B + 1 `offsets` (what a received message carries,
+    an int32 tensor of the values' library) or as B lengths (a batch built for sending may have
+    either).  Build one for sending with `ragged`."""
+
+    __slots__ = ("values", "offsets", "_lengths")
+
+    def __init__(self, values, offsets=None, lengths=None):
+        if (offsets is None) == (lengths is None):
+            raise TypeError("a ragged batch takes exactly one of lengths and offsets")
+        self.values, self.offsets, self._lengths = values, offsets, lengths
+
+    def lengths(self):
+        """The B list lengths, `offsets[1:] - offsets[:-1]` in the offsets' own library."""
+        if self._lengths is not None:
+            return self._lengths
+        return self.offsets[1:] - self.offsets[:-1]
+
+    def _bounds(self):
+        part = self.offsets if self.offsets is not None else self._lengths
+        part = part.tolist() if hasattr(part, "tolist") else list(part)
+        if self.offsets is not None:
+            return part
+        out = [0]
+        for n in part:
+            out.append(out[-1] + n)
+        return out
+
+    def unbind(self):
+        """The B lists as row views of `values` (dicts of views for a record).  The offsets are
+        read on the host: on a device batch this synchronises with the stream that wrote them."""
+        o = self._bounds()
+        if isinstance(self.values, dict):
+            return [{k: v[a:b] for k, v in self.values.items()} for a, b in zip(o, o[1:])]
+        return [self.values[a:b] for a, b in zip(o, o[1:])]
+
+    def __len__(self):
+        part = self.offsets if self.offsets is not None else self._lengths
+        return len(part) - (self.offsets is not None)
+
+    def __repr__(self):
+        return f"Ragged({len(self)} lists over {self.values!r})"
+
+
+def ragged(values, *, lengths=None, offsets=None):
+    """The ragged batch of `values` (a tensor, or a dict of at most 8 tensors sharing their
+    leading extent N) cut into lists by exactly one of `lengths` (B of them) and `offsets`
+    (B + 1): what `send_output` sends as one `List` message."""
+    return Ragged(values, offsets=offsets, lengths=lengths)
+
+
+def ragged_type(values):
+    """The pyarrow type of a ragged-batch message: `values` is the `(dtype, shape)` of a tensor
+    or maps each field name to one (the counterpart of `struct_type`)."""
+    import pyarrow as pa
+    if isinstance(values, dict):
+        return pa.list_(struct_type(values))
+    dtype, shape = values
+    return pa.list_(tensor_type(dtype, shape))
+
+
+def _host_offsets(n, lengths, offsets):
+    import numpy as np
+    if (offsets is None) == (lengths is None):
+        raise TypeError("a ragged batch takes exactly one of lengths and offsets")
+    if offsets is not None:
+        o = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    else:
+        o = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64).reshape(-1))])
+    if len(o) < 1 or o[0] != 0 or o[-1] != n or (np.diff(o) < 0).any():
+        raise ValueError(f"the partition does not cut {n} rows into lists")
+    return o.astype(np.int32)
+
+
+def from_numpy_ragged(values, *, lengths=None, offsets=None):
+    """The pyarrow ListArray of a numpy array, or of a dict of numpy arrays sharing their leading
+    extent, cut by `lengths` or `offsets` (the counterpart of `from_numpy_struct`): what
+    `send_output(output_id, ragged(values, ..))` puts on the wire."""
+    import pyarrow as pa
+    child = from_numpy_struct(values) if isinstance(values, dict) else from_numpy(values)
+    o = _host_offsets(len(child), lengths, offsets)
+    return pa.ListArray.from_arrays(pa.array(o, pa.int32()), child)
+
+
 def to_numpy(arr):
     """The numpy array of a nested pyarrow array (a host receiver's `event["value"]`): shape
-    `(len, s1, .., sk)`; of a struct of tensor columns, the dict `{name: array}`.  Nulls at any
-    level, the struct's own included, are refused."""
+    `(len, s1, .., sk)`; of a struct of tensor columns, the dict `{name: array}`; of a List over
+    either, the `Ragged` of the child's values and this array's int32 offsets, which index them.
+    Nulls at any level, the struct's and the list's own included, are refused."""
     import pyarrow as pa
+    if pa.types.is_list(arr.type):
+        if arr.null_count:
+            raise TypeError("a tensor message has no nulls")
+        import numpy as np
+        return Ragged(to_numpy(arr.values), offsets=np.array(arr.offsets, dtype=np.int32))
     if pa.types.is_struct(arr.type):
         if arr.null_count:
             raise TypeError("a tensor message has no nulls")
@@ -101,10 +207,22 @@ def to_torch(value):
     """The torch tensor of a received tensor message: zero-copy over the HBM sample for a device
     receiver's `event["value"]` (DLPack, kDLROCM; the tensor keeps the input alive), a copy of
     the nested pyarrow array for a host receiver's.  A struct of tensor columns gives the dict
-    `{name: tensor}`, each a view of the one sample.  Nulls at any level are refused."""
+    `{name: tensor}`, each a view of the one sample; a List over either gives `Ragged(values,
+    offsets)`, on a device receiver both zero-copy over the one sample.  Nulls at any level are
+    refused."""
     import torch
     import pyarrow as pa
     t = getattr(value, "type", None)
+    if t is not None and pa.types.is_list(t):
+        if hasattr(value, "list_values"):  # a DeviceArray: zero-copy child and offsets
+            offsets = torch.from_dlpack(value.list_offsets())
+            return Ragged(to_torch(value.list_values()), offsets=offsets)
+        import numpy as np
+        r = to_numpy(value)
+        vals = r.values
+        vals = ({k: torch.from_numpy(np.array(x)) for k, x in vals.items()}
+                if isinstance(vals, dict) else torch.from_numpy(np.array(vals)))
+        return Ragged(vals, offsets=torch.from_numpy(r.offsets))
     if t is not None and pa.types.is_struct(t):
         if hasattr(value, "field_views"):  # a DeviceArray: zero-copy children
             return {name: torch.from_dlpack(v) for name, v in value.field_views().items()}
@@ -158,4 +276,22 @@ def _describe_fields(names, tensors) -> tuple:
     return arr, (enc, tensors)
 
 
-__all__ = ["tensor_type", "struct_type", "from_numpy", "from_numpy_struct", "to_numpy", "to_torch"]
+def _describe_list(names, tensors, partition, form, partition_device) -> tuple:
+    """The `dora_tensor_list` over the `Tensor`s of `_describe` (`names` None: the one bare
+    tensor) and the partition's `Tensor`, and what the caller keeps alive with it."""
+    arr = (TensorField * len(tensors))()
+    enc = [n.encode() for n in names] if names is not None else [None] * len(tensors)
+    for k, (n, t) in enumerate(zip(enc, tensors)):
+        arr[k].name = n
+        arr[k].tensor = t
+    lst = TensorList()
+    lst.fields = arr
+    lst.n = len(tensors)
+    lst.partition = partition
+    lst.partition_form = form
+    lst.partition_device = partition_device
+    return lst, (arr, enc, tensors, partition)
+
+
+__all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_numpy_struct",
+           "from_numpy_ragged", "to_numpy", "to_torch", "Ragged", "ragged"]

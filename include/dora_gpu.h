@@ -263,6 +263,47 @@ typedef struct dora_tensor_field {
 } dora_tensor_field;
 int dora_gpu_plan_tensor_struct(const dora_tensor_field* fields, size_t n,
                                 ArrowDeviceType device_type, dora_plan** out);
+/*
+ * A ragged batch as one message: the N rows of `fields` (a record as dora_gpu_plan_tensor_struct
+ * takes it, or n == 1 with a NULL name: a bare tensor) cut into B lists by `partition`, a 1-D
+ * dense tensor of int32 or int64 holding B lengths (partition_form DORA_PARTITION_LENGTHS) or
+ * B + 1 offsets (DORA_PARTITION_OFFSETS).  On the wire it is the Arrow array of length B and type
+ * List<item: T> (int32 offsets, child field `item`, nullable, as pyarrow.list_(T) makes it), T the
+ * type the tensor or struct plan gives the values; the sample is the reference layout of
+ * pyarrow.ListArray.from_arrays(offsets, child): the (B + 1) * 4 bytes of offsets first, then the
+ * child's leaves as the struct plan lays them out, each padded to its element size.  A reference
+ * node reads it as a ListArray.  B == 0 (one offset, N == 0) and N == 0 with B > 0 (empty lists)
+ * are valid.  LargeList is not produced: N or B + 1 >= 2^31 is DORA_ERR_UNSUPPORTED.
+ *
+ * Where the partition lives (`partition_device`) decides how strict the plan is.
+ *   On the host (ARROW_DEVICE_CPU, ARROW_DEVICE_ROCM_HOST), with values anywhere: it is read and
+ *   checked here.  Lengths must be non-negative and sum to N; offsets must start at 0, never
+ *   decrease and end at N; anything else is DORA_ERR_INVALID naming the first offending index.  The
+ *   int32 offsets are a host source segment the plan owns: with host values segment 0 of an
+ *   ordinary host plan; with device values a prefix that is copied into the sample on the stream
+ *   of, and ahead of, the pack (all-dense fields: copy segments) or the one gather launch.
+ *   In HBM (ARROW_DEVICE_ROCM; the values must be device values too, DORA_ERR_INVALID otherwise:
+ *   pass the partition as a host list): it is never read on the host and the send adds no
+ *   synchronisation.  One workgroup of the plan's one launch (gather_struct_kernel) scans it and
+ *   writes the offsets.  Whatever the words hold, the message is a well-formed List,
+ *   0 <= o[0] <= .. <= o[B] <= N: from lengths o[i] = min(N, sum_{j<i} max(len_j, 0)), from
+ *   offsets o[i] = min(N, max(0, max_{j<=i} in_j)).  A partition that does not describe N rows is
+ *   the producer's bug: it yields a well-formed message with other list boundaries, never a
+ *   malformed one, where the host form refuses.  The words are range-checked against their
+ *   allocation like every device field.  More than 2^20 words are DORA_ERR_UNSUPPORTED: one
+ *   workgroup scans them.
+ * The values' own refusals pass through unchanged (with the field prefix for a record).
+ */
+enum { DORA_PARTITION_LENGTHS = 0, DORA_PARTITION_OFFSETS = 1 };
+typedef struct dora_tensor_list {
+  const dora_tensor_field* fields;
+  size_t n;
+  dora_tensor partition;
+  uint32_t partition_form;
+  ArrowDeviceType partition_device;
+} dora_tensor_list;
+int dora_gpu_plan_tensor_list(const dora_tensor_list* list, ArrowDeviceType device_type,
+                              dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -465,6 +506,16 @@ int dora_node_send_output_tensor_struct(dora_node* node, const char* output_id,
                                         const dora_tensor_field* fields, size_t n,
                                         ArrowDeviceType device_type, const uint8_t* params,
                                         size_t params_len, uint32_t flags);
+/* Send a ragged batch as one List message (dora_gpu_plan_tensor_list: wire type, layout, where
+ * the partition lives, refusals).  Host values take every path of a multi-segment host plan,
+ * inline below 4096 B included.  Device values go where the struct send's go, the offsets with
+ * them: a host partition's as a small copy on the fill stream ahead of the pack or gather, a
+ * device partition's written by the launch itself.  A synchronous send returns once the kernel has
+ * read every field and the partition; with DORA_SEND_ASYNC, once it is queued, and the caller
+ * keeps the fields and a device partition alive and unwritten until dora_node_sync. */
+int dora_node_send_output_tensor_list(dora_node* node, const char* output_id,
+                                      const dora_tensor_list* list, ArrowDeviceType device_type,
+                                      const uint8_t* params, size_t params_len, uint32_t flags);
 /* Make DORA_SEND_ASYNC the default of every send of this node (also DORA_GPU_SEND_ASYNC=1). */
 int dora_node_set_async_sends(dora_node* node, int enable);
 /* Event-stream thread (the reference's event_stream_loop, apis/rust/node/src/event_stream/

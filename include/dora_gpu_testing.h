@@ -86,6 +86,15 @@ int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, s
                              int* gather, uint64_t* dst_off, uint64_t* bytes, int* kind,
                              const void** src, int* nd, uint64_t* row, uint32_t* elem,
                              int64_t* shape, int64_t* stride, int64_t* lo, int64_t* hi);
+/* Test tool (host only): how a ragged-batch plan (dora_gpu_plan_tensor_list) gets its offsets.
+ * *scan 1 if the plan's launch scans a partition in HBM: then *src its words, *count how many,
+ * *wide 1 for int64, *offsets_form 1 for offsets, *rows the clamp N, [*lo, *hi] the bytes from
+ * *src that are checked against the allocation.  *scan 0: *prefix_bytes the length of the host
+ * offsets copied ahead of a device plan's pack or gather (0: they are segment 0 of a host plan).
+ * DORA_ERR_INVALID for any other plan. */
+int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, uint64_t* count,
+                            int* wide, int* offsets_form, uint64_t* rows, int64_t* lo, int64_t* hi,
+                            uint64_t* prefix_bytes);
 /* Test and probe tool: which kernel gathers strided device tensor views of this process from now
  * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
  * it applies (short contiguous extents included). */
