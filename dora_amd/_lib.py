@@ -72,6 +72,14 @@ class TensorList(ctypes.Structure):
                 ("partition_form", c_uint32), ("partition_device", c_int32)]
 
 
+class TensorTake(ctypes.Structure):
+    """dora_tensor_take of include/dora_gpu.h: the fields rows are taken from, the index that
+    takes them and, for a ragged batch over the taken rows, the partition (else NULL)."""
+    _fields_ = [("fields", POINTER(TensorField)), ("n", c_size_t), ("index", Tensor),
+                ("index_device", c_int32), ("partition", POINTER(Tensor)),
+                ("partition_form", c_uint32), ("partition_device", c_int32)]
+
+
 class FillTicket(ctypes.Structure):
     """dora_fill_ticket of include/dora_fill_ticket.h (32 bytes): what dora_sample_fill_ticket
     issues and a publishing kernel takes by value."""
@@ -117,6 +125,9 @@ _SIGS = {
                                                     c_int32, c_char_p, c_size_t, c_uint32]),
     "dora_gpu_plan_tensor_list": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_list": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
+                                                  c_size_t, c_uint32]),
+    "dora_gpu_plan_tensor_take": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_take": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                                   c_size_t, c_uint32]),
     "dora_node_send_output_tensor": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                              c_size_t, c_uint32]),
@@ -257,6 +268,10 @@ _TEST_SIGS = {
                                         POINTER(c_uint64), POINTER(c_int), POINTER(c_int),
                                         POINTER(c_uint64), POINTER(ctypes.c_int64),
                                         POINTER(ctypes.c_int64), POINTER(c_uint64)]),
+    "dora_gpu_test_plan_take": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
+                                        POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int),
+                                        POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
+                                        POINTER(ctypes.c_int64)]),
     "dora_gpu_test_aql_hold": (c_int, [c_int, c_int]),
     "dora_gpu_test_reduce_timeout": (c_int, [c_uint64]),
     "dora_gpu_test_d2h_copy_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_uint64, c_void_p]),

@@ -382,7 +382,9 @@ DORA_HD void store_phase(const Args& a, const Origin& o, uint32_t thread, M& m) 
 // getting the grid its own kernel would have used, and a workgroup finds its field by scanning
 // the table of first workgroups.  A field's writes stay inside [dst, dst + total) of its own
 // arguments — the head / tail bytes and the tile predicates see to that — so the padding between
-// fields and the neighbours' bytes are never touched.
+// fields and the neighbours' bytes are never touched.  The fields of a take (take:: below) are a
+// third kind, all of a launch or none: the rows body reading row index[i] for row i, with the
+// rows body's grid.
 // ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // The offsets of a ragged batch whose partition lives in HBM (one more share of
@@ -495,11 +497,189 @@ DORA_HD uint64_t store_phase(const Args& a, uint64_t tile, uint32_t thread, cons
 
 }  // namespace scan
 
+// ------------------------------------------------------------------------------------------
+// Rows taken by an index (one more field kind of gather_struct_kernel): the output's row i0 of
+// dimension 0 is the source's row index[i0], so the message is `values[index]` without the
+// indexed copy.  It is the rows body with one level of indirection: the field's Args describe
+// dimensions 1.. of the view (shape[] / stride[], `inner` rows of `row` bytes per taken row),
+// and the dimension-0 term of a row's source offset is index[i0] * stride0 instead of
+// i0 * stride0, in take_pos and in the odometer step alike.
+//
+// A word is valid when 0 <= word < N, compared as a signed 64-bit value before anything is
+// multiplied (an int64 word whose low half alone would pass does not).  A row whose word is not
+// valid is `missing`: every unit or byte of it is zero and nothing is loaded for it — in all
+// three unit paths, the piece-by-piece one included, where one unit may span several taken rows
+// of which some are missing.  [lo, hi] was computed over all N source rows, so a valid word cannot
+// leave it whatever the index holds.  Index words go through the policy's load_index(i), i < K
+// always: neighbouring units read the same words again, so these are plain cached loads.
+// ------------------------------------------------------------------------------------------
+namespace take {
+
+// The index of a launch, shared by its fields.
+struct Index {
+  const uint8_t* src;  // K words
+  uint64_t k;          // rows taken: the output's leading extent
+  uint64_t n;          // rows of the source: valid words are [0, n)
+  uint32_t wide;       // 0: int32 words, 1: int64
+  uint32_t pad;
+};
+
+struct Args {
+  gather::Args g;    // dimensions 1.. of the view; total = K * inner * row, [lo, hi] over N rows
+  int64_t stride0;   // bytes per step of dimension 0 (signed, 0 allowed)
+  uint64_t inner;    // rows of g.row bytes per taken row
+};
+
+// `g` holds dimensions 1.. of the field (total already K rows' worth), `stride0` dimension 0.
+DORA_HD Args make_args(const GatherDesc& g, int64_t stride0, uint8_t* dst) {
+  Args a{};
+  a.g = gather::make_args(g, dst);
+  a.stride0 = stride0;
+  a.inner = 1;
+  for (int i = 0; i < g.view.nd; ++i) a.inner *= static_cast<uint64_t>(g.view.shape[i]);
+  return a;
+}
+
+// A row of a taken field: the taken row it belongs to, its place inside that row, and — unless
+// the taken row's word is not valid — where the taken row starts in the source.
+struct Pos {
+  RowPos p;       // over dimensions 1..: p.off is the offset inside the taken row
+  uint64_t i0;    // the taken row
+  uint64_t in;    // the row inside it, < inner
+  int64_t base;   // index[i0] * stride0
+  bool missing;
+};
+
+// The word of taken row `i0` -> base / missing.  i0 == K (the row after the last) reads nothing.
+template <class M>
+DORA_HD void take_row(const Args& a, const Index& ix, uint64_t i0, Pos& t, M& m) {
+  t.i0 = i0;
+  t.base = 0;
+  t.missing = true;
+  if (i0 >= ix.k) return;
+  const int64_t w = m.load_index(i0);
+  if (w < 0 || w >= static_cast<int64_t>(ix.n)) return;
+  t.missing = false;
+  t.base = w * a.stride0;
+}
+
+// Row `r` of the output (row-major over K and shape[]) -> Pos.
+template <class M>
+DORA_HD void take_pos(const Args& a, const Index& ix, uint64_t r, Pos& t, M& m) {
+  uint64_t i0 = r;
+  t.in = 0;
+  if (a.inner != 1) {
+    if ((r | a.inner) >> 32) {
+      i0 = r / a.inner;
+    } else {
+      i0 = static_cast<uint32_t>(r) / static_cast<uint32_t>(a.inner);
+    }
+    t.in = r - i0 * a.inner;
+  }
+  row_pos(a.g, t.in, t.p);
+  take_row(a, ix, i0, t, m);
+}
+
+// The odometer: the next row; past the last row of a taken row, the next taken row's word.
+template <class M>
+DORA_HD void next_taken(const Args& a, const Index& ix, Pos& t, M& m) {
+  next_row(a.g, t.p);  // (wraps to offset 0 after the last inner row)
+  if (++t.in < a.inner) return;
+  t.in = 0;
+  take_row(a, ix, t.i0 + 1, t, m);
+}
+
+template <int G, class M>
+DORA_HD U16 take_pieces(const Args& a, const Index& ix, Pos& t, uint64_t b, M& m) {
+  U16 v = {{0, 0, 0, 0}};
+#pragma unroll
+  for (int j = 0; j < 16 / G; ++j) {
+    const uint64_t x =
+        t.missing ? 0 : m.template load_piece<G>(t.base + t.p.off + static_cast<int64_t>(b));
+    constexpr int kPerWord = G >= 4 ? 1 : 4 / G;
+    if constexpr (G == 8) {
+      v.w[2 * j] = static_cast<uint32_t>(x);
+      v.w[2 * j + 1] = static_cast<uint32_t>(x >> 32);
+    } else {
+      v.w[j / kPerWord] |= static_cast<uint32_t>(x) << (8 * G * (j % kPerWord));
+    }
+    b += G;
+    if (b >= a.g.row) {
+      b = 0;
+      next_taken(a, ix, t, m);
+    }
+  }
+  return v;
+}
+
+// Whole unit `u` of the output: gather_unit's three paths behind the indirection.
+template <class M>
+DORA_HD void take_unit(const Args& a, const Index& ix, uint64_t u, M& m) {
+  const gather::Args& g = a.g;
+  const uint64_t o = g.head + 16 * u;
+  uint64_t r, b;
+  out_pos(g, o, &r, &b);
+  Pos t;
+  take_pos(a, ix, r, t, m);
+  if (b + 16 <= g.row) {
+    if (t.missing) {
+      m.store16(o, U16{{0, 0, 0, 0}});
+      return;
+    }
+    const int64_t s = t.base + t.p.off + static_cast<int64_t>(b);
+    const uint32_t mis = static_cast<uint32_t>(
+        (reinterpret_cast<uintptr_t>(g.src) + static_cast<uint64_t>(s)) & 15);
+    if ((mis & 3) == 0) {
+      m.store16(o, m.load16(s));
+      return;
+    }
+    if (s - g.lo >= static_cast<int64_t>(mis) && s - static_cast<int64_t>(mis) <= g.hi - 31) {
+      const int64_t w = s - static_cast<int64_t>(mis);
+      m.store16(o, m.funnel(m.load16(w), m.load16(w + 16), mis));
+      return;
+    }
+  }
+  U16 v;
+  switch (g.piece) {
+    case 8: v = take_pieces<8>(a, ix, t, b, m); break;
+    case 4: v = take_pieces<4>(a, ix, t, b, m); break;
+    case 2: v = take_pieces<2>(a, ix, t, b, m); break;
+    default: v = take_pieces<1>(a, ix, t, b, m); break;
+  }
+  m.store16(o, v);
+}
+
+template <class M>
+DORA_HD void take_byte(const Args& a, const Index& ix, uint64_t o, M& m) {
+  uint64_t r, b;
+  out_pos(a.g, o, &r, &b);
+  Pos t;
+  take_pos(a, ix, r, t, m);
+  m.store1(o, t.missing ? uint8_t(0)
+                        : static_cast<uint8_t>(m.template load_piece<1>(
+                              t.base + t.p.off + static_cast<int64_t>(b))));
+}
+
+// gather_lane's division of the work, over the taken body.
+template <class M>
+DORA_HD void take_lane(const Args& a, const Index& ix, uint64_t lane, uint64_t lanes, M& m) {
+  const gather::Args& g = a.g;
+  if (lane < 16) {
+    if (lane < g.head) take_byte(a, ix, lane, m);
+  } else if (lane < 32) {
+    const uint64_t t0 = g.head + 16 * g.nunits;  // <= total
+    if (lane - 16 < g.total - t0) take_byte(a, ix, t0 + (lane - 16), m);
+  }
+  for (uint64_t u = lane; u < g.nunits; u += lanes) take_unit(a, ix, u, m);
+}
+
+}  // namespace take
+
 namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
 // (a scan share, kScan, is no Field: it has no view; it runs workgroups [0, wg_begin[0]))
-enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2 };
+enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3 };
 
 struct Field {
   uint32_t kind;
@@ -507,14 +687,17 @@ struct Field {
   union {
     gather::Args rows;
     tile::Args tile;
+    take::Args taken;
   };
 };
+static_assert(sizeof(take::Args) <= sizeof(tile::Args), "a taken field does not grow Field");
 
 struct Args {
   uint32_t n;
   uint32_t wg_begin[kMaxFields + 1];  // field k runs workgroups [wg_begin[k], wg_begin[k + 1])
   Field f[kMaxFields];
   scan::Args scan;  // src null: no scan share, wg_begin[0] == 0
+  take::Index take; // the index of the kRowsTaken fields (all or none of a launch's fields)
 };
 static_assert(sizeof(Args) <= 4096, "multi::Args is passed by value: the kernel-argument limit");
 
@@ -544,6 +727,34 @@ DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile
       f.rows = gather::make_args(g[k], dst + off[k]);
       wg += static_cast<uint32_t>(gather::grid_for(f.rows));
     }
+  }
+  for (int k = n; k <= kMaxFields; ++k) a.wg_begin[k] = wg;
+  return a;
+}
+
+// Arguments of a take: every field g[k] (dimensions 1.. of its view, stride0[k] its dimension 0)
+// through the taken body into dst + off[k], all by the index `tk`; each field gets the grid the
+// rows body would have for its bytes.  `sc` as above.
+DORA_HD Args make_taken_args(const GatherDesc* g, const int64_t* stride0, const uint64_t* off,
+                             int n, uint8_t* dst, const TakeDesc& tk,
+                             const ScanDesc* sc = nullptr) {
+  Args a{};
+  a.n = static_cast<uint32_t>(n);
+  a.take.src = tk.src;
+  a.take.k = tk.count;
+  a.take.n = tk.n;
+  a.take.wide = tk.wide;
+  uint32_t wg = 0;
+  if (sc) {
+    a.scan = scan::make_args(*sc, dst);
+    wg = 1;
+  }
+  for (int k = 0; k < n; ++k) {
+    a.wg_begin[k] = wg;
+    Field& f = a.f[k];
+    f.kind = kRowsTaken;
+    f.taken = take::make_args(g[k], stride0[k], dst + off[k]);
+    wg += static_cast<uint32_t>(gather::grid_for(f.taken.g));
   }
   for (int k = n; k <= kMaxFields; ++k) a.wg_begin[k] = wg;
   return a;

@@ -243,6 +243,18 @@ struct GatherMem {
   __device__ __forceinline__ void store1(uint64_t o, uint8_t v) const { st1<2>(dst + o, v); }
 };
 
+// The taken body's memory (gather_device.h take::): a field's bytes as GatherMem moves them, and
+// the launch's index words with plain cached loads — neighbouring units read the same words
+// again, and the word is naturally aligned (the plan refuses an index that is not).
+struct TakeMem : GatherMem {
+  const uint8_t* index;
+  uint32_t wide;
+  __device__ __forceinline__ int64_t load_index(uint64_t i) const {
+    return wide ? reinterpret_cast<const int64_t*>(index)[i]
+                : static_cast<int64_t>(reinterpret_cast<const int32_t*>(index)[i]);
+  }
+};
+
 __global__ __launch_bounds__(gather::kThreads) void gather_rows_kernel(gather::Args a) {
   GatherMem m{a.src, a.dst};
   gather::gather_lane(a, uint64_t(blockIdx.x) * gather::kThreads + threadIdx.x,
@@ -338,7 +350,9 @@ __device__ __forceinline__ void scan_share(const gather::scan::Args& a, uint64_t
 // register count take 33 of its 160 KiB, so the buffer costs the rows fields no occupancy,
 // DESIGN §4).  A ragged batch whose partition is in HBM adds one workgroup in front of the
 // fields' (w < wg_begin[0]): it scans the partition into the sample's offsets through the first
-// 4 KiB of the same buffer.
+// 4 KiB of the same buffer.  The fields of a take run the taken body (kRowsTaken: the rows body
+// reading row index[i] for row i, zeros where the word is not a row), a branch that is uniform
+// over the workgroup like the other two.
 static_assert(gather::scan::kLds <= gather::tile::kLds, "the scan's rows fit the tile buffer");
 __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather::multi::Args a) {
   __shared__ uint64_t lds[gather::tile::kLds];
@@ -353,6 +367,12 @@ __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather:
   if (f.kind == gather::multi::kRows) {
     GatherMem m{f.rows.src, f.rows.dst};
     gather::gather_lane(f.rows, local * gather::kThreads + threadIdx.x, share * gather::kThreads, m);
+    return;
+  }
+  if (f.kind == gather::multi::kRowsTaken) {
+    TakeMem m{{f.taken.g.src, f.taken.g.dst}, a.take.src, a.take.wide};
+    gather::take::take_lane(f.taken, a.take, local * gather::kThreads + threadIdx.x,
+                            share * gather::kThreads, m);
     return;
   }
   switch (f.tile.elem) {
@@ -576,7 +596,17 @@ int check_plan_range(const dora_plan& plan, int device) {
       return fail(rc, "partition: %s", why.c_str());
     }
   }
-  if (plan.fields.empty()) return plan.list ? DORA_OK : check_device_range(plan.gd, device);
+  if (plan.take_on && plan.take.count) {
+    // a take's index in HBM: its words like any field
+    const int rc = check_device_range(take_reach(plan.take), device);
+    if (rc != DORA_OK) {
+      const std::string why = dora_gpu_last_error();
+      return fail(rc, "index: %s", why.c_str());
+    }
+    if (plan.take.n == 0) return DORA_OK;  // rows of zeros: no field is read
+  }
+  if (plan.fields.empty())
+    return plan.list || plan.taken ? DORA_OK : check_device_range(plan.gd, device);
   for (size_t k = 0; k < plan.fields.size(); ++k) {
     const int rc = check_device_range(plan.fields[k].gd, device);
     if (rc == DORA_OK) continue;
@@ -642,7 +672,8 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEven
 }
 
 int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
-                         hipEvent_t ev_start, hipEvent_t ev_stop, const ScanDesc* scan) {
+                         hipEvent_t ev_start, hipEvent_t ev_stop, const ScanDesc* scan,
+                         const TakeDesc* take) {
   if ((n == 0 && !scan) || n > size_t(gather::multi::kMaxFields))
     return fail(DORA_ERR_INVALID, "gather of %zu struct fields", n);
   if (scan && (scan->count > kMaxScanEntries || (reinterpret_cast<uintptr_t>(dst) & 3) ||
@@ -650,17 +681,25 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
     return fail(DORA_ERR_INVALID, "scan of %llu words into %p: at most %llu words, offsets and "
                 "words aligned", static_cast<unsigned long long>(scan->count),
                 static_cast<void*>(dst), static_cast<unsigned long long>(kMaxScanEntries));
+  if (take && n && (!take->count || (reinterpret_cast<uintptr_t>(take->src) & (take->wide ? 7u : 3u))))
+    return fail(DORA_ERR_INVALID, "take of %llu rows by the index at %p: at least one word, "
+                "words aligned", static_cast<unsigned long long>(take->count),
+                static_cast<const void*>(take->src));
   GatherDesc g[gather::multi::kMaxFields];
   uint64_t off[gather::multi::kMaxFields];
   int tile_c[gather::multi::kMaxFields];
+  int64_t stride0[gather::multi::kMaxFields];
   for (size_t k = 0; k < n; ++k) {
     if (!fields[k].bytes) return fail(DORA_ERR_INVALID, "gather of an empty struct field");
     g[k] = fields[k].gd;
     off[k] = fields[k].dst_off;
-    tile_c[k] = select_tile_dim(g[k], dst + off[k]);  // each field as it would go on its own
+    stride0[k] = fields[k].stride0;
+    // each field as it would go on its own; a taken field always the rows body
+    tile_c[k] = take ? -1 : select_tile_dim(g[k], dst + off[k]);
   }
   const gather::multi::Args a =
-      gather::multi::make_args(g, off, tile_c, static_cast<int>(n), dst, scan);
+      take ? gather::multi::make_taken_args(g, stride0, off, static_cast<int>(n), dst, *take, scan)
+           : gather::multi::make_args(g, off, tile_c, static_cast<int>(n), dst, scan);
   const dim3 grid(gather::multi::grid_for(a));
   if (ev_start || ev_stop) {
     hipExtLaunchKernelGGL(gather_struct_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
@@ -674,9 +713,10 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
 
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start, hipEvent_t ev_stop) {
-  if (plan.list)
+  if (plan.list || plan.taken)
     return launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
-                                ev_stop, plan.scan_on ? &plan.scan : nullptr);
+                                ev_stop, plan.scan_on ? &plan.scan : nullptr,
+                                plan.take_on ? &plan.take : nullptr);
   return plan.fields.empty()
              ? launch_gather(plan.gd, dst, stream, ev_start, ev_stop)
              : launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,

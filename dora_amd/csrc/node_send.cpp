@@ -1052,6 +1052,25 @@ int dora_node_send_output_tensor_list(dora_node* n, const char* output_id,
   DORA_GUARD_END
 }
 
+int dora_node_send_output_tensor_take(dora_node* n, const char* output_id,
+                                      const dora_tensor_take* take, ArrowDeviceType device_type,
+                                      const uint8_t* params, size_t params_len, uint32_t flags) {
+  if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  dora_plan* plan = nullptr;
+  {
+    dora::SubSpan sp(dora::SP_SEND_PLAN);
+    const int rc = dora::build_tensor_take_plan(take, device_type, &plan);
+    if (rc != DORA_OK) return rc;
+  }
+  // a host index: the taken rows are in the plan's staging buffer, a host plan like any other; a
+  // device index: a gather plan, which goes where the struct and list sends' gathers go, the index
+  // one more source its launch reads
+  std::unique_ptr<dora_plan> owner(plan);
+  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
+  DORA_GUARD_END
+}
+
 int dora_node_send_output_bytes(dora_node* n, const char* output_id, const void* data, size_t len,
                                 ArrowDeviceType device_type, const uint8_t* params,
                                 size_t params_len) {

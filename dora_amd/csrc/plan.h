@@ -107,7 +107,33 @@ struct PlanField {
   GatherDesc gd;
   uint64_t dst_off;
   uint64_t bytes;
+  // a take plan (dora_gpu_plan_tensor_take): `gd.view` is then dimensions 1.. of the field (its
+  // total the K taken rows' bytes) and this the byte stride of dimension 0, which keeps an entry
+  // of its own whatever its extent or stride; [gd.lo, gd.hi] covers all N source rows
+  int64_t stride0 = 0;
 };
+
+// The index of a take plan when it lives in HBM: `count` (K) dense words of 4 or 8 bytes at `src`,
+// never read on the host; a word outside [0, n) yields a row of zero bytes (gather_device.h
+// take::).  take_reach is what check_plan_range holds against the allocation of `src`.
+struct TakeDesc {
+  const uint8_t* src;
+  uint64_t count;  // K: rows taken
+  uint64_t n;      // N: rows of the source
+  uint32_t wide;   // 0: int32 words, 1: int64
+};
+static_assert(sizeof(TakeDesc) <= sizeof(GatherDesc), "a plan holds either in one place");
+// The K words as a dense view: bytes [0, K * width) from `src`.
+inline GatherDesc take_reach(const TakeDesc& t) {
+  GatherDesc r{};
+  r.view.src = t.src;
+  r.view.total = t.count * (t.wide ? 8 : 4);
+  r.view.row = r.view.total;
+  r.elem = t.wide ? 8 : 4;
+  r.lo = 0;
+  r.hi = static_cast<int64_t>(r.view.total) - 1;
+  return r;
+}
 
 // The partition of a ragged-batch plan (dora_gpu_plan_tensor_list) when it lives in HBM: `count`
 // dense words of 4 or 8 bytes at `src` (B lengths, or B + 1 offsets), never read on the host.  One
@@ -179,16 +205,18 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream,
 // nothing between fields and nothing at or past the last field's end.
 // With `scan` (a ragged-batch plan whose partition is in HBM; n may then be 0) one more workgroup
 // of the same launch writes the sample's offsets at dst + 0 (dst a whole number of dwords).
+// With `take` (a take plan) every field goes through the taken body: row i0 of its bytes is row
+// take->src[i0] of the field, or zeros where that word is not in [0, take->n).
 int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
                          hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                         const ScanDesc* scan = nullptr);
+                         const ScanDesc* scan = nullptr, const TakeDesc* take = nullptr);
 // The host-source segments a device plan carries beside what its kernel reads (a ragged batch's
 // offsets computed in the plan): copied into `dst` on `stream`, ahead of the pack or gather that
 // follows on the same stream.  The bytes are pageable memory of the plan: the runtime has staged
 // them when the call returns.
 int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
 // The gather a gather plan asks for: launch_gather of its view, or launch_gather_struct of its
-// fields.
+// fields (with the scan of a ragged batch's device partition, by the index of a take).
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
@@ -220,6 +248,8 @@ int build_tensor_struct_plan(const dora_tensor_field* fields, size_t n, ArrowDev
                              dora_plan** out);
 // A ragged batch: the fields' rows cut into lists by a partition (dora_gpu_plan_tensor_list).
 int build_tensor_list_plan(const dora_tensor_list* list, ArrowDeviceType dev, dora_plan** out);
+// Rows taken by an index, as a tensor, a record or a ragged batch (dora_gpu_plan_tensor_take).
+int build_tensor_take_plan(const dora_tensor_take* take, ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -240,7 +270,17 @@ struct dora_plan {
   // than `segs` (then empty) reads it
   bool dev_tensor = false;
   bool gather = false;
-  dora::GatherDesc gd{};
+  // take plans (tensor_plan.cpp): `take.count` / `take.n` always; with `take_on` a device plan
+  // whose one launch reads every field through the index `take.src` (always a gather, never
+  // segments), else a host plan whose taken rows are already in `staged`
+  bool taken = false;
+  bool take_on = false;
+  // (a plan reads one view, `gd`, or the fields of a record, by the index `take` if it is a take
+  // plan: never both, and a plan of any other kind stays the size it was)
+  union {
+    dora::GatherDesc gd{};
+    dora::TakeDesc take;
+  };
   // struct-of-tensors plans (dev_tensor): one entry per field instead of `gd`; with `gather`,
   // gather_struct_kernel reads all of them in one launch (a multi-gather plan), else `segs` does
   std::vector<dora::PlanField> fields;

@@ -474,6 +474,107 @@ PyObject* py_send_tensor_list(PyObject*, PyObject* const* args, Py_ssize_t nargs
   return PyLong_FromLong(rc);
 }
 
+// send_tensor_take(handle, output_id, names, capsules, index, index_device, partition, form,
+// partition_device, device_type, metadata, flags) -> status: rows taken by an index as
+// dora_node_send_output_tensor_take.  `names` / `capsules` as send_tensor_list takes them; `index`
+// a "dltensor" capsule of the 1-D row numbers; `partition` one of lengths or offsets over the
+// taken rows, or None (no lists).  Every capsule is consumed as send_tensor_list consumes its own.
+PyObject* py_send_tensor_take(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  const char* usage = "send_tensor_take(handle, output_id, names, capsules, index, index_device, "
+                      "partition, form, partition_device, device_type, metadata, flags): names is "
+                      "None over one capsule or a tuple as long as the tuple of capsules";
+  if (nargs != 12 || !PyTuple_Check(args[3]) ||
+      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
+                           : PyTuple_Check(args[2]) &&
+                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+    PyErr_SetString(PyExc_TypeError, usage);
+    return nullptr;
+  }
+  void* h = nullptr;
+  if (!as_ptr(args[0], &h)) return nullptr;
+  const char* oid = as_cstr(args[1]);
+  if (!oid) return nullptr;
+  const size_t n = static_cast<size_t>(PyTuple_GET_SIZE(args[3]));
+  const bool lists = args[6] != Py_None;
+  std::vector<dora_tensor_field> fields(n);
+  std::vector<PyObject*> caps(n + 1 + (lists ? 1 : 0));  // the fields', the index's, the partition's
+  for (size_t k = 0; k < caps.size(); ++k) {
+    PyObject* cap = k < n ? PyTuple_GET_ITEM(args[3], Py_ssize_t(k)) : k == n ? args[4] : args[6];
+    if (k < n) {
+      fields[k].name = nullptr;
+      if (args[2] != Py_None) {
+        fields[k].name = as_cstr(PyTuple_GET_ITEM(args[2], Py_ssize_t(k)));
+        if (!fields[k].name) return nullptr;
+      }
+    }
+    if (!PyCapsule_IsValid(cap, "dltensor")) {
+      if (k < n)
+        PyErr_Format(PyExc_TypeError, "field %zu: expected a DLPack capsule named \"dltensor\" (an "
+                                      "unused, unversioned one)", k);
+      else
+        PyErr_Format(PyExc_TypeError, "%s: expected a DLPack capsule named \"dltensor\" (an "
+                                      "unused, unversioned one)", k == n ? "index" : "partition");
+      return nullptr;
+    }
+    for (size_t j = 0; j < k; ++j)
+      if (caps[j] == cap) {
+        PyErr_Format(PyExc_TypeError, "capsules %zu and %zu are one capsule", j, k);
+        return nullptr;
+      }
+    caps[k] = cap;
+  }
+  long num[4];  // index_device, form, partition_device, device_type
+  const int where[4] = {5, 7, 8, 9};
+  for (int i = 0; i < 4; ++i) {
+    num[i] = PyLong_AsLong(args[where[i]]);
+    if (num[i] == -1 && PyErr_Occurred()) return nullptr;
+  }
+  const unsigned long flags = PyLong_AsUnsignedLong(args[11]);
+  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
+  std::string& params = t_params;
+  if (!encode(args[10], params)) return nullptr;
+  dora_tensor_take take{};
+  dora_tensor partition{};
+  std::vector<DlManaged*> managed(caps.size());
+  for (size_t k = 0; k < caps.size(); ++k) {
+    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(caps[k], "dltensor"));
+    if (!m || PyCapsule_SetName(caps[k], "used_dltensor") != 0) {
+      // (cannot happen after the checks above; the capsules renamed so far are released)
+      for (size_t j = 0; j < k; ++j)
+        if (managed[j]->deleter) managed[j]->deleter(managed[j]);
+      return nullptr;
+    }
+    managed[k] = m;
+    dora_tensor& t = k < n ? fields[k].tensor : k == n ? take.index : partition;
+    t = dora_tensor{};
+    t.data = m->t.data;
+    t.byte_offset = m->t.byte_offset;
+    t.dtype_code = m->t.code;
+    t.dtype_bits = m->t.bits;
+    t.dtype_lanes = m->t.lanes;
+    t.ndim = m->t.ndim;
+    t.shape = m->t.shape;
+    t.strides = m->t.strides;
+  }
+  take.fields = fields.data();
+  take.n = n;
+  take.index_device = static_cast<ArrowDeviceType>(num[0]);
+  take.partition = lists ? &partition : nullptr;
+  take.partition_form = static_cast<uint32_t>(num[1]);
+  take.partition_device = static_cast<ArrowDeviceType>(num[2]);
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor_take(static_cast<dora_node*>(h), oid, &take,
+                                         static_cast<ArrowDeviceType>(num[3]),
+                                         reinterpret_cast<const uint8_t*>(params.data()),
+                                         params.size(), static_cast<uint32_t>(flags));
+  Py_END_ALLOW_THREADS
+  // (deleters under the GIL and after the status has been taken, as in send_tensor)
+  for (DlManaged* m : managed)
+    if (m->deleter) m->deleter(m);
+  return PyLong_FromLong(rc);
+}
+
 // MetadataParameters bytes -> dict (the inverse of encode; dora_amd.node.decode_parameters).
 PyObject* decode(const uint8_t* p, size_t n) {
   PyObject* out = PyDict_New();
@@ -935,6 +1036,9 @@ PyMethodDef methods[] = {
     {"send_tensor_list",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_list)),
      METH_FASTCALL, "dora_node_send_output_tensor_list of DLPack capsules, which it consumes."},
+    {"send_tensor_take",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_take)),
+     METH_FASTCALL, "dora_node_send_output_tensor_take of DLPack capsules, which it consumes."},
     {"send_array", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_array)),
      METH_FASTCALL, "dora_node_send_output with parameters encoded from a dict."},
     {nullptr, nullptr, 0, nullptr}};

@@ -17,6 +17,12 @@
 // A ragged batch (dora_gpu_plan_tensor_list) is the List array over such a tensor or record: the
 // int32 offsets first, then the same leaves behind them.  A host partition is checked and turned
 // into offsets here; one in HBM is never read, and the plan's one launch scans it.
+//
+// Selected rows (dora_gpu_plan_tensor_take) are any of the three with the K words of an index in
+// place of the leading extent: `values[index]` along dimension 0 without the indexed copy.  The
+// same builders lay the message out; a taken field keeps dimension 0 apart from the canonical
+// view of the others.  A host index is checked and the rows gathered here; one in HBM is never
+// read, and the plan's one launch takes the rows by it (gather_device.h take::).
 #include <cstring>
 #include <memory>
 #include <string>
@@ -174,7 +180,9 @@ struct TensorView {
 };
 
 // Validation, canonical view and reach of `t`; the failure recorded otherwise.
-int describe_tensor(const dora_tensor* t, ArrowDeviceType dev, TensorView& out) {
+// (`need_data` false: a NULL `data` passes, for a view that will never be read)
+int describe_tensor(const dora_tensor* t, ArrowDeviceType dev, TensorView& out,
+                    bool need_data = true) {
   if (!t) return fail(DORA_ERR_INVALID, "tensor is NULL");
   const char* leaf = leaf_format(*t);
   if (!leaf) return DORA_ERR_UNSUPPORTED;
@@ -196,7 +204,7 @@ int describe_tensor(const dora_tensor* t, ArrowDeviceType dev, TensorView& out) 
   if (__builtin_mul_overflow(inner, static_cast<uint64_t>(t->shape[0]), &count) ||
       __builtin_mul_overflow(count, static_cast<uint64_t>(elem), &bytes) || bytes >> 63)
     return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
-  if (!t->data && count) return fail(DORA_ERR_INVALID, "tensor data is NULL");
+  if (!t->data && count && need_data) return fail(DORA_ERR_INVALID, "tensor data is NULL");
 
   // canonical view: no extents of 1, mergeable neighbours merged
   Dim dims[kMaxTensorDims];
@@ -248,6 +256,59 @@ int describe_tensor(const dora_tensor* t, ArrowDeviceType dev, TensorView& out) 
   out.gd.elem = static_cast<uint32_t>(elem);
   // device strides are not trusted; a host view's reach is its producer's word
   if (dev == ARROW_DEVICE_ROCM && !reach(g, &out.gd.lo, &out.gd.hi))
+    return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
+                "stride, summed over its dimensions)");
+  return DORA_OK;
+}
+
+// A field of a take (dora_gpu_plan_tensor_take): `k` rows taken along dimension 0 of `t`.
+// Dimensions 1.. are described as a tensor of their own — validated, canonicalised, an innermost
+// unit stride folded into the row — while dimension 0 keeps its entry, extent N and `*stride0`
+// bytes, whatever they are.  out.bytes and the view's total are the k taken rows'; a device
+// field's reach covers all N source rows (nothing is read when N == 0).
+int describe_taken(const dora_tensor& t, ArrowDeviceType dev, uint64_t k, TensorView& out,
+                   int64_t* stride0) {
+  if (t.ndim < 1) return fail(DORA_ERR_INVALID, "tensor has %d dimensions (at least 1)", t.ndim);
+  if (!t.shape) return fail(DORA_ERR_INVALID, "tensor shape is NULL");
+  for (int i = 0; i < t.ndim; ++i) {
+    if (t.shape[i] < 0)
+      return fail(DORA_ERR_INVALID, "tensor extent %lld in dimension %d is negative",
+                  static_cast<long long>(t.shape[i]), i);
+    if (i && t.shape[i] == 0)
+      return fail(DORA_ERR_INVALID, "tensor extent 0 in dimension %d (only the first may be 0: a "
+                  "fixed-size list of 0 values has no length to recover)", i);
+  }
+  const int64_t rows = t.shape[0];
+  static const int64_t kOne = 1;
+  dora_tensor in = t;  // dimensions 1.., or one element
+  in.ndim = t.ndim > 1 ? t.ndim - 1 : 1;
+  in.shape = t.ndim > 1 ? t.shape + 1 : &kOne;
+  in.strides = t.ndim > 1 && t.strides ? t.strides + 1 : nullptr;
+  const int rc = describe_tensor(&in, dev, out, rows != 0);
+  if (rc != DORA_OK) return rc;
+  const int64_t elem = t.dtype_bits / 8;
+  const uint64_t inner = out.bytes;  // bytes per taken row, >= elem
+  if (t.strides) {
+    if (__builtin_mul_overflow(t.strides[0], elem, stride0))
+      return fail(DORA_ERR_INVALID, "tensor stride 0 overflows 64 bits");
+  } else {
+    *stride0 = static_cast<int64_t>(inner);
+  }
+  if (__builtin_mul_overflow(inner, k, &out.bytes) || out.bytes >> 63)
+    return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
+  if (out.bytes == 0) return DORA_OK;
+  out.gd.view.total = out.bytes;
+  if (dev != ARROW_DEVICE_ROCM) return DORA_OK;
+  if (rows == 0) {  // k rows of zeros: no byte of the field is reachable
+    out.gd.lo = 0;
+    out.gd.hi = -1;
+    return DORA_OK;
+  }
+  int64_t span, width;
+  GatherDesc& g = out.gd;
+  if (__builtin_mul_overflow(rows - 1, *stride0, &span) ||
+      __builtin_add_overflow(span < 0 ? g.lo : g.hi, span, span < 0 ? &g.lo : &g.hi) ||
+      __builtin_sub_overflow(g.hi, g.lo, &width))
     return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
                 "stride, summed over its dimensions)");
   return DORA_OK;
@@ -329,9 +390,11 @@ struct FieldLayout {
 // Validation, view and type info of every field of `f[0..n)`, each leaf at the running offset
 // padded to its element size: PlanFields into `p`, type info into nodes[k].  `bare`: the one
 // field is a tensor of its own (no name; its chain's head is called `head`).
+// `taken` >= 0: the fields of a take of that many rows (describe_taken): every leaf, type and
+// byte count has the leading extent `taken` where the field's own is N.
 int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                   const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
-                  FieldLayout& lay) {
+                  FieldLayout& lay, int64_t taken = -1) {
   p.fields.resize(n);
   lay.chains.resize(n);
   lay.kids.resize(n);
@@ -348,7 +411,9 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     }
     const dora_tensor& t = f[k].tensor;
     TensorView v;
-    const int rc = describe_tensor(&t, dev, v);
+    int64_t stride0 = 0;
+    const int rc = taken < 0 ? describe_tensor(&t, dev, v)
+                             : describe_taken(t, dev, static_cast<uint64_t>(taken), v, &stride0);
     if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
     if (t.shape[0] != f[0].tensor.shape[0])
       return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
@@ -368,11 +433,20 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     pf.gd = v.gd;
     pf.dst_off = off;
     pf.bytes = v.bytes;
-    lay.chains[k].reset(new TypeChain(v.leaf, t.shape, t.ndim, name));
+    pf.stride0 = stride0;
+    const int64_t* shape = t.shape;  // as sent
+    std::vector<int64_t> kshape;
+    if (taken >= 0) {
+      kshape.assign(t.shape, t.shape + t.ndim);
+      kshape[0] = taken;
+      shape = kshape.data();
+    }
+    lay.chains[k].reset(new TypeChain(v.leaf, shape, t.ndim, name));
     lay.kids[k] = &lay.chains[k]->sch[0];
-    tensor_type_info(*lay.chains[k], t.shape, t.ndim, off, v.bytes, nodes[k]);
+    tensor_type_info(*lay.chains[k], shape, t.ndim, off, v.bytes, nodes[k]);
     off = end;
-    const bool stage = dev == ARROW_DEVICE_ROCM_HOST || (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
+    const bool stage = taken >= 0 || dev == ARROW_DEVICE_ROCM_HOST ||
+                       (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
     if (stage) lay.staged += v.bytes;  // (<= off)
     lay.strided |= v.gd.view.nd != 0;
   }
@@ -397,35 +471,114 @@ void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
   p.fields.clear();  // (device plans keep them for the range check and the gather)
 }
 
-}  // namespace
+// A 1-D dense tensor of int32 or int64 words: the partition of a ragged batch, the index of a
+// take.
+struct Partition {
+  const uint8_t* src = nullptr;
+  uint64_t count = 0;
+  bool wide = false;
+};
 
-int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceType dev,
-                             dora_plan** out) {
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a struct of tensors has at least one field");
-  if (n > kMaxStructFields)
-    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
-                kMaxStructFields, n);
+// Word `i` of a host one (any alignment).
+int64_t word_at(const Partition& pt, uint64_t i) {
+  if (pt.wide) {
+    int64_t v;
+    std::memcpy(&v, pt.src + 8 * i, 8);
+    return v;
+  }
+  int32_t v;
+  std::memcpy(&v, pt.src + 4 * i, 4);
+  return v;
+}
+
+// The index of a take as its builders see it: K words, on the host or in HBM.
+struct TakeIn {
+  Partition ix;
+  bool device = false;
+};
+
+// Where the taken fields' bytes come from (none of them empty: K > 0), after layout_fields.
+//   Host: the index is read and checked — the first word outside [0, n) is refused, naming it —
+//   and the CPU gathers row index[i] of every field into the staging buffer, dense fields and an
+//   identity index included: the segments of an ordinary host plan.
+//   Device: nothing is read; the plan is a gather with the index as one more source, each with
+//   the reach check_plan_range holds against its allocation.
+int place_taken(dora_plan& p, const TakeIn& tk, uint64_t rows, uint64_t staged) {
+  const uint64_t k = tk.ix.count;
+  p.take.src = tk.ix.src;
+  p.take.count = k;
+  p.take.n = rows;
+  p.take.wide = tk.ix.wide ? 1 : 0;
+  if (tk.device) {
+    p.dev_tensor = true;
+    p.gather = true;
+    p.take_on = true;
+    return DORA_OK;
+  }
+  for (uint64_t i = 0; i < k; ++i) {
+    const int64_t w = word_at(tk.ix, i);
+    if (w < 0 || w >= static_cast<int64_t>(rows))
+      return fail(DORA_ERR_INVALID, "index: word %llu is %lld, outside the %llu rows of the values "
+                  "(valid: 0 <= i < N, no negative wrap-around)",
+                  static_cast<unsigned long long>(i), static_cast<long long>(w),
+                  static_cast<unsigned long long>(rows));
+  }
+  p.staged.resize(staged);
+  uint64_t at = 0;
+  for (const PlanField& pf : p.fields) {
+    StridedView one = pf.gd.view;  // one taken row: dimensions 1..
+    one.total = pf.bytes / k;
+    for (uint64_t i = 0; i < k; ++i) {
+      one.src = pf.gd.view.src + word_at(tk.ix, i) * pf.stride0;
+      gather_host(one, p.staged.data() + at + i * one.total);
+    }
+    p.segs.push_back({p.staged.data() + at, pf.dst_off, pf.bytes});
+    at += pf.bytes;
+  }
+  p.fields.clear();
+  return DORA_OK;
+}
+
+// A tensor (`bare`: one field without a name) or a record of tensors as one message; with `tk`
+// the rows of it that the index takes.
+int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
+                 const TakeIn* tk, dora_plan** out) {
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
+  p->taken = tk != nullptr;
   FieldLayout lay;
-  const int rc = layout_fields(f, n, dev, false, nullptr, *p, p->root.children, lay);
+  std::vector<TypeInfoNode> solo;
+  const int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
+                               tk ? static_cast<int64_t>(tk->ix.count) : -1);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
-  ArrowSchema top;
-  std::memset(&top, 0, sizeof(top));
-  top.format = "+s";
-  top.name = "";
-  top.children = lay.kids.data();
-  top.n_children = static_cast<int64_t>(n);
-  serialize_schema(&top, true, p->root.schema);
-  p->root.len = static_cast<uint64_t>(f[0].tensor.shape[0]);
+  if (bare) {
+    p->root = std::move(solo[0]);
+  } else {
+    ArrowSchema top;
+    std::memset(&top, 0, sizeof(top));
+    top.format = "+s";
+    top.name = "";
+    top.children = lay.kids.data();
+    top.n_children = static_cast<int64_t>(n);
+    serialize_schema(&top, true, p->root.schema);
+    p->root.len = tk ? tk->ix.count : static_cast<uint64_t>(f[0].tensor.shape[0]);
+  }
   p->size = off;
+  if (tk) {
+    p->take.count = tk->ix.count;
+    p->take.n = static_cast<uint64_t>(f[0].tensor.shape[0]);
+    p->take.wide = tk->ix.wide ? 1 : 0;
+  }
   if (off == 0) {  // d0 == 0: an empty message, nothing to read
     p->fields.clear();
+    *out = p.release();
+    return DORA_OK;
+  }
+  if (tk) {
+    const int rt = place_taken(*p, *tk, static_cast<uint64_t>(f[0].tensor.shape[0]), lay.staged);
+    if (rt != DORA_OK) return rt;
     *out = p.release();
     return DORA_OK;
   }
@@ -446,51 +599,57 @@ int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceTy
   DORA_GUARD_END
 }
 
+}  // namespace
+
+int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceType dev,
+                             dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a struct of tensors has at least one field");
+  if (n > kMaxStructFields)
+    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
+                kMaxStructFields, n);
+  return build_record(f, n, dev, false, nullptr, out);
+}
+
 namespace {
 
-// The partition of a ragged batch as words: a 1-D dense tensor of int32 or int64.
-struct Partition {
-  const uint8_t* src = nullptr;
-  uint64_t count = 0;
-  bool wide = false;
-};
-
-int describe_partition(const dora_tensor& t, Partition& out) {
+// The words of `what` (the partition of a ragged batch, holding `holds`; the index of a take).
+// `aligned`: the words must sit on their own size (anything a kernel reads).
+int describe_words(const dora_tensor& t, const char* what, const char* holds, bool aligned,
+                   Partition& out) {
   if (t.dtype_code != DL_INT || t.dtype_lanes != 1 || (t.dtype_bits != 32 && t.dtype_bits != 64))
-    return fail(DORA_ERR_INVALID, "partition dtype (code %u, %u bits, %u lanes) is not int32 or "
-                "int64", unsigned(t.dtype_code), unsigned(t.dtype_bits), unsigned(t.dtype_lanes));
+    return fail(DORA_ERR_INVALID, "%s dtype (code %u, %u bits, %u lanes) is not int32 or "
+                "int64", what, unsigned(t.dtype_code), unsigned(t.dtype_bits),
+                unsigned(t.dtype_lanes));
   if (t.ndim != 1 || !t.shape)
-    return fail(DORA_ERR_INVALID, "partition has %d dimensions (a 1-D tensor of lengths or "
-                "offsets)", t.ndim);
+    return fail(DORA_ERR_INVALID, "%s has %d dimensions (a 1-D tensor of %s)", what, t.ndim,
+                holds);
   if (t.shape[0] < 0)
-    return fail(DORA_ERR_INVALID, "partition extent %lld is negative",
+    return fail(DORA_ERR_INVALID, "%s extent %lld is negative", what,
                 static_cast<long long>(t.shape[0]));
   if (t.strides && t.shape[0] > 1 && t.strides[0] != 1)
-    return fail(DORA_ERR_INVALID, "partition stride %lld: the partition is dense",
-                static_cast<long long>(t.strides[0]));
-  if (!t.data && t.shape[0]) return fail(DORA_ERR_INVALID, "partition data is NULL");
+    return fail(DORA_ERR_INVALID, "%s stride %lld: the %s is dense", what,
+                static_cast<long long>(t.strides[0]), what);
+  if (!t.data && t.shape[0]) return fail(DORA_ERR_INVALID, "%s data is NULL", what);
   out.src = static_cast<const uint8_t*>(t.data) + t.byte_offset;
   out.count = static_cast<uint64_t>(t.shape[0]);
   out.wide = t.dtype_bits == 64;
-  if (out.count && (reinterpret_cast<uintptr_t>(out.src) & (out.wide ? 7u : 3u)))
-    return fail(DORA_ERR_INVALID, "partition data %p is not aligned to its %d-byte words",
+  if (aligned && out.count && (reinterpret_cast<uintptr_t>(out.src) & (out.wide ? 7u : 3u)))
+    return fail(DORA_ERR_INVALID, "%s data %p is not aligned to its %d-byte words", what,
                 static_cast<const void*>(out.src), out.wide ? 8 : 4);
   return DORA_OK;
+}
+
+int describe_partition(const dora_tensor& t, Partition& out) {
+  return describe_words(t, "partition", "lengths or offsets", true, out);
 }
 
 // The B + 1 offsets of a host partition over `rows` rows, checked: DORA_ERR_INVALID naming the
 // first word that breaks the rule.
 int host_offsets(const Partition& pt, bool offsets_form, uint64_t rows, std::vector<int32_t>& o) {
-  auto word = [&](uint64_t i) -> int64_t {
-    if (pt.wide) {
-      int64_t v;
-      std::memcpy(&v, pt.src + 8 * i, 8);
-      return v;
-    }
-    int32_t v;
-    std::memcpy(&v, pt.src + 4 * i, 4);
-    return v;
-  };
+  auto word = [&](uint64_t i) -> int64_t { return word_at(pt, i); };
   const int64_t n = static_cast<int64_t>(rows);
   if (offsets_form) {
     o.resize(pt.count);
@@ -544,10 +703,10 @@ int host_offsets(const Partition& pt, bool offsets_form, uint64_t rows, std::vec
 
 }  // namespace
 
-int build_tensor_list_plan(const dora_tensor_list* l, ArrowDeviceType dev, dora_plan** out) {
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  if (!l) return fail(DORA_ERR_INVALID, "list is NULL");
+namespace {
+
+// A ragged batch over the fields' rows; with `tk` over the rows of them that the index takes.
+int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk, dora_plan** out) {
   if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
   if (!known_device(l->partition_device))
     return fail(DORA_ERR_INVALID, "unsupported partition_device %d", l->partition_device);
@@ -594,9 +753,18 @@ int build_tensor_list_plan(const dora_tensor_list* l, ArrowDeviceType dev, dora_
   FieldLayout lay;
   lay.off = obytes;
   std::vector<TypeInfoNode> solo;
-  rc = layout_fields(f, n, dev, bare, "item", *p, bare ? solo : child.children, lay);
+  rc = layout_fields(f, n, dev, bare, "item", *p, bare ? solo : child.children, lay,
+                     tk ? static_cast<int64_t>(tk->ix.count) : -1);
   if (rc != DORA_OK) return rc;
-  const uint64_t rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
+  // the rows the partition cuts: the fields' own, or the K taken ones
+  const uint64_t rows = tk ? tk->ix.count : static_cast<uint64_t>(f[0].tensor.shape[0]);
+  const uint64_t src_rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
+  if (tk) {
+    p->taken = true;
+    p->take.count = rows;
+    p->take.n = src_rows;
+    p->take.wide = tk->ix.wide ? 1 : 0;
+  }
   if (rows >> 31)
     return fail(DORA_ERR_UNSUPPORTED, "a ragged batch over %llu rows needs 64-bit offsets "
                 "(LargeList), which is not produced", static_cast<unsigned long long>(rows));
@@ -636,12 +804,22 @@ int build_tensor_list_plan(const dora_tensor_list* l, ArrowDeviceType dev, dora_
       // host values (or none): an ordinary multi-segment host plan, the offsets its first segment
       p->dev = ARROW_DEVICE_CPU;
       p->segs.push_back(oseg);
-      if (!empty) stage_host_fields(*p, dev, lay.staged);
+      if (!empty) {
+        if (tk) rc = place_taken(*p, *tk, src_rows, lay.staged);
+        else stage_host_fields(*p, dev, lay.staged);
+        if (rc != DORA_OK) return rc;
+      }
       *out = p.release();
       return DORA_OK;
     }
     // device values: the offsets go ahead on the pack's stream, the fields as in the struct plan
     p->prefix.push_back(oseg);
+    if (tk) {  // (always the one launch, dense fields included)
+      rc = place_taken(*p, *tk, src_rows, lay.staged);
+      if (rc != DORA_OK) return rc;
+      *out = p.release();
+      return DORA_OK;
+    }
     p->dev_tensor = true;
     p->gather = lay.strided;
     if (!lay.strided)
@@ -666,9 +844,60 @@ int build_tensor_list_plan(const dora_tensor_list* l, ArrowDeviceType dev, dora_
   sc.reach.elem = pt.wide ? 8 : 4;
   sc.reach.lo = 0;
   sc.reach.hi = static_cast<int64_t>(sc.reach.view.total) - 1;
+  if (tk && !empty) {
+    rc = place_taken(*p, *tk, src_rows, lay.staged);
+    if (rc != DORA_OK) return rc;
+  }
   *out = p.release();
   return DORA_OK;
   DORA_GUARD_END
+}
+
+}  // namespace
+
+int build_tensor_list_plan(const dora_tensor_list* l, ArrowDeviceType dev, dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!l) return fail(DORA_ERR_INVALID, "list is NULL");
+  return build_list(l, dev, nullptr, out);
+}
+
+int build_tensor_take_plan(const dora_tensor_take* t, ArrowDeviceType dev, dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!t) return fail(DORA_ERR_INVALID, "take is NULL");
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (!known_device(t->index_device))
+    return fail(DORA_ERR_INVALID, "unsupported index_device %d", t->index_device);
+  if (t->n == 0 || !t->fields)
+    return fail(DORA_ERR_INVALID, "a take has values: at least one field");
+  if (t->n > kMaxStructFields)
+    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
+                kMaxStructFields, t->n);
+  TakeIn tk;
+  tk.device = t->index_device == ARROW_DEVICE_ROCM;
+  if (tk.device != (dev == ARROW_DEVICE_ROCM))
+    return fail(DORA_ERR_INVALID, "the index is in %s memory and the values are in %s memory: "
+                "move the index next to the values (a host index for host values, an index in "
+                "this node's HBM for device values)", tk.device ? "device" : "host",
+                tk.device ? "host" : "device");
+  // (a host index may sit at any address: only a kernel needs its words aligned)
+  const int rc = describe_words(t->index, "index", "row numbers", tk.device, tk.ix);
+  if (rc != DORA_OK) return rc;
+  if (t->partition) {
+    if (tk.ix.count >> 31)
+      return fail(DORA_ERR_UNSUPPORTED, "a ragged batch over %llu rows needs 64-bit offsets "
+                  "(LargeList), which is not produced",
+                  static_cast<unsigned long long>(tk.ix.count));
+    dora_tensor_list l{};
+    l.fields = t->fields;
+    l.n = t->n;
+    l.partition = *t->partition;
+    l.partition_form = t->partition_form;
+    l.partition_device = t->partition_device;
+    return build_list(&l, dev, &tk, out);
+  }
+  return build_record(t->fields, t->n, dev, t->n == 1 && !t->fields[0].name, &tk, out);
 }
 
 }  // namespace dora
@@ -688,6 +917,11 @@ int dora_gpu_plan_tensor_struct(const dora_tensor_field* fields, size_t n,
 int dora_gpu_plan_tensor_list(const dora_tensor_list* list, ArrowDeviceType device_type,
                               dora_plan** out) {
   return dora::build_tensor_list_plan(list, device_type, out);
+}
+
+int dora_gpu_plan_tensor_take(const dora_tensor_take* take, ArrowDeviceType device_type,
+                              dora_plan** out) {
+  return dora::build_tensor_take_plan(take, device_type, out);
 }
 
 }  // extern "C"

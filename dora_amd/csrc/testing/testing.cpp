@@ -348,7 +348,8 @@ int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, s
   if (gather) *gather = plan->gather;
   if (dst_off) *dst_off = f.dst_off;
   if (bytes) *bytes = f.bytes;
-  if (kind) *kind = dora::select_tile_dim(g, static_cast<const uint8_t*>(dst) + f.dst_off);
+  if (kind && plan->take_on) *kind = -1;
+  else if (kind) *kind = dora::select_tile_dim(g, static_cast<const uint8_t*>(dst) + f.dst_off);
   if (src) *src = g.view.src;
   if (nd) *nd = g.view.nd;
   if (row) *row = g.view.row;
@@ -376,6 +377,23 @@ int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, 
   if (lo) *lo = s.reach.lo;
   if (hi) *hi = s.reach.hi;
   if (prefix_bytes) *prefix_bytes = plan->prefix.empty() ? 0 : plan->prefix[0].len;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_take(const dora_plan* plan, int* device, const void** index,
+                            uint64_t* k, uint64_t* n, int* wide, int64_t* lo, int64_t* hi,
+                            int64_t* stride0) {
+  if (!plan || !plan->taken) return dora::fail(DORA_ERR_INVALID, "not a take plan");
+  const dora::TakeDesc& t = plan->take;
+  if (device) *device = plan->take_on;
+  if (index) *index = plan->take_on ? t.src : nullptr;
+  if (k) *k = t.count;
+  if (n) *n = t.n;
+  if (wide) *wide = static_cast<int>(t.wide);
+  if (lo) *lo = plan->take_on ? dora::take_reach(t).lo : 0;
+  if (hi) *hi = plan->take_on ? dora::take_reach(t).hi : -1;
+  for (size_t i = 0; stride0 && i < dora::kMaxStructFields; ++i)
+    stride0[i] = plan->take_on && i < plan->fields.size() ? plan->fields[i].stride0 : 0;
   return DORA_OK;
 }
 

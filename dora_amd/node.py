@@ -33,6 +33,7 @@ _DL_CPU = 1
 _DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinned)
 from .device import DeviceArray, DeviceBuffer
 from .tensor import Ragged as _Ragged
+from .tensor import Taken as _Taken
 from .type_info import decode
 
 try:
@@ -237,10 +238,13 @@ class Node:
             rc = self._send_tensor_struct(output_id, data, metadata, f)
         elif isinstance(data, _Ragged):
             rc = self._send_ragged(output_id, data, metadata, f)
+        elif isinstance(data, _Taken):
+            rc = self._send_take(output_id, data, None, metadata, f)
         else:
             raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer, "
                             "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU), "
-                            "a dict of such tensors or a ragged batch of either "
+                            "a dict of such tensors, rows of either taken by an index "
+                            "(dora_amd.tensor.take) or a ragged batch of any of these "
                             "(dora_amd.tensor.ragged)")
         if rc:
             _lib.check(rc)
@@ -381,6 +385,121 @@ class Node:
             return "host"
         raise TypeError(f"{what}: tensors of DLPack device type {dev_type} cannot be sent")
 
+    def _values_kind(self, values) -> tuple:
+        """(kind, tensors, names) of the values of a message: a tensor (`names` None) or a dict
+        of tensors, all "host" or all "device"."""
+        if not isinstance(values, dict):
+            return self._tensor_kind(values, "the values"), [values], None
+        if not values:
+            raise TypeError("a struct of tensors has at least one field")
+        for name in values:
+            if not isinstance(name, str):
+                raise TypeError(f"field names are str, not {type(name).__name__}")
+        kinds = {name: self._tensor_kind(v, f"field `{name}`") for name, v in values.items()}
+        first = next(iter(kinds))
+        for name, kind in kinds.items():
+            if kind != kinds[first]:
+                raise TypeError(f"field `{first}` is a {kinds[first]} tensor and field `{name}` "
+                                f"a {kind} tensor: the fields of one message are all host "
+                                "tensors or all on this node's GPU")
+        return kinds[first], list(values.values()), tuple(values)
+
+    def _host_words(self, words, what: str):
+        """A fresh 1-D int32 or int64 numpy array of host `words` (a sequence, numpy, a CPU
+        tensor), which the call reads and drops."""
+        import numpy as np
+        a = np.asarray(words)
+        if a.size == 0:
+            a = a.astype(np.int64)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"the {what} holds {a.dtype}, not integers")
+        return np.array(a.reshape(-1), dtype=a.dtype if a.dtype in (np.int32, np.int64)
+                        else np.int64, copy=True)
+
+    def _partition_of(self, data, kind: str) -> tuple:
+        """(partition, form, device) of a ragged batch over values of `kind`: a device tensor
+        as it is, anything on the host as `_host_words`."""
+        from ._lib import PARTITION_LENGTHS, PARTITION_OFFSETS
+        part = data.offsets if data.offsets is not None else data._lengths
+        form = PARTITION_OFFSETS if data.offsets is not None else PARTITION_LENGTHS
+        if hasattr(part, "__dlpack_device__") and int(part.__dlpack_device__()[0]) not in _DL_HOST:
+            if self._tensor_kind(part, "the partition") == "device" and kind != "device":
+                raise TypeError("a partition in device memory needs values on this node's GPU: "
+                                "with host values pass the partition as a host list (.tolist())")
+            return part, form, ARROW_DEVICE_ROCM
+        return self._host_words(part, "partition"), form, ARROW_DEVICE_CPU
+
+    def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
+        """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with
+        `batch`, the ragged batch over them — List message of `values[index]`
+        (dora_node_send_output_tensor_take), without the indexed copy.
+
+        The index lives where the values live.  Host values take an index on the host (a
+        sequence, numpy, a CPU tensor), which is checked inside the call: a word outside
+        [0, N) raises, naming it, and nothing is sent.  Values on this node's GPU take an index
+        there: it does the `__dlpack__(stream=<the node stream>)` handshake like every field, is
+        never read on the host, a word outside [0, N) gives a row of zeros, and an asynchronous
+        send holds it with the values until `sync()`."""
+        from ._lib import PARTITION_LENGTHS
+        kind, tensors, names = self._values_kind(taken.values)
+        index = taken.index
+        on_device = hasattr(index, "__dlpack_device__") and \
+            int(index.__dlpack_device__()[0]) not in _DL_HOST
+        if on_device:
+            self._tensor_kind(index, "the index")
+        if on_device != (kind == "device"):
+            raise TypeError(f"the index is in {'device' if on_device else 'host'} memory and the "
+                            f"values are {kind} tensors: move the index next to the values")
+        part, form, part_dev = None, PARTITION_LENGTHS, ARROW_DEVICE_CPU
+        if batch is not None:
+            part, form, part_dev = self._partition_of(batch, kind)
+        if kind == "device":
+            _require_one_hip_runtime()
+            held = bool(flags & SEND_ASYNC) or self._async_default
+            if held and len(self._async_tensors) + len(tensors) + 2 > self._ASYNC_TENSORS_MAX:
+                self.sync()
+            stream = int(self._lib.dora_node_stream(self.handle))
+            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
+            icap = index.__dlpack__(stream=stream)
+            pcap = None
+            if part is not None:
+                pcap = part.__dlpack__(stream=stream) if part_dev == ARROW_DEVICE_ROCM \
+                    else part.__dlpack__()
+            rc = _fast.send_tensor_take(self.handle, output_id, names, caps, icap,
+                                        ARROW_DEVICE_ROCM, pcap, form, part_dev, ARROW_DEVICE_ROCM,
+                                        metadata, flags)
+            if held and not rc:
+                self._async_tensors.extend(tensors)
+                self._async_tensors.append(index)
+                if part_dev == ARROW_DEVICE_ROCM:
+                    self._async_tensors.append(part)
+            return rc
+        index = self._host_words(index, "index")
+        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
+        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
+        try:
+            caps = tuple(v.__dlpack__() for v in tensors)
+        except BufferError:
+            # (read-only numpy arrays: every field through its array interface, as in
+            # _send_tensor_struct)
+            if not all(hasattr(v, "__array_interface__") for v in tensors):
+                raise
+            from .tensor import _describe_array, _describe_take
+            described = [_describe_array(v) for v in tensors]
+            it, ikeep = _describe_array(index)
+            pt, pkeep = _describe_array(part) if part is not None else (None, None)
+            tk, keep = _describe_take(names, [t for t, _ in described], it, ARROW_DEVICE_CPU, pt,
+                                      form, part_dev)
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_take(
+                self.handle, output_id.encode(), byref(tk), dev, params, len(params), flags)
+            del keep, described, ikeep, pkeep
+            return rc
+        return _fast.send_tensor_take(self.handle, output_id, names, caps, index.__dlpack__(),
+                                      ARROW_DEVICE_CPU,
+                                      part.__dlpack__() if part is not None else None, form,
+                                      part_dev, dev, metadata, flags)
+
     def _send_ragged(self, output_id: str, data, metadata, flags: int) -> int:
         """A ragged batch (dora_amd.tensor.ragged) as one List message
         (dora_node_send_output_tensor_list): the values as `_send_tensor` or `_send_tensor_struct`
@@ -392,43 +511,10 @@ class Node:
         `__dlpack__(stream=<the node stream>)` handshake like every field, is never read on the
         host, and is held with the values until `sync()` by an asynchronous send.  Its words are
         clamped into a well-formed List by the kernel, not checked (dora_amd.tensor)."""
-        import numpy as np
-        from ._lib import PARTITION_LENGTHS, PARTITION_OFFSETS
-        values = data.values
-        record = isinstance(values, dict)
-        if record:
-            if not values:
-                raise TypeError("a struct of tensors has at least one field")
-            for name in values:
-                if not isinstance(name, str):
-                    raise TypeError(f"field names are str, not {type(name).__name__}")
-            kinds = {name: self._tensor_kind(v, f"field `{name}`") for name, v in values.items()}
-            first = next(iter(kinds))
-            for name, kind in kinds.items():
-                if kind != kinds[first]:
-                    raise TypeError(f"field `{first}` is a {kinds[first]} tensor and field `{name}` "
-                                    f"a {kind} tensor: the fields of one message are all host "
-                                    "tensors or all on this node's GPU")
-            kind, tensors, names = kinds[first], list(values.values()), tuple(values)
-        else:
-            kind, tensors, names = self._tensor_kind(values, "the values"), [values], None
-        part = data.offsets if data.offsets is not None else data._lengths
-        form = PARTITION_OFFSETS if data.offsets is not None else PARTITION_LENGTHS
-        part_dev = ARROW_DEVICE_CPU
-        if hasattr(part, "__dlpack_device__") and int(part.__dlpack_device__()[0]) not in _DL_HOST:
-            if self._tensor_kind(part, "the partition") == "device" and kind != "device":
-                raise TypeError("a partition in device memory needs values on this node's GPU: "
-                                "with host values pass the partition as a host list (.tolist())")
-            part_dev = ARROW_DEVICE_ROCM
-        else:
-            # a fresh int32 or int64 array the call reads and drops
-            a = np.asarray(part)
-            if a.size == 0:
-                a = a.astype(np.int64)
-            if a.dtype.kind not in "iu":
-                raise TypeError(f"the partition holds {a.dtype}, not integers")
-            part = np.array(a.reshape(-1), dtype=a.dtype if a.dtype in (np.int32, np.int64)
-                            else np.int64, copy=True)
+        if isinstance(data.values, _Taken):
+            return self._send_take(output_id, data.values, data, metadata, flags)
+        kind, tensors, names = self._values_kind(data.values)
+        part, form, part_dev = self._partition_of(data, kind)
         if kind == "device":
             _require_one_hip_runtime()
             held = bool(flags & SEND_ASYNC) or self._async_default

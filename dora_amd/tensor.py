@@ -35,6 +35,23 @@ host: the send's one kernel launch turns it into offsets, clamped so that the me
 well-formed List whatever the words hold — a partition that does not describe N rows is then the
 producer's bug and shows as other list boundaries, not as an error.
 
+Selected rows — what NMS, a score threshold or top-k end in — travel without the indexed copy:
+`take(values, index)` stands for `values[index]` along dimension 0 (`values` a tensor or a dict
+of tensors sharing N, `index` K int32 or int64 row numbers, repeats allowed) and is sent as
+exactly the message `values[index]` would be, a tensor, a struct or, under `ragged`, a List whose
+partition describes the K taken rows:
+
+    node.send_output("det", tensor.take({"bbox": out[:, :4], "conf": out[:, 4]}, keep))
+    node.send_output("det", tensor.ragged(tensor.take(fields, keep), lengths=per_image_counts))
+
+The index lives where the values live.  A host index is checked inside the send: a word outside
+[0, N) raises (no negative wrap-around) and nothing leaves.  An index in this node's HBM is never
+read on the host: the send's one kernel launch reads row `index[i]` of every field straight into
+the sample, no intermediate tensor and no synchronisation, and writes a row of zeros where a word
+is not a row — a bad index is the producer's bug and shows as zero rows, never as a malformed
+message or a stray read.  Not offered: boolean masks (the message length would need a host
+synchronisation), other dimensions, a host index over device values.
+
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
 is copied once, so every source has been read when `send_output` returns.  A tensor in device
 memory is read by a kernel: in place when dense, gathered by the gfx950 gather kernel when it is a
@@ -45,7 +62,7 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import Tensor, TensorField, TensorList
+from ._lib import Tensor, TensorField, TensorList, TensorTake
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -136,10 +153,38 @@ class Ragged:
         return f"Ragged({len(self)} lists over {self.values!r})"
 
 
+class Taken:
+    """Rows taken along dimension 0: `values`, a tensor or a dict of tensors of leading extent N,
+    and `index`, K row numbers into them.  It stands for `values[index]` in a send and copies
+    nothing itself.  Build one with `take`."""
+
+    __slots__ = ("values", "index")
+
+    def __init__(self, values, index):
+        self.values, self.index = values, index
+
+    def __len__(self):
+        return len(self.index)
+
+    def __repr__(self):
+        return f"Taken({len(self)} rows of {self.values!r})"
+
+
+def take(values, index):
+    """`values[index]` along dimension 0 as a message: `values` a tensor or a dict of at most 8
+    tensors sharing their leading extent N, `index` a 1-D sequence or tensor of K int32 or int64
+    row numbers, 0 <= i < N, next to the values (host with host, this node's HBM with device
+    tensors).  `send_output` sends it, bare or under `ragged`, as what `values[index]` would be."""
+    if isinstance(values, (Taken, Ragged)):
+        raise TypeError("take selects rows of a tensor or of a dict of tensors")
+    return Taken(values, index)
+
+
 def ragged(values, *, lengths=None, offsets=None):
     """The ragged batch of `values` (a tensor, or a dict of at most 8 tensors sharing their
-    leading extent N) cut into lists by exactly one of `lengths` (B of them) and `offsets`
-    (B + 1): what `send_output` sends as one `List` message."""
+    leading extent N, or rows of either taken by `take`: N is then the K taken rows) cut into
+    lists by exactly one of `lengths` (B of them) and `offsets` (B + 1): what `send_output` sends
+    as one `List` message."""
     return Ragged(values, offsets=offsets, lengths=lengths)
 
 
@@ -174,6 +219,34 @@ def from_numpy_ragged(values, *, lengths=None, offsets=None):
     child = from_numpy_struct(values) if isinstance(values, dict) else from_numpy(values)
     o = _host_offsets(len(child), lengths, offsets)
     return pa.ListArray.from_arrays(pa.array(o, pa.int32()), child)
+
+
+def from_numpy_take(values, index, *, lengths=None, offsets=None):
+    """The pyarrow array of rows `index` of a numpy array or of a dict of numpy arrays sharing
+    their leading extent, cut into lists when `lengths` or `offsets` is given: `from_numpy`,
+    `from_numpy_struct` or `from_numpy_ragged` of `values[index]`, what
+    `send_output(output_id, take(values, index))` (under `ragged` with a partition) puts on the
+    wire.  Row numbers outside [0, N) are refused; there is no negative wrap-around."""
+    import numpy as np
+    index = np.asarray(index).reshape(-1)
+    if index.size == 0:
+        index = index.astype(np.int64)
+    if index.dtype.kind not in "iu":
+        raise TypeError(f"the index holds {index.dtype}, not integers")
+    record = isinstance(values, dict)
+    cols = {k: np.asarray(v) for k, v in values.items()} if record else {"": np.asarray(values)}
+    for name, v in cols.items():
+        if v.ndim < 1:
+            raise ValueError("a tensor message has at least one dimension")
+        bad = np.flatnonzero((index < 0) | (index >= v.shape[0]))
+        if len(bad):
+            raise IndexError(f"index word {bad[0]} is {index[bad[0]]}, outside the {v.shape[0]} "
+                             "rows of the values")
+    taken = {k: v[index] for k, v in cols.items()}
+    taken = taken if record else taken[""]
+    if lengths is not None or offsets is not None:
+        return from_numpy_ragged(taken, lengths=lengths, offsets=offsets)
+    return from_numpy_struct(taken) if record else from_numpy(taken)
 
 
 def to_numpy(arr):
@@ -293,5 +366,29 @@ def _describe_list(names, tensors, partition, form, partition_device) -> tuple:
     return lst, (arr, enc, tensors, partition)
 
 
+def _describe_take(names, tensors, index, index_device, partition, form,
+                   partition_device) -> tuple:
+    """The `dora_tensor_take` over the `Tensor`s of `_describe` (`names` None: the one bare
+    tensor), the index's `Tensor` and the partition's (None: no lists), and what the caller keeps
+    alive with it."""
+    from ctypes import pointer
+    arr = (TensorField * len(tensors))()
+    enc = [n.encode() for n in names] if names is not None else [None] * len(tensors)
+    for k, (n, t) in enumerate(zip(enc, tensors)):
+        arr[k].name = n
+        arr[k].tensor = t
+    tk = TensorTake()
+    tk.fields = arr
+    tk.n = len(tensors)
+    tk.index = index
+    tk.index_device = index_device
+    if partition is not None:
+        tk.partition = pointer(partition)
+    tk.partition_form = form
+    tk.partition_device = partition_device
+    return tk, (arr, enc, tensors, index, partition)
+
+
 __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_numpy_struct",
-           "from_numpy_ragged", "to_numpy", "to_torch", "Ragged", "ragged"]
+           "from_numpy_ragged", "from_numpy_take", "to_numpy", "to_torch", "Ragged", "ragged",
+           "Taken", "take"]

@@ -304,6 +304,63 @@ typedef struct dora_tensor_list {
 } dora_tensor_list;
 int dora_gpu_plan_tensor_list(const dora_tensor_list* list, ArrowDeviceType device_type,
                               dora_plan** out);
+/*
+ * Selected rows as one message: `values[index]` along dimension 0, without the indexed copy.
+ * `fields` is a record as dora_gpu_plan_tensor_struct takes it, or n == 1 with a NULL name: a
+ * bare tensor; every field has shape[0] = N.  `index` is a 1-D dense tensor of K int32 or int64
+ * words (what NMS, a score threshold or top-k end in).  On the wire the message is exactly what
+ * planning the materialised `values[index]` gives today: a bare tensor the nested FixedSizeList
+ * array of length K, a record the Struct array of length K, and with `partition` (as
+ * dora_tensor_list's, form and device included; NULL: no lists) the List over either, the
+ * partition describing the K taken rows.  Type info, leaf offsets and padding are those plans'
+ * with the leading extent K; there is no new Arrow type and a reference node reads the message
+ * as before.  K == 0 is an empty message; K may exceed N (repeats).  A valid word is
+ * 0 <= i < N: there is no negative wrap-around.
+ *
+ * Dimensions 1.. of a taken field are canonicalised as dora_gpu_plan_tensor does; dimension 0
+ * keeps an entry of its own (extent N, its byte stride), never merged and never dropped, even at
+ * extent 1 or stride 0.  More than 8 dimensions after that is DORA_ERR_UNSUPPORTED.
+ *
+ * The index lives where the values live (`index_device` against `device_type`): host values
+ * (ARROW_DEVICE_CPU, ARROW_DEVICE_ROCM_HOST) take a host index, device values an index in this
+ * node's HBM; any other pairing is DORA_ERR_INVALID (move the index next to the values; no upload
+ * path exists).
+ *   Host index (the host partition's rule): it is read and checked here; the first word outside
+ *   [0, N) is DORA_ERR_INVALID naming its position and value.  The CPU gathers the taken rows into
+ *   the plan's staging buffer — always, dense values and an identity index included — and the plan
+ *   is an ordinary host plan taking every host path; every source has been read on return.
+ *   Device index (the device partition's rule): it is never read on the host and adds no
+ *   synchronisation.  The plan never has copy segments, dense fields included: it is one launch
+ *   of gather_struct_kernel (n == 1 for a bare tensor), whose rows body reads row index[i] where
+ *   the plain one reads row i; a device partition's scan share goes in front, a host partition's
+ *   offsets as the small copy ahead of the launch.  A row whose word is not valid is written as
+ *   zero bytes and nothing is read for it (an int64 word whose low 32 bits alone would be valid
+ *   included): whatever the words hold, the message is well-formed and no address outside the
+ *   checked reach is touched.  A bad index is the producer's bug and shows as zero rows.  Each
+ *   field's reach is computed over all N source rows with the overflow checks of
+ *   dora_gpu_plan_tensor and held against the field's allocation before anything is launched, so
+ *   a valid word cannot leave it; the K index words are held against theirs the same way.
+ *   N == 0 with K > 0 gives K zero rows (`data` may then be NULL).
+ * DORA_ERR_INVALID on top of the values' own refusals: an index that is not 1-D, not dense
+ * (stride != 1 with K > 1), not int32 or int64 with lanes == 1, a device index not aligned to its
+ * word size, a NULL index with K > 0.  The partition rules of dora_gpu_plan_tensor_list apply with
+ * N replaced by K: a host partition must describe K rows, a device partition is clamped to K and
+ * needs device values; K or B + 1 >= 2^31 with a partition is DORA_ERR_UNSUPPORTED.
+ * Not provided: selection by a boolean mask (K is then only known on the GPU while the message
+ * length travels in the descriptor: it would need a host synchronisation), selection along
+ * another dimension, and a host index over device values.
+ */
+typedef struct dora_tensor_take {
+  const dora_tensor_field* fields; /* a record, or n == 1 with a NULL name: a bare tensor */
+  size_t n;
+  dora_tensor index;               /* 1-D dense int32 / int64, K words */
+  ArrowDeviceType index_device;
+  const dora_tensor* partition;    /* NULL: no lists; else as dora_tensor_list, over the K taken rows */
+  uint32_t partition_form;
+  ArrowDeviceType partition_device;
+} dora_tensor_take;
+int dora_gpu_plan_tensor_take(const dora_tensor_take* take, ArrowDeviceType device_type,
+                              dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -515,6 +572,17 @@ int dora_node_send_output_tensor_struct(dora_node* node, const char* output_id,
  * keeps the fields and a device partition alive and unwritten until dora_node_sync. */
 int dora_node_send_output_tensor_list(dora_node* node, const char* output_id,
                                       const dora_tensor_list* list, ArrowDeviceType device_type,
+                                      const uint8_t* params, size_t params_len, uint32_t flags);
+/* Send selected rows (dora_gpu_plan_tensor_take: wire form, where the index lives, zero rows,
+ * refusals).  Host values with a host index take every path of a host plan, inline below 4096 B
+ * included, and everything has been read on return.  Device values with a device index go where
+ * the struct and list sends' gathers go — one launch on a fill stream ordered after the node
+ * stream, the stream raises the fill flag, receivers without a GPU stage the slot — with the
+ * index as one more borrowed source: a synchronous send returns once the launch has read every
+ * field, the index and a device partition; with DORA_SEND_ASYNC, once it is queued, and the
+ * caller keeps all of them alive and unwritten until dora_node_sync. */
+int dora_node_send_output_tensor_take(dora_node* node, const char* output_id,
+                                      const dora_tensor_take* take, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags);
 /* Make DORA_SEND_ASYNC the default of every send of this node (also DORA_GPU_SEND_ASYNC=1). */
 int dora_node_set_async_sends(dora_node* node, int enable);

@@ -95,6 +95,15 @@ int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, s
 int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, uint64_t* count,
                             int* wide, int* offsets_form, uint64_t* rows, int64_t* lo, int64_t* hi,
                             uint64_t* prefix_bytes);
+/* Test tool (host only): whether `plan` is a take (dora_gpu_plan_tensor_take; DORA_ERR_INVALID for
+ * any other plan) and what it takes by.  *k the rows taken, *n the rows of the source, *wide 1 for
+ * int64 words.  *device 1 if the plan's launch reads the index in HBM: then *index its words,
+ * [*lo, *hi] the bytes from *index that are checked against the allocation, and stride0[8] the
+ * byte stride of dimension 0 of every field, whose dimensions 1.. dora_gpu_test_plan_field
+ * reports (its reach over all *n source rows, *kind always -1 under the taken body).  *device 0: a
+ * host plan, the taken rows already in its staging buffer (or an empty message). */
+int dora_gpu_test_plan_take(const dora_plan* plan, int* device, const void** index, uint64_t* k,
+                            uint64_t* n, int* wide, int64_t* lo, int64_t* hi, int64_t* stride0);
 /* Test and probe tool: which kernel gathers strided device tensor views of this process from now
  * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
  * it applies (short contiguous extents included). */
