@@ -80,6 +80,13 @@ class TensorTake(ctypes.Structure):
                 ("partition_form", c_uint32), ("partition_device", c_int32)]
 
 
+class TensorCast(ctypes.Structure):
+    """dora_tensor_cast of include/dora_gpu.h: what one field is converted to on send
+    (dtype_bits 0: sent as it is) and the optional float32 factor."""
+    _fields_ = [("dtype_code", c_uint8), ("dtype_bits", c_uint8), ("has_scale", ctypes.c_uint16),
+                ("scale", c_float)]
+
+
 class FillTicket(ctypes.Structure):
     """dora_fill_ticket of include/dora_fill_ticket.h (32 bytes): what dora_sample_fill_ticket
     issues and a publishing kernel takes by value."""
@@ -129,6 +136,10 @@ _SIGS = {
     "dora_gpu_plan_tensor_take": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_take": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                                   c_size_t, c_uint32]),
+    "dora_gpu_plan_tensor_cast": (c_int, [c_void_p, c_size_t, c_void_p, c_int32,
+                                          POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_cast": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p,
+                                                  c_int32, c_char_p, c_size_t, c_uint32]),
     "dora_node_send_output_tensor": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                              c_size_t, c_uint32]),
     "dora_gpu_plan_compact": (c_int, [POINTER(ArrowArray), POINTER(ArrowSchema), c_int32,
@@ -268,6 +279,10 @@ _TEST_SIGS = {
                                         POINTER(c_uint64), POINTER(c_int), POINTER(c_int),
                                         POINTER(c_uint64), POINTER(ctypes.c_int64),
                                         POINTER(ctypes.c_int64), POINTER(c_uint64)]),
+    "dora_gpu_test_plan_cast": (c_int, [c_void_p, c_size_t, POINTER(c_size_t), POINTER(c_int),
+                                        POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                        POINTER(c_int), POINTER(c_int), POINTER(c_float),
+                                        POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "dora_gpu_test_plan_take": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int),
                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),

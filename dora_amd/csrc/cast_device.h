@@ -1,0 +1,331 @@
+// Device code of the converting gather (a field of a cast plan, tensor_plan.cpp): the row-major
+// elements of a strided view read once as their source type, converted, and written once as
+// float16 or float32 — y = to_dst(to_f32(x) [* scale]), element by element.
+//
+// It is gather_device.h's rows body restated per element, in the same style: every address
+// computation is plain C++ in functions that compile for host and device alike, all memory and
+// every conversion goes through a policy object `M`, and nothing here uses an intrinsic.  The
+// kernel (kernels.hip, gather_cast_kernel) passes a policy of real loads, stores and the
+// hardware's converts; the host emulation of tests/test_cast_index_host.py passes one that runs
+// the same functions lane by lane over the whole grid with every offset and alignment checked,
+// and converts with the plain-integer routines below, which the host plan uses as well.
+//
+// The view is gather::Args with rows counted in elements (cast::Args, gather_device.h); the
+// odometer (RowPos, row_pos, next_row) is the gather's own.  The output is cut into 16-byte units
+// on absolute 16-byte boundaries of the destination, E = 16 / dsize elements each; the up to
+// E - 1 elements before the first and after the last whole unit are written one by one, so
+// nothing is written at or past dst + total * dsize.  The destination is a multiple of dsize
+// (the launcher refuses any other), the source of ssize (the plan does).
+//
+// A unit takes one of two paths.  Vector: its E elements lie in one contiguous run and their
+// E * ssize bytes start on a multiple of min(E * ssize, 16): one load of 4, 8 or 16 bytes (two of
+// 16 for float32 -> float16), converted in registers.  Element: every other unit loads its
+// elements one by one (ssize bytes each, naturally aligned), walking the odometer as rows end;
+// permuted views (HWC -> CHW) take this path.  Either way one 16-byte store.  A tiled transpose
+// that converts is not provided.
+#pragma once
+
+#include <cstdint>
+
+#include "gather_device.h"
+
+namespace dora {
+namespace gather {
+namespace cast {
+
+// DLPack (code, bits) -> Src, or -1 when the dtype is no cast source.
+DORA_HD int src_kind(unsigned code, unsigned bits) {
+  if (code == 1) return bits == 8 ? int(kU8) : bits == 16 ? int(kU16) : -1;
+  if (code == 0) return bits == 8 ? int(kI8) : bits == 16 ? int(kI16) : -1;
+  if (code == 2) return bits == 16 ? int(kF16) : bits == 32 ? int(kF32) : -1;
+  if (code == 4) return bits == 16 ? int(kBF16) : -1;
+  return -1;
+}
+
+template <uint32_t K>
+constexpr int kSize = K <= kI8 ? 1 : K <= kBF16 ? 2 : 4;
+
+// ------------------------------------------------------------------------------------------
+// Conversions in plain integer arithmetic, for policies without the hardware's (the host
+// compiler may have no _Float16).  Bit patterns in, bit patterns out.
+// ------------------------------------------------------------------------------------------
+DORA_HD uint32_t bits_of(float x) {
+  uint32_t u;
+  __builtin_memcpy(&u, &x, 4);
+  return u;
+}
+DORA_HD float f32_of(uint32_t u) {
+  float x;
+  __builtin_memcpy(&x, &u, 4);
+  return x;
+}
+
+// float16 -> float32: exact, subnormals normalised, a NaN stays a NaN.
+DORA_HD uint32_t f16_to_f32_bits(uint32_t h) {
+  const uint32_t sign = (h & 0x8000u) << 16;
+  const uint32_t exp = (h >> 10) & 31;
+  uint32_t man = h & 0x3ffu;
+  if (exp == 31) return sign | 0x7f800000u | (man << 13);
+  if (exp) return sign | ((exp + 112) << 23) | (man << 13);
+  if (!man) return sign;
+  uint32_t shift = 0;  // man * 2^-24 = 1.f * 2^(-14 - shift)
+  while (!(man & 0x400u)) {
+    man <<= 1;
+    ++shift;
+  }
+  return sign | ((113 - shift) << 23) | ((man & 0x3ffu) << 13);
+}
+
+// float32 -> float16, round to nearest even: overflow gives infinity (65520 and up), results
+// below 2^-14 are float16 subnormals (not flushed), a NaN gives a quiet NaN.
+DORA_HD uint32_t f32_to_f16_bits(uint32_t x) {
+  const uint32_t sign = (x >> 16) & 0x8000u;
+  const uint32_t mag = x & 0x7fffffffu;
+  if (mag > 0x7f800000u) return sign | 0x7e00u;
+  const int32_t e = static_cast<int32_t>(mag >> 23) - 112;  // the float16 exponent field
+  if (e >= 31) return sign | 0x7c00u;
+  uint32_t m = mag & 0x7fffffu, q, rem, half;
+  if (e <= 0) {
+    if (e < -10) return sign;  // below half the smallest subnormal (float32 subnormals too)
+    m |= 0x800000u;            // m * 2^(e - 38): in units of 2^-24, m >> (14 - e)
+    const uint32_t s = static_cast<uint32_t>(14 - e);  // 14..24
+    q = m >> s;
+    rem = m & ((1u << s) - 1);
+    half = 1u << (s - 1);
+  } else {
+    q = (static_cast<uint32_t>(e) << 10) | (m >> 13);
+    rem = m & 0x1fffu;
+    half = 0x1000u;
+  }
+  if (rem > half || (rem == half && (q & 1))) ++q;  // (a carry runs into the exponent, up to inf)
+  return sign | q;
+}
+
+// An integer source element (zero-extended raw bits) as float32: exact for 8 and 16 bits.
+template <uint32_t K>
+DORA_HD float int_to_f32(uint32_t raw) {
+  if constexpr (K == kU8) return static_cast<float>(static_cast<uint8_t>(raw));
+  if constexpr (K == kI8) return static_cast<float>(static_cast<int8_t>(raw));
+  if constexpr (K == kU16) return static_cast<float>(static_cast<uint16_t>(raw));
+  return static_cast<float>(static_cast<int16_t>(raw));
+}
+
+// The conversions of a policy without hardware converts (host plans, the emulation).  The
+// product is the host's own float32 multiplication: IEEE, round to nearest even, subnormals kept.
+struct HostCvt {
+  template <uint32_t K>
+  float to_f32(uint32_t raw) const {
+    if constexpr (K == kF32) return f32_of(raw);
+    else if constexpr (K == kBF16) return f32_of(raw << 16);
+    else if constexpr (K == kF16) return f32_of(f16_to_f32_bits(raw));
+    else return int_to_f32<K>(raw);
+  }
+  float mul(float x, float s) const { return x * s; }
+  uint32_t to_f16(float y) const { return f32_to_f16_bits(bits_of(y)); }
+  uint32_t f32_bits(float y) const { return bits_of(y); }
+};
+
+// ------------------------------------------------------------------------------------------
+// Arguments
+// ------------------------------------------------------------------------------------------
+
+// Arguments of the cast of `g` (the source view, in source bytes) by `c` into `dst`.
+DORA_HD Args make_args(const GatherDesc& g, const CastDesc& c, uint8_t* dst) {
+  Args a{};
+  const uint32_t ss = g.elem, ds = c.dst_bits / 8u;
+  a.g.src = g.view.src;
+  a.g.dst = dst;
+  a.g.total = c.count;
+  a.g.row = g.view.row / ss;
+  const uint64_t mis = ((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) / ds;
+  a.g.head = mis < a.g.total ? mis : a.g.total;
+  a.g.nunits = (a.g.total - a.g.head) / (16u / ds);
+  a.g.lo = g.lo;
+  a.g.hi = g.hi;
+  a.g.piece = ss;
+  a.g.pad = 0;
+  for (int k = 0; k < kDims; ++k) {
+    const int i = k - (kDims - g.view.nd);
+    a.g.shape[k] = i >= 0 ? g.view.shape[i] : 1;
+    a.g.stride[k] = i >= 0 ? g.view.stride[i] : 0;
+  }
+  const int kind = src_kind(c.src_code, c.src_bits);
+  a.src = static_cast<uint32_t>(kind < 0 ? 0 : kind);
+  a.dsize = ds;
+  a.has_scale = c.has_scale;
+  a.scale = c.scale;
+  return a;
+}
+
+DORA_HD uint64_t grid_for(const Args& a) { return gather::grid_for(a.g); }
+
+// ------------------------------------------------------------------------------------------
+// The body.  Loading is written once per destination size, with the source element size a
+// run-time value (uniform over a field's share): it yields the unit's E * ssize source bytes as
+// they would lie in one contiguous run.  Converting is written once per source type over that
+// image, so every shift in it is a constant.
+// ------------------------------------------------------------------------------------------
+
+// Element `j` of S bytes of the image `v` (little-endian), zero-extended.
+template <int S>
+DORA_HDI uint32_t elem_of(const U16* v, int j) {
+  if constexpr (S == 1) return (v[0].w[j / 4] >> (8 * (j % 4))) & 0xffu;
+  else if constexpr (S == 2) return (v[0].w[j / 2] >> (16 * (j % 2))) & 0xffffu;
+  else return v[j / 4].w[j % 4];
+}
+
+// The source bytes of the E elements from output element `e` on into v[0..1]: one vector load
+// where they are contiguous and the load is naturally aligned, else element by element across
+// rows.
+template <int D, class M>
+DORA_HDI void load_unit(const Args& a, uint64_t e, M& m, U16* v) {
+  constexpr int E = 16 / D;
+  const uint32_t ss = a.g.piece, n = E * ss;  // n: 4, 8, 16 or 32 source bytes a unit
+  uint64_t r, b;
+  out_pos(a.g, e, &r, &b);
+  RowPos p;
+  row_pos(a.g, r, p);
+  v[0] = v[1] = U16{{0, 0, 0, 0}};
+  if (b + E <= a.g.row) {
+    const int64_t s = p.off + static_cast<int64_t>(b * ss);
+    const uint32_t align = n > 16 ? 16 : n;
+    if (((reinterpret_cast<uintptr_t>(a.g.src) + static_cast<uint64_t>(s)) & (align - 1)) == 0) {
+      switch (n) {
+        case 4: v[0] = m.template load_vec<4>(s); break;
+        case 8: v[0] = m.template load_vec<8>(s); break;
+        case 16: v[0] = m.template load_vec<16>(s); break;
+        default:
+          v[0] = m.template load_vec<16>(s);
+          v[1] = m.template load_vec<16>(s + 16);
+          break;
+      }
+      return;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < E; ++j) {
+    const int64_t s = p.off + static_cast<int64_t>(b * ss);
+    switch (ss) {
+      case 1: v[0].w[j / 4] |= m.template load_elem<1>(s) << (8 * (j % 4)); break;
+      case 2: v[0].w[j / 2] |= m.template load_elem<2>(s) << (16 * (j % 2)); break;
+      default: v[j / 4].w[j % 4] = m.template load_elem<4>(s); break;
+    }
+    if (++b >= a.g.row) {
+      b = 0;
+      next_row(a.g, p);
+    }
+  }
+}
+
+// The image's E elements of source type K -> the unit's 16 output bytes.
+template <uint32_t K, int D, class M>
+DORA_HDI U16 convert_as(const Args& a, const U16* v, M& m) {
+  constexpr int E = 16 / D;
+  U16 out = {{0, 0, 0, 0}};
+#pragma unroll
+  for (int j = 0; j < E; ++j) {
+    float y = m.template to_f32<K>(elem_of<kSize<K>>(v, j));
+    if (a.has_scale) y = m.mul(y, a.scale);
+    if constexpr (D == 2) out.w[j / 2] |= m.to_f16(y) << (16 * (j % 2));
+    else out.w[j] = m.f32_bits(y);
+  }
+  return out;
+}
+
+template <int D, class M>
+DORA_HDI U16 convert_unit(const Args& a, const U16* v, M& m) {
+  switch (a.src) {
+    case kU8: return convert_as<kU8, D>(a, v, m);
+    case kI8: return convert_as<kI8, D>(a, v, m);
+    case kU16: return convert_as<kU16, D>(a, v, m);
+    case kI16: return convert_as<kI16, D>(a, v, m);
+    case kF16: return convert_as<kF16, D>(a, v, m);
+    case kBF16: return convert_as<kBF16, D>(a, v, m);
+    default: return convert_as<kF32, D>(a, v, m);
+  }
+}
+
+// Whole unit `u` of the output.
+template <int D, class M>
+DORA_HDI void cast_unit(const Args& a, uint64_t u, M& m) {
+  const uint64_t e = a.g.head + static_cast<uint64_t>(16 / D) * u;
+  U16 v[2];
+  load_unit<D>(a, e, m, v);
+  m.store16(e * D, convert_unit<D>(a, v, m));
+}
+
+// Output element `e` on its own (the elements before the first and after the last whole unit):
+// element 0 of an image that holds nothing else.
+template <int D, class M>
+DORA_HDI void cast_elem(const Args& a, uint64_t e, M& m) {
+  const uint32_t ss = a.g.piece;
+  uint64_t r, b;
+  out_pos(a.g, e, &r, &b);
+  RowPos p;
+  row_pos(a.g, r, p);
+  const int64_t s = p.off + static_cast<int64_t>(b * ss);
+  U16 v[2] = {{{0, 0, 0, 0}}, {{0, 0, 0, 0}}};
+  v[0].w[0] = ss == 1 ? m.template load_elem<1>(s)
+                      : ss == 2 ? m.template load_elem<2>(s) : m.template load_elem<4>(s);
+  const U16 y = convert_unit<D>(a, v, m);
+  m.template store_elem<D>(e, D == 2 ? y.w[0] & 0xffffu : y.w[0]);
+}
+
+// gather_lane's division of the work: lanes 0..15 a head element each, lanes 16..31 a tail
+// element each (fewer than E <= 8 of either), and every lane the whole units lane, lane + lanes, ..
+template <int D, class M>
+DORA_HDI void cast_lane_as(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+  constexpr int E = 16 / D;
+  if (lane < 16) {
+    if (lane < a.g.head) cast_elem<D>(a, lane, m);
+  } else if (lane < 32) {
+    const uint64_t t0 = a.g.head + static_cast<uint64_t>(E) * a.g.nunits;  // <= total
+    if (lane - 16 < a.g.total - t0) cast_elem<D>(a, t0 + (lane - 16), m);
+  }
+  for (uint64_t u = lane; u < a.g.nunits; u += lanes) cast_unit<D>(a, u, m);
+}
+
+// Everything lane `lane` of `lanes` does.
+template <class M>
+DORA_HDI void cast_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+  if (a.dsize == 2) cast_lane_as<2>(a, lane, lanes, m);
+  else cast_lane_as<4>(a, lane, lanes, m);
+}
+
+}  // namespace cast
+
+namespace multi {
+
+// Arguments of a cast plan's launch (gather_cast_kernel): field k through the cast body where
+// c[k].on (g[k] its source view), else as make_args places it (rows or tile by tile_c[k]); each
+// field gets the grid its body would have on its own.
+DORA_HD Args make_cast_args(const GatherDesc* g, const CastDesc* c, const uint64_t* off,
+                            const int* tile_c, int n, uint8_t* dst) {
+  Args a{};
+  a.n = static_cast<uint32_t>(n);
+  uint32_t wg = 0;
+  for (int k = 0; k < n; ++k) {
+    a.wg_begin[k] = wg;
+    Field& f = a.f[k];
+    if (c[k].on) {
+      f.kind = kRowsCast;
+      f.cast = cast::make_args(g[k], c[k], dst + off[k]);
+      wg += static_cast<uint32_t>(cast::grid_for(f.cast));
+    } else if (tile_c[k] >= 0) {
+      f.kind = kTile;
+      f.tile = tile::make_args(g[k], dst + off[k], tile_c[k]);
+      wg += static_cast<uint32_t>(tile::grid_for(f.tile));
+    } else {
+      f.kind = kRows;
+      f.rows = gather::make_args(g[k], dst + off[k]);
+      wg += static_cast<uint32_t>(gather::grid_for(f.rows));
+    }
+  }
+  for (int k = n; k <= kMaxFields; ++k) a.wg_begin[k] = wg;
+  return a;
+}
+
+}  // namespace multi
+
+}  // namespace gather
+}  // namespace dora

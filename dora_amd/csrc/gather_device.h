@@ -17,10 +17,15 @@
 
 #include "plan.h"
 
+// DORA_HD: a function of this header, for host and device.  DORA_HDI: one that is always inlined
+// into its caller on the device (cast_device.h's body: a call there would pass the kernel's
+// by-value arguments by address, which copies them into scratch).
 #if defined(__HIPCC__)
 #define DORA_HD __host__ __device__ inline
+#define DORA_HDI __host__ __device__ inline __attribute__((always_inline))
 #else
 #define DORA_HD inline
+#define DORA_HDI inline
 #endif
 
 namespace dora {
@@ -675,11 +680,36 @@ DORA_HD void take_lane(const Args& a, const Index& ix, uint64_t lane, uint64_t l
 
 }  // namespace take
 
+// ------------------------------------------------------------------------------------------
+// A field converted on the way (one more field kind, run by gather_cast_kernel only): the rows
+// body restated per element, source elements of one type read, converted and written as float16
+// or float32.  Only the arguments live here, where multi::Field needs them; the body is
+// cast_device.h.
+// ------------------------------------------------------------------------------------------
+namespace cast {
+
+// What the source elements are; every value of each is exact in float32.
+enum Src : uint32_t { kU8 = 0, kI8 = 1, kU16 = 2, kI16 = 3, kF16 = 4, kBF16 = 5, kF32 = 6 };
+
+struct Args {
+  // the view with rows counted in elements: `total` elements in all, `row` contiguous elements
+  // per row, `head` elements before the first whole 16-byte unit of the output, `nunits` whole
+  // units; `piece` the source element size; shape[] / stride[] and [lo, hi] in source bytes
+  gather::Args g;
+  uint32_t src;        // Src
+  uint32_t dsize;      // destination element size: 2 (float16) or 4 (float32)
+  uint32_t has_scale;
+  float scale;
+};
+
+}  // namespace cast
+
 namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
 // (a scan share, kScan, is no Field: it has no view; it runs workgroups [0, wg_begin[0]))
-enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3 };
+// (kRowsCast fields are run by gather_cast_kernel only: gather_struct_kernel's launches hold none)
+enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4 };
 
 struct Field {
   uint32_t kind;
@@ -688,9 +718,11 @@ struct Field {
     gather::Args rows;
     tile::Args tile;
     take::Args taken;
+    cast::Args cast;
   };
 };
 static_assert(sizeof(take::Args) <= sizeof(tile::Args), "a taken field does not grow Field");
+static_assert(sizeof(cast::Args) <= sizeof(tile::Args), "a cast field does not grow Field");
 
 struct Args {
   uint32_t n;

@@ -16,6 +16,7 @@
 
 #include "aql.h"
 #include "common.h"
+#include "cast_device.h"
 #include "gather_device.h"
 #include "pack_device.h"
 #include "plan.h"
@@ -342,6 +343,69 @@ __device__ __forceinline__ void scan_share(const gather::scan::Args& a, uint64_t
   }
 }
 
+// The cast body's memory and conversions (cast_device.h): a unit's contiguous source elements in
+// one naturally aligned load of 4, 8 or 16 bytes, non-temporal like the rows body's (each is read
+// once); single elements with plain cached loads (a permuted source line is touched by many
+// units); the sample with the pack's write-through stores.  The conversions are plain casts,
+// which the compiler turns into the hardware's (v_cvt_f32_ubyte0..3, v_cvt_f32_f16,
+// v_cvt_pk_f16_f32 ..): round to nearest even, subnormals kept in both directions — the kernel
+// descriptor's denormal modes are the default, and no build flag changes them.
+struct CastMem {
+  const uint8_t* src;
+  uint8_t* dst;
+  template <int N>
+  __device__ __forceinline__ gather::U16 load_vec(int64_t s) const {
+    const uint8_t* p = src + s;
+    if constexpr (N == 16) {
+      const u32x4 v = ld16<1, false>(p);
+      return {{v.x, v.y, v.z, v.w}};
+    } else if constexpr (N == 8) {
+      const uint64_t v = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(p));
+      return {{static_cast<uint32_t>(v), static_cast<uint32_t>(v >> 32), 0, 0}};
+    } else {
+      return {{__builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)), 0, 0, 0}};
+    }
+  }
+  template <int S>
+  __device__ __forceinline__ uint32_t load_elem(int64_t s) const {
+    const uint8_t* p = src + s;
+    if constexpr (S == 4) return *reinterpret_cast<const uint32_t*>(p);
+    else if constexpr (S == 2) return *reinterpret_cast<const uint16_t*>(p);
+    else return *p;
+  }
+  template <uint32_t K>
+  __device__ __forceinline__ float to_f32(uint32_t raw) const {
+    namespace c = gather::cast;
+    if constexpr (K == c::kF32) {
+      return __builtin_bit_cast(float, raw);
+    } else if constexpr (K == c::kBF16) {
+      return __builtin_bit_cast(float, raw << 16);
+    } else if constexpr (K == c::kF16) {
+      return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(raw)));
+    } else {
+      return c::int_to_f32<K>(raw);
+    }
+  }
+  __device__ __forceinline__ float mul(float x, float s) const { return x * s; }
+  __device__ __forceinline__ uint32_t to_f16(float y) const {
+    return __builtin_bit_cast(uint16_t, static_cast<_Float16>(y));
+  }
+  __device__ __forceinline__ uint32_t f32_bits(float y) const {
+    return __builtin_bit_cast(uint32_t, y);
+  }
+  __device__ __forceinline__ void store16(uint64_t o, gather::U16 v) const {
+    st16<2>(dst + o, u32x4{v.w[0], v.w[1], v.w[2], v.w[3]});
+  }
+  template <int D>
+  __device__ __forceinline__ void store_elem(uint64_t e, uint32_t bits) const {
+    if constexpr (D == 4) {
+      st4<2>(dst + 4 * e, bits);
+    } else {
+      __builtin_nontemporal_store(static_cast<uint16_t>(bits), reinterpret_cast<uint16_t*>(dst) + e);
+    }
+  }
+};
+
 // gather_struct_kernel: the fields of a struct-of-tensors plan in one launch (gather_device.h
 // multi::).  A workgroup finds its field in the table (a uniform scan of at most 7 steps) and
 // runs that field's own body over the field's share of the grid: gather_lane with the lane
@@ -354,12 +418,19 @@ __device__ __forceinline__ void scan_share(const gather::scan::Args& a, uint64_t
 // reading row index[i] for row i, zeros where the word is not a row), a branch that is uniform
 // over the workgroup like the other two.
 static_assert(gather::scan::kLds <= gather::tile::kLds, "the scan's rows fit the tile buffer");
-__global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather::multi::Args a) {
-  __shared__ uint64_t lds[gather::tile::kLds];
+
+// What a workgroup of a multi-field launch does, for both kernels below.  With kCast the cast kind
+// takes the place of the scan share and the taken kind, which no cast plan has: with all of them
+// in one kernel the compiler no longer follows every read back to the by-value arguments and
+// keeps a copy of the 2.3 KB in scratch.
+template <bool kCast>
+__device__ __forceinline__ void struct_share(const gather::multi::Args& a, uint64_t* lds) {
   const uint32_t w = blockIdx.x;
-  if (w < a.wg_begin[0]) {
-    scan_share(a.scan, lds);
-    return;
+  if constexpr (!kCast) {
+    if (w < a.wg_begin[0]) {
+      scan_share(a.scan, lds);
+      return;
+    }
   }
   const int k = gather::multi::field_of(a, w);
   const gather::multi::Field& f = a.f[k];
@@ -369,11 +440,24 @@ __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather:
     gather::gather_lane(f.rows, local * gather::kThreads + threadIdx.x, share * gather::kThreads, m);
     return;
   }
-  if (f.kind == gather::multi::kRowsTaken) {
-    TakeMem m{{f.taken.g.src, f.taken.g.dst}, a.take.src, a.take.wide};
-    gather::take::take_lane(f.taken, a.take, local * gather::kThreads + threadIdx.x,
-                            share * gather::kThreads, m);
-    return;
+  if constexpr (!kCast) {
+    if (f.kind == gather::multi::kRowsTaken) {
+      TakeMem m{{f.taken.g.src, f.taken.g.dst}, a.take.src, a.take.wide};
+      gather::take::take_lane(f.taken, a.take, local * gather::kThreads + threadIdx.x,
+                              share * gather::kThreads, m);
+      return;
+    }
+  }
+  if constexpr (kCast) {
+    if (f.kind == gather::multi::kRowsCast) {
+      // (a copy of its own: the body reads its arguments in more places than the compiler
+      // follows back to the kernel's by-value arguments, which it would then keep in scratch)
+      const gather::cast::Args c = f.cast;
+      CastMem m{c.g.src, c.g.dst};
+      gather::cast::cast_lane(c, local * gather::kThreads + threadIdx.x, share * gather::kThreads,
+                              m);
+      return;
+    }
   }
   switch (f.tile.elem) {
     case 1: tile_loop(f.tile, local, share, reinterpret_cast<uint8_t*>(lds)); break;
@@ -381,6 +465,19 @@ __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather:
     case 4: tile_loop(f.tile, local, share, reinterpret_cast<uint32_t*>(lds)); break;
     default: tile_loop(f.tile, local, share, lds); break;
   }
+}
+
+__global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  struct_share<false>(a, lds);
+}
+
+// gather_cast_kernel: the fields of a cast plan in one launch: the same body with the cast kind
+// enabled, so a record that mixes converted and plain fields is still one launch, the plain ones
+// through their usual rows or tile body.
+__global__ __launch_bounds__(gather::kThreads) void gather_cast_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  struct_share<true>(a, lds);
 }
 
 unsigned grid_for(uint64_t items) {
@@ -711,8 +808,54 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
   return DORA_OK;
 }
 
+int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
+                       hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (n == 0 || n > size_t(gather::multi::kMaxFields))
+    return fail(DORA_ERR_INVALID, "gather of %zu struct fields", n);
+  GatherDesc g[gather::multi::kMaxFields];
+  CastDesc c[gather::multi::kMaxFields];
+  uint64_t off[gather::multi::kMaxFields];
+  int tile_c[gather::multi::kMaxFields];
+  for (size_t k = 0; k < n; ++k) {
+    const PlanField& f = fields[k];
+    if (!f.bytes) return fail(DORA_ERR_INVALID, "gather of an empty struct field");
+    g[k] = f.gd;
+    c[k] = f.cast;
+    off[k] = f.dst_off;
+    tile_c[k] = -1;
+    if (!f.cast.on) {
+      tile_c[k] = select_tile_dim(g[k], dst + off[k]);
+      continue;
+    }
+    // the body's stores are whole elements and whole 16-byte units of them
+    const unsigned ds = f.cast.dst_bits / 8u;
+    if (gather::cast::src_kind(f.cast.src_code, f.cast.src_bits) < 0 || (ds != 2 && ds != 4) ||
+        (reinterpret_cast<uintptr_t>(f.gd.view.src) & (f.gd.elem - 1)))
+      return fail(DORA_ERR_INVALID, "field %zu `%s`: not a cast this kernel runs", k,
+                  f.name.c_str());
+    if (reinterpret_cast<uintptr_t>(dst + off[k]) & (ds - 1))
+      return fail(DORA_ERR_INVALID, "field %zu `%s`: the converted field would start at %p, not a "
+                  "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
+                  static_cast<void*>(dst + off[k]), ds);
+  }
+  const gather::multi::Args a =
+      gather::multi::make_cast_args(g, c, off, tile_c, static_cast<int>(n), dst);
+  const dim3 grid(gather::multi::grid_for(a));
+  if (ev_start || ev_stop) {
+    hipExtLaunchKernelGGL(gather_cast_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
+                          ev_stop, 0, a);
+  } else {
+    hipLaunchKernelGGL(gather_cast_kernel, grid, dim3(gather::kThreads), 0, stream, a);
+  }
+  DORA_HIP(hipGetLastError());
+  return DORA_OK;
+}
+
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (plan.cast)
+    return launch_gather_cast(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
+                              ev_stop);
   if (plan.list || plan.taken)
     return launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
                                 ev_stop, plan.scan_on ? &plan.scan : nullptr,

@@ -98,6 +98,17 @@ struct GatherDesc {
   int64_t lo, hi;
 };
 
+// A field converted on send (dora_gpu_plan_tensor_cast): `count` elements of the source dtype
+// (a DLPack code and width, bfloat16 included) become float16 or float32, through float32 and one
+// optional float32 multiplication.  `on` false: the field is sent as it is.
+struct CastDesc {
+  bool on = false;
+  uint8_t src_code = 0, src_bits = 0, dst_bits = 0;
+  uint32_t has_scale = 0;
+  float scale = 1.0f;
+  uint64_t count = 0;
+};
+
 // One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
 // own tensor plan would describe it (dense: nd == 0), where its row-major values start in the
 // sample and how many bytes they are.  Fields follow one another in destination order.
@@ -111,6 +122,9 @@ struct PlanField {
   // total the K taken rows' bytes) and this the byte stride of dimension 0, which keeps an entry
   // of its own whatever its extent or stride; [gd.lo, gd.hi] covers all N source rows
   int64_t stride0 = 0;
+  // a cast plan (dora_gpu_plan_tensor_cast), `cast.on`: `gd` is the source view in source bytes
+  // (elem the source element size, view.total the source bytes), `bytes` the converted bytes
+  CastDesc cast;
 };
 
 // The index of a take plan when it lives in HBM: `count` (K) dense words of 4 or 8 bytes at `src`,
@@ -215,6 +229,12 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
 // follows on the same stream.  The bytes are pageable memory of the plan: the runtime has staged
 // them when the call returns.
 int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
+// Launch a cast plan's fields in one launch of gather_cast_kernel (kernels.hip): the cast fields
+// converted element by element (cast_device.h), the others as launch_gather_struct moves them.
+// DORA_ERR_INVALID, nothing launched, when a cast field would not start on a multiple of its
+// destination element size.
+int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
+                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // The gather a gather plan asks for: launch_gather of its view, or launch_gather_struct of its
 // fields (with the scan of a ragged batch's device partition, by the index of a take).
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
@@ -250,6 +270,9 @@ int build_tensor_struct_plan(const dora_tensor_field* fields, size_t n, ArrowDev
 int build_tensor_list_plan(const dora_tensor_list* list, ArrowDeviceType dev, dora_plan** out);
 // Rows taken by an index, as a tensor, a record or a ragged batch (dora_gpu_plan_tensor_take).
 int build_tensor_take_plan(const dora_tensor_take* take, ArrowDeviceType dev, dora_plan** out);
+// Tensors converted to float16 / float32 on send, bare or as a record (dora_gpu_plan_tensor_cast).
+int build_tensor_cast_plan(const dora_tensor_field* fields, size_t n, const dora_tensor_cast* casts,
+                           ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -275,6 +298,9 @@ struct dora_plan {
   // segments), else a host plan whose taken rows are already in `staged`
   bool taken = false;
   bool take_on = false;
+  // cast plans (tensor_plan.cpp) with device values: a gather whose fields, a bare tensor's one
+  // included, go through gather_cast_kernel (a host cast plan is converted in `staged`)
+  bool cast = false;
   // (a plan reads one view, `gd`, or the fields of a record, by the index `take` if it is a take
   // plan: never both, and a plan of any other kind stays the size it was)
   union {

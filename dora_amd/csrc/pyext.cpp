@@ -376,6 +376,114 @@ PyObject* py_send_tensor_struct(PyObject*, PyObject* const* args, Py_ssize_t nar
   return PyLong_FromLong(rc);
 }
 
+// send_tensor_cast(handle, output_id, names, capsules, casts, device_type, metadata, flags) ->
+// status: tensors converted on send as dora_node_send_output_tensor_cast.  `names` / `capsules` as
+// send_tensor_list takes them; `casts` a tuple as long, each entry None (the field is sent as it
+// is) or (dtype_code, dtype_bits, scale or None).  Every capsule is consumed as send_tensor_struct
+// consumes its own.
+PyObject* py_send_tensor_cast(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  const char* usage = "send_tensor_cast(handle, output_id, names, capsules, casts, device_type, "
+                      "metadata, flags): names is None over one capsule or a tuple as long as the "
+                      "tuple of capsules; casts a tuple as long, of None or (code, bits, scale)";
+  if (nargs != 8 || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
+      PyTuple_GET_SIZE(args[4]) != PyTuple_GET_SIZE(args[3]) ||
+      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
+                           : PyTuple_Check(args[2]) &&
+                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+    PyErr_SetString(PyExc_TypeError, usage);
+    return nullptr;
+  }
+  void* h = nullptr;
+  if (!as_ptr(args[0], &h)) return nullptr;
+  const char* oid = as_cstr(args[1]);
+  if (!oid) return nullptr;
+  const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
+  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
+  std::vector<dora_tensor_cast> casts(static_cast<size_t>(n));
+  std::vector<DlManaged*> managed(static_cast<size_t>(n));
+  for (Py_ssize_t k = 0; k < n; ++k) {
+    fields[size_t(k)].name = nullptr;
+    if (args[2] != Py_None) {
+      fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
+      if (!fields[size_t(k)].name) return nullptr;
+    }
+    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
+    if (!PyCapsule_IsValid(cap, "dltensor")) {
+      PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
+                                    "unused, unversioned one)", k);
+      return nullptr;
+    }
+    for (Py_ssize_t j = 0; j < k; ++j)
+      if (PyTuple_GET_ITEM(args[3], j) == cap) {
+        PyErr_Format(PyExc_TypeError, "fields %zd and %zd share one capsule", j, k);
+        return nullptr;
+      }
+    dora_tensor_cast& c = casts[size_t(k)];
+    c = dora_tensor_cast{};
+    PyObject* entry = PyTuple_GET_ITEM(args[4], k);
+    if (entry == Py_None) continue;
+    if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 3) {
+      PyErr_SetString(PyExc_TypeError, usage);
+      return nullptr;
+    }
+    const long code = PyLong_AsLong(PyTuple_GET_ITEM(entry, 0));
+    const long bits = PyLong_AsLong(PyTuple_GET_ITEM(entry, 1));
+    if (PyErr_Occurred()) return nullptr;
+    if (code < 0 || code > 255 || bits < 1 || bits > 255) {
+      PyErr_Format(PyExc_TypeError, "field %zd: cast dtype (code %ld, %ld bits)", k, code, bits);
+      return nullptr;
+    }
+    c.dtype_code = static_cast<uint8_t>(code);
+    c.dtype_bits = static_cast<uint8_t>(bits);
+    PyObject* scale = PyTuple_GET_ITEM(entry, 2);
+    if (scale != Py_None) {
+      const double v = PyFloat_AsDouble(scale);
+      if (v == -1.0 && PyErr_Occurred()) return nullptr;
+      c.has_scale = 1;
+      c.scale = static_cast<float>(v);
+    }
+  }
+  const long dev = PyLong_AsLong(args[5]);
+  if (dev == -1 && PyErr_Occurred()) return nullptr;
+  const unsigned long flags = PyLong_AsUnsignedLong(args[7]);
+  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
+  std::string& params = t_params;
+  if (!encode(args[6], params)) return nullptr;
+  for (Py_ssize_t k = 0; k < n; ++k) {
+    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
+    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
+    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
+      // (cannot happen after the checks above; the capsules renamed so far are released)
+      for (Py_ssize_t j = 0; j < k; ++j)
+        if (managed[size_t(j)]->deleter) managed[size_t(j)]->deleter(managed[size_t(j)]);
+      return nullptr;
+    }
+    managed[size_t(k)] = m;
+    dora_tensor& t = fields[size_t(k)].tensor;
+    t = dora_tensor{};
+    t.data = m->t.data;
+    t.byte_offset = m->t.byte_offset;
+    t.dtype_code = m->t.code;
+    t.dtype_bits = m->t.bits;
+    t.dtype_lanes = m->t.lanes;
+    t.ndim = m->t.ndim;
+    t.shape = m->t.shape;
+    t.strides = m->t.strides;
+  }
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor_cast(static_cast<dora_node*>(h), oid, fields.data(),
+                                         fields.size(), casts.data(),
+                                         static_cast<ArrowDeviceType>(dev),
+                                         reinterpret_cast<const uint8_t*>(params.data()),
+                                         params.size(), static_cast<uint32_t>(flags));
+  Py_END_ALLOW_THREADS
+  // (deleters under the GIL and after the status has been taken, as in send_tensor)
+  for (DlManaged* m : managed)
+    if (m->deleter) m->deleter(m);
+  return PyLong_FromLong(rc);
+}
+
 // send_tensor_list(handle, output_id, names, capsules, partition, form, partition_device,
 // device_type, metadata, flags) -> status: a ragged batch as dora_node_send_output_tensor_list.
 // `names` is a tuple of str over the tuple `capsules`, or None over a tuple of one capsule (a bare
@@ -1036,6 +1144,9 @@ PyMethodDef methods[] = {
     {"send_tensor_list",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_list)),
      METH_FASTCALL, "dora_node_send_output_tensor_list of DLPack capsules, which it consumes."},
+    {"send_tensor_cast",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_cast)),
+     METH_FASTCALL, "dora_node_send_output_tensor_cast of DLPack capsules, which it consumes."},
     {"send_tensor_take",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_take)),
      METH_FASTCALL, "dora_node_send_output_tensor_take of DLPack capsules, which it consumes."},

@@ -23,11 +23,18 @@
 // same builders lay the message out; a taken field keeps dimension 0 apart from the canonical
 // view of the others.  A host index is checked and the rows gathered here; one in HBM is never
 // read, and the plan's one launch takes the rows by it (gather_device.h take::).
+//
+// Converted tensors (dora_gpu_plan_tensor_cast) are a tensor or a record laid out for the
+// destination dtypes: a cast field is validated and viewed as its source, and converted on the way
+// — by the CPU here for host values, by the plan's one launch for device values (cast_device.h).
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
+#include <cmath>
+
+#include "cast_device.h"
 #include "common.h"
 #include "plan.h"
 
@@ -314,6 +321,85 @@ int describe_taken(const dora_tensor& t, ArrowDeviceType dev, uint64_t k, Tensor
   return DORA_OK;
 }
 
+// A dtype by name, for refusals.
+std::string dtype_name(unsigned code, unsigned bits, unsigned lanes) {
+  static const char* const kNames[] = {"int", "uint", "float", nullptr, "bfloat", "complex", "bool"};
+  std::string s = code < 7 && kNames[code] ? kNames[code] : "code" + std::to_string(code) + "_";
+  if (code != DL_BOOL) s += std::to_string(bits);
+  if (lanes != 1) s += "x" + std::to_string(lanes);
+  return s;
+}
+
+// Whether `c` converts `t` at all: dtype_bits == 0 and a destination equal to the source without
+// a scale do not.  The cast's own refusals otherwise (UNSUPPORTED naming the dtype, INVALID).
+int describe_cast(const dora_tensor& t, const dora_tensor_cast& c, CastDesc& out) {
+  out = CastDesc{};
+  if (c.dtype_bits == 0) return DORA_OK;
+  if (c.dtype_code != DL_FLOAT || (c.dtype_bits != 16 && c.dtype_bits != 32))
+    return fail(DORA_ERR_UNSUPPORTED, "cast destination dtype %s is not supported: float16 and "
+                "float32 are", dtype_name(c.dtype_code, c.dtype_bits, 1).c_str());
+  if (c.has_scale && !std::isfinite(c.scale))
+    return fail(DORA_ERR_INVALID, "cast scale %f is not finite", static_cast<double>(c.scale));
+  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
+    return fail(DORA_ERR_UNSUPPORTED, "cast source dtype %s is not supported: uint8, int8, uint16, "
+                "int16, float16, bfloat16 and float32 are",
+                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  if (!c.has_scale && t.dtype_code == c.dtype_code && t.dtype_bits == c.dtype_bits) return DORA_OK;
+  out.on = true;
+  out.src_code = t.dtype_code;
+  out.src_bits = t.dtype_bits;
+  out.dst_bits = c.dtype_bits;
+  out.has_scale = c.has_scale ? 1 : 0;
+  out.scale = c.has_scale ? c.scale : 1.0f;
+  return DORA_OK;
+}
+
+// The CPU's conversion of a cast field: the view's rows in row-major order, each element through
+// the integer routines of cast_device.h, into `dst` (any alignment).
+template <uint32_t K>
+void cast_row(const uint8_t* src, uint64_t n, const CastDesc& c, uint8_t* dst) {
+  constexpr int S = gather::cast::kSize<K>;
+  const gather::cast::HostCvt cv;
+  for (uint64_t i = 0; i < n; ++i) {
+    uint32_t raw = 0;
+    std::memcpy(&raw, src + i * S, S);  // (little-endian)
+    float y = cv.to_f32<K>(raw);
+    if (c.has_scale) y = cv.mul(y, c.scale);
+    if (c.dst_bits == 16) {
+      const uint16_t h = static_cast<uint16_t>(cv.to_f16(y));
+      std::memcpy(dst + 2 * i, &h, 2);
+    } else {
+      std::memcpy(dst + 4 * i, &y, 4);
+    }
+  }
+}
+
+void cast_host(const StridedView& g, const CastDesc& c, uint8_t* dst) {
+  namespace gc = gather::cast;
+  const uint64_t ss = c.src_bits / 8u, ds = c.dst_bits / 8u, n = g.row / ss;
+  void (*row)(const uint8_t*, uint64_t, const CastDesc&, uint8_t*) = nullptr;
+  switch (gc::src_kind(c.src_code, c.src_bits)) {
+    case gc::kU8: row = cast_row<gc::kU8>; break;
+    case gc::kI8: row = cast_row<gc::kI8>; break;
+    case gc::kU16: row = cast_row<gc::kU16>; break;
+    case gc::kI16: row = cast_row<gc::kI16>; break;
+    case gc::kF16: row = cast_row<gc::kF16>; break;
+    case gc::kBF16: row = cast_row<gc::kBF16>; break;
+    default: row = cast_row<gc::kF32>; break;
+  }
+  int64_t idx[kMaxTensorDims] = {0};
+  int64_t off = 0;
+  for (uint64_t done = 0; done < c.count; done += n) {
+    row(g.src + off, n, c, dst + done * ds);
+    for (int k = g.nd - 1; k >= 0; --k) {
+      off += g.stride[k];
+      if (++idx[k] < g.shape[k]) break;
+      off -= g.stride[k] * g.shape[k];
+      idx[k] = 0;
+    }
+  }
+}
+
 bool known_device(ArrowDeviceType dev) {
   return dev == ARROW_DEVICE_CPU || dev == ARROW_DEVICE_ROCM_HOST || dev == ARROW_DEVICE_ROCM;
 }
@@ -385,6 +471,7 @@ struct FieldLayout {
   uint64_t off = 0;     // in: where the first leaf may start; out: the end of the last
   uint64_t staged = 0;  // bytes of host fields that are gathered or copied now
   bool strided = false;
+  bool cast = false;    // any field is converted (layout_fields with `casts`)
 };
 
 // Validation, view and type info of every field of `f[0..n)`, each leaf at the running offset
@@ -392,9 +479,12 @@ struct FieldLayout {
 // field is a tensor of its own (no name; its chain's head is called `head`).
 // `taken` >= 0: the fields of a take of that many rows (describe_taken): every leaf, type and
 // byte count has the leading extent `taken` where the field's own is N.
+// `casts` (n entries, never with `taken`): field k converted by casts[k] (describe_cast) is
+// validated and viewed as its source — the view and its reach in source bytes — while its leaf,
+// byte count and padding are the destination dtype's.
 int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                   const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
-                  FieldLayout& lay, int64_t taken = -1) {
+                  FieldLayout& lay, int64_t taken = -1, const dora_tensor_cast* casts = nullptr) {
   p.fields.resize(n);
   lay.chains.resize(n);
   lay.kids.resize(n);
@@ -412,16 +502,41 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     const dora_tensor& t = f[k].tensor;
     TensorView v;
     int64_t stride0 = 0;
-    const int rc = taken < 0 ? describe_tensor(&t, dev, v)
-                             : describe_taken(t, dev, static_cast<uint64_t>(taken), v, &stride0);
+    CastDesc cd;
+    int rc = casts ? describe_cast(t, casts[k], cd) : DORA_OK;
     if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
+    if (cd.on) {
+      // the view of the source: any accepted dtype of its width describes it (Arrow has no
+      // bfloat16, and the leaf is the destination's anyway)
+      dora_tensor src = t;
+      src.dtype_code = DL_UINT;
+      rc = describe_tensor(&src, dev, v);
+      if (rc == DORA_OK && v.bytes &&
+          (reinterpret_cast<uintptr_t>(v.gd.view.src) & (cd.src_bits / 8u - 1)))
+        rc = fail(DORA_ERR_INVALID, "cast source data %p (data + byte_offset) is not a multiple "
+                  "of its %u-byte elements", static_cast<const void*>(v.gd.view.src),
+                  cd.src_bits / 8u);
+      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
+      cd.count = v.bytes / (cd.src_bits / 8u);
+      v.leaf = cd.dst_bits == 16 ? "e" : "f";
+      v.bytes = cd.count * (cd.dst_bits / 8u);  // (at most twice the source's, which is < 2^63)
+      if (v.bytes >> 63) {
+        rc = fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
+        return bare ? rc : field_fail(rc, k, name);
+      }
+      lay.cast = true;
+    } else {
+      rc = taken < 0 ? describe_tensor(&t, dev, v)
+                     : describe_taken(t, dev, static_cast<uint64_t>(taken), v, &stride0);
+      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
+    }
     if (t.shape[0] != f[0].tensor.shape[0])
       return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
                   "%lld: the fields of a struct share shape[0] (give tensors of unrelated shapes "
                   "a leading extent of 1)", k, name, static_cast<long long>(t.shape[0]),
                   f[0].name, static_cast<long long>(f[0].tensor.shape[0]));
     // the running offset padded to the leaf's element size (a power of two)
-    const uint64_t elem = t.dtype_bits / 8;
+    const uint64_t elem = cd.on ? cd.dst_bits / 8u : t.dtype_bits / 8u;
     uint64_t padded, end;
     if (__builtin_add_overflow(off, elem - 1, &padded) ||
         __builtin_add_overflow(padded & ~(elem - 1), v.bytes, &end) || end >> 63)
@@ -434,6 +549,7 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     pf.dst_off = off;
     pf.bytes = v.bytes;
     pf.stride0 = stride0;
+    pf.cast = cd;
     const int64_t* shape = t.shape;  // as sent
     std::vector<int64_t> kshape;
     if (taken >= 0) {
@@ -445,7 +561,7 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     lay.kids[k] = &lay.chains[k]->sch[0];
     tensor_type_info(*lay.chains[k], shape, t.ndim, off, v.bytes, nodes[k]);
     off = end;
-    const bool stage = taken >= 0 || dev == ARROW_DEVICE_ROCM_HOST ||
+    const bool stage = taken >= 0 || cd.on || dev == ARROW_DEVICE_ROCM_HOST ||
                        (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
     if (stage) lay.staged += v.bytes;  // (<= off)
     lay.strided |= v.gd.view.nd != 0;
@@ -454,17 +570,18 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
   return DORA_OK;
 }
 
-// Host fields (none of them empty): dense pageable ones read in place, the others gathered now
-// into one staging buffer — the segments of an ordinary multi-segment host plan.
+// Host fields (none of them empty): dense pageable ones read in place, the others gathered — a
+// cast field converted — now into one staging buffer — the segments of an ordinary multi-segment host plan.
 void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
   p.staged.resize(staged);
   uint64_t at = 0;
   for (const PlanField& pf : p.fields) {
-    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0) {
+    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0 && !pf.cast.on) {
       p.segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
       continue;
     }
-    gather_host(pf.gd.view, p.staged.data() + at);
+    if (pf.cast.on) cast_host(pf.gd.view, pf.cast, p.staged.data() + at);
+    else gather_host(pf.gd.view, p.staged.data() + at);
     p.segs.push_back({p.staged.data() + at, pf.dst_off, pf.bytes});
     at += pf.bytes;
   }
@@ -542,7 +659,7 @@ int place_taken(dora_plan& p, const TakeIn& tk, uint64_t rows, uint64_t staged) 
 // A tensor (`bare`: one field without a name) or a record of tensors as one message; with `tk`
 // the rows of it that the index takes.
 int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
-                 const TakeIn* tk, dora_plan** out) {
+                 const TakeIn* tk, dora_plan** out, const dora_tensor_cast* casts = nullptr) {
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
@@ -550,7 +667,7 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   FieldLayout lay;
   std::vector<TypeInfoNode> solo;
   const int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
-                               tk ? static_cast<int64_t>(tk->ix.count) : -1);
+                               tk ? static_cast<int64_t>(tk->ix.count) : -1, casts);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
   if (bare) {
@@ -585,10 +702,12 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   if (dev == ARROW_DEVICE_ROCM) {
     // never dereferenced here.  All dense: the copy segments of any device plan (every device
     // path, the AQL multi-segment packs included); any strided: no segments, one launch of
-    // gather_struct_kernel over every field.  Either way each field's reach is checked first.
+    // gather_struct_kernel over every field; any cast: no segments, one launch of
+    // gather_cast_kernel.  Either way each field's reach is checked first.
     p->dev_tensor = true;
-    p->gather = lay.strided;
-    if (!lay.strided)
+    p->cast = lay.cast;
+    p->gather = lay.strided || lay.cast;
+    if (!p->gather)
       for (const PlanField& pf : p->fields) p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
     *out = p.release();
     return DORA_OK;
@@ -611,6 +730,31 @@ int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceTy
     return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
                 kMaxStructFields, n);
   return build_record(f, n, dev, false, nullptr, out);
+}
+
+int build_tensor_cast_plan(const dora_tensor_field* f, size_t n, const dora_tensor_cast* casts,
+                           ArrowDeviceType dev, dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a cast has values: at least one field");
+  if (!casts) return fail(DORA_ERR_INVALID, "casts is NULL (one entry per field)");
+  if (n > kMaxStructFields)
+    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
+                kMaxStructFields, n);
+  const bool bare = n == 1 && !f[0].name;
+  // no field converted at all (after every cast's own refusals): the plain plan, whatever it is
+  bool any = false;
+  for (size_t k = 0; k < n; ++k) {
+    CastDesc cd;
+    const int rc = describe_cast(f[k].tensor, casts[k], cd);
+    if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, f[k].name);
+    any |= cd.on;
+  }
+  if (!any)
+    return bare ? build_tensor_plan(&f[0].tensor, dev, out)
+                : build_tensor_struct_plan(f, n, dev, out);
+  return build_record(f, n, dev, bare, nullptr, out, casts);
 }
 
 namespace {
@@ -917,6 +1061,12 @@ int dora_gpu_plan_tensor_struct(const dora_tensor_field* fields, size_t n,
 int dora_gpu_plan_tensor_list(const dora_tensor_list* list, ArrowDeviceType device_type,
                               dora_plan** out) {
   return dora::build_tensor_list_plan(list, device_type, out);
+}
+
+int dora_gpu_plan_tensor_cast(const dora_tensor_field* fields, size_t n,
+                              const dora_tensor_cast* casts, ArrowDeviceType device_type,
+                              dora_plan** out) {
+  return dora::build_tensor_cast_plan(fields, n, casts, device_type, out);
 }
 
 int dora_gpu_plan_tensor_take(const dora_tensor_take* take, ArrowDeviceType device_type,

@@ -1,0 +1,274 @@
+// Host emulation of gather_cast_kernel (cast_device.h, and gather_device.h's rows body for the
+// fields that are not cast), a stand-alone program that tests/test_cast_index_host.py compiles
+// with the host compiler and -fsanitize=address,undefined and runs once per group of cases; it is
+// part of no library.
+//
+// It builds multi::Args with multi::make_cast_args and then does what the kernel does for every
+// workgroup of the grid: multi::field_of finds the field and cast_lane (or gather_lane) runs for
+// all 256 threads with the workgroup numbered inside the field's share, through a memory policy
+// that performs nothing unchecked:
+//   (a) every source byte read for field k lies in that field's [lo, hi];
+//   (b) every load of a cast field is naturally aligned at the address the kernel would see (a
+//       vector load of 4, 8 or 16 bytes, an element load of its size), every 16-byte load of a
+//       plain field a whole number of dwords;
+//   (c) every 16-byte store lands on a 16-byte boundary, every element store on its own size;
+//   (d) every byte of every field's [off, off + bytes) is written exactly once, by that field;
+//   (e) no byte between the fields and none at or past `size` is written;
+//   (f) the sample is appended to `out_file` (unwritten bytes 0xA5) for the caller to compare.
+// Conversions are cast_device.h's plain-integer ones (HostCvt).
+//
+//   cast_emulate spec_file [out_file]
+//
+// `spec_file` holds whitespace-separated integers, any number of cases one after another:
+//   n dst_addr size
+// then per field
+//   cast src_code src_bits dst_bits has_scale scale_bits count elem row src_total dst_bytes lo hi
+//   src_addr off nd shape[nd] stride[nd] source_file
+// `cast` 1: the field is converted (`src_code` / `src_bits` the DLPack source dtype, `dst_bits` 16
+// or 32, `scale_bits` the float32 factor's bit pattern, `count` elements); `elem`, `row`,
+// `src_total`, [lo, hi], shape and stride describe the source view in source bytes, `dst_bytes` /
+// `off` the field's bytes in the sample.  `source_file` holds the hi - lo + 1 bytes of
+// [src + lo, src + hi].  `dst_addr` / `src_addr` are the addresses the kernel would see (only
+// their alignment matters; neither is dereferenced).
+// Exit status 0 and "ok" when every check held in every case.
+#include <cinttypes>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "cast_device.h"
+
+namespace {
+
+using dora::gather::U16;
+namespace mt = dora::gather::multi;
+namespace ct = dora::gather::cast;
+
+int g_case = 0;
+
+[[noreturn]] void die(int field, const char* what, int64_t a, int64_t b) {
+  std::printf("FAIL case %d field %d: %s (%" PRId64 ", %" PRId64 ")\n", g_case, field, what, a, b);
+  std::exit(1);
+}
+
+// The whole sample: which field may write which byte, and how often each was written.
+struct Sample {
+  uint64_t size;
+  uint64_t addr;  // the address the kernel would see
+  std::vector<int8_t> owner;  // field of each byte, -1: padding
+  std::vector<uint8_t> out, writes;
+  void write(int field, uint64_t at, uint8_t v) {
+    if (at >= size) die(field, "write at or past the sample's size", int64_t(at), int64_t(size));
+    if (owner[at] != field)
+      die(field, owner[at] < 0 ? "padding byte written" : "another field's byte written",
+          int64_t(at), owner[at]);
+    if (++writes[at] != 1) die(field, "output byte written twice", int64_t(at), 0);
+    out[at] = v;
+  }
+};
+
+// One field's memory for one lane at a time, for the cast body and the rows body alike.
+struct EmuMem : ct::HostCvt {
+  int field;
+  std::vector<uint8_t> win;  // bytes of [lo, hi]
+  int64_t lo, hi;
+  uint64_t src_addr;
+  uint64_t at;  // the field's dst minus the sample's
+  Sample* s;
+  uint64_t loads = 0, vec_loads = 0;
+
+  void src_check(int64_t o, int n, int align) {
+    if (o < lo || o > hi || hi - o < n - 1) die(field, "source offset outside [lo, hi]", o, n);
+    if (align > 1 && ((src_addr + uint64_t(o)) & uint64_t(align - 1)))
+      die(field, "load not naturally aligned", o, align);
+    ++loads;
+  }
+  uint64_t bytes(int64_t o, int n) const {
+    uint64_t x = 0;
+    for (int i = 0; i < n; ++i) x |= uint64_t(win[size_t(o - lo) + size_t(i)]) << (8 * i);
+    return x;
+  }
+  U16 read16(int64_t o, int n) const {
+    uint8_t b[16] = {0};
+    for (int i = 0; i < n; ++i) b[i] = win[size_t(o - lo) + size_t(i)];
+    U16 v;
+    std::memcpy(v.w, b, 16);
+    return v;
+  }
+  // the cast body
+  template <int N>
+  U16 load_vec(int64_t o) {
+    src_check(o, N, N);
+    ++vec_loads;
+    return read16(o, N);
+  }
+  template <int S>
+  uint32_t load_elem(int64_t o) {
+    src_check(o, S, S);
+    return static_cast<uint32_t>(bytes(o, S));
+  }
+  template <int D>
+  void store_elem(uint64_t e, uint32_t bits) {
+    if ((s->addr + at + e * D) % D) die(field, "element store not aligned", int64_t(e), D);
+    for (int i = 0; i < D; ++i) s->write(field, at + e * D + uint64_t(i), uint8_t(bits >> (8 * i)));
+  }
+  // the rows body
+  U16 load16(int64_t o) {
+    src_check(o, 16, 4);
+    return read16(o, 16);
+  }
+  template <int G>
+  uint64_t load_piece(int64_t o) {
+    src_check(o, G, 1);
+    return bytes(o, G);
+  }
+  U16 funnel(U16 l, U16 h, uint32_t mis) {
+    if (mis >= 16) die(field, "funnel shift", mis, 0);
+    uint8_t b[32];
+    std::memcpy(b, l.w, 16);
+    std::memcpy(b + 16, h.w, 16);
+    U16 v;
+    std::memcpy(v.w, b + mis, 16);
+    return v;
+  }
+  void store16(uint64_t o, U16 v) {
+    if ((s->addr + at + o) & 15) die(field, "16-byte store not aligned", int64_t(o), 0);
+    uint8_t b[16];
+    std::memcpy(b, v.w, 16);
+    for (int i = 0; i < 16; ++i) s->write(field, at + o + uint64_t(i), b[i]);
+  }
+  void store1(uint64_t o, uint8_t v) { s->write(field, at + o, v); }
+};
+
+bool read_file(const std::string& name, std::vector<uint8_t>& into, uint64_t want) {
+  into.resize(want);
+  if (!want) return true;
+  FILE* f = std::fopen(name.c_str(), "rb");
+  const bool ok = f && std::fread(into.data(), 1, want, f) == want;
+  if (f) std::fclose(f);
+  return ok;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc < 2) {
+    std::printf("usage: see the file's head\n");
+    return 2;
+  }
+  std::ifstream in(argv[1]);
+  FILE* out = argc > 2 ? std::fopen(argv[2], "wb") : nullptr;
+  if (argc > 2 && !out) {
+    std::printf("FAIL output file\n");
+    return 2;
+  }
+  uint64_t loads = 0, vec_loads = 0, grid_sum = 0;
+  int64_t n = 0;
+  while (in >> n) {
+    uint64_t dst_addr = 0, size = 0;
+    in >> dst_addr >> size;
+    if (!in || n < 1 || n > mt::kMaxFields) {
+      std::printf("FAIL bad case %d\n", g_case);
+      return 2;
+    }
+    uint8_t* dst = reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(dst_addr));
+    dora::GatherDesc g[mt::kMaxFields] = {};
+    dora::CastDesc c[mt::kMaxFields];
+    uint64_t off[mt::kMaxFields], dst_bytes[mt::kMaxFields];
+    int tile_c[mt::kMaxFields];
+    Sample s{size, dst_addr, std::vector<int8_t>(size, -1), std::vector<uint8_t>(size, 0xA5),
+             std::vector<uint8_t>(size, 0)};
+    std::vector<EmuMem> mem(static_cast<size_t>(n));
+    for (int k = 0; k < n; ++k) {
+      uint64_t src = 0;
+      uint32_t on = 0, code = 0, sbits = 0, dbits = 0, has_scale = 0, scale_bits = 0;
+      std::string file;
+      in >> on >> code >> sbits >> dbits >> has_scale >> scale_bits >> c[k].count >> g[k].elem >>
+          g[k].view.row >> g[k].view.total >> dst_bytes[k] >> g[k].lo >> g[k].hi >> src >> off[k] >>
+          g[k].view.nd;
+      if (!in || g[k].view.nd < 0 || g[k].view.nd > dora::kMaxTensorDims || on > 1) {
+        std::printf("FAIL bad field %d of case %d\n", k, g_case);
+        return 2;
+      }
+      for (int i = 0; i < g[k].view.nd; ++i) in >> g[k].view.shape[i];
+      for (int i = 0; i < g[k].view.nd; ++i) in >> g[k].view.stride[i];
+      in >> file;
+      if (!in || off[k] > size || dst_bytes[k] > size - off[k] || !dst_bytes[k] || g[k].hi < g[k].lo) {
+        std::printf("FAIL field %d of case %d does not fit the sample\n", k, g_case);
+        return 2;
+      }
+      c[k].on = on != 0;
+      c[k].src_code = uint8_t(code);
+      c[k].src_bits = uint8_t(sbits);
+      c[k].dst_bits = uint8_t(dbits);
+      c[k].has_scale = has_scale;
+      c[k].scale = ct::f32_of(scale_bits);
+      if (c[k].on && (ct::src_kind(code, sbits) < 0 || (dbits != 16 && dbits != 32) ||
+                      c[k].count * (dbits / 8) != dst_bytes[k] || sbits / 8 != g[k].elem)) {
+        std::printf("FAIL field %d of case %d is no cast\n", k, g_case);
+        return 2;
+      }
+      tile_c[k] = -1;
+      g[k].view.src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(src));
+      for (uint64_t b = 0; b < dst_bytes[k]; ++b) {
+        if (s.owner[off[k] + b] >= 0) die(k, "fields overlap", int64_t(off[k] + b), 0);
+        s.owner[off[k] + b] = int8_t(k);
+      }
+      EmuMem& m = mem[size_t(k)];
+      m.field = k;
+      m.lo = g[k].lo;
+      m.hi = g[k].hi;
+      m.src_addr = src;
+      m.s = &s;
+      if (!read_file(file, m.win, uint64_t(g[k].hi - g[k].lo) + 1)) {
+        std::printf("FAIL source file of field %d of case %d\n", k, g_case);
+        return 2;
+      }
+    }
+    const mt::Args a = mt::make_cast_args(g, c, off, tile_c, int(n), dst);
+    const uint32_t grid = mt::grid_for(a);
+    for (int k = 0; k < n; ++k) {
+      const uint32_t want = c[k].on ? mt::kRowsCast : mt::kRows;
+      if (a.f[k].kind != want) die(k, "field of the wrong kind", a.f[k].kind, want);
+      mem[size_t(k)].at = uint64_t((c[k].on ? a.f[k].cast.g.dst : a.f[k].rows.dst) - dst);
+      if (mem[size_t(k)].at != off[k]) die(k, "field at the wrong offset", int64_t(off[k]), 0);
+      if (a.wg_begin[k + 1] <= a.wg_begin[k]) die(k, "field without a workgroup", a.wg_begin[k], 0);
+    }
+    for (uint32_t w = 0; w < grid; ++w) {
+      const int k = mt::field_of(a, w);
+      if (k < 0 || k >= n || w < a.wg_begin[k] || w >= a.wg_begin[k + 1])
+        die(k, "workgroup outside its field's share", w, 0);
+      const uint64_t local = w - a.wg_begin[k], share = a.wg_begin[k + 1] - a.wg_begin[k];
+      EmuMem& m = mem[size_t(k)];
+      for (uint32_t th = 0; th < uint32_t(dora::gather::kThreads); ++th) {
+        const uint64_t lane = local * dora::gather::kThreads + th;
+        if (c[k].on) ct::cast_lane(a.f[k].cast, lane, share * dora::gather::kThreads, m);
+        else dora::gather::gather_lane(a.f[k].rows, lane, share * dora::gather::kThreads, m);
+      }
+    }
+    for (uint64_t b = 0; b < size; ++b)
+      if (s.owner[b] >= 0 && s.writes[b] != 1)
+        die(s.owner[b], "output byte never written", int64_t(b), 0);
+    if (out && std::fwrite(s.out.data(), 1, s.out.size(), out) != s.out.size()) {
+      std::printf("FAIL output file\n");
+      return 2;
+    }
+    for (const EmuMem& m : mem) {
+      loads += m.loads;
+      vec_loads += m.vec_loads;
+    }
+    grid_sum += grid;
+    ++g_case;
+  }
+  if (out) std::fclose(out);
+  if (!g_case) {
+    std::printf("FAIL no case\n");
+    return 2;
+  }
+  std::printf("ok cases=%d grid=%" PRIu64 " loads=%" PRIu64 " vector_loads=%" PRIu64 "\n", g_case,
+              grid_sum, loads, vec_loads);
+  return 0;
+}

@@ -397,6 +397,28 @@ int dora_gpu_test_plan_take(const dora_plan* plan, int* device, const void** ind
   return DORA_OK;
 }
 
+int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, int* is_cast,
+                            int* src_code, int* src_bits, int* dst_code, int* dst_bits,
+                            int* has_scale, float* scale, uint64_t* elements,
+                            uint64_t* src_bytes, uint64_t* dst_bytes) {
+  if (!plan || !plan->dev_tensor || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a device plan with a field %zu", i);
+  const dora::PlanField& f = plan->fields[i];
+  const dora::CastDesc& c = f.cast;
+  if (n_fields) *n_fields = plan->fields.size();
+  if (is_cast) *is_cast = plan->cast && c.on;
+  if (src_code) *src_code = c.on ? c.src_code : -1;
+  if (src_bits) *src_bits = c.on ? c.src_bits : static_cast<int>(f.gd.elem * 8);
+  if (dst_code) *dst_code = c.on ? 2 : -1;
+  if (dst_bits) *dst_bits = c.on ? c.dst_bits : static_cast<int>(f.gd.elem * 8);
+  if (has_scale) *has_scale = c.on && c.has_scale;
+  if (scale) *scale = c.on ? c.scale : 1.0f;
+  if (elements) *elements = c.on ? c.count : f.bytes / f.gd.elem;
+  if (src_bytes) *src_bytes = f.gd.view.total;
+  if (dst_bytes) *dst_bytes = f.bytes;
+  return DORA_OK;
+}
+
 int dora_gpu_test_ide_output(const char* dataflow_id, const char* node_id,
                                         const char* output_id, const uint8_t* type_info,
                                         size_t type_info_len, const uint8_t* params,

@@ -32,6 +32,7 @@ _DL_ROCM = 10          # DLPack device types: kDLROCM
 _DL_CPU = 1
 _DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinned)
 from .device import DeviceArray, DeviceBuffer
+from .tensor import Cast as _Cast
 from .tensor import Ragged as _Ragged
 from .tensor import Taken as _Taken
 from .type_info import decode
@@ -234,6 +235,9 @@ class Node:
                                       ctypes.addressof(c.schema), ARROW_DEVICE_CPU, metadata)
         elif hasattr(data, "__dlpack__") and hasattr(data, "__dlpack_device__"):
             rc = self._send_tensor(output_id, data, metadata, f)
+        elif isinstance(data, _Cast) or (isinstance(data, dict) and
+                                         any(isinstance(v, _Cast) for v in data.values())):
+            rc = self._send_tensor_cast(output_id, data, metadata, f)
         elif isinstance(data, dict):
             rc = self._send_tensor_struct(output_id, data, metadata, f)
         elif isinstance(data, _Ragged):
@@ -244,8 +248,9 @@ class Node:
             raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer, "
                             "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU), "
                             "a dict of such tensors, rows of either taken by an index "
-                            "(dora_amd.tensor.take) or a ragged batch of any of these "
-                            "(dora_amd.tensor.ragged)")
+                            "(dora_amd.tensor.take), a ragged batch of any of these "
+                            "(dora_amd.tensor.ragged) or tensors converted on send "
+                            "(dora_amd.tensor.cast)")
         if rc:
             _lib.check(rc)
 
@@ -428,6 +433,56 @@ class Node:
                                 "with host values pass the partition as a host list (.tolist())")
             return part, form, ARROW_DEVICE_ROCM
         return self._host_words(part, "partition"), form, ARROW_DEVICE_CPU
+
+    def _send_tensor_cast(self, output_id: str, data, metadata, flags: int) -> int:
+        """A tensor converted on send (dora_amd.tensor.cast), or a dict of tensors of which some
+        are, as the tensor or Struct message of the converted values
+        (dora_node_send_output_tensor_cast).  Host tensors are converted by the CPU inside the
+        call and have been read on return.  Tensors on this node's GPU do the
+        `__dlpack__(stream=<the node stream>)` handshake each and are read, converted and written
+        by one kernel launch; an asynchronous send holds them until `sync()`.  A torch bfloat16
+        tensor goes through DLPack like any other (type code 4)."""
+        record = isinstance(data, dict)
+        items = data if record else {None: data}
+        casts = [v if isinstance(v, _Cast) else None for v in items.values()]
+        plain = {k: (v.values if isinstance(v, _Cast) else v) for k, v in items.items()}
+        kind, tensors, names = self._values_kind(plain if record else plain[None])
+        entries = tuple(c._entry() if c is not None else None for c in casts)
+        if kind == "device":
+            _require_one_hip_runtime()
+            held = bool(flags & SEND_ASYNC) or self._async_default
+            if held and len(self._async_tensors) + len(tensors) > self._ASYNC_TENSORS_MAX:
+                self.sync()
+            stream = int(self._lib.dora_node_stream(self.handle))
+            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
+            rc = _fast.send_tensor_cast(self.handle, output_id, names, caps, entries,
+                                        ARROW_DEVICE_ROCM, metadata, flags)
+            if held and not rc:
+                self._async_tensors.extend(tensors)
+            return rc
+        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
+        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
+        try:
+            caps = tuple(v.__dlpack__() for v in tensors)
+        except BufferError:
+            # (read-only numpy arrays: every field through its array interface, as in
+            # _send_tensor_struct)
+            if not all(hasattr(v, "__array_interface__") for v in tensors):
+                raise
+            from ._lib import Tensor
+            from .tensor import _describe_array, _describe_casts, _describe_list
+            described = [_describe_array(v) for v in tensors]
+            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
+                                       ARROW_DEVICE_CPU)
+            carr = _describe_casts(casts)
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_cast(
+                self.handle, output_id.encode(), lst.fields, len(tensors), carr, dev, params,
+                len(params), flags)
+            del keep, described, carr
+            return rc
+        return _fast.send_tensor_cast(self.handle, output_id, names, caps, entries, dev, metadata,
+                                      flags)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
         """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with

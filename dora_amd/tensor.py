@@ -52,6 +52,24 @@ is not a row — a bad index is the producer's bug and shows as zero rows, never
 message or a stray read.  Not offered: boolean masks (the message length would need a host
 synchronisation), other dimensions, a host index over device values.
 
+A tensor whose consumer wants another element type is converted inside the send:
+`cast(x, dtype, scale=None)` stands for "`x` converted to `dtype`" (float16 or float32, from uint8,
+int8, uint16, int16, float16, bfloat16 or float32) and is sent as exactly the message the converted
+tensor would be, bare or as a field of a dict next to fields that are sent as they are:
+
+    node.send_output("image", tensor.cast(frame.permute(2, 0, 1), "float16", scale=1 / 255))
+    node.send_output("det", {"image": tensor.cast(img, "float16", scale=1 / 255), "conf": conf})
+    node.send_output("logits", tensor.cast(bf16_logits, "float32"))   # the way to send bfloat16
+
+Element by element the result is `to_dtype(float32(x) * float32(scale))`: one float32
+multiplication and one round-to-nearest-even conversion, float16 subnormals kept, overflow to
+inf — `from_numpy_cast` states it in numpy and the send is bit-exact against it except for the
+payload of a NaN.  Multiplying by `1 / 255` is not dividing by 255: the two differ in the last bit
+for some inputs.  Host tensors are converted by the CPU inside the send; tensors in this node's
+HBM by the send's one kernel launch, which reads the source once and writes the sample once, no
+`.to(dtype)` and no intermediate tensor.  Not offered: a cast under `ragged` or `take`, integer
+and bfloat16 destinations.
+
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
 is copied once, so every source has been read when `send_output` returns.  A tensor in device
 memory is read by a kernel: in place when dense, gathered by the gfx950 gather kernel when it is a
@@ -62,7 +80,7 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import Tensor, TensorField, TensorList, TensorTake
+from ._lib import Tensor, TensorCast, TensorField, TensorList, TensorTake
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -170,6 +188,76 @@ class Taken:
         return f"Taken({len(self)} rows of {self.values!r})"
 
 
+def _has_cast(values):
+    if isinstance(values, dict):
+        return any(isinstance(v, Cast) for v in values.values())
+    return isinstance(values, Cast)
+
+
+def _cast_dtype(dtype):
+    """(DLPack code, bits, name) of a cast destination given as a name, a numpy dtype or a torch
+    dtype; the library refuses all but float16 and float32."""
+    import numpy as np
+    if str(dtype).startswith("torch."):
+        name = str(dtype)[len("torch."):]
+        if name == "bfloat16":
+            return 4, 16, name
+        dtype = {"half": "float16", "float": "float32", "double": "float64"}.get(name, name)
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise TypeError(f"cast: {dtype!r} is not a dtype") from None
+    return _DL_CODES.get(dt.kind, 255), dt.itemsize * 8, dt.name
+
+
+class Cast:
+    """A tensor converted on send: `values`, a tensor, and the `dtype` it is sent as, after one
+    optional multiplication by `scale`.  It copies and converts nothing itself.  Build one with
+    `cast`."""
+
+    __slots__ = ("values", "dtype", "scale", "_code", "_bits")
+
+    def __init__(self, values, dtype, scale=None):
+        self.values = values
+        self._code, self._bits, self.dtype = _cast_dtype(dtype)
+        self.scale = None if scale is None else float(scale)
+
+    def _entry(self):
+        return (self._code, self._bits, self.scale)
+
+    def __repr__(self):
+        by = "" if self.scale is None else f" * {self.scale!r}"
+        return f"Cast({self.values!r}{by} -> {self.dtype})"
+
+
+def cast(values, dtype, scale=None):
+    """`values` converted to `dtype` as a message: `values` a tensor of uint8, int8, uint16, int16,
+    float16, bfloat16 or float32 (host memory or this node's HBM), `dtype` "float16" or "float32"
+    (or the numpy or torch dtype), `scale` an optional finite factor applied in float32 first.
+    `send_output` sends it, on its own or as a value of a dict of tensors, as what
+    `from_numpy_cast` states."""
+    if isinstance(values, (Cast, Taken, Ragged, dict)):
+        raise TypeError("cast converts one tensor: give a dict's fields a cast each; a cast under "
+                        "ragged or take is not offered")
+    return Cast(values, dtype, scale)
+
+
+def from_numpy_cast(x, dtype, scale=None, *, bfloat16=False):
+    """The nested pyarrow array of `(x.astype(float32) * float32(scale)).astype(dtype)`, the
+    statement of record of `cast` and the counterpart of `from_numpy`: what
+    `send_output(output_id, cast(x, dtype, scale))` puts on the wire.  `bfloat16`: `x` holds the
+    bits of bfloat16 values as uint16 (numpy has no such dtype)."""
+    import numpy as np
+    x = np.asarray(x)
+    if bfloat16:
+        x = (x.astype(np.uint32) << 16).view(np.float32)
+    y = x.astype(np.float32)
+    if scale is not None:
+        y = y * np.float32(scale)
+    with np.errstate(over="ignore"):
+        return from_numpy(y.astype(np.dtype(_cast_dtype(dtype)[2])))
+
+
 def take(values, index):
     """`values[index]` along dimension 0 as a message: `values` a tensor or a dict of at most 8
     tensors sharing their leading extent N, `index` a 1-D sequence or tensor of K int32 or int64
@@ -177,6 +265,9 @@ def take(values, index):
     tensors).  `send_output` sends it, bare or under `ragged`, as what `values[index]` would be."""
     if isinstance(values, (Taken, Ragged)):
         raise TypeError("take selects rows of a tensor or of a dict of tensors")
+    if _has_cast(values):
+        raise TypeError("cast under take is not offered: convert the taken rows with .to(dtype), "
+                        "or send the cast without the take")
     return Taken(values, index)
 
 
@@ -185,6 +276,9 @@ def ragged(values, *, lengths=None, offsets=None):
     leading extent N, or rows of either taken by `take`: N is then the K taken rows) cut into
     lists by exactly one of `lengths` (B of them) and `offsets` (B + 1): what `send_output` sends
     as one `List` message."""
+    if _has_cast(values):
+        raise TypeError("cast under ragged is not offered: convert the values with .to(dtype), or "
+                        "send the cast without the partition")
     return Ragged(values, offsets=offsets, lengths=lengths)
 
 
@@ -349,6 +443,19 @@ def _describe_fields(names, tensors) -> tuple:
     return arr, (enc, tensors)
 
 
+def _describe_casts(casts) -> "ctypes.Array":
+    """The `dora_tensor_cast` array of `casts`, each a `Cast` or None (the field is sent as it
+    is)."""
+    arr = (TensorCast * len(casts))()
+    for k, c in enumerate(casts):
+        if c is None:
+            continue
+        arr[k].dtype_code, arr[k].dtype_bits = c._code, c._bits
+        arr[k].has_scale = 0 if c.scale is None else 1
+        arr[k].scale = 0.0 if c.scale is None else c.scale
+    return arr
+
+
 def _describe_list(names, tensors, partition, form, partition_device) -> tuple:
     """The `dora_tensor_list` over the `Tensor`s of `_describe` (`names` None: the one bare
     tensor) and the partition's `Tensor`, and what the caller keeps alive with it."""
@@ -391,4 +498,4 @@ def _describe_take(names, tensors, index, index_device, partition, form,
 
 __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_numpy_struct",
            "from_numpy_ragged", "from_numpy_take", "to_numpy", "to_torch", "Ragged", "ragged",
-           "Taken", "take"]
+           "Taken", "take", "Cast", "cast", "from_numpy_cast"]

@@ -212,7 +212,8 @@ int dora_gpu_plan_bytes(const void* src, size_t len, ArrowDeviceType device_type
  *
  * Accepted dtypes: int and uint of 8/16/32/64 bits, float of 16/32/64 bits, lanes == 1.
  * DORA_ERR_UNSUPPORTED, with a message naming the dtype: bool (Arrow's is a bitmap), bfloat16 and
- * complex (Arrow has neither: send a view as uint16 or as pairs of floats), lanes != 1, and a
+ * complex (Arrow has neither: send a view as uint16 or as pairs of floats; a bfloat16 tensor is
+ * sent as float32 or float16 with dora_gpu_plan_tensor_cast, below), lanes != 1, and a
  * view of more than 8 dimensions after merging.  DORA_ERR_INVALID: ndim < 1, a negative extent,
  * an extent of 0 in any dimension but the first, a byte count that overflows 64 bits, a NULL
  * `data` with a non-zero element count.  d0 == 0 plans an empty message.
@@ -361,6 +362,57 @@ typedef struct dora_tensor_take {
 } dora_tensor_take;
 int dora_gpu_plan_tensor_take(const dora_tensor_take* take, ArrowDeviceType device_type,
                               dora_plan** out);
+/*
+ * Converted tensors as one message: field k "converted to casts[k]'s dtype", the conversion run
+ * inside the send's one read of the source and one write of the sample.  `fields` is a record as
+ * dora_gpu_plan_tensor_struct takes it, or n == 1 with a NULL name: a bare tensor; `casts` has n
+ * entries, and one with dtype_bits == 0 leaves its field as it is.  On the wire the message is
+ * exactly what planning the converted tensors gives: type info, sample size and leaf offsets are
+ * those of tensors of the destination dtypes with the same shapes (padding by the destination
+ * element size); there is no new Arrow type and a reference node reads the message as before.
+ * d0 == 0 is an empty message of that type.
+ *
+ * Element by element y = to_dst(to_f32(x) [* scale]).
+ *   Sources: uint8, int8, uint16, int16, float16, bfloat16 (DLPack code 4, 16 bits) and float32;
+ *   every value of each is exact in float32, so to_f32 never rounds.  int32, int64, float64, bool,
+ *   complex and anything else are DORA_ERR_UNSUPPORTED as cast sources, naming the dtype.
+ *   Destinations: float16 and float32 (code 2, 16 or 32 bits); anything else is
+ *   DORA_ERR_UNSUPPORTED (float-to-integer and bfloat16 destinations are not provided).
+ *   Scale (has_scale != 0): a finite float32; NaN or infinite is DORA_ERR_INVALID.  The product is
+ *   one IEEE float32 multiplication, round to nearest even, subnormals kept.  to_dst for float16
+ *   is one round-to-nearest-even conversion: overflow gives +-inf, float16 subnormals are produced,
+ *   not flushed.
+ *   The statement of record is numpy's (x.astype(float32) * float32(scale)).astype(dst), bfloat16
+ *   taken as uint16 bits << 16: results are bit-exact against it for every input that is not a
+ *   NaN; a NaN gives some NaN, payload unspecified.  Multiplying by float32(1/255) is not dividing
+ *   by 255: the two differ in the last bit for some inputs, and the statement above is the contract.
+ *   Identity: a cast whose destination equals the source dtype, without a scale, is no cast.  A
+ *   call in which no field is cast plans exactly as dora_gpu_plan_tensor (bare) or
+ *   dora_gpu_plan_tensor_struct does: segments, type info and gather.  With a scale it is a cast.
+ *
+ * Host values (ARROW_DEVICE_CPU, ARROW_DEVICE_ROCM_HOST): the CPU gathers and converts every cast
+ * field inside this call into the plan's staging buffer, dense views included; the plan is an
+ * ordinary host plan and every cast source has been read on return.
+ * Device values: never read on the host.  Any cast field makes the plan one launch of
+ * gather_cast_kernel (gfx950) and no segments, as "any field strided" does for a record; fields
+ * that are not cast go through their usual body in the same launch.  Each field's reach is
+ * computed with the source element size and the overflow checks of dora_gpu_plan_tensor and held
+ * against the field's allocation before anything is launched.
+ * DORA_ERR_INVALID, naming the field, on top of the record's and the tensors' own refusals: a
+ * NULL `casts`, a cast field whose data + byte_offset is not a multiple of the source element
+ * size.  dora_gpu_pack to a destination where a cast field would not start on a multiple of its
+ * destination element size is DORA_ERR_INVALID with nothing launched (a node's samples never are).
+ * Not provided: a cast under a ragged batch or a take.
+ */
+typedef struct dora_tensor_cast { /* dtype_bits == 0: this field is sent as it is */
+  uint8_t dtype_code;
+  uint8_t dtype_bits;
+  uint16_t has_scale;
+  float scale;
+} dora_tensor_cast;
+int dora_gpu_plan_tensor_cast(const dora_tensor_field* fields, size_t n,
+                              const dora_tensor_cast* casts /* n entries */,
+                              ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -583,6 +635,16 @@ int dora_node_send_output_tensor_list(dora_node* node, const char* output_id,
  * caller keeps all of them alive and unwritten until dora_node_sync. */
 int dora_node_send_output_tensor_take(dora_node* node, const char* output_id,
                                       const dora_tensor_take* take, ArrowDeviceType device_type,
+                                      const uint8_t* params, size_t params_len, uint32_t flags);
+/* Send converted tensors (dora_gpu_plan_tensor_cast: semantics, wire form, refusals), with the
+ * contract of dora_node_send_output_tensor_struct.  Host values have been read and converted on
+ * return and take every path of a host plan.  Device values go where the struct send's gather
+ * goes, one launch of gather_cast_kernel on a fill stream ordered after the node stream: a
+ * synchronous send returns once the launch has read every field; with DORA_SEND_ASYNC, once it
+ * is queued, and the caller keeps the fields alive and unwritten until dora_node_sync. */
+int dora_node_send_output_tensor_cast(dora_node* node, const char* output_id,
+                                      const dora_tensor_field* fields, size_t n,
+                                      const dora_tensor_cast* casts, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags);
 /* Make DORA_SEND_ASYNC the default of every send of this node (also DORA_GPU_SEND_ASYNC=1). */
 int dora_node_set_async_sends(dora_node* node, int enable);

@@ -104,6 +104,17 @@ int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, 
  * host plan, the taken rows already in its staging buffer (or an empty message). */
 int dora_gpu_test_plan_take(const dora_plan* plan, int* device, const void** index, uint64_t* k,
                             uint64_t* n, int* wide, int64_t* lo, int64_t* hi, int64_t* stride0);
+/* Test tool (host only): field `i` of a device plan of dora_gpu_plan_tensor_cast (or of any device
+ * plan that keeps its fields).  *is_cast 1 when gather_cast_kernel converts the field: then
+ * *src_code / *src_bits the source dtype (DLPack), *dst_code / *dst_bits the destination's,
+ * *has_scale and *scale the factor.  A field sent as it is reports codes of -1 and its element
+ * width twice.  *elements the field's element count, *src_bytes the bytes of its source view,
+ * *dst_bytes those it has in the sample.  dora_gpu_test_plan_field keeps reporting view and reach
+ * (of a cast field: in source bytes). */
+int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, int* is_cast,
+                            int* src_code, int* src_bits, int* dst_code, int* dst_bits,
+                            int* has_scale, float* scale, uint64_t* elements,
+                            uint64_t* src_bytes, uint64_t* dst_bytes);
 /* Test and probe tool: which kernel gathers strided device tensor views of this process from now
  * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
  * it applies (short contiguous extents included). */
