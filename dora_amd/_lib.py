@@ -87,6 +87,14 @@ class TensorCast(ctypes.Structure):
                 ("scale", c_float)]
 
 
+class TensorMask(ctypes.Structure):
+    """dora_tensor_mask of include/dora_gpu.h: the fields rows are selected from, the mask that
+    selects them and, for more than one list, the partition of the N source rows (else NULL)."""
+    _fields_ = [("fields", POINTER(TensorField)), ("n", c_size_t), ("mask", Tensor),
+                ("mask_device", c_int32), ("partition", POINTER(Tensor)),
+                ("partition_form", c_uint32), ("partition_device", c_int32)]
+
+
 class FillTicket(ctypes.Structure):
     """dora_fill_ticket of include/dora_fill_ticket.h (32 bytes): what dora_sample_fill_ticket
     issues and a publishing kernel takes by value."""
@@ -140,6 +148,10 @@ _SIGS = {
                                           POINTER(c_void_p)]),
     "dora_node_send_output_tensor_cast": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p,
                                                   c_int32, c_char_p, c_size_t, c_uint32]),
+    "dora_gpu_plan_tensor_mask": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_mask": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
+                                                  c_size_t, c_uint32]),
+    "dora_gpu_plan_workspace_size": (c_size_t, [c_void_p]),
     "dora_node_send_output_tensor": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                              c_size_t, c_uint32]),
     "dora_gpu_plan_compact": (c_int, [POINTER(ArrowArray), POINTER(ArrowSchema), c_int32,
@@ -287,6 +299,10 @@ _TEST_SIGS = {
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int),
                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
                                         POINTER(ctypes.c_int64)]),
+    "dora_gpu_test_plan_mask": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
+                                        POINTER(c_uint64), POINTER(ctypes.c_int64),
+                                        POINTER(ctypes.c_int64), POINTER(c_uint64),
+                                        POINTER(c_uint64), POINTER(ctypes.c_int64)]),
     "dora_gpu_test_aql_hold": (c_int, [c_int, c_int]),
     "dora_gpu_test_reduce_timeout": (c_int, [c_uint64]),
     "dora_gpu_test_d2h_copy_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_uint64, c_void_p]),

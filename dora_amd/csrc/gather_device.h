@@ -681,6 +681,196 @@ DORA_HD void take_lane(const Args& a, const Index& ix, uint64_t lane, uint64_t l
 }  // namespace take
 
 // ------------------------------------------------------------------------------------------
+// Rows selected by a mask of N bytes (two kernels in front of gather_struct_kernel): the stream
+// compaction that turns the mask into what a take reads — N int32 index words, of which the
+// first K are the selected rows in source order and the rest -1 (the taken body's zero rows) — and
+// into the counts C[0..N], C[i] the number of selected rows among rows [0, i), which a ragged
+// batch's offsets are looked up in.  Any non-zero byte selects.
+//
+// Rows are counted from the 16-byte line the mask starts in: position v = row + shift, shift the
+// mask's address mod 16, so that a thread's kUnit positions are one aligned 16-byte load wherever
+// all of them are rows; the positions of a unit that holds the mask's head or tail go byte by
+// byte, rows only, so nothing outside [mask, mask + N) is read.  A tile is kTile positions, one
+// unit per thread.
+//
+//   mask_count_kernel, per tile: count_load (the thread's count into LDS; the tile's index words
+//   set to -1, consecutive threads consecutive words), kSteps reduce_phase steps, count_store
+//   (totals[tile]).
+//   mask_compact_kernel, per tile: carry_load (the totals of the tiles before it, strided over the
+//   threads — at most 4097 words, which is what caps N at kMaxRows), kSteps reduce_phase steps,
+//   carry_read; scan_load (the thread's flags again), kSteps scan_step steps of the doubling scan
+//   through two LDS rows, scan_store (C[i] for its rows, index[C[i]] = i for the selected ones;
+//   the last tile's last thread writes C[N] = K and, for a message of one list, its offsets).
+// A barrier stands between any two phases.  No workgroup waits for another and nothing is atomic:
+// the kernel boundary orders the index words' -1 before their rows and the totals before their sum.
+// ------------------------------------------------------------------------------------------
+namespace mask {
+
+constexpr int kUnit = 16;                    // positions per thread and tile
+constexpr int kTile = kThreads * kUnit;      // positions per tile
+constexpr int kSteps = 8;                    // log2(kThreads)
+constexpr int kLds = 2 * kThreads;           // two rows of thread counts (4-byte words)
+constexpr uint64_t kMaxRows = 1ull << 24;
+static_assert((1 << kSteps) == kThreads, "the doubling scan covers the workgroup");
+
+struct Args {
+  const uint8_t* mask;  // N bytes, any alignment
+  uint64_t n;           // rows
+  uint32_t shift;       // the mask's address mod 16
+  uint32_t one_list;    // 1: the last tile writes the sample's offsets [0, K]
+  uint8_t* index;       // N int32 words
+  uint8_t* counts;      // N + 1 int32 words: C
+  uint8_t* totals;      // one int32 word per tile
+  uint8_t* offsets;     // the sample's offsets buffer (one_list)
+};
+
+DORA_HD uint64_t tiles_for(uint64_t n, uint32_t shift) {
+  return n ? (n + shift + kTile - 1) / kTile : 0;
+}
+DORA_HD uint64_t tiles(const Args& a) { return tiles_for(a.n, a.shift); }
+
+// The workspace of a mask plan behind a sample of `size` bytes: 4-byte words from the first
+// multiple of 4 at or past `size` — the index, C, the totals and `part` words of a host
+// partition's offsets.  Offsets from the sample's start; `end` is what the destination must hold.
+struct Workspace {
+  uint64_t index, counts, totals, part, end;
+};
+DORA_HD Workspace workspace(uint64_t size, uint64_t n, uint64_t part_words) {
+  Workspace w{};
+  w.index = (size + 3) & ~uint64_t(3);
+  w.counts = w.index + 4 * n;
+  w.totals = w.counts + 4 * (n + 1);
+  w.part = w.totals + 4 * tiles_for(n, 15);  // (whatever the mask's alignment turns out to be)
+  w.end = w.part + 4 * part_words;
+  return w;
+}
+
+DORA_HD Args make_args(const uint8_t* mask, uint64_t n, uint8_t* dst, const Workspace& w,
+                       bool one_list) {
+  Args a{};
+  a.mask = mask;
+  a.n = n;
+  a.shift = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(mask) & 15);
+  a.one_list = one_list ? 1 : 0;
+  a.index = dst + w.index;
+  a.counts = dst + w.counts;
+  a.totals = dst + w.totals;
+  a.offsets = dst;
+  return a;
+}
+
+// Bit j: byte j of the unit is not zero.
+DORA_HD uint32_t nonzero_bytes(const U16& u) {
+  uint32_t f = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    uint32_t t = u.w[k];
+    t |= t >> 4;
+    t |= t >> 2;
+    t |= t >> 1;
+    t &= 0x01010101u;
+    f |= ((t & 1) | ((t >> 7) & 2) | ((t >> 14) & 4) | ((t >> 21) & 8)) << (4 * k);
+  }
+  return f;
+}
+
+// Whether position v is a row; then v - shift is the row.
+DORA_HD bool live(const Args& a, uint64_t v) { return v >= a.shift && v < a.n + a.shift; }
+
+// The thread's unit of the tile: bit j set where position first + j is a selected row.
+template <class M>
+DORA_HD uint32_t unit_flags(const Args& a, uint64_t tile, uint32_t thread, M& m) {
+  const uint64_t first = tile * kTile + static_cast<uint64_t>(thread) * kUnit;
+  if (first >= a.n + a.shift || first + kUnit <= a.shift) return 0;
+  if (first >= a.shift && first + kUnit <= a.n + a.shift) return nonzero_bytes(m.load16(first));
+  uint32_t f = 0;
+  for (int j = 0; j < kUnit; ++j) {
+    const uint64_t v = first + static_cast<uint64_t>(j);
+    if (live(a, v) && m.load_byte(v - a.shift)) f |= 1u << j;
+  }
+  return f;
+}
+
+DORA_HD uint32_t popcount(uint32_t f) { return static_cast<uint32_t>(__builtin_popcount(f)); }
+
+// One halving step of a sum over row 0 of the LDS buffer: after kSteps of them slot 0 is the sum.
+template <class M>
+DORA_HD void reduce_phase(uint32_t thread, int step, M& m) {
+  const uint32_t d = static_cast<uint32_t>(kThreads) >> (step + 1);
+  if (thread < d) m.lds_write(thread, m.lds_read(thread) + m.lds_read(thread + d));
+}
+
+template <class M>
+DORA_HD void count_load(const Args& a, uint64_t tile, uint32_t thread, M& m) {
+  m.lds_write(thread, popcount(unit_flags(a, tile, thread, m)));
+#pragma unroll
+  for (int j = 0; j < kUnit; ++j) {
+    const uint64_t v = tile * kTile + static_cast<uint64_t>(j) * kThreads + thread;
+    if (live(a, v)) m.store_index(v - a.shift, -1);
+  }
+}
+
+template <class M>
+DORA_HD void count_store(const Args&, uint64_t tile, uint32_t thread, M& m) {
+  if (thread == 0) m.store_total(tile, m.lds_read(0));
+}
+
+template <class M>
+DORA_HD void carry_load(const Args&, uint64_t tile, uint32_t thread, M& m) {
+  uint32_t s = 0;  // (at most N <= 2^24 in all)
+  for (uint64_t i = thread; i < tile; i += kThreads) s += m.load_total(i);
+  m.lds_write(thread, s);
+}
+
+template <class M>
+DORA_HD uint32_t carry_read(M& m) { return m.lds_read(0); }
+
+template <class M>
+DORA_HD uint32_t scan_load(const Args& a, uint64_t tile, uint32_t thread, M& m) {
+  const uint32_t f = unit_flags(a, tile, thread, m);
+  m.lds_write(thread, popcount(f));
+  return f;
+}
+
+// Step `step` of the doubling scan over the thread counts: row (step & 1) -> the other row.
+template <class M>
+DORA_HD void scan_step(uint32_t thread, int step, M& m) {
+  const uint32_t from = static_cast<uint32_t>(step & 1) * kThreads, to = kThreads - from;
+  const uint32_t d = 1u << step;
+  uint32_t v = m.lds_read(from + thread);
+  if (thread >= d) v += m.lds_read(from + thread - d);
+  m.lds_write(to + thread, v);
+}
+
+// After kSteps steps (an even number) the inclusive counts are back in row 0.
+template <class M>
+DORA_HD void scan_store(const Args& a, uint64_t tile, uint32_t thread, uint32_t f, uint32_t carry,
+                        M& m) {
+  static_assert(kSteps % 2 == 0, "the counts end in row 0");
+  const uint32_t before = carry + (thread ? m.lds_read(thread - 1) : 0);
+  const uint64_t first = tile * kTile + static_cast<uint64_t>(thread) * kUnit;
+#pragma unroll
+  for (int j = 0; j < kUnit; ++j) {
+    const uint64_t v = first + static_cast<uint64_t>(j);
+    if (!live(a, v)) continue;
+    const uint64_t row = v - a.shift;
+    const uint32_t c = before + popcount(f & ((1u << j) - 1));  // < N: a scatter position
+    m.store_count(row, c);
+    if ((f >> j) & 1) m.store_index(c, static_cast<int32_t>(row));
+  }
+  if (tile + 1 == tiles(a) && thread == static_cast<uint32_t>(kThreads) - 1) {
+    const uint32_t k = carry + m.lds_read(kThreads - 1);
+    m.store_count(a.n, k);
+    if (a.one_list) {
+      m.store_offset(0, 0);
+      m.store_offset(1, k);
+    }
+  }
+}
+
+}  // namespace mask
+
+// ------------------------------------------------------------------------------------------
 // A field converted on the way (one more field kind, run by gather_cast_kernel only): the rows
 // body restated per element, source elements of one type read, converted and written as float16
 // or float32.  Only the arguments live here, where multi::Field needs them; the body is
@@ -730,6 +920,9 @@ struct Args {
   Field f[kMaxFields];
   scan::Args scan;  // src null: no scan share, wg_begin[0] == 0
   take::Index take; // the index of the kRowsTaken fields (all or none of a launch's fields)
+  // a mask plan's launch (mask:: above): the counts C[0..n] its scan share's words are looked up
+  // in on their way into the sample (o -> C[o], o <= n already); null for every other launch
+  const uint8_t* lookup;
 };
 static_assert(sizeof(Args) <= 4096, "multi::Args is passed by value: the kernel-argument limit");
 

@@ -309,6 +309,7 @@ struct ScanMem {
   uint8_t* dst;
   uint64_t* lds;
   uint32_t wide;
+  const uint8_t* lookup;  // a mask plan's counts C: the word stored is C[v] (null: v itself)
   __device__ __forceinline__ int64_t load_word(uint64_t i) const {
     return wide ? reinterpret_cast<const int64_t*>(src)[i]
                 : static_cast<int64_t>(reinterpret_cast<const int32_t*>(src)[i]);
@@ -316,6 +317,7 @@ struct ScanMem {
   __device__ __forceinline__ void lds_write(uint32_t i, uint64_t v) const { lds[i] = v; }
   __device__ __forceinline__ uint64_t lds_read(uint32_t i) const { return lds[i]; }
   __device__ __forceinline__ void store_word(uint64_t i, uint32_t v) const {
+    if (lookup) v = reinterpret_cast<const uint32_t*>(lookup)[v];
     st4<2>(dst + 4 * i, v);
   }
 };
@@ -323,9 +325,10 @@ struct ScanMem {
 // The whole scan share, run by one workgroup: tile by tile with the carry in a register of every
 // thread (gather_device.h scan::).  The barrier that ends a tile keeps the next tile's totals out
 // of row 0 until every thread has read this tile's.
-__device__ __forceinline__ void scan_share(const gather::scan::Args& a, uint64_t* lds) {
+__device__ __forceinline__ void scan_share(const gather::scan::Args& a, uint64_t* lds,
+                                           const uint8_t* lookup) {
   namespace sc = gather::scan;
-  ScanMem m{a.src, a.dst, lds, a.wide};
+  ScanMem m{a.src, a.dst, lds, a.wide, lookup};
   sc::head(a, threadIdx.x, m);
   uint64_t carry = 0;
   const uint64_t nt = sc::tiles(a);
@@ -428,7 +431,7 @@ __device__ __forceinline__ void struct_share(const gather::multi::Args& a, uint6
   const uint32_t w = blockIdx.x;
   if constexpr (!kCast) {
     if (w < a.wg_begin[0]) {
-      scan_share(a.scan, lds);
+      scan_share(a.scan, lds, a.lookup);
       return;
     }
   }
@@ -478,6 +481,95 @@ __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather:
 __global__ __launch_bounds__(gather::kThreads) void gather_cast_kernel(gather::multi::Args a) {
   __shared__ uint64_t lds[gather::tile::kLds];
   struct_share<true>(a, lds);
+}
+
+// The mask kernels' memory (gather_device.h mask::): the mask with one aligned 16-byte
+// non-temporal load per thread (each byte is read once by each kernel) or byte by byte at its
+// head and tail; the thread counts in LDS; the workspace's index, counts and totals with plain
+// stores and loads, which the kernel boundary orders for the launch that follows; the sample's
+// own two offsets with the pack's write-through stores.
+struct MaskMem {
+  const uint8_t* mask;
+  const uint8_t* line;  // mask - shift: the 16-byte line the mask starts in
+  uint8_t* index;
+  uint8_t* counts;
+  uint8_t* totals;
+  uint8_t* offsets;
+  uint32_t* lds;
+  __device__ __forceinline__ gather::U16 load16(uint64_t v) const {
+    const u32x4 x = ld16<1, false>(line + v);
+    return {{x.x, x.y, x.z, x.w}};
+  }
+  __device__ __forceinline__ uint8_t load_byte(uint64_t row) const { return mask[row]; }
+  __device__ __forceinline__ void lds_write(uint32_t i, uint32_t v) const { lds[i] = v; }
+  __device__ __forceinline__ uint32_t lds_read(uint32_t i) const { return lds[i]; }
+  __device__ __forceinline__ void store_index(uint64_t i, int32_t v) const {
+    reinterpret_cast<int32_t*>(index)[i] = v;
+  }
+  __device__ __forceinline__ void store_count(uint64_t i, uint32_t v) const {
+    reinterpret_cast<uint32_t*>(counts)[i] = v;
+  }
+  __device__ __forceinline__ void store_total(uint64_t t, uint32_t v) const {
+    reinterpret_cast<uint32_t*>(totals)[t] = v;
+  }
+  __device__ __forceinline__ uint32_t load_total(uint64_t t) const {
+    return reinterpret_cast<const uint32_t*>(totals)[t];
+  }
+  __device__ __forceinline__ void store_offset(uint64_t i, uint32_t v) const {
+    st4<2>(offsets + 4 * i, v);
+  }
+};
+
+__device__ __forceinline__ MaskMem mask_mem(const gather::mask::Args& a, uint32_t* lds) {
+  return MaskMem{a.mask, a.mask - a.shift, a.index, a.counts, a.totals, a.offsets, lds};
+}
+
+// mask_count_kernel: every tile's count of selected rows into totals[tile], its index words -1.
+__global__ __launch_bounds__(gather::kThreads) void mask_count_kernel(gather::mask::Args a) {
+  namespace mk = gather::mask;
+  __shared__ uint32_t lds[mk::kLds];
+  MaskMem m = mask_mem(a, lds);
+  const uint64_t nt = mk::tiles(a);
+  for (uint64_t t = blockIdx.x; t < nt; t += gridDim.x) {
+    mk::count_load(a, t, threadIdx.x, m);
+    __syncthreads();
+#pragma unroll
+    for (int step = 0; step < mk::kSteps; ++step) {
+      mk::reduce_phase(threadIdx.x, step, m);
+      __syncthreads();
+    }
+    mk::count_store(a, t, threadIdx.x, m);
+    __syncthreads();  // slot 0 is read before the next tile's counts land
+  }
+}
+
+// mask_compact_kernel: every tile's rows scanned behind the sum of the totals before it: the
+// counts C and the selected rows' numbers, in source order, into the index.
+__global__ __launch_bounds__(gather::kThreads) void mask_compact_kernel(gather::mask::Args a) {
+  namespace mk = gather::mask;
+  __shared__ uint32_t lds[mk::kLds];
+  MaskMem m = mask_mem(a, lds);
+  const uint64_t nt = mk::tiles(a);
+  for (uint64_t t = blockIdx.x; t < nt; t += gridDim.x) {
+    mk::carry_load(a, t, threadIdx.x, m);
+    __syncthreads();
+#pragma unroll
+    for (int step = 0; step < mk::kSteps; ++step) {
+      mk::reduce_phase(threadIdx.x, step, m);
+      __syncthreads();
+    }
+    const uint32_t carry = mk::carry_read(m);
+    __syncthreads();
+    const uint32_t f = mk::scan_load(a, t, threadIdx.x, m);
+    __syncthreads();
+#pragma unroll
+    for (int step = 0; step < mk::kSteps; ++step) {
+      mk::scan_step(threadIdx.x, step, m);
+      __syncthreads();
+    }
+    mk::scan_store(a, t, threadIdx.x, f, carry, m);
+    __syncthreads();
+  }
 }
 
 unsigned grid_for(uint64_t items) {
@@ -685,12 +777,21 @@ int check_device_range(const GatherDesc& g, int device) {
 }
 
 int check_plan_range(const dora_plan& plan, int device) {
-  if (plan.scan_on && plan.scan.count) {
-    // a ragged batch's partition in HBM: its words like any field
+  if (plan.scan_on && plan.scan.count && !(plan.masked && plan.mask.part_words)) {
+    // a ragged batch's partition in HBM: its words like any field (a mask plan's host partition
+    // is in the plan itself: its scan reads the copy in the workspace)
     const int rc = check_device_range(plan.scan.reach, device);
     if (rc != DORA_OK) {
       const std::string why = dora_gpu_last_error();
       return fail(rc, "partition: %s", why.c_str());
+    }
+  }
+  if (plan.masked) {
+    // a mask in HBM: its N bytes like any field
+    const int rc = check_device_range(mask_reach(plan.mask), device);
+    if (rc != DORA_OK) {
+      const std::string why = dora_gpu_last_error();
+      return fail(rc, "mask: %s", why.c_str());
     }
   }
   if (plan.take_on && plan.take.count) {
@@ -703,7 +804,7 @@ int check_plan_range(const dora_plan& plan, int device) {
     if (plan.take.n == 0) return DORA_OK;  // rows of zeros: no field is read
   }
   if (plan.fields.empty())
-    return plan.list || plan.taken ? DORA_OK : check_device_range(plan.gd, device);
+    return plan.list || plan.taken || plan.masked ? DORA_OK : check_device_range(plan.gd, device);
   for (size_t k = 0; k < plan.fields.size(); ++k) {
     const int rc = check_device_range(plan.fields[k].gd, device);
     if (rc == DORA_OK) continue;
@@ -770,7 +871,7 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEven
 
 int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
                          hipEvent_t ev_start, hipEvent_t ev_stop, const ScanDesc* scan,
-                         const TakeDesc* take) {
+                         const TakeDesc* take, const uint8_t* lookup) {
   if ((n == 0 && !scan) || n > size_t(gather::multi::kMaxFields))
     return fail(DORA_ERR_INVALID, "gather of %zu struct fields", n);
   if (scan && (scan->count > kMaxScanEntries || (reinterpret_cast<uintptr_t>(dst) & 3) ||
@@ -794,9 +895,10 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
     // each field as it would go on its own; a taken field always the rows body
     tile_c[k] = take ? -1 : select_tile_dim(g[k], dst + off[k]);
   }
-  const gather::multi::Args a =
+  gather::multi::Args a =
       take ? gather::multi::make_taken_args(g, stride0, off, static_cast<int>(n), dst, *take, scan)
            : gather::multi::make_args(g, off, tile_c, static_cast<int>(n), dst, scan);
+  a.lookup = lookup;
   const dim3 grid(gather::multi::grid_for(a));
   if (ev_start || ev_stop) {
     hipExtLaunchKernelGGL(gather_struct_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
@@ -851,8 +953,55 @@ int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStrea
   return DORA_OK;
 }
 
+uint64_t plan_workspace(const dora_plan& plan) {
+  if (!plan.masked || !plan.gather) return 0;
+  return gather::mask::workspace(plan.size, plan.mask.n, plan.mask.part_words).end - plan.size;
+}
+
+// A mask plan's three launches on `stream`: count, compact, then the fields through the taken
+// body by the workspace's index (with the scan share when the message has a partition, its words
+// looked up in C).  The workspace follows the sample in `dst` (mask::workspace).
+int launch_mask(const dora_plan& plan, uint8_t* dst, hipStream_t stream, hipEvent_t ev_start,
+                hipEvent_t ev_stop) {
+  namespace mk = gather::mask;
+  const MaskDesc& md = plan.mask;
+  if (!md.n || md.n > mk::kMaxRows || (reinterpret_cast<uintptr_t>(dst) & 3))
+    return fail(DORA_ERR_INVALID, "mask of %llu rows into %p: 1 to %llu rows, the sample on a "
+                "multiple of 4", static_cast<unsigned long long>(md.n), static_cast<void*>(dst),
+                static_cast<unsigned long long>(mk::kMaxRows));
+  const mk::Workspace w = mk::workspace(plan.size, md.n, md.part_words);
+  const mk::Args a = mk::make_args(md.src, md.n, dst, w, !plan.scan_on);
+  const dim3 grid(static_cast<unsigned>(mk::tiles(a)));
+  if (ev_start) {
+    hipExtLaunchKernelGGL(mask_count_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
+                          nullptr, 0, a);
+  } else {
+    hipLaunchKernelGGL(mask_count_kernel, grid, dim3(gather::kThreads), 0, stream, a);
+  }
+  DORA_HIP(hipGetLastError());
+  hipLaunchKernelGGL(mask_compact_kernel, grid, dim3(gather::kThreads), 0, stream, a);
+  DORA_HIP(hipGetLastError());
+  TakeDesc take{};
+  take.src = a.index;
+  take.count = md.n;
+  take.n = md.n;
+  take.wide = 0;
+  ScanDesc scan = plan.scan;
+  if (plan.scan_on && md.part_words) {
+    // a host partition: its checked offsets, which the prefix copy has put into the workspace
+    scan.src = dst + w.part;
+    scan.count = md.part_words;
+    scan.wide = 0;
+    scan.offsets = 1;
+  }
+  return launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, nullptr,
+                              ev_stop, plan.scan_on ? &scan : nullptr, &take,
+                              plan.scan_on ? a.counts : nullptr);
+}
+
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (plan.masked) return launch_mask(plan, dst, stream, ev_start, ev_stop);
   if (plan.cast)
     return launch_gather_cast(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
                               ev_stop);
@@ -1055,6 +1204,10 @@ int launch_fill_ticket(void* dst, size_t len, uint64_t seed, const dora_fill_tic
 
 extern "C" {
 
+size_t dora_gpu_plan_workspace_size(const dora_plan* plan) {
+  return plan ? static_cast<size_t>(dora::plan_workspace(*plan)) : 0;
+}
+
 int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_t stream) {
   if (!plan) return dora::fail(DORA_ERR_INVALID, "plan is NULL");
   if (dst_len < plan->size)
@@ -1063,6 +1216,11 @@ int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_
                       "target buffer too small (total_len: %zu, required_len: %llu)", dst_len,
                       static_cast<unsigned long long>(plan->size));
   if (plan->segs.empty() && !plan->gather) return DORA_OK;
+  if (plan->masked && dst_len - plan->size < dora::plan_workspace(*plan))
+    return dora::fail(DORA_ERR_INVALID, "a mask plan's target holds the sample and its workspace "
+                      "(total_len: %zu, sample: %llu, workspace: %llu): nothing was launched",
+                      dst_len, static_cast<unsigned long long>(plan->size),
+                      static_cast<unsigned long long>(dora::plan_workspace(*plan)));
   if (!dst) return dora::fail(DORA_ERR_INVALID, "dst is NULL");
   if (plan->dev_tensor) {
     // a device tensor view: inside one allocation of the current GPU before anything reads it

@@ -172,8 +172,11 @@ void wait_for_send_credit(dora_node* n, uint64_t len) {
 // `host_inline`: the sample will be written by the host (a host-resident source), so below the
 // zero-copy threshold it takes the reference's inline `DataMessage::Vec` (mod.rs:303-319) on a
 // device node too: no slot, no H2D copy, no fill signal.
+// `workspace`: scratch bytes of the fill's launches behind the sample (a mask plan's): the slot
+// holds them, the sample's lengths — what the descriptor names and anything downstream moves — do
+// not.
 int alloc_sample(dora_node* n, uint64_t len, dora_sample** out, uint64_t ext_len = 0,
-                 bool host_inline = false) {  // mod.rs:303-319
+                 bool host_inline = false, uint64_t workspace = 0) {  // mod.rs:303-319
   if (n->core->device < 0 && len >= kZeroCopyThreshold) {
     // host-only node: a POSIX shared-memory slot (the reference's allocate_shared_memory)
     auto* s = new dora_sample();
@@ -218,7 +221,7 @@ int alloc_sample(dora_node* n, uint64_t len, dora_sample** out, uint64_t ext_len
     sp_wait.stop();
     s->ext_len = std::max(len, ext_len);
     SubSpan sp_slot(SP_ALLOC_SLOT);
-    int rc = allocate_slot(n, s->ext_len, &s->slot);
+    int rc = allocate_slot(n, s->ext_len + workspace, &s->slot);
     if (rc != DORA_OK) {
       delete s;
       return rc;
@@ -629,7 +632,8 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
       clear_error();
     }
   }
-  int rc = s ? DORA_OK : alloc_sample(n, plan->size, &s, plan->fill_size(), host_src);
+  int rc = s ? DORA_OK
+             : alloc_sample(n, plan->size, &s, plan->fill_size(), host_src, plan_workspace(*plan));
   if (rc != DORA_OK) return rc;
   const uint64_t t1 = mono_ns();
   uint64_t t2 = t1, t3 = t1;
@@ -1085,6 +1089,25 @@ int dora_node_send_output_tensor_take(dora_node* n, const char* output_id,
   // a host index: the taken rows are in the plan's staging buffer, a host plan like any other; a
   // device index: a gather plan, which goes where the struct and list sends' gathers go, the index
   // one more source its launch reads
+  std::unique_ptr<dora_plan> owner(plan);
+  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
+  DORA_GUARD_END
+}
+
+int dora_node_send_output_tensor_mask(dora_node* n, const char* output_id,
+                                      const dora_tensor_mask* mask, ArrowDeviceType device_type,
+                                      const uint8_t* params, size_t params_len, uint32_t flags) {
+  if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  dora_plan* plan = nullptr;
+  {
+    dora::SubSpan sp(dora::SP_SEND_PLAN);
+    const int rc = dora::build_tensor_mask_plan(mask, device_type, &plan);
+    if (rc != DORA_OK) return rc;
+  }
+  // a host mask: the compacted rows are in the plan's staging buffer, a host plan like any other;
+  // a device mask: a gather plan, which goes where the take's goes, its slot allocated with the
+  // workspace behind the sample
   std::unique_ptr<dora_plan> owner(plan);
   return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
   DORA_GUARD_END

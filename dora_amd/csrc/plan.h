@@ -149,6 +149,28 @@ inline GatherDesc take_reach(const TakeDesc& t) {
   return r;
 }
 
+// The mask of a mask plan (dora_gpu_plan_tensor_mask) when it lives in HBM: `n` dense bytes at
+// `src`, any alignment, never read on the host; any non-zero byte selects its row.  `part_words`:
+// the B + 1 checked offsets of a host partition, which travel in the plan's prefix into the
+// workspace behind the sample, where the launch's scan share reads them (0: no partition, or one
+// in HBM).  mask_reach is what check_plan_range holds against the allocation of `src`.
+struct MaskDesc {
+  const uint8_t* src;
+  uint64_t n;
+  uint64_t part_words;
+};
+static_assert(sizeof(MaskDesc) <= sizeof(GatherDesc), "a plan holds either in one place");
+inline GatherDesc mask_reach(const MaskDesc& m) {
+  GatherDesc r{};
+  r.view.src = m.src;
+  r.view.total = m.n;
+  r.view.row = m.n;
+  r.elem = 1;
+  r.lo = 0;
+  r.hi = static_cast<int64_t>(m.n) - 1;
+  return r;
+}
+
 // The partition of a ragged-batch plan (dora_gpu_plan_tensor_list) when it lives in HBM: `count`
 // dense words of 4 or 8 bytes at `src` (B lengths, or B + 1 offsets), never read on the host.  One
 // workgroup of the plan's launch scans them into the sample's B + 1 int32 offsets, every one
@@ -221,9 +243,12 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream,
 // of the same launch writes the sample's offsets at dst + 0 (dst a whole number of dwords).
 // With `take` (a take plan) every field goes through the taken body: row i0 of its bytes is row
 // take->src[i0] of the field, or zeros where that word is not in [0, take->n).
+// With `lookup` (a mask plan: scan->n + 1 int32 counts in HBM) the scan share stores lookup[o]
+// where it would store the offset o.
 int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
                          hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                         const ScanDesc* scan = nullptr, const TakeDesc* take = nullptr);
+                         const ScanDesc* scan = nullptr, const TakeDesc* take = nullptr,
+                         const uint8_t* lookup = nullptr);
 // The host-source segments a device plan carries beside what its kernel reads (a ragged batch's
 // offsets computed in the plan): copied into `dst` on `stream`, ahead of the pack or gather that
 // follows on the same stream.  The bytes are pageable memory of the plan: the runtime has staged
@@ -236,7 +261,9 @@ int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
 int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // The gather a gather plan asks for: launch_gather of its view, or launch_gather_struct of its
-// fields (with the scan of a ragged batch's device partition, by the index of a take).
+// fields (with the scan of a ragged batch's device partition, by the index of a take); for a
+// mask plan the two compaction launches and then the fields by the index they wrote, `dst` then
+// holding the sample and plan_workspace bytes behind it.
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
@@ -270,6 +297,11 @@ int build_tensor_struct_plan(const dora_tensor_field* fields, size_t n, ArrowDev
 int build_tensor_list_plan(const dora_tensor_list* list, ArrowDeviceType dev, dora_plan** out);
 // Rows taken by an index, as a tensor, a record or a ragged batch (dora_gpu_plan_tensor_take).
 int build_tensor_take_plan(const dora_tensor_take* take, ArrowDeviceType dev, dora_plan** out);
+// Rows selected by a mask of N bytes, as one List message (dora_gpu_plan_tensor_mask).
+int build_tensor_mask_plan(const dora_tensor_mask* mask, ArrowDeviceType dev, dora_plan** out);
+// Bytes a mask plan's launches need behind the sample (dora_gpu_plan_workspace_size); 0 for
+// every other plan (kernels.hip).
+uint64_t plan_workspace(const dora_plan& plan);
 // Tensors converted to float16 / float32 on send, bare or as a record (dora_gpu_plan_tensor_cast).
 int build_tensor_cast_plan(const dora_tensor_field* fields, size_t n, const dora_tensor_cast* casts,
                            ArrowDeviceType dev, dora_plan** out);
@@ -301,11 +333,16 @@ struct dora_plan {
   // cast plans (tensor_plan.cpp) with device values: a gather whose fields, a bare tensor's one
   // included, go through gather_cast_kernel (a host cast plan is converted in `staged`)
   bool cast = false;
+  // mask plans (tensor_plan.cpp) with device values: a gather without segments whose launches
+  // compact `mask` into a workspace behind the sample and read every field through it (host
+  // values: an ordinary host plan, compacted in `staged`)
+  bool masked = false;
   // (a plan reads one view, `gd`, or the fields of a record, by the index `take` if it is a take
   // plan: never both, and a plan of any other kind stays the size it was)
   union {
     dora::GatherDesc gd{};
     dora::TakeDesc take;
+    dora::MaskDesc mask;
   };
   // struct-of-tensors plans (dev_tensor): one entry per field instead of `gd`; with `gather`,
   // gather_struct_kernel reads all of them in one launch (a multi-gather plan), else `segs` does

@@ -587,10 +587,18 @@ PyObject* py_send_tensor_list(PyObject*, PyObject* const* args, Py_ssize_t nargs
 // dora_node_send_output_tensor_take.  `names` / `capsules` as send_tensor_list takes them; `index`
 // a "dltensor" capsule of the 1-D row numbers; `partition` one of lengths or offsets over the
 // taken rows, or None (no lists).  Every capsule is consumed as send_tensor_list consumes its own.
-PyObject* py_send_tensor_take(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
-  const char* usage = "send_tensor_take(handle, output_id, names, capsules, index, index_device, "
-                      "partition, form, partition_device, device_type, metadata, flags): names is "
-                      "None over one capsule or a tuple as long as the tuple of capsules";
+//
+// send_tensor_masked takes the same twelve arguments with the mask (a "dltensor" capsule of the N
+// bool or uint8 elements) and its device where the index and its device are, the partition over
+// the N source rows, and sends as dora_node_send_output_tensor_mask.
+PyObject* send_selected(PyObject* const* args, Py_ssize_t nargs, bool masked) {
+  const char* usage = masked
+      ? "send_tensor_masked(handle, output_id, names, capsules, mask, mask_device, "
+        "partition, form, partition_device, device_type, metadata, flags): names is "
+        "None over one capsule or a tuple as long as the tuple of capsules"
+      : "send_tensor_take(handle, output_id, names, capsules, index, index_device, "
+        "partition, form, partition_device, device_type, metadata, flags): names is "
+        "None over one capsule or a tuple as long as the tuple of capsules";
   if (nargs != 12 || !PyTuple_Check(args[3]) ||
       !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
                            : PyTuple_Check(args[2]) &&
@@ -621,7 +629,7 @@ PyObject* py_send_tensor_take(PyObject*, PyObject* const* args, Py_ssize_t nargs
                                       "unused, unversioned one)", k);
       else
         PyErr_Format(PyExc_TypeError, "%s: expected a DLPack capsule named \"dltensor\" (an "
-                                      "unused, unversioned one)", k == n ? "index" : "partition");
+                                      "unused, unversioned one)", k == n ? (masked ? "mask" : "index") : "partition");
       return nullptr;
     }
     for (size_t j = 0; j < k; ++j)
@@ -642,6 +650,7 @@ PyObject* py_send_tensor_take(PyObject*, PyObject* const* args, Py_ssize_t nargs
   std::string& params = t_params;
   if (!encode(args[10], params)) return nullptr;
   dora_tensor_take take{};
+  dora_tensor_mask mask{};
   dora_tensor partition{};
   std::vector<DlManaged*> managed(caps.size());
   for (size_t k = 0; k < caps.size(); ++k) {
@@ -653,7 +662,7 @@ PyObject* py_send_tensor_take(PyObject*, PyObject* const* args, Py_ssize_t nargs
       return nullptr;
     }
     managed[k] = m;
-    dora_tensor& t = k < n ? fields[k].tensor : k == n ? take.index : partition;
+    dora_tensor& t = k < n ? fields[k].tensor : k == n ? (masked ? mask.mask : take.index) : partition;
     t = dora_tensor{};
     t.data = m->t.data;
     t.byte_offset = m->t.byte_offset;
@@ -670,17 +679,37 @@ PyObject* py_send_tensor_take(PyObject*, PyObject* const* args, Py_ssize_t nargs
   take.partition = lists ? &partition : nullptr;
   take.partition_form = static_cast<uint32_t>(num[1]);
   take.partition_device = static_cast<ArrowDeviceType>(num[2]);
+  mask.fields = fields.data();
+  mask.n = n;
+  mask.mask_device = take.index_device;
+  mask.partition = take.partition;
+  mask.partition_form = take.partition_form;
+  mask.partition_device = take.partition_device;
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  rc = dora_node_send_output_tensor_take(static_cast<dora_node*>(h), oid, &take,
-                                         static_cast<ArrowDeviceType>(num[3]),
-                                         reinterpret_cast<const uint8_t*>(params.data()),
-                                         params.size(), static_cast<uint32_t>(flags));
+  if (masked)
+    rc = dora_node_send_output_tensor_mask(static_cast<dora_node*>(h), oid, &mask,
+                                           static_cast<ArrowDeviceType>(num[3]),
+                                           reinterpret_cast<const uint8_t*>(params.data()),
+                                           params.size(), static_cast<uint32_t>(flags));
+  else
+    rc = dora_node_send_output_tensor_take(static_cast<dora_node*>(h), oid, &take,
+                                           static_cast<ArrowDeviceType>(num[3]),
+                                           reinterpret_cast<const uint8_t*>(params.data()),
+                                           params.size(), static_cast<uint32_t>(flags));
   Py_END_ALLOW_THREADS
   // (deleters under the GIL and after the status has been taken, as in send_tensor)
   for (DlManaged* m : managed)
     if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
+}
+
+PyObject* py_send_tensor_take(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  return send_selected(args, nargs, false);
+}
+
+PyObject* py_send_tensor_masked(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  return send_selected(args, nargs, true);
 }
 
 // MetadataParameters bytes -> dict (the inverse of encode; dora_amd.node.decode_parameters).
@@ -1150,6 +1179,9 @@ PyMethodDef methods[] = {
     {"send_tensor_take",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_take)),
      METH_FASTCALL, "dora_node_send_output_tensor_take of DLPack capsules, which it consumes."},
+    {"send_tensor_masked",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_masked)),
+     METH_FASTCALL, "dora_node_send_output_tensor_mask of DLPack capsules, which it consumes."},
     {"send_array", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_array)),
      METH_FASTCALL, "dora_node_send_output with parameters encoded from a dict."},
     {nullptr, nullptr, 0, nullptr}};

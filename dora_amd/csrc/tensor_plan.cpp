@@ -656,6 +656,46 @@ int place_taken(dora_plan& p, const TakeIn& tk, uint64_t rows, uint64_t staged) 
   return DORA_OK;
 }
 
+// The mask of a mask plan as its builder sees it: N bytes, on the host or in HBM.  `one_list`: the
+// caller gave no partition (the builder was handed the one list of all N rows in its place).
+struct MaskIn {
+  const uint8_t* src = nullptr;
+  uint64_t count = 0;
+  bool device = false;
+  bool one_list = false;
+};
+
+// Host values under a host mask (N > 0, after layout_fields with `taken` = N): the CPU reads the
+// mask, gathers the selected rows of every field to the front of the field's N rows in the
+// staging buffer (the rest stays zero) and replaces the checked offsets p_b by C[p_b]: the
+// segments of an ordinary host plan.
+void place_masked_host(dora_plan& p, const MaskIn& mk, uint64_t staged) {
+  const uint64_t n = mk.count;
+  std::vector<int32_t> c(n + 1);
+  int32_t k = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    c[i] = k;
+    k += mk.src[i] != 0;
+  }
+  c[n] = k;
+  for (int32_t& o : p.list_offsets) o = c[static_cast<size_t>(o)];
+  p.staged.assign(staged, 0);
+  uint64_t at = 0;
+  for (const PlanField& pf : p.fields) {
+    StridedView one = pf.gd.view;  // one row: dimensions 1..
+    one.total = pf.bytes / n;
+    uint64_t j = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (!mk.src[i]) continue;
+      one.src = pf.gd.view.src + static_cast<int64_t>(i) * pf.stride0;
+      gather_host(one, p.staged.data() + at + j++ * one.total);
+    }
+    p.segs.push_back({p.staged.data() + at, pf.dst_off, pf.bytes});
+    at += pf.bytes;
+  }
+  p.fields.clear();
+}
+
 // A tensor (`bare`: one field without a name) or a record of tensors as one message; with `tk`
 // the rows of it that the index takes.
 int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
@@ -849,8 +889,11 @@ int host_offsets(const Partition& pt, bool offsets_form, uint64_t rows, std::vec
 
 namespace {
 
-// A ragged batch over the fields' rows; with `tk` over the rows of them that the index takes.
-int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk, dora_plan** out) {
+// A ragged batch over the fields' rows; with `tk` over the rows of them that the index takes;
+// with `mk` (never with `tk`) over the N source rows of which the mask keeps K in front: the
+// child keeps its N rows and the offsets become C[p_b].
+int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk, dora_plan** out,
+               const MaskIn* mk = nullptr) {
   if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
   if (!known_device(l->partition_device))
     return fail(DORA_ERR_INVALID, "unsupported partition_device %d", l->partition_device);
@@ -897,9 +940,35 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
   FieldLayout lay;
   lay.off = obytes;
   std::vector<TypeInfoNode> solo;
+  // (a mask's fields are described as a take of all N rows describes them; a first field that has
+  // no shape[0] to read is refused by the layout whatever N is taken to be)
+  const dora_tensor& t0 = f[0].tensor;
+  const int64_t mask_rows = mk && t0.shape && t0.ndim >= 1 && t0.shape[0] > 0 ? t0.shape[0] : 0;
   rc = layout_fields(f, n, dev, bare, "item", *p, bare ? solo : child.children, lay,
-                     tk ? static_cast<int64_t>(tk->ix.count) : -1);
+                     tk ? static_cast<int64_t>(tk->ix.count) : mk ? mask_rows : -1);
   if (rc != DORA_OK) return rc;
+  if (mk) {
+    // (a host plan, or an empty one, keeps N and no pointer: nothing of it is launched)
+    p->masked = true;
+    p->mask.src = nullptr;
+    p->mask.n = static_cast<uint64_t>(mask_rows);
+    p->mask.part_words = 0;
+    if (mk->count != static_cast<uint64_t>(mask_rows))
+      return fail(DORA_ERR_INVALID, "mask has %llu elements, the values have %lld rows: one mask "
+                  "element per row", static_cast<unsigned long long>(mk->count),
+                  static_cast<long long>(mask_rows));
+    if (mk->count > gather::mask::kMaxRows)
+      return fail(DORA_ERR_UNSUPPORTED, "a mask over %llu rows: at most %llu (one workgroup sums "
+                  "the totals of the tiles before its own)",
+                  static_cast<unsigned long long>(mk->count),
+                  static_cast<unsigned long long>(gather::mask::kMaxRows));
+    // (a host partition's offsets are scanned on the device too, on their way through C)
+    if (dev == ARROW_DEVICE_ROCM && !dev_part && !mk->one_list && lists + 1 > kMaxScanEntries)
+      return fail(DORA_ERR_UNSUPPORTED, "a partition over masked device values has at most %llu "
+                  "offsets (%llu given): one workgroup looks them up",
+                  static_cast<unsigned long long>(kMaxScanEntries),
+                  static_cast<unsigned long long>(lists + 1));
+  }
   // the rows the partition cuts: the fields' own, or the K taken ones
   const uint64_t rows = tk ? tk->ix.count : static_cast<uint64_t>(f[0].tensor.shape[0]);
   const uint64_t src_rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
@@ -950,8 +1019,29 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
       p->segs.push_back(oseg);
       if (!empty) {
         if (tk) rc = place_taken(*p, *tk, src_rows, lay.staged);
+        else if (mk) place_masked_host(*p, *mk, lay.staged);
         else stage_host_fields(*p, dev, lay.staged);
         if (rc != DORA_OK) return rc;
+      }
+      *out = p.release();
+      return DORA_OK;
+    }
+    if (mk) {
+      // a mask in HBM: never read here.  Always the three launches, no segments; the checked
+      // offsets of a partition go ahead into the workspace, where the scan share finds them
+      p->dev_tensor = true;
+      p->gather = true;
+      p->masked = true;
+      p->mask.src = mk->src;
+      p->mask.n = rows;
+      p->mask.part_words = mk->one_list ? 0 : lists + 1;
+      if (!mk->one_list) {
+        p->scan_on = true;
+        p->scan.count = lists + 1;
+        p->scan.n = rows;
+        p->scan.offsets = 1;
+        p->prefix.push_back({p->list_offsets.data(),
+                             gather::mask::workspace(p->size, rows, lists + 1).part, obytes});
       }
       *out = p.release();
       return DORA_OK;
@@ -968,6 +1058,14 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
     p->gather = lay.strided;
     if (!lay.strided)
       for (const PlanField& pf : p->fields) p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
+    *out = p.release();
+    return DORA_OK;
+  }
+  if (mk && empty) {
+    // no rows: every offset is 0 whatever the partition holds, which is then never read
+    p->list_offsets.assign(lists + 1, 0);
+    p->dev = ARROW_DEVICE_CPU;
+    p->segs.push_back({p->list_offsets.data(), 0, obytes});
     *out = p.release();
     return DORA_OK;
   }
@@ -991,6 +1089,12 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
   if (tk && !empty) {
     rc = place_taken(*p, *tk, src_rows, lay.staged);
     if (rc != DORA_OK) return rc;
+  }
+  if (mk) {  // (the scan's words are then looked up in the counts the mask gives)
+    p->masked = true;
+    p->mask.src = mk->src;
+    p->mask.n = rows;
+    p->mask.part_words = 0;
   }
   *out = p.release();
   return DORA_OK;
@@ -1044,9 +1148,69 @@ int build_tensor_take_plan(const dora_tensor_take* t, ArrowDeviceType dev, dora_
   return build_record(t->fields, t->n, dev, t->n == 1 && !t->fields[0].name, &tk, out);
 }
 
+int build_tensor_mask_plan(const dora_tensor_mask* m, ArrowDeviceType dev, dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!m) return fail(DORA_ERR_INVALID, "mask is NULL");
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (!known_device(m->mask_device))
+    return fail(DORA_ERR_INVALID, "unsupported mask_device %d", m->mask_device);
+  if (m->n == 0 || !m->fields)
+    return fail(DORA_ERR_INVALID, "a mask has values: at least one field");
+  MaskIn mk;
+  mk.device = m->mask_device == ARROW_DEVICE_ROCM;
+  if (mk.device != (dev == ARROW_DEVICE_ROCM))
+    return fail(DORA_ERR_INVALID, "the mask is in %s memory and the values are in %s memory: "
+                "move the mask next to the values (a host mask for host values, a mask in this "
+                "node's HBM for device values)", mk.device ? "device" : "host",
+                mk.device ? "host" : "device");
+  const dora_tensor& t = m->mask;
+  if (t.dtype_lanes != 1 || t.dtype_bits != 8 || (t.dtype_code != DL_BOOL && t.dtype_code != DL_UINT))
+    return fail(DORA_ERR_INVALID, "mask dtype %s is not bool or uint8",
+                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  if (t.ndim != 1 || !t.shape)
+    return fail(DORA_ERR_INVALID, "mask has %d dimensions (a 1-D tensor, one element per row)",
+                t.ndim);
+  if (t.shape[0] < 0)
+    return fail(DORA_ERR_INVALID, "mask extent %lld is negative",
+                static_cast<long long>(t.shape[0]));
+  if (t.strides && t.shape[0] > 1 && t.strides[0] != 1)
+    return fail(DORA_ERR_INVALID, "mask stride %lld: the mask is dense",
+                static_cast<long long>(t.strides[0]));
+  if (!t.data && t.shape[0]) return fail(DORA_ERR_INVALID, "mask data is NULL");
+  mk.src = static_cast<const uint8_t*>(t.data) + t.byte_offset;
+  mk.count = static_cast<uint64_t>(t.shape[0]);
+  dora_tensor_list l{};
+  l.fields = m->fields;
+  l.n = m->n;
+  // without a partition: the one list of all N rows, whose offsets [0, N] become [0, K]
+  const int64_t all = static_cast<int64_t>(mk.count), one = 1;
+  if (m->partition) {
+    l.partition = *m->partition;
+    l.partition_form = m->partition_form;
+    l.partition_device = m->partition_device;
+  } else {
+    mk.one_list = true;
+    l.partition.data = const_cast<int64_t*>(&all);
+    l.partition.dtype_code = DL_INT;
+    l.partition.dtype_bits = 64;
+    l.partition.dtype_lanes = 1;
+    l.partition.ndim = 1;
+    l.partition.shape = &one;
+    l.partition_form = DORA_PARTITION_LENGTHS;
+    l.partition_device = ARROW_DEVICE_CPU;
+  }
+  return build_list(&l, dev, nullptr, out, &mk);
+}
+
 }  // namespace dora
 
 extern "C" {
+
+int dora_gpu_plan_tensor_mask(const dora_tensor_mask* mask, ArrowDeviceType device_type,
+                              dora_plan** out) {
+  return dora::build_tensor_mask_plan(mask, device_type, out);
+}
 
 int dora_gpu_plan_tensor(const dora_tensor* tensor, ArrowDeviceType device_type,
                          dora_plan** out) {

@@ -24,6 +24,7 @@
 #include "dora_gpu.h"
 #include "dora_gpu_testing.h"
 #include "fence_probes.h"
+#include "gather_device.h"
 #include "plan.h"
 #include "shm.h"
 
@@ -348,7 +349,7 @@ int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, s
   if (gather) *gather = plan->gather;
   if (dst_off) *dst_off = f.dst_off;
   if (bytes) *bytes = f.bytes;
-  if (kind && plan->take_on) *kind = -1;
+  if (kind && (plan->take_on || plan->masked)) *kind = -1;
   else if (kind) *kind = dora::select_tile_dim(g, static_cast<const uint8_t*>(dst) + f.dst_off);
   if (src) *src = g.view.src;
   if (nd) *nd = g.view.nd;
@@ -416,6 +417,29 @@ int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, i
   if (elements) *elements = c.on ? c.count : f.bytes / f.gd.elem;
   if (src_bytes) *src_bytes = f.gd.view.total;
   if (dst_bytes) *dst_bytes = f.bytes;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mask, uint64_t* n,
+                            int64_t* lo, int64_t* hi, uint64_t* workspace, uint64_t* part_words,
+                            int64_t* stride0) {
+  if (!plan || !plan->masked) return dora::fail(DORA_ERR_INVALID, "not a mask plan");
+  const bool dev = plan->gather;
+  const dora::MaskDesc& m = plan->mask;
+  if (device) *device = dev;
+  if (mask) *mask = dev ? m.src : nullptr;
+  if (n) *n = m.n;
+  if (lo) *lo = dev ? dora::mask_reach(m).lo : 0;
+  if (hi) *hi = dev ? dora::mask_reach(m).hi : -1;
+  if (part_words) *part_words = dev ? m.part_words : 0;
+  if (workspace) {
+    const dora::gather::mask::Workspace w =
+        dora::gather::mask::workspace(plan->size, m.n, m.part_words);
+    const uint64_t at[5] = {w.index, w.counts, w.totals, w.part, w.end};
+    for (int i = 0; i < 5; ++i) workspace[i] = dev ? at[i] : 0;
+  }
+  for (size_t i = 0; stride0 && i < dora::kMaxStructFields; ++i)
+    stride0[i] = dev && i < plan->fields.size() ? plan->fields[i].stride0 : 0;
   return DORA_OK;
 }
 

@@ -34,6 +34,7 @@ _DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinne
 from .device import DeviceArray, DeviceBuffer
 from .tensor import Cast as _Cast
 from .tensor import Ragged as _Ragged
+from .tensor import Masked as _Masked
 from .tensor import Taken as _Taken
 from .type_info import decode
 
@@ -244,11 +245,14 @@ class Node:
             rc = self._send_ragged(output_id, data, metadata, f)
         elif isinstance(data, _Taken):
             rc = self._send_take(output_id, data, None, metadata, f)
+        elif isinstance(data, _Masked):
+            rc = self._send_tensor_masked(output_id, data, None, metadata, f)
         else:
             raise TypeError("data must be bytes, a pyarrow.Array, a DeviceArray, a DeviceBuffer, "
                             "a tensor with __dlpack__ (numpy, torch; host memory or this node's GPU), "
                             "a dict of such tensors, rows of either taken by an index "
-                            "(dora_amd.tensor.take), a ragged batch of any of these "
+                            "(dora_amd.tensor.take) or selected by a mask "
+                            "(dora_amd.tensor.masked), a ragged batch of any of these "
                             "(dora_amd.tensor.ragged) or tensors converted on send "
                             "(dora_amd.tensor.cast)")
         if rc:
@@ -555,6 +559,73 @@ class Node:
                                       part.__dlpack__() if part is not None else None, form,
                                       part_dev, dev, metadata, flags)
 
+    def _send_tensor_masked(self, output_id: str, sel, batch, metadata, flags: int) -> int:
+        """Rows selected by a mask (dora_amd.tensor.masked) as the List message of
+        `from_numpy_masked` (dora_node_send_output_tensor_mask): N rows, the K selected ones in
+        front, the offsets `[0, K]` or — with `batch`, the ragged batch over the N source rows —
+        `C[p]`, without `values[mask]` and without `nonzero`.
+
+        The mask lives where the values live.  Host values take a mask on the host (a sequence,
+        numpy, a CPU tensor of bool or uint8), which the CPU reads inside the call.  Values on
+        this node's GPU take a mask there: it does the `__dlpack__(stream=<the node stream>)`
+        handshake like every field and a device partition, is never read on the host, and an
+        asynchronous send holds it with the values until `sync()`."""
+        import numpy as np
+        from ._lib import PARTITION_LENGTHS
+        kind, tensors, names = self._values_kind(sel.values)
+        mask = sel.mask
+        on_device = hasattr(mask, "__dlpack_device__") and \
+            int(mask.__dlpack_device__()[0]) not in _DL_HOST
+        if on_device:
+            self._tensor_kind(mask, "the mask")
+        if on_device != (kind == "device"):
+            raise TypeError(f"the mask is in {'device' if on_device else 'host'} memory and the "
+                            f"values are {kind} tensors: move the mask next to the values")
+        part, form, part_dev = None, PARTITION_LENGTHS, ARROW_DEVICE_CPU
+        if batch is not None:
+            part, form, part_dev = self._partition_of(batch, kind)
+        if kind == "device":
+            _require_one_hip_runtime()
+            held = bool(flags & SEND_ASYNC) or self._async_default
+            if held and len(self._async_tensors) + len(tensors) + 2 > self._ASYNC_TENSORS_MAX:
+                self.sync()
+            stream = int(self._lib.dora_node_stream(self.handle))
+            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
+            mcap = mask.__dlpack__(stream=stream)
+            pcap = None
+            if part is not None:
+                pcap = part.__dlpack__(stream=stream) if part_dev == ARROW_DEVICE_ROCM \
+                    else part.__dlpack__()
+            rc = _fast.send_tensor_masked(self.handle, output_id, names, caps, mcap,
+                                          ARROW_DEVICE_ROCM, pcap, form, part_dev,
+                                          ARROW_DEVICE_ROCM, metadata, flags)
+            if held and not rc:
+                self._async_tensors.extend(tensors)
+                self._async_tensors.append(mask)
+                if part_dev == ARROW_DEVICE_ROCM:
+                    self._async_tensors.append(part)
+            return rc
+        # (the mask as it is: the call has read it when it returns, and what it cannot take — a
+        # dtype, a shape, a stride — is refused there)
+        mask = np.asarray(mask)
+        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
+        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
+        # (numpy exports no bool through DLPack before 1.25, and read-only arrays never: the
+        # array interface describes every field, the mask and the partition alike)
+        from .tensor import _describe_array, _describe_mask
+        if not all(hasattr(v, "__array_interface__") for v in tensors):
+            tensors = [np.from_dlpack(v) for v in tensors]
+        described = [_describe_array(v) for v in tensors]
+        mt, mkeep = _describe_array(mask)
+        pt, pkeep = _describe_array(part) if part is not None else (None, None)
+        mk, keep = _describe_mask(names, [t for t, _ in described], mt, ARROW_DEVICE_CPU, pt,
+                                  form, part_dev)
+        params = encode_parameters(metadata)
+        rc = self._lib.dora_node_send_output_tensor_mask(
+            self.handle, output_id.encode(), byref(mk), dev, params, len(params), flags)
+        del keep, described, mkeep, pkeep
+        return rc
+
     def _send_ragged(self, output_id: str, data, metadata, flags: int) -> int:
         """A ragged batch (dora_amd.tensor.ragged) as one List message
         (dora_node_send_output_tensor_list): the values as `_send_tensor` or `_send_tensor_struct`
@@ -568,6 +639,8 @@ class Node:
         clamped into a well-formed List by the kernel, not checked (dora_amd.tensor)."""
         if isinstance(data.values, _Taken):
             return self._send_take(output_id, data.values, data, metadata, flags)
+        if isinstance(data.values, _Masked):
+            return self._send_tensor_masked(output_id, data.values, data, metadata, flags)
         kind, tensors, names = self._values_kind(data.values)
         part, form, part_dev = self._partition_of(data, kind)
         if kind == "device":

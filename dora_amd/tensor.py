@@ -49,8 +49,26 @@ The index lives where the values live.  A host index is checked inside the send:
 read on the host: the send's one kernel launch reads row `index[i]` of every field straight into
 the sample, no intermediate tensor and no synchronisation, and writes a row of zeros where a word
 is not a row — a bad index is the producer's bug and shows as zero rows, never as a malformed
-message or a stray read.  Not offered: boolean masks (the message length would need a host
-synchronisation), other dimensions, a host index over device values.
+message or a stray read.  Not offered: other dimensions, a host index over device values.
+
+Rows selected by a mask — what a score threshold, a point-cloud crop or a range filter produce —
+travel without `values[mask]` and without `nonzero`, both of which synchronise with the GPU:
+`masked(values, mask)` (`values` a tensor or a dict of tensors sharing N, `mask` N bool or uint8
+elements, any non-zero one selecting its row) is sent as a `List` message whose child keeps the
+**capacity** of N rows — the K selected rows in source order in front, zero rows behind — and
+whose offsets, written where the mask is, say how many are live: `[0, K]` on its own, `C[p]` under
+`ragged`, whose partition `p` then describes the N *source* rows (`C[i]` counts the selected rows
+before row i), because K is not known on the host:
+
+    node.send_output("det", tensor.masked({"bbox": out[:, :4], "conf": out[:, 4]}, conf > 0.5))
+    node.send_output("det", tensor.ragged(tensor.masked(fields, keep), lengths=candidates_per_image))
+    r = tensor.to_torch(event["value"])    # Ragged: r.values has N rows, r.offsets[-1] == K live
+
+The mask lives where the values live.  The wire form is the same either way — `from_numpy_masked`
+states it — so a host producer that wants the tight message sends `values[mask]` itself.  A mask
+in this node's HBM is never read on the host: two small gfx950 kernels compact it into an index
+and running counts in scratch behind the sample, and the send's gather reads the rows through it.
+Not offered: masks along other dimensions, a host mask over device values, a cast under a mask.
 
 A tensor whose consumer wants another element type is converted inside the send:
 `cast(x, dtype, scale=None)` stands for "`x` converted to `dtype`" (float16 or float32, from uint8,
@@ -80,7 +98,7 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import Tensor, TensorCast, TensorField, TensorList, TensorTake
+from ._lib import Tensor, TensorCast, TensorField, TensorList, TensorMask, TensorTake
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -188,6 +206,23 @@ class Taken:
         return f"Taken({len(self)} rows of {self.values!r})"
 
 
+class Masked:
+    """Rows selected along dimension 0: `values`, a tensor or a dict of tensors of leading extent
+    N, and `mask`, N bool or uint8 elements.  It stands in a send for the N-row message whose
+    first K rows are the selected ones and copies nothing itself.  Build one with `masked`."""
+
+    __slots__ = ("values", "mask")
+
+    def __init__(self, values, mask):
+        self.values, self.mask = values, mask
+
+    def __len__(self):
+        return len(self.mask)
+
+    def __repr__(self):
+        return f"Masked({len(self)} rows of {self.values!r})"
+
+
 def _has_cast(values):
     if isinstance(values, dict):
         return any(isinstance(v, Cast) for v in values.values())
@@ -236,7 +271,7 @@ def cast(values, dtype, scale=None):
     (or the numpy or torch dtype), `scale` an optional finite factor applied in float32 first.
     `send_output` sends it, on its own or as a value of a dict of tensors, as what
     `from_numpy_cast` states."""
-    if isinstance(values, (Cast, Taken, Ragged, dict)):
+    if isinstance(values, (Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("cast converts one tensor: give a dict's fields a cast each; a cast under "
                         "ragged or take is not offered")
     return Cast(values, dtype, scale)
@@ -263,7 +298,7 @@ def take(values, index):
     tensors sharing their leading extent N, `index` a 1-D sequence or tensor of K int32 or int64
     row numbers, 0 <= i < N, next to the values (host with host, this node's HBM with device
     tensors).  `send_output` sends it, bare or under `ragged`, as what `values[index]` would be."""
-    if isinstance(values, (Taken, Ragged)):
+    if isinstance(values, (Taken, Masked, Ragged)):
         raise TypeError("take selects rows of a tensor or of a dict of tensors")
     if _has_cast(values):
         raise TypeError("cast under take is not offered: convert the taken rows with .to(dtype), "
@@ -271,9 +306,24 @@ def take(values, index):
     return Taken(values, index)
 
 
+def masked(values, mask):
+    """The rows of `values` that `mask` selects as a message: `values` a tensor or a dict of at
+    most 8 tensors sharing their leading extent N, `mask` a 1-D dense sequence or tensor of N bool
+    or uint8 elements next to the values (host with host, this node's HBM with device tensors),
+    any non-zero element selecting its row.  `send_output` sends it, bare or under `ragged`, as
+    what `from_numpy_masked` states: N rows, the K selected ones in front."""
+    if isinstance(values, (Taken, Masked, Ragged)):
+        raise TypeError("masked selects rows of a tensor or of a dict of tensors")
+    if _has_cast(values):
+        raise TypeError("cast under a mask is not offered: convert the values with .to(dtype), or "
+                        "send the cast without the mask")
+    return Masked(values, mask)
+
+
 def ragged(values, *, lengths=None, offsets=None):
     """The ragged batch of `values` (a tensor, or a dict of at most 8 tensors sharing their
-    leading extent N, or rows of either taken by `take`: N is then the K taken rows) cut into
+    leading extent N, or rows of either taken by `take`: N is then the K taken rows; or rows of
+    either selected by `masked`: the partition then describes the N source rows) cut into
     lists by exactly one of `lengths` (B of them) and `offsets` (B + 1): what `send_output` sends
     as one `List` message."""
     if _has_cast(values):
@@ -341,6 +391,37 @@ def from_numpy_take(values, index, *, lengths=None, offsets=None):
     if lengths is not None or offsets is not None:
         return from_numpy_ragged(taken, lengths=lengths, offsets=offsets)
     return from_numpy_struct(taken) if record else from_numpy(taken)
+
+
+def from_numpy_masked(values, mask, *, lengths=None, offsets=None):
+    """The pyarrow ListArray `send_output(output_id, masked(values, mask))` (under `ragged` with
+    a partition) puts on the wire, wherever the values live: the child is `values` (a numpy array
+    or a dict of numpy arrays sharing N) compacted by `mask` and zero-padded back to N rows, the
+    offsets are `C[p]` — `p` the offsets of the partition of the N source rows (`[0, N]` without
+    one), `C[i]` the number of selected rows among rows [0, i)."""
+    import numpy as np
+    import pyarrow as pa
+    mask = np.asarray(mask)
+    if mask.ndim != 1 or mask.dtype not in (np.bool_, np.uint8):
+        raise TypeError(f"the mask is {mask.ndim}-D {mask.dtype}, not 1-D bool or uint8")
+    keep = mask != 0
+    record = isinstance(values, dict)
+    cols = {k: np.asarray(v) for k, v in values.items()} if record else {"": np.asarray(values)}
+    padded = {}
+    for name, v in cols.items():
+        if v.ndim < 1:
+            raise ValueError("a tensor message has at least one dimension")
+        if v.shape[0] != len(keep):
+            raise ValueError(f"the mask has {len(keep)} elements, the values have {v.shape[0]} rows")
+        out = np.zeros(v.shape, v.dtype)
+        out[:int(keep.sum())] = v[keep]
+        padded[name] = out
+    child = from_numpy_struct(padded) if record else from_numpy(padded[""])
+    n = len(keep)
+    p = _host_offsets(n, lengths, offsets) if lengths is not None or offsets is not None \
+        else np.array([0, n], np.int32)
+    c = np.concatenate([[0], np.cumsum(keep)]).astype(np.int32)
+    return pa.ListArray.from_arrays(pa.array(c[p], pa.int32()), child)
 
 
 def to_numpy(arr):
@@ -496,6 +577,30 @@ def _describe_take(names, tensors, index, index_device, partition, form,
     return tk, (arr, enc, tensors, index, partition)
 
 
+def _describe_mask(names, tensors, mask, mask_device, partition, form,
+                   partition_device) -> tuple:
+    """The `dora_tensor_mask` over the `Tensor`s of `_describe` (`names` None: the one bare
+    tensor), the mask's `Tensor` and the partition's (None: one list), and what the caller keeps
+    alive with it."""
+    from ctypes import pointer
+    arr = (TensorField * len(tensors))()
+    enc = [n.encode() for n in names] if names is not None else [None] * len(tensors)
+    for k, (n, t) in enumerate(zip(enc, tensors)):
+        arr[k].name = n
+        arr[k].tensor = t
+    mk = TensorMask()
+    mk.fields = arr
+    mk.n = len(tensors)
+    mk.mask = mask
+    mk.mask_device = mask_device
+    if partition is not None:
+        mk.partition = pointer(partition)
+    mk.partition_form = form
+    mk.partition_device = partition_device
+    return mk, (arr, enc, tensors, mask, partition)
+
+
 __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_numpy_struct",
-           "from_numpy_ragged", "from_numpy_take", "to_numpy", "to_torch", "Ragged", "ragged",
-           "Taken", "take", "Cast", "cast", "from_numpy_cast"]
+           "from_numpy_ragged", "from_numpy_take", "from_numpy_masked", "to_numpy", "to_torch",
+           "Ragged", "ragged", "Taken", "take", "Masked", "masked", "Cast", "cast",
+           "from_numpy_cast"]

@@ -347,8 +347,7 @@ int dora_gpu_plan_tensor_list(const dora_tensor_list* list, ArrowDeviceType devi
  * word size, a NULL index with K > 0.  The partition rules of dora_gpu_plan_tensor_list apply with
  * N replaced by K: a host partition must describe K rows, a device partition is clamped to K and
  * needs device values; K or B + 1 >= 2^31 with a partition is DORA_ERR_UNSUPPORTED.
- * Not provided: selection by a boolean mask (K is then only known on the GPU while the message
- * length travels in the descriptor: it would need a host synchronisation), selection along
+ * Selection by a boolean mask is dora_gpu_plan_tensor_mask below.  Not provided: selection along
  * another dimension, and a host index over device values.
  */
 typedef struct dora_tensor_take {
@@ -361,6 +360,61 @@ typedef struct dora_tensor_take {
   ArrowDeviceType partition_device;
 } dora_tensor_take;
 int dora_gpu_plan_tensor_take(const dora_tensor_take* take, ArrowDeviceType device_type,
+                              dora_plan** out);
+/*
+ * Rows selected by a mask as one message, without `values[mask]`, without `nonzero` and, for
+ * device values, without a host synchronisation.  `fields` is a record as
+ * dora_gpu_plan_tensor_struct takes it, or n == 1 with a NULL name: a bare tensor; every field has
+ * shape[0] = N.  `mask` is a 1-D dense tensor of N elements of bool (DLPack code 6, 8 bits) or
+ * uint8, at any byte alignment; any non-zero byte selects its row.
+ *
+ * The number of selected rows K is only known where the mask is, so the message keeps the values'
+ * capacity and says in its offsets how many rows are live.  Whether the values are in host memory
+ * or in HBM, the message is `List<item: T>` of length B, T what dora_gpu_plan_tensor (bare) or
+ * dora_gpu_plan_tensor_struct gives the values:
+ *   the child has N rows: rows [0, K) are the selected rows in source order, rows [K, N) are zero
+ *   bytes;
+ *   offsets o[b] = C[p_b], C[i] the number of selected rows among source rows [0, i), p the
+ *   partition of the N source rows (not of the K selected ones as under a take);
+ *   without a partition (NULL) B = 1 and the offsets are [0, K].
+ * Type info, leaf offsets and padding are those of dora_gpu_plan_tensor_list over the N rows:
+ * there is no new Arrow type, and a reference node reads the message as before (a List whose
+ * child is longer than its last offset is valid Arrow).  N == 0 is an empty child and all-zero
+ * offsets.  A host producer that wants the tight message sends `values[mask]` itself.
+ *
+ * The mask lives where the values live (`mask_device` against `device_type`): host with host, this
+ * node's HBM with device values; any other pairing is DORA_ERR_INVALID.
+ *   Host: the CPU compacts the rows into the plan's staging buffer, zero-pads them to N rows and
+ *   computes the offsets; a host partition is checked against N with the list plan's rules; the
+ *   plan is an ordinary host plan and every source has been read on return.
+ *   Device: the mask is never read on the host.  The plan is always a gather without segments, its
+ *   fields described as a take describes them (dimension 0 kept apart, reach over all N rows, held
+ *   against the field's allocation before anything is launched); the mask's N bytes are held
+ *   against theirs the same way, a refusal naming `mask:`.  Three launches on one stream:
+ *   mask_count_kernel and mask_compact_kernel turn the mask into N int32 index words (the first K
+ *   the selected rows, the rest -1) and the counts C in a workspace, and gather_struct_kernel
+ *   takes every field by that index, its scan share — over a device partition's words, clamped as
+ *   dora_gpu_plan_tensor_list clamps them, or over a host partition's checked offsets — storing
+ *   C[o] for the offset o.  No workgroup waits for another and nothing is atomic.
+ *   The workspace is dora_gpu_plan_workspace_size bytes directly behind the sample: it is scratch
+ *   of the launches, not part of the message, and nothing that moves the sample moves it.
+ * DORA_ERR_INVALID on top of the values' own refusals: a mask that is not 1-D, not dense, not
+ * bool or uint8 with lanes == 1, whose extent is not N, a NULL mask with N > 0.
+ * DORA_ERR_UNSUPPORTED: N > 2^24 rows (one workgroup sums the per-tile totals before its tile, at
+ * most 4097 words), a device partition of more than 2^20 entries.
+ * Not provided: masks along another dimension, a host mask over device values, a cast under a
+ * mask.
+ */
+typedef struct dora_tensor_mask {
+  const dora_tensor_field* fields; /* a record, or n == 1 with a NULL name: a bare tensor */
+  size_t n;
+  dora_tensor mask;                /* 1-D dense bool / uint8, N elements */
+  ArrowDeviceType mask_device;
+  const dora_tensor* partition;    /* NULL: one list; else as dora_tensor_list, over the N source rows */
+  uint32_t partition_form;
+  ArrowDeviceType partition_device;
+} dora_tensor_mask;
+int dora_gpu_plan_tensor_mask(const dora_tensor_mask* mask, ArrowDeviceType device_type,
                               dora_plan** out);
 /*
  * Converted tensors as one message: field k "converted to casts[k]'s dtype", the conversion run
@@ -416,6 +470,10 @@ int dora_gpu_plan_tensor_cast(const dora_tensor_field* fields, size_t n,
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
+/* Scratch bytes the plan's launches need directly behind the sample, alignment slack included: a
+ * device mask plan's index, counts and totals (dora_gpu_plan_tensor_mask); 0 for every other
+ * plan.  They are no part of the message. */
+size_t dora_gpu_plan_workspace_size(const dora_plan* plan);
 size_t dora_gpu_plan_num_segments(const dora_plan* plan);
 /* Segment i: source pointer, destination offset in the sample, length. */
 int dora_gpu_plan_segment(const dora_plan* plan, size_t i, const void** src, uint64_t* dst_off,
@@ -433,6 +491,8 @@ int dora_gpu_plan_type_info(const dora_plan* plan, uint8_t* buf, size_t cap, siz
 /*
  * copy_array_into_sample (arrow_utils.rs:23-71): copy every buffer to its aligned offset in
  * `dst` (device memory, `dst_len` >= plan size) on `stream`; async.  Padding is not written.
+ * A device mask plan needs `dst_len` >= size + dora_gpu_plan_workspace_size and `dst` on a
+ * multiple of 4: otherwise DORA_ERR_INVALID naming both numbers, with nothing launched.
  */
 int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_t stream);
 /* ------------------------------------------------------------------------------------------ */
@@ -645,6 +705,17 @@ int dora_node_send_output_tensor_take(dora_node* node, const char* output_id,
 int dora_node_send_output_tensor_cast(dora_node* node, const char* output_id,
                                       const dora_tensor_field* fields, size_t n,
                                       const dora_tensor_cast* casts, ArrowDeviceType device_type,
+                                      const uint8_t* params, size_t params_len, uint32_t flags);
+/* Send rows selected by a mask (dora_gpu_plan_tensor_mask: wire form, where the mask lives,
+ * refusals), with the contract of the take send: host values with a host mask take every path of
+ * a host plan and everything has been read on return; device values with a device mask go where
+ * the take's gather goes, the mask one more borrowed source and the workspace in the sample's own
+ * slot behind the sample, so that samples in flight share nothing and receivers, relays and
+ * staging move the sample alone.  A synchronous send returns once the launches have read every
+ * field, the mask and a device partition; with DORA_SEND_ASYNC, once they are queued, and the
+ * caller keeps all of them alive and unwritten until dora_node_sync. */
+int dora_node_send_output_tensor_mask(dora_node* node, const char* output_id,
+                                      const dora_tensor_mask* mask, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags);
 /* Make DORA_SEND_ASYNC the default of every send of this node (also DORA_GPU_SEND_ASYNC=1). */
 int dora_node_set_async_sends(dora_node* node, int enable);

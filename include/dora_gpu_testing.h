@@ -115,6 +115,18 @@ int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, i
                             int* src_code, int* src_bits, int* dst_code, int* dst_bits,
                             int* has_scale, float* scale, uint64_t* elements,
                             uint64_t* src_bytes, uint64_t* dst_bytes);
+/* Test tool (host only): whether `plan` is a mask plan (dora_gpu_plan_tensor_mask; DORA_ERR_INVALID
+ * for any other plan) and what it selects by.  *n the rows of the source.  *device 1 if the plan's
+ * launches read the mask in HBM: then *mask its bytes, [*lo, *hi] the bytes from *mask that are
+ * checked against the allocation, workspace[5] the offsets from the sample's start of the index
+ * words, the counts, the per-tile totals, a host partition's offsets (*part_words of them, 0:
+ * none) and the workspace's end — dora_gpu_plan_size + dora_gpu_plan_workspace_size — and
+ * stride0[8] the byte stride of dimension 0 of every field, whose dimensions 1..
+ * dora_gpu_test_plan_field reports (reach over all *n rows, *kind always -1).  *device 0: a host
+ * plan, the compacted rows already in its staging buffer (or a message without rows). */
+int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mask, uint64_t* n,
+                            int64_t* lo, int64_t* hi, uint64_t* workspace, uint64_t* part_words,
+                            int64_t* stride0);
 /* Test and probe tool: which kernel gathers strided device tensor views of this process from now
  * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
  * it applies (short contiguous extents included). */
