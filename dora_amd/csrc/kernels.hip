@@ -389,7 +389,15 @@ struct CastMem {
       return c::int_to_f32<K>(raw);
     }
   }
-  __device__ __forceinline__ float mul(float x, float s) const { return x * s; }
+  // The product is made opaque: left to itself the compiler fuses a float16 source's widening,
+  // this multiplication and the rounding to float16 into one v_fma_mixlo_f16 x, s, 0, and
+  // (-0) + (+0) is +0 — a zero product (x or s +-0) lost its sign.  Behind the empty asm it is a
+  // v_mul_f32 and a v_cvt_f16_f32, which is the statement of record.
+  __device__ __forceinline__ float mul(float x, float s) const {
+    float y = x * s;
+    asm volatile("" : "+v"(y));
+    return y;
+  }
   __device__ __forceinline__ uint32_t to_f16(float y) const {
     return __builtin_bit_cast(uint16_t, static_cast<_Float16>(y));
   }

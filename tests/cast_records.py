@@ -53,9 +53,9 @@ def want(view, c):
     if c is None:
         return np.ascontiguousarray(view)
     y = to_f32(view, c["src"])
-    if c["scale"] is not None:
-        y = y * np.float32(c["scale"])
-    with np.errstate(over="ignore"):
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        if c["scale"] is not None:
+            y = y * np.float32(c["scale"])
         return y.astype(c["dst"])
 
 
@@ -186,6 +186,16 @@ def all_patterns(src):
     return np.arange(n, dtype=np.uint32).astype({1: np.uint8, 2: np.uint16}[dt.itemsize]).view(dt)
 
 
+# scales of the float16 and bfloat16 sources: products in the float16 subnormals, far below the
+# float32 normals, inexact, negated, and exactly zero of either sign
+FLOAT_SCALES = (2.0 ** -14, 2.0 ** -120, 1 / 255, 3.0, -1.0, 0.0, -0.0)
+# scales of float32 -> float32 over the float16 values: products rounded inside the float32
+# subnormal range, overflow to infinity, a scale that is itself subnormal
+F32_SCALES = (float(np.float32(2.0 ** -118 / 255)), 2.0 ** 114, 2.0 ** -140)
+# len(value_sets()), for parametrising without computing them at collection time
+N_VALUE_SETS = 3 + 4 * 2 * 3 + 2 * 2 * len(FLOAT_SCALES) + 3 + len(F32_SCALES)
+
+
 @functools.lru_cache(maxsize=None)
 def value_sets():
     """[(label, 1-D source array, cast)]: the conversions' whole domain where it is small
@@ -197,7 +207,31 @@ def value_sets():
         for dst in DESTS:
             for s in SCALES:
                 out.append((f"{src}->{dst} * {s!r}", all_patterns(src), cast(src, dst, s)))
+    # float sources under a scale, the multiplication over its domain: products that land in the
+    # float16 and the float32 subnormals, that underflow to a signed zero and that overflow;
+    # signed zeros, infinities and NaNs through the multiply; scales that are negative, +-0 and
+    # themselves subnormal
+    for src in ("float16", "bfloat16"):
+        for dst in DESTS:
+            for s in FLOAT_SCALES:
+                out.append((f"{src}->{dst} * {s!r}", all_patterns(src), cast(src, dst, s)))
+    for s in (2.0 ** 8, 2.0 ** -8, 3.0):  # (the first two are exact: the boundaries move)
+        out.append((f"f32->f16 rounding * {s!r}", f16_rounding_inputs(), cast("float32", "float16", s)))
+    widened = all_patterns("float16").astype(np.float32)
+    for s in F32_SCALES:
+        out.append((f"f32->f32 f16 values * {s!r}", widened, cast("float32", "float32", s)))
     return out
+
+
+def cut_from_wider(x, run=67):
+    """(base, view) holding the 1-D value set `x` as rows of `run` elements cut from rows 3 wider:
+    an odd run, so units straddle rows and a row's first element meets every alignment.  The last
+    row is padded with x[0] (+0 in every set), which so sits at many places of a 16-byte unit."""
+    rows = -(-len(x) // run)
+    b = np.full((rows, run + 3), x[0], x.dtype)
+    v = b[:, 1:run + 1]
+    v[...] = np.resize(np.concatenate([x, np.full(rows * run - len(x), x[0], x.dtype)]), (rows, run))
+    return b, v
 
 
 # ---------------------------------------------------------------------------------------------

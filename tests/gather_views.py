@@ -43,3 +43,9 @@ def describe_view(b, v, ptr):
     memory at `ptr` holding b's bytes."""
     off = v.__array_interface__["data"][0] - b.__array_interface__["data"][0]
     return v.shape, [s // v.dtype.itemsize for s in v.strides], v.dtype, off
+
+
+def misalignment(b):
+    """How many bytes past a multiple of its element size base `b` starts (numpy's own allocations
+    are aligned: 0 except for a base laid over a shifted buffer, tests/random_views.py)."""
+    return b.__array_interface__["data"][0] % b.itemsize

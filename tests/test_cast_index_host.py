@@ -11,7 +11,8 @@ Contiguous runs of 1, 3, 7, 8, 9, 17 and 1024 elements (dense and cut from a wid
 5 x 7 x 3 image permuted to 3 x 5 x 7, a negative and a zero stride in dimension 0, d0 in 1, 63,
 64, 65 and 257, destinations at every multiple of the destination element size mod 16, every
 source/destination pair, and a record of a cast from uint8, a plain float32 field and a cast from
-float32 to float16 whose fields start at 2 and 4 mod 16.
+float32 to float16 whose fields start at 2 and 4 mod 16.  The value sets of scaled float sources
+(tests/cast_records.py) run dense and cut from a wider base.
 
 tests/test_gpu_tensor_cast_device.py runs the same cases on the GPU, each after it passed here."""
 import os
@@ -24,6 +25,7 @@ import pytest
 from dora_amd._lib import ARROW_DEVICE_ROCM
 from tests import cast_records as cr
 from tests import struct_records as sr
+from tests.gather_views import misalignment
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = 0x7F10_0000_0000  # never dereferenced
@@ -61,7 +63,7 @@ class Batch:
 
     def add(self, label, rec, dst):
         bases = cr.bases_of(rec)
-        addr = {id(b): FAKE + (1 << 26) * i for i, b in enumerate(bases)}
+        addr = {id(b): FAKE + (1 << 26) * i + misalignment(b) for i, b in enumerate(bases)}
         with cr.plan_cast(rec, lambda b: addr[id(b)], ARROW_DEVICE_ROCM) as p:
             assert p.segments() == [], label
             fields, casts = sr.plan_fields(p, dst), cr.plan_casts(p)
@@ -148,6 +150,19 @@ def test_a_record_of_three_fields(lib, emulator, tmp_path):
             starts |= {(DST + mis + ranges[k][0]) % 16 for k in (0, 2)}
             assert ranges[1][0] % 4 == 0
     assert {2, 4} <= starts, starts
+    batch.run(emulator)
+
+
+@pytest.mark.parametrize("k", range(3 + 4 * 2 * 3, cr.N_VALUE_SETS))
+def test_scaled_float_sources_over_their_domain(lib, emulator, tmp_path, k):
+    """The value sets of scaled float sources (tests/cast_records.py) through the emulated body,
+    dense and cut from a wider base: the plain-integer converts and the host's float32 product
+    give numpy's bits, subnormal products, signed zeros and overflow included."""
+    label, x, c = cr.value_sets()[k]
+    batch = Batch(tmp_path)
+    batch.add(label, [(None, x, x, c)], DST)
+    b, v = cr.cut_from_wider(x)
+    batch.add(label + ", cut from a wider base", [(None, b, v, c)], DST + 4)
     batch.run(emulator)
 
 

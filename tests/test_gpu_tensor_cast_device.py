@@ -5,8 +5,9 @@ into a poisoned destination with 4 KiB guard bands on both sides.  Every field's
 numpy's `(x.astype(float32) * float32(scale)).astype(dst)` bit for bit (a NaN for a NaN), the
 guard bands and every padding byte keep the poison, the type info is the oracle's.  The shapes are
 those of test_cast_index_host.py, each of which passed the sanitized host emulation there; the
-value sets of test_tensor_cast_host.py run at one dense shape each, which is where the hardware's
-converts meet numpy, subnormals included.  A field that leaves its allocation by one source byte
+value sets of test_tensor_cast_host.py run at one dense shape each and at one cut from a wider base,
+which is where the hardware's converts and its float32 multiplication meet numpy: subnormal
+products, signed zeros, overflow and NaNs under every scale of tests/cast_records.py included.  A field that leaves its allocation by one source byte
 and a destination that is not a multiple of the destination element size are refused with
 nothing launched."""
 import numpy as np
@@ -92,10 +93,12 @@ def test_a_plain_field_takes_the_tile_body_beside_a_cast(dev):
     run_record(rec, dev, (0, 2, 4, 8), "tile beside cast")
 
 
-@pytest.mark.parametrize("k", range(3 + 4 * 2 * 3))
+@pytest.mark.parametrize("k", range(cr.N_VALUE_SETS))
 def test_the_hardwares_conversions_over_their_domain(dev, k):
     label, x, c = cr.value_sets()[k]
     run_record([(None, x, x, c)], dev, (0,), label)
+    b, v = cr.cut_from_wider(x)
+    run_record([(None, b, v, c)], dev, (0,), label + ", cut from a wider base")
 
 
 def test_refused_with_nothing_launched(dev):

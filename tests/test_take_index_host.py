@@ -26,6 +26,7 @@ import pytest
 from dora_amd._lib import ARROW_DEVICE_CPU, ARROW_DEVICE_ROCM, PARTITION_LENGTHS
 from tests import gather_views as gv
 from tests import struct_records as sr
+from tests.gather_views import misalignment
 from tests import take_records as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -67,7 +68,7 @@ class Batch:
         """Plan the take of `rec` by `index` (with `part`: the ragged batch over it, lengths on
         the host) for a sample at `dst`; K == 0 plans an empty message and no case."""
         bases = sr.bases_of(rec)
-        addr = {id(b): FAKE + (1 << 26) * i for i, b in enumerate(bases)}
+        addr = {id(b): FAKE + (1 << 26) * i + misalignment(b) for i, b in enumerate(bases)}
         kw = {} if part is None else dict(part=part, form=PARTITION_LENGTHS, part_dev=ARROW_DEVICE_CPU)
         with tr.plan_take(rec, lambda b: addr[id(b)], ARROW_DEVICE_ROCM, index, ARROW_DEVICE_ROCM,
                           index_ptr=INDEX, **kw) as p:

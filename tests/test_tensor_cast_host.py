@@ -5,7 +5,8 @@ the oracle's type info; and the CPU's conversions, the plain-integer float32 -> 
 float16 -> float32 of cast_device.h among them, are checked through the host plan over their
 whole domain: around every float16 (exact values, midpoints, midpoints +-1 ulp), every float16 and
 bfloat16 bit pattern, every 8- and 16-bit integer under scales that reach the float16
-subnormals."""
+subnormals, and the float sources under scales whose products land in the float16 and float32
+subnormals, are zero of either sign, or overflow."""
 import ctypes
 
 import numpy as np
@@ -118,13 +119,35 @@ def test_value_sets_cover_what_they_claim(sets):
     for v in (65504.0, 65520.0, np.float32(65519.996)):
         assert (r == np.float32(v)).any()
     assert len(by["f16->f32 all"]) == len(by["bf16->f32 all"]) == 65536
-    assert len(sets) == 3 + 4 * 2 * 3
+    assert len(sets) == cr.N_VALUE_SETS and len({label for label, _, _ in sets}) == len(sets)
+    assert [label for label, _, _ in sets[:3]] == ["f32->f16 rounding", "f16->f32 all", "bf16->f32 all"]
+    # scaled float sources: products inside the float16 and the float32 subnormals, rounded
+    # there, zero products of both signs, overflow, and a scale that is itself subnormal
+    def results(label):
+        _, x, c = next(t for t in sets if t[0] == label)
+        return cr.to_f32(x, c["src"]), cr.want(x, c)
+    x, y = results("float16->float16 * 6.103515625e-05")
+    assert ((y != 0) & (np.abs(y) < 2.0 ** -14)).any()
+    x, y = results("bfloat16->float32 * 7.52316384526264e-37")
+    assert ((y != 0) & (np.abs(y) < 2.0 ** -126)).any() and ((y == 0) & (x != 0)).any()
+    for label in ("float16->float32 * 0.0", "bfloat16->float16 * -0.0", "float16->float16 * -1.0"):
+        x, y = results(label)
+        zero = y == 0
+        assert (np.signbit(y[zero])).any() and (~np.signbit(y[zero])).any(), label
+    x, y = results(f"f32->f32 f16 values * {cr.F32_SCALES[0]!r}")
+    sub = (y != 0) & (np.abs(y) < 2.0 ** -126)
+    with np.errstate(invalid="ignore"):  # (the signalling NaNs among the inputs)
+        exact = x.astype(np.float64) * np.float64(np.float32(cr.F32_SCALES[0]))
+    assert sub.sum() > 1000 and (y[sub].astype(np.float64) != exact[sub]).any()  # rounded there
+    x, y = results(f"f32->f32 f16 values * {cr.F32_SCALES[1]!r}")
+    assert (np.isinf(y) & np.isfinite(x)).any()
+    assert 0 < cr.F32_SCALES[2] < 2.0 ** -126
     # the smallest scale drives float16 results into the subnormal range
     x = cr.want(cr.all_patterns("uint8"), cr.cast("uint8", "float16", 2.0 ** -20))
     assert ((x != 0) & (np.abs(x) < 2.0 ** -14)).any()
 
 
-@pytest.mark.parametrize("k", range(3 + 4 * 2 * 3))
+@pytest.mark.parametrize("k", range(cr.N_VALUE_SETS))
 def test_host_conversions_over_their_domain(lib, sets, k):
     """Through the host plan (the CPU converts inside the call, dense views included): bit-equal
     to numpy where numpy gives no NaN, a NaN where it does."""
