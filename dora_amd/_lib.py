@@ -87,6 +87,13 @@ class TensorCast(ctypes.Structure):
                 ("scale", c_float)]
 
 
+class TensorQuant(ctypes.Structure):
+    """dora_tensor_quant of include/dora_gpu.h: the integer dtype one field is quantised to on
+    send (dtype_bits 0: not quantised), the optional float32 factor and the zero point."""
+    _fields_ = [("dtype_code", c_uint8), ("dtype_bits", c_uint8), ("has_scale", ctypes.c_uint16),
+                ("scale", c_float), ("zero_point", c_int32)]
+
+
 class TensorMask(ctypes.Structure):
     """dora_tensor_mask of include/dora_gpu.h: the fields rows are selected from, the mask that
     selects them and, for more than one list, the partition of the N source rows (else NULL)."""
@@ -148,6 +155,11 @@ _SIGS = {
                                           POINTER(c_void_p)]),
     "dora_node_send_output_tensor_cast": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t, c_void_p,
                                                   c_int32, c_char_p, c_size_t, c_uint32]),
+    "dora_gpu_plan_tensor_convert": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_int32,
+                                             POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_convert": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
+                                                     c_void_p, c_void_p, c_int32, c_char_p,
+                                                     c_size_t, c_uint32]),
     "dora_gpu_plan_tensor_mask": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_mask": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                                   c_size_t, c_uint32]),
@@ -295,6 +307,8 @@ _TEST_SIGS = {
                                         POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                         POINTER(c_int), POINTER(c_int), POINTER(c_float),
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "dora_gpu_test_plan_quant": (c_int, [c_void_p, c_size_t, POINTER(c_int), POINTER(c_int),
+                                         POINTER(c_int), POINTER(c_int)]),
     "dora_gpu_test_plan_take": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int),
                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),

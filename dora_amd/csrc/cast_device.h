@@ -1,11 +1,13 @@
 // Device code of the converting gather (a field of a cast plan, tensor_plan.cpp): the row-major
 // elements of a strided view read once as their source type, converted, and written once as
-// float16 or float32 — y = to_dst(to_f32(x) [* scale]), element by element.
+// float16 or float32 — y = to_dst(to_f32(x) [* scale]), element by element — or, a quantised field,
+// as uint8, int8, uint16 or int16: q = int(clip(rint(y), lo - zp, hi - zp)) + zp with a NaN taken
+// as 0, [lo, hi] the destination's range and zp the zero point inside it.
 //
 // It is gather_device.h's rows body restated per element, in the same style: every address
 // computation is plain C++ in functions that compile for host and device alike, all memory and
 // every conversion goes through a policy object `M`, and nothing here uses an intrinsic.  The
-// kernel (kernels.hip, gather_cast_kernel) passes a policy of real loads, stores and the
+// kernel (kernels.hip, gather_cast_kernel and gather_quant_kernel) passes a policy of real loads, stores and the
 // hardware's converts; the host emulation of tests/test_cast_index_host.py passes one that runs
 // the same functions lane by lane over the whole grid with every offset and alignment checked,
 // and converts with the plain-integer routines below, which the host plan uses as well.
@@ -18,8 +20,9 @@
 // (the launcher refuses any other), the source of ssize (the plan does).
 //
 // A unit takes one of two paths.  Vector: its E elements lie in one contiguous run and their
-// E * ssize bytes start on a multiple of min(E * ssize, 16): one load of 4, 8 or 16 bytes (two of
-// 16 for float32 -> float16), converted in registers.  Element: every other unit loads its
+// E * ssize bytes start on a multiple of min(E * ssize, 16): one load of 4, 8 or 16 bytes, or two
+// or four of 16 (float32 -> float16 is 32 bytes a unit; an 8-bit destination has E = 16 and a
+// source image of 16, 32 or 64 bytes), converted in registers.  Element: every other unit loads its
 // elements one by one (ssize bytes each, naturally aligned), walking the odometer as rows end;
 // permuted views (HWC -> CHW) take this path.  Either way one 16-byte store.  A tiled transpose
 // that converts is not provided.
@@ -101,6 +104,40 @@ DORA_HD uint32_t f32_to_f16_bits(uint32_t x) {
   return sign | q;
 }
 
+// float32 -> clamped integer: the value rounded to the nearest integer, ties to even, a NaN as 0,
+// clamped to [lo, hi] (|lo|, |hi| < 2^24, lo <= 0 <= hi: the caller's range less its zero point),
+// plus zp.  On the bit pattern alone, so the floating-point environment has no say.
+DORA_HD int32_t quantize_bits(uint32_t x, int32_t lo, int32_t hi, int32_t zp) {
+  const bool neg = (x >> 31) != 0;
+  const uint32_t mag = x & 0x7fffffffu, e = mag >> 23;
+  int32_t r;
+  if (mag > 0x7f800000u || e < 126) {
+    r = 0;  // a NaN; |y| < 0.5
+  } else if (e >= 150) {
+    r = neg ? lo : hi;  // |y| >= 2^24 (an integer past either bound), +-inf
+  } else {
+    const uint32_t m = (mag & 0x7fffffu) | 0x800000u, s = 150 - e;  // |y| = m * 2^-s, s in 1..24
+    uint32_t q = m >> s;
+    const uint32_t rem = m & ((1u << s) - 1), half = 1u << (s - 1);
+    if (rem > half || (rem == half && (q & 1))) ++q;
+    r = neg ? -static_cast<int32_t>(q) : static_cast<int32_t>(q);
+    r = r < lo ? lo : r > hi ? hi : r;
+  }
+  return r + zp;
+}
+
+// The range of a quantised destination.
+DORA_HD int32_t dst_lo(uint32_t d) { return d == kDstI8 ? -128 : d == kDstI16 ? -32768 : 0; }
+DORA_HD int32_t dst_hi(uint32_t d) {
+  return d == kDstU8 ? 255 : d == kDstI8 ? 127 : d == kDstU16 ? 65535 : 32767;
+}
+// DLPack (code, bits) -> Dst of a quantised field, or -1 when the dtype is no such destination.
+DORA_HD int dst_kind(unsigned code, unsigned bits) {
+  if (code == 1) return bits == 8 ? int(kDstU8) : bits == 16 ? int(kDstU16) : -1;
+  if (code == 0) return bits == 8 ? int(kDstI8) : bits == 16 ? int(kDstI16) : -1;
+  return -1;
+}
+
 // An integer source element (zero-extended raw bits) as float32: exact for 8 and 16 bits.
 template <uint32_t K>
 DORA_HD float int_to_f32(uint32_t raw) {
@@ -123,6 +160,9 @@ struct HostCvt {
   float mul(float x, float s) const { return x * s; }
   uint32_t to_f16(float y) const { return f32_to_f16_bits(bits_of(y)); }
   uint32_t f32_bits(float y) const { return bits_of(y); }
+  int32_t to_int(float y, int32_t lo, int32_t hi, int32_t zp) const {
+    return quantize_bits(bits_of(y), lo, hi, zp);
+  }
 };
 
 // ------------------------------------------------------------------------------------------
@@ -154,6 +194,9 @@ DORA_HD Args make_args(const GatherDesc& g, const CastDesc& c, uint8_t* dst) {
   a.dsize = ds;
   a.has_scale = c.has_scale;
   a.scale = c.scale;
+  const int dk = c.dst_code == 2 ? int(kDstFloat) : dst_kind(c.dst_code, c.dst_bits);
+  a.dst = static_cast<uint32_t>(dk < 0 ? 0 : dk);
+  a.zp = c.zero_point;
   return a;
 }
 
@@ -166,26 +209,32 @@ DORA_HD uint64_t grid_for(const Args& a) { return gather::grid_for(a.g); }
 // image, so every shift in it is a constant.
 // ------------------------------------------------------------------------------------------
 
+// 16-byte words of a unit's source image: E * 4 bytes at most.
+template <int D>
+constexpr int kImage = D == 1 ? 4 : 2;
+
 // Element `j` of S bytes of the image `v` (little-endian), zero-extended.
 template <int S>
 DORA_HDI uint32_t elem_of(const U16* v, int j) {
-  if constexpr (S == 1) return (v[0].w[j / 4] >> (8 * (j % 4))) & 0xffu;
-  else if constexpr (S == 2) return (v[0].w[j / 2] >> (16 * (j % 2))) & 0xffffu;
-  else return v[j / 4].w[j % 4];
+  const int w = j * S / 4;
+  if constexpr (S == 1) return (v[w / 4].w[w % 4] >> (8 * (j % 4))) & 0xffu;
+  else if constexpr (S == 2) return (v[w / 4].w[w % 4] >> (16 * (j % 2))) & 0xffffu;
+  else return v[w / 4].w[w % 4];
 }
 
-// The source bytes of the E elements from output element `e` on into v[0..1]: one vector load
-// where they are contiguous and the load is naturally aligned, else element by element across
-// rows.
+// The source bytes of the E elements from output element `e` on into v[0..kImage<D>): vector
+// loads where they are contiguous and the first is naturally aligned, else element by element
+// across rows.
 template <int D, class M>
 DORA_HDI void load_unit(const Args& a, uint64_t e, M& m, U16* v) {
   constexpr int E = 16 / D;
-  const uint32_t ss = a.g.piece, n = E * ss;  // n: 4, 8, 16 or 32 source bytes a unit
+  const uint32_t ss = a.g.piece, n = E * ss;  // n: 4, 8, 16, 32 or 64 source bytes a unit
   uint64_t r, b;
   out_pos(a.g, e, &r, &b);
   RowPos p;
   row_pos(a.g, r, p);
-  v[0] = v[1] = U16{{0, 0, 0, 0}};
+#pragma unroll
+  for (int k = 0; k < kImage<D>; ++k) v[k] = U16{{0, 0, 0, 0}};
   if (b + E <= a.g.row) {
     const int64_t s = p.off + static_cast<int64_t>(b * ss);
     const uint32_t align = n > 16 ? 16 : n;
@@ -194,9 +243,15 @@ DORA_HDI void load_unit(const Args& a, uint64_t e, M& m, U16* v) {
         case 4: v[0] = m.template load_vec<4>(s); break;
         case 8: v[0] = m.template load_vec<8>(s); break;
         case 16: v[0] = m.template load_vec<16>(s); break;
-        default:
+        case 32:
           v[0] = m.template load_vec<16>(s);
           v[1] = m.template load_vec<16>(s + 16);
+          break;
+        default:
+          if constexpr (D == 1) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = m.template load_vec<16>(s + 16 * k);
+          }
           break;
       }
       return;
@@ -207,7 +262,7 @@ DORA_HDI void load_unit(const Args& a, uint64_t e, M& m, U16* v) {
     const int64_t s = p.off + static_cast<int64_t>(b * ss);
     switch (ss) {
       case 1: v[0].w[j / 4] |= m.template load_elem<1>(s) << (8 * (j % 4)); break;
-      case 2: v[0].w[j / 2] |= m.template load_elem<2>(s) << (16 * (j % 2)); break;
+      case 2: v[j / 8].w[(j % 8) / 2] |= m.template load_elem<2>(s) << (16 * (j % 2)); break;
       default: v[j / 4].w[j % 4] = m.template load_elem<4>(s); break;
     }
     if (++b >= a.g.row) {
@@ -217,46 +272,55 @@ DORA_HDI void load_unit(const Args& a, uint64_t e, M& m, U16* v) {
   }
 }
 
-// The image's E elements of source type K -> the unit's 16 output bytes.
-template <uint32_t K, int D, class M>
+// The image's E elements of source type K -> the unit's 16 output bytes: floats of D bytes, or
+// with Q integers of D bytes, each the product quantised into the destination's range.
+template <uint32_t K, int D, bool Q, class M>
 DORA_HDI U16 convert_as(const Args& a, const U16* v, M& m) {
   constexpr int E = 16 / D;
   U16 out = {{0, 0, 0, 0}};
+  // (the clip bounds less the zero point: exact as integers and as float32)
+  const int32_t lo = Q ? dst_lo(a.dst) - a.zp : 0, hi = Q ? dst_hi(a.dst) - a.zp : 0;
 #pragma unroll
   for (int j = 0; j < E; ++j) {
     float y = m.template to_f32<K>(elem_of<kSize<K>>(v, j));
     if (a.has_scale) y = m.mul(y, a.scale);
-    if constexpr (D == 2) out.w[j / 2] |= m.to_f16(y) << (16 * (j % 2));
-    else out.w[j] = m.f32_bits(y);
+    if constexpr (Q) {
+      const uint32_t q = static_cast<uint32_t>(m.to_int(y, lo, hi, a.zp));
+      if constexpr (D == 1) out.w[j / 4] |= (q & 0xffu) << (8 * (j % 4));
+      else out.w[j / 2] |= (q & 0xffffu) << (16 * (j % 2));
+    } else {
+      if constexpr (D == 2) out.w[j / 2] |= m.to_f16(y) << (16 * (j % 2));
+      else out.w[j] = m.f32_bits(y);
+    }
   }
   return out;
 }
 
-template <int D, class M>
+template <int D, bool Q, class M>
 DORA_HDI U16 convert_unit(const Args& a, const U16* v, M& m) {
   switch (a.src) {
-    case kU8: return convert_as<kU8, D>(a, v, m);
-    case kI8: return convert_as<kI8, D>(a, v, m);
-    case kU16: return convert_as<kU16, D>(a, v, m);
-    case kI16: return convert_as<kI16, D>(a, v, m);
-    case kF16: return convert_as<kF16, D>(a, v, m);
-    case kBF16: return convert_as<kBF16, D>(a, v, m);
-    default: return convert_as<kF32, D>(a, v, m);
+    case kU8: return convert_as<kU8, D, Q>(a, v, m);
+    case kI8: return convert_as<kI8, D, Q>(a, v, m);
+    case kU16: return convert_as<kU16, D, Q>(a, v, m);
+    case kI16: return convert_as<kI16, D, Q>(a, v, m);
+    case kF16: return convert_as<kF16, D, Q>(a, v, m);
+    case kBF16: return convert_as<kBF16, D, Q>(a, v, m);
+    default: return convert_as<kF32, D, Q>(a, v, m);
   }
 }
 
 // Whole unit `u` of the output.
-template <int D, class M>
+template <int D, bool Q, class M>
 DORA_HDI void cast_unit(const Args& a, uint64_t u, M& m) {
   const uint64_t e = a.g.head + static_cast<uint64_t>(16 / D) * u;
-  U16 v[2];
+  U16 v[kImage<D>];
   load_unit<D>(a, e, m, v);
-  m.store16(e * D, convert_unit<D>(a, v, m));
+  m.store16(e * D, convert_unit<D, Q>(a, v, m));
 }
 
 // Output element `e` on its own (the elements before the first and after the last whole unit):
 // element 0 of an image that holds nothing else.
-template <int D, class M>
+template <int D, bool Q, class M>
 DORA_HDI void cast_elem(const Args& a, uint64_t e, M& m) {
   const uint32_t ss = a.g.piece;
   uint64_t r, b;
@@ -264,32 +328,48 @@ DORA_HDI void cast_elem(const Args& a, uint64_t e, M& m) {
   RowPos p;
   row_pos(a.g, r, p);
   const int64_t s = p.off + static_cast<int64_t>(b * ss);
-  U16 v[2] = {{{0, 0, 0, 0}}, {{0, 0, 0, 0}}};
+  U16 v[kImage<D>] = {};
   v[0].w[0] = ss == 1 ? m.template load_elem<1>(s)
                       : ss == 2 ? m.template load_elem<2>(s) : m.template load_elem<4>(s);
-  const U16 y = convert_unit<D>(a, v, m);
-  m.template store_elem<D>(e, D == 2 ? y.w[0] & 0xffffu : y.w[0]);
+  const U16 y = convert_unit<D, Q>(a, v, m);
+  m.template store_elem<D>(e, D == 1 ? y.w[0] & 0xffu : D == 2 ? y.w[0] & 0xffffu : y.w[0]);
 }
 
 // gather_lane's division of the work: lanes 0..15 a head element each, lanes 16..31 a tail
-// element each (fewer than E <= 8 of either), and every lane the whole units lane, lane + lanes, ..
-template <int D, class M>
+// element each (at most E - 1 <= 15 of either: the head ends at the first 16-byte boundary, the
+// tail is less than a unit), and every lane the whole units lane, lane + lanes, ..
+template <int D, bool Q, class M>
 DORA_HDI void cast_lane_as(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
   constexpr int E = 16 / D;
+  static_assert(E - 1 <= 15, "16 lanes each for the head's and the tail's elements");
   if (lane < 16) {
-    if (lane < a.g.head) cast_elem<D>(a, lane, m);
+    if (lane < a.g.head) cast_elem<D, Q>(a, lane, m);
   } else if (lane < 32) {
     const uint64_t t0 = a.g.head + static_cast<uint64_t>(E) * a.g.nunits;  // <= total
-    if (lane - 16 < a.g.total - t0) cast_elem<D>(a, t0 + (lane - 16), m);
+    if (lane - 16 < a.g.total - t0) cast_elem<D, Q>(a, t0 + (lane - 16), m);
   }
-  for (uint64_t u = lane; u < a.g.nunits; u += lanes) cast_unit<D>(a, u, m);
+  for (uint64_t u = lane; u < a.g.nunits; u += lanes) cast_unit<D, Q>(a, u, m);
+}
+
+// Everything lane `lane` of `lanes` does for a field cast to float16 or float32.
+template <class M>
+DORA_HDI void cast_lane_float(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+  if (a.dsize == 2) cast_lane_as<2, false>(a, lane, lanes, m);
+  else cast_lane_as<4, false>(a, lane, lanes, m);
+}
+
+// The same for a quantised field: 8- or 16-bit integers.
+template <class M>
+DORA_HDI void cast_lane_quant(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+  if (a.dsize == 1) cast_lane_as<1, true>(a, lane, lanes, m);
+  else cast_lane_as<2, true>(a, lane, lanes, m);
 }
 
 // Everything lane `lane` of `lanes` does.
 template <class M>
 DORA_HDI void cast_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
-  if (a.dsize == 2) cast_lane_as<2>(a, lane, lanes, m);
-  else cast_lane_as<4>(a, lane, lanes, m);
+  if (a.dst == kDstFloat) cast_lane_float(a, lane, lanes, m);
+  else cast_lane_quant(a, lane, lanes, m);
 }
 
 }  // namespace cast

@@ -871,15 +871,19 @@ DORA_HD void scan_store(const Args& a, uint64_t tile, uint32_t thread, uint32_t 
 }  // namespace mask
 
 // ------------------------------------------------------------------------------------------
-// A field converted on the way (one more field kind, run by gather_cast_kernel only): the rows
+// A field converted on the way (one more field kind, run by gather_cast_kernel and
+// gather_quant_kernel only): the rows
 // body restated per element, source elements of one type read, converted and written as float16
-// or float32.  Only the arguments live here, where multi::Field needs them; the body is
+// or float32, or quantised to an 8- or 16-bit integer.  Only the arguments live here, where multi::Field needs them; the body is
 // cast_device.h.
 // ------------------------------------------------------------------------------------------
 namespace cast {
 
 // What the source elements are; every value of each is exact in float32.
 enum Src : uint32_t { kU8 = 0, kI8 = 1, kU16 = 2, kI16 = 3, kF16 = 4, kBF16 = 5, kF32 = 6 };
+// What the destination elements are: a float of `dsize` bytes, or (a quantised field) an integer
+// of `dsize` bytes that the rounded product is clamped to.
+enum Dst : uint32_t { kDstFloat = 0, kDstU8 = 1, kDstI8 = 2, kDstU16 = 3, kDstI16 = 4 };
 
 struct Args {
   // the view with rows counted in elements: `total` elements in all, `row` contiguous elements
@@ -887,9 +891,11 @@ struct Args {
   // units; `piece` the source element size; shape[] / stride[] and [lo, hi] in source bytes
   gather::Args g;
   uint32_t src;        // Src
-  uint32_t dsize;      // destination element size: 2 (float16) or 4 (float32)
+  uint32_t dsize;      // destination element size: 2 (float16) or 4 (float32); quantised: 1 or 2
   uint32_t has_scale;
   float scale;
+  uint32_t dst;        // Dst
+  int32_t zp;          // a quantised field's zero point, inside the destination's range
 };
 
 }  // namespace cast
@@ -898,7 +904,7 @@ namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
 // (a scan share, kScan, is no Field: it has no view; it runs workgroups [0, wg_begin[0]))
-// (kRowsCast fields are run by gather_cast_kernel only: gather_struct_kernel's launches hold none)
+// (kRowsCast fields are run by gather_cast_kernel / gather_quant_kernel only: gather_struct_kernel's launches hold none)
 enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4 };
 
 struct Field {

@@ -404,6 +404,15 @@ struct CastMem {
   __device__ __forceinline__ uint32_t f32_bits(float y) const {
     return __builtin_bit_cast(uint32_t, y);
   }
+  // A quantised element: round to nearest even (v_rndne_f32), a NaN as 0, the clamp against the
+  // two bounds (exact in float32) and only then the conversion, which so never sees a value
+  // outside int32 (v_cvt_i32_f32).  The product comes from `mul` above, opaque as it is there.
+  __device__ __forceinline__ int32_t to_int(float y, int32_t lo, int32_t hi, int32_t zp) const {
+    float r = __builtin_rintf(y);
+    r = y != y ? 0.0f : r;
+    r = fminf(fmaxf(r, static_cast<float>(lo)), static_cast<float>(hi));
+    return static_cast<int32_t>(r) + zp;
+  }
   __device__ __forceinline__ void store16(uint64_t o, gather::U16 v) const {
     st16<2>(dst + o, u32x4{v.w[0], v.w[1], v.w[2], v.w[3]});
   }
@@ -411,6 +420,8 @@ struct CastMem {
   __device__ __forceinline__ void store_elem(uint64_t e, uint32_t bits) const {
     if constexpr (D == 4) {
       st4<2>(dst + 4 * e, bits);
+    } else if constexpr (D == 1) {
+      st1<2>(dst + e, static_cast<uint8_t>(bits));
     } else {
       __builtin_nontemporal_store(static_cast<uint16_t>(bits), reinterpret_cast<uint16_t*>(dst) + e);
     }
@@ -430,11 +441,12 @@ struct CastMem {
 // over the workgroup like the other two.
 static_assert(gather::scan::kLds <= gather::tile::kLds, "the scan's rows fit the tile buffer");
 
-// What a workgroup of a multi-field launch does, for both kernels below.  With kCast the cast kind
-// takes the place of the scan share and the taken kind, which no cast plan has: with all of them
+// What a workgroup of a multi-field launch does, for the kernels below.  kCast 0: no cast kind;
+// 1: the cast kind with float destinations only; 2: with the quantised destinations too.  With
+// kCast the cast kind takes the place of the scan share and the taken kind, which no cast plan has: with all of them
 // in one kernel the compiler no longer follows every read back to the by-value arguments and
 // keeps a copy of the 2.3 KB in scratch.
-template <bool kCast>
+template <int kCast>
 __device__ __forceinline__ void struct_share(const gather::multi::Args& a, uint64_t* lds) {
   const uint32_t w = blockIdx.x;
   if constexpr (!kCast) {
@@ -465,8 +477,12 @@ __device__ __forceinline__ void struct_share(const gather::multi::Args& a, uint6
       // follows back to the kernel's by-value arguments, which it would then keep in scratch)
       const gather::cast::Args c = f.cast;
       CastMem m{c.g.src, c.g.dst};
-      gather::cast::cast_lane(c, local * gather::kThreads + threadIdx.x, share * gather::kThreads,
-                              m);
+      if constexpr (kCast == 1)
+        gather::cast::cast_lane_float(c, local * gather::kThreads + threadIdx.x,
+                                      share * gather::kThreads, m);
+      else
+        gather::cast::cast_lane(c, local * gather::kThreads + threadIdx.x,
+                                share * gather::kThreads, m);
       return;
     }
   }
@@ -480,7 +496,7 @@ __device__ __forceinline__ void struct_share(const gather::multi::Args& a, uint6
 
 __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather::multi::Args a) {
   __shared__ uint64_t lds[gather::tile::kLds];
-  struct_share<false>(a, lds);
+  struct_share<0>(a, lds);
 }
 
 // gather_cast_kernel: the fields of a cast plan in one launch: the same body with the cast kind
@@ -488,7 +504,17 @@ __global__ __launch_bounds__(gather::kThreads) void gather_struct_kernel(gather:
 // through their usual rows or tile body.
 __global__ __launch_bounds__(gather::kThreads) void gather_cast_kernel(gather::multi::Args a) {
   __shared__ uint64_t lds[gather::tile::kLds];
-  struct_share<true>(a, lds);
+  struct_share<1>(a, lds);
+}
+
+// gather_quant_kernel: the same for a plan with a quantised field (integer destinations; its cast
+// fields to float16 / float32 run here too).  In one kernel with the float destinations the body
+// kept its 97 VGPRs, no scratch and four waves a SIMD but spilled 106 SGPRs into VGPR lanes
+// instead of 49: a kernel of its own, chosen per plan, leaves the float casts the
+// code they had.
+__global__ __launch_bounds__(gather::kThreads) void gather_quant_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  struct_share<2>(a, lds);
 }
 
 // The mask kernels' memory (gather_device.h mask::): the mask with one aligned 16-byte
@@ -939,7 +965,10 @@ int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStrea
     }
     // the body's stores are whole elements and whole 16-byte units of them
     const unsigned ds = f.cast.dst_bits / 8u;
-    if (gather::cast::src_kind(f.cast.src_code, f.cast.src_bits) < 0 || (ds != 2 && ds != 4) ||
+    const bool dst_ok = f.cast.quant()
+                            ? gather::cast::dst_kind(f.cast.dst_code, f.cast.dst_bits) >= 0
+                            : ds == 2 || ds == 4;
+    if (gather::cast::src_kind(f.cast.src_code, f.cast.src_bits) < 0 || !dst_ok ||
         (reinterpret_cast<uintptr_t>(f.gd.view.src) & (f.gd.elem - 1)))
       return fail(DORA_ERR_INVALID, "field %zu `%s`: not a cast this kernel runs", k,
                   f.name.c_str());
@@ -951,11 +980,13 @@ int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStrea
   const gather::multi::Args a =
       gather::multi::make_cast_args(g, c, off, tile_c, static_cast<int>(n), dst);
   const dim3 grid(gather::multi::grid_for(a));
+  bool quant = false;
+  for (size_t k = 0; k < n; ++k) quant |= c[k].quant();
+  auto* kernel = quant ? gather_quant_kernel : gather_cast_kernel;
   if (ev_start || ev_stop) {
-    hipExtLaunchKernelGGL(gather_cast_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
-                          ev_stop, 0, a);
+    hipExtLaunchKernelGGL(kernel, grid, dim3(gather::kThreads), 0, stream, ev_start, ev_stop, 0, a);
   } else {
-    hipLaunchKernelGGL(gather_cast_kernel, grid, dim3(gather::kThreads), 0, stream, a);
+    hipLaunchKernelGGL(kernel, grid, dim3(gather::kThreads), 0, stream, a);
   }
   DORA_HIP(hipGetLastError());
   return DORA_OK;

@@ -1057,6 +1057,27 @@ int dora_node_send_output_tensor_cast(dora_node* n, const char* output_id,
   DORA_GUARD_END
 }
 
+int dora_node_send_output_tensor_convert(dora_node* n, const char* output_id,
+                                         const dora_tensor_field* fields, size_t count,
+                                         const dora_tensor_cast* casts,
+                                         const dora_tensor_quant* quants,
+                                         ArrowDeviceType device_type, const uint8_t* params,
+                                         size_t params_len, uint32_t flags) {
+  if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  dora_plan* plan = nullptr;
+  {
+    dora::SubSpan sp(dora::SP_SEND_PLAN);
+    const int rc =
+        dora::build_tensor_convert_plan(fields, count, casts, quants, device_type, &plan);
+    if (rc != DORA_OK) return rc;
+  }
+  // (as the cast send: a host plan converted in its staging buffer, or a gather plan of one launch)
+  std::unique_ptr<dora_plan> owner(plan);
+  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
+  DORA_GUARD_END
+}
+
 int dora_node_send_output_tensor_list(dora_node* n, const char* output_id,
                                       const dora_tensor_list* list, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags) {

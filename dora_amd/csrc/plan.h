@@ -101,12 +101,18 @@ struct GatherDesc {
 // A field converted on send (dora_gpu_plan_tensor_cast): `count` elements of the source dtype
 // (a DLPack code and width, bfloat16 included) become float16 or float32, through float32 and one
 // optional float32 multiplication.  `on` false: the field is sent as it is.
+// A quantised field (dora_gpu_plan_tensor_convert) is the same with an integer destination:
+// `dst_code` DL_INT or DL_UINT, `dst_bits` 8 or 16, and the product rounded to the nearest
+// integer, clamped and moved by `zero_point` (cast_device.h).
 struct CastDesc {
   bool on = false;
   uint8_t src_code = 0, src_bits = 0, dst_bits = 0;
   uint32_t has_scale = 0;
   float scale = 1.0f;
   uint64_t count = 0;
+  uint8_t dst_code = 2;  // DL_FLOAT: a cast
+  int32_t zero_point = 0;
+  bool quant() const { return on && dst_code != 2; }
 };
 
 // One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
@@ -254,7 +260,8 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
 // follows on the same stream.  The bytes are pageable memory of the plan: the runtime has staged
 // them when the call returns.
 int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
-// Launch a cast plan's fields in one launch of gather_cast_kernel (kernels.hip): the cast fields
+// Launch a cast plan's fields in one launch of gather_cast_kernel (kernels.hip;
+// gather_quant_kernel when a field is quantised): the cast fields
 // converted element by element (cast_device.h), the others as launch_gather_struct moves them.
 // DORA_ERR_INVALID, nothing launched, when a cast field would not start on a multiple of its
 // destination element size.
@@ -305,6 +312,10 @@ uint64_t plan_workspace(const dora_plan& plan);
 // Tensors converted to float16 / float32 on send, bare or as a record (dora_gpu_plan_tensor_cast).
 int build_tensor_cast_plan(const dora_tensor_field* fields, size_t n, const dora_tensor_cast* casts,
                            ArrowDeviceType dev, dora_plan** out);
+// The same with fields quantised to uint8 / int8 / uint16 / int16 (dora_gpu_plan_tensor_convert).
+int build_tensor_convert_plan(const dora_tensor_field* fields, size_t n,
+                              const dora_tensor_cast* casts, const dora_tensor_quant* quants,
+                              ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -331,7 +342,7 @@ struct dora_plan {
   bool taken = false;
   bool take_on = false;
   // cast plans (tensor_plan.cpp) with device values: a gather whose fields, a bare tensor's one
-  // included, go through gather_cast_kernel (a host cast plan is converted in `staged`)
+  // included, go through gather_cast_kernel or gather_quant_kernel (a host cast plan is converted in `staged`)
   bool cast = false;
   // mask plans (tensor_plan.cpp) with device values: a gather without segments whose launches
   // compact `mask` into a workspace behind the sample and read every field through it (host

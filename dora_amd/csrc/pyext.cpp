@@ -381,10 +381,16 @@ PyObject* py_send_tensor_struct(PyObject*, PyObject* const* args, Py_ssize_t nar
 // send_tensor_list takes them; `casts` a tuple as long, each entry None (the field is sent as it
 // is) or (dtype_code, dtype_bits, scale or None).  Every capsule is consumed as send_tensor_struct
 // consumes its own.
-PyObject* py_send_tensor_cast(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
-  const char* usage = "send_tensor_cast(handle, output_id, names, capsules, casts, device_type, "
-                      "metadata, flags): names is None over one capsule or a tuple as long as the "
-                      "tuple of capsules; casts a tuple as long, of None or (code, bits, scale)";
+// send_tensor_convert takes the same arguments and sends as dora_node_send_output_tensor_convert:
+// an entry may then also be (dtype_code, dtype_bits, scale or None, zero_point), a quantised field.
+PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) {
+  const char* usage = convert
+      ? "send_tensor_convert(handle, output_id, names, capsules, entries, device_type, metadata, "
+        "flags): names is None over one capsule or a tuple as long as the tuple of capsules; "
+        "entries a tuple as long, of None, (code, bits, scale) or (code, bits, scale, zero_point)"
+      : "send_tensor_cast(handle, output_id, names, capsules, casts, device_type, "
+        "metadata, flags): names is None over one capsule or a tuple as long as the "
+        "tuple of capsules; casts a tuple as long, of None or (code, bits, scale)";
   if (nargs != 8 || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
       PyTuple_GET_SIZE(args[4]) != PyTuple_GET_SIZE(args[3]) ||
       !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
@@ -400,6 +406,7 @@ PyObject* py_send_tensor_cast(PyObject*, PyObject* const* args, Py_ssize_t nargs
   const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
   std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
   std::vector<dora_tensor_cast> casts(static_cast<size_t>(n));
+  std::vector<dora_tensor_quant> quants(convert ? static_cast<size_t>(n) : 0);
   std::vector<DlManaged*> managed(static_cast<size_t>(n));
   for (Py_ssize_t k = 0; k < n; ++k) {
     fields[size_t(k)].name = nullptr;
@@ -422,10 +429,12 @@ PyObject* py_send_tensor_cast(PyObject*, PyObject* const* args, Py_ssize_t nargs
     c = dora_tensor_cast{};
     PyObject* entry = PyTuple_GET_ITEM(args[4], k);
     if (entry == Py_None) continue;
-    if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 3) {
+    if (!PyTuple_Check(entry) ||
+        !(PyTuple_GET_SIZE(entry) == 3 || (convert && PyTuple_GET_SIZE(entry) == 4))) {
       PyErr_SetString(PyExc_TypeError, usage);
       return nullptr;
     }
+    const bool quant = PyTuple_GET_SIZE(entry) == 4;
     const long code = PyLong_AsLong(PyTuple_GET_ITEM(entry, 0));
     const long bits = PyLong_AsLong(PyTuple_GET_ITEM(entry, 1));
     if (PyErr_Occurred()) return nullptr;
@@ -433,14 +442,33 @@ PyObject* py_send_tensor_cast(PyObject*, PyObject* const* args, Py_ssize_t nargs
       PyErr_Format(PyExc_TypeError, "field %zd: cast dtype (code %ld, %ld bits)", k, code, bits);
       return nullptr;
     }
+    PyObject* scale = PyTuple_GET_ITEM(entry, 2);
+    double factor = 0.0;
+    if (scale != Py_None) {
+      factor = PyFloat_AsDouble(scale);
+      if (factor == -1.0 && PyErr_Occurred()) return nullptr;
+    }
+    if (quant) {
+      const long zp = PyLong_AsLong(PyTuple_GET_ITEM(entry, 3));
+      if (zp == -1 && PyErr_Occurred()) return nullptr;
+      if (zp < INT32_MIN || zp > INT32_MAX) {
+        PyErr_Format(PyExc_TypeError, "field %zd: zero point %ld", k, zp);
+        return nullptr;
+      }
+      dora_tensor_quant& q = quants[size_t(k)];
+      q = dora_tensor_quant{};
+      q.dtype_code = static_cast<uint8_t>(code);
+      q.dtype_bits = static_cast<uint8_t>(bits);
+      q.has_scale = scale != Py_None;
+      q.scale = static_cast<float>(factor);
+      q.zero_point = static_cast<int32_t>(zp);
+      continue;
+    }
     c.dtype_code = static_cast<uint8_t>(code);
     c.dtype_bits = static_cast<uint8_t>(bits);
-    PyObject* scale = PyTuple_GET_ITEM(entry, 2);
     if (scale != Py_None) {
-      const double v = PyFloat_AsDouble(scale);
-      if (v == -1.0 && PyErr_Occurred()) return nullptr;
       c.has_scale = 1;
-      c.scale = static_cast<float>(v);
+      c.scale = static_cast<float>(factor);
     }
   }
   const long dev = PyLong_AsLong(args[5]);
@@ -472,16 +500,30 @@ PyObject* py_send_tensor_cast(PyObject*, PyObject* const* args, Py_ssize_t nargs
   }
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  rc = dora_node_send_output_tensor_cast(static_cast<dora_node*>(h), oid, fields.data(),
-                                         fields.size(), casts.data(),
-                                         static_cast<ArrowDeviceType>(dev),
-                                         reinterpret_cast<const uint8_t*>(params.data()),
-                                         params.size(), static_cast<uint32_t>(flags));
+  if (convert)
+    rc = dora_node_send_output_tensor_convert(static_cast<dora_node*>(h), oid, fields.data(),
+                                              fields.size(), casts.data(), quants.data(),
+                                              static_cast<ArrowDeviceType>(dev),
+                                              reinterpret_cast<const uint8_t*>(params.data()),
+                                              params.size(), static_cast<uint32_t>(flags));
+  else
+    rc = dora_node_send_output_tensor_cast(static_cast<dora_node*>(h), oid, fields.data(),
+                                           fields.size(), casts.data(),
+                                           static_cast<ArrowDeviceType>(dev),
+                                           reinterpret_cast<const uint8_t*>(params.data()),
+                                           params.size(), static_cast<uint32_t>(flags));
   Py_END_ALLOW_THREADS
   // (deleters under the GIL and after the status has been taken, as in send_tensor)
   for (DlManaged* m : managed)
     if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
+}
+
+PyObject* py_send_tensor_cast(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  return send_converted(args, nargs, false);
+}
+PyObject* py_send_tensor_convert(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  return send_converted(args, nargs, true);
 }
 
 // send_tensor_list(handle, output_id, names, capsules, partition, form, partition_device,
@@ -1176,6 +1218,9 @@ PyMethodDef methods[] = {
     {"send_tensor_cast",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_cast)),
      METH_FASTCALL, "dora_node_send_output_tensor_cast of DLPack capsules, which it consumes."},
+    {"send_tensor_convert",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_convert)),
+     METH_FASTCALL, "dora_node_send_output_tensor_convert of DLPack capsules, which it consumes."},
     {"send_tensor_take",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_take)),
      METH_FASTCALL, "dora_node_send_output_tensor_take of DLPack capsules, which it consumes."},

@@ -24,8 +24,9 @@
 // view of the others.  A host index is checked and the rows gathered here; one in HBM is never
 // read, and the plan's one launch takes the rows by it (gather_device.h take::).
 //
-// Converted tensors (dora_gpu_plan_tensor_cast) are a tensor or a record laid out for the
-// destination dtypes: a cast field is validated and viewed as its source, and converted on the way
+// Converted tensors (dora_gpu_plan_tensor_cast; with quantised fields,
+// dora_gpu_plan_tensor_convert) are a tensor or a record laid out for the
+// destination dtypes: a cast or quantised field is validated and viewed as its source, and converted on the way
 // — by the CPU here for host values, by the plan's one launch for device values (cast_device.h).
 #include <cstring>
 #include <memory>
@@ -337,7 +338,9 @@ int describe_cast(const dora_tensor& t, const dora_tensor_cast& c, CastDesc& out
   if (c.dtype_bits == 0) return DORA_OK;
   if (c.dtype_code != DL_FLOAT || (c.dtype_bits != 16 && c.dtype_bits != 32))
     return fail(DORA_ERR_UNSUPPORTED, "cast destination dtype %s is not supported: float16 and "
-                "float32 are", dtype_name(c.dtype_code, c.dtype_bits, 1).c_str());
+                "float32 are (8- and 16-bit integers are quantised: "
+                "dora_gpu_plan_tensor_convert)",
+                dtype_name(c.dtype_code, c.dtype_bits, 1).c_str());
   if (c.has_scale && !std::isfinite(c.scale))
     return fail(DORA_ERR_INVALID, "cast scale %f is not finite", static_cast<double>(c.scale));
   if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
@@ -354,18 +357,68 @@ int describe_cast(const dora_tensor& t, const dora_tensor_cast& c, CastDesc& out
   return DORA_OK;
 }
 
+// What quantises `t` (dora_gpu_plan_tensor_convert): dtype_bits == 0 does not; any other entry
+// does, whatever the source dtype (no identity rule).  UNSUPPORTED naming the dtype, INVALID.
+int describe_quant(const dora_tensor& t, const dora_tensor_quant& q, CastDesc& out) {
+  out = CastDesc{};
+  if (q.dtype_bits == 0) return DORA_OK;
+  const int kind = gather::cast::dst_kind(q.dtype_code, q.dtype_bits);
+  if (kind < 0)
+    return fail(DORA_ERR_UNSUPPORTED, "quantise destination dtype %s is not supported: uint8, "
+                "int8, uint16 and int16 are",
+                dtype_name(q.dtype_code, q.dtype_bits, 1).c_str());
+  const int32_t lo = gather::cast::dst_lo(static_cast<uint32_t>(kind)),
+                hi = gather::cast::dst_hi(static_cast<uint32_t>(kind));
+  if (q.zero_point < lo || q.zero_point > hi)
+    return fail(DORA_ERR_INVALID, "quantise zero point %d is outside the range [%d, %d] of %s",
+                q.zero_point, lo, hi, dtype_name(q.dtype_code, q.dtype_bits, 1).c_str());
+  if (q.has_scale && !std::isfinite(q.scale))
+    return fail(DORA_ERR_INVALID, "quantise scale %f is not finite", static_cast<double>(q.scale));
+  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
+    return fail(DORA_ERR_UNSUPPORTED, "quantise source dtype %s is not supported: uint8, int8, "
+                "uint16, int16, float16, bfloat16 and float32 are",
+                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  out.on = true;
+  out.src_code = t.dtype_code;
+  out.src_bits = t.dtype_bits;
+  out.dst_code = q.dtype_code;
+  out.dst_bits = q.dtype_bits;
+  out.has_scale = q.has_scale ? 1 : 0;
+  out.scale = q.has_scale ? q.scale : 1.0f;
+  out.zero_point = q.zero_point;
+  return DORA_OK;
+}
+
+// What converts field `t`: its cast entry, its quantise entry, or neither (`c`, `q` may be NULL).
+// A field with both is INVALID.
+int describe_convert(const dora_tensor& t, const dora_tensor_cast* c, const dora_tensor_quant* q,
+                     CastDesc& out) {
+  out = CastDesc{};
+  if (c && q && c->dtype_bits && q->dtype_bits)
+    return fail(DORA_ERR_INVALID, "the field is both cast and quantised: one conversion a field");
+  if (q && q->dtype_bits) return describe_quant(t, *q, out);
+  return c ? describe_cast(t, *c, out) : DORA_OK;
+}
+
 // The CPU's conversion of a cast field: the view's rows in row-major order, each element through
 // the integer routines of cast_device.h, into `dst` (any alignment).
 template <uint32_t K>
 void cast_row(const uint8_t* src, uint64_t n, const CastDesc& c, uint8_t* dst) {
   constexpr int S = gather::cast::kSize<K>;
   const gather::cast::HostCvt cv;
+  const bool quant = c.quant();
+  const int dk = quant ? gather::cast::dst_kind(c.dst_code, c.dst_bits) : 0;
+  const int32_t lo = quant ? gather::cast::dst_lo(uint32_t(dk)) - c.zero_point : 0,
+                hi = quant ? gather::cast::dst_hi(uint32_t(dk)) - c.zero_point : 0;
   for (uint64_t i = 0; i < n; ++i) {
     uint32_t raw = 0;
     std::memcpy(&raw, src + i * S, S);  // (little-endian)
     float y = cv.to_f32<K>(raw);
     if (c.has_scale) y = cv.mul(y, c.scale);
-    if (c.dst_bits == 16) {
+    if (quant) {
+      const uint32_t q = static_cast<uint32_t>(cv.to_int(y, lo, hi, c.zero_point));
+      std::memcpy(dst + (c.dst_bits / 8u) * i, &q, c.dst_bits / 8u);  // (little-endian)
+    } else if (c.dst_bits == 16) {
       const uint16_t h = static_cast<uint16_t>(cv.to_f16(y));
       std::memcpy(dst + 2 * i, &h, 2);
     } else {
@@ -479,12 +532,14 @@ struct FieldLayout {
 // field is a tensor of its own (no name; its chain's head is called `head`).
 // `taken` >= 0: the fields of a take of that many rows (describe_taken): every leaf, type and
 // byte count has the leading extent `taken` where the field's own is N.
-// `casts` (n entries, never with `taken`): field k converted by casts[k] (describe_cast) is
+// `casts`, `quants` (n entries each or NULL, never with `taken`): field k converted by casts[k]
+// or quantised by quants[k] (describe_convert) is
 // validated and viewed as its source — the view and its reach in source bytes — while its leaf,
 // byte count and padding are the destination dtype's.
 int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                   const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
-                  FieldLayout& lay, int64_t taken = -1, const dora_tensor_cast* casts = nullptr) {
+                  FieldLayout& lay, int64_t taken = -1, const dora_tensor_cast* casts = nullptr,
+                  const dora_tensor_quant* quants = nullptr) {
   p.fields.resize(n);
   lay.chains.resize(n);
   lay.kids.resize(n);
@@ -503,7 +558,7 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     TensorView v;
     int64_t stride0 = 0;
     CastDesc cd;
-    int rc = casts ? describe_cast(t, casts[k], cd) : DORA_OK;
+    int rc = describe_convert(t, casts ? &casts[k] : nullptr, quants ? &quants[k] : nullptr, cd);
     if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
     if (cd.on) {
       // the view of the source: any accepted dtype of its width describes it (Arrow has no
@@ -518,7 +573,11 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
                   cd.src_bits / 8u);
       if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
       cd.count = v.bytes / (cd.src_bits / 8u);
-      v.leaf = cd.dst_bits == 16 ? "e" : "f";
+      if (cd.quant())
+        v.leaf = cd.dst_code == DL_UINT ? (cd.dst_bits == 8 ? "C" : "S")
+                                        : (cd.dst_bits == 8 ? "c" : "s");
+      else
+        v.leaf = cd.dst_bits == 16 ? "e" : "f";
       v.bytes = cd.count * (cd.dst_bits / 8u);  // (at most twice the source's, which is < 2^63)
       if (v.bytes >> 63) {
         rc = fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
@@ -699,7 +758,8 @@ void place_masked_host(dora_plan& p, const MaskIn& mk, uint64_t staged) {
 // A tensor (`bare`: one field without a name) or a record of tensors as one message; with `tk`
 // the rows of it that the index takes.
 int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
-                 const TakeIn* tk, dora_plan** out, const dora_tensor_cast* casts = nullptr) {
+                 const TakeIn* tk, dora_plan** out, const dora_tensor_cast* casts = nullptr,
+                 const dora_tensor_quant* quants = nullptr) {
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
@@ -707,7 +767,7 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   FieldLayout lay;
   std::vector<TypeInfoNode> solo;
   const int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
-                               tk ? static_cast<int64_t>(tk->ix.count) : -1, casts);
+                               tk ? static_cast<int64_t>(tk->ix.count) : -1, casts, quants);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
   if (bare) {
@@ -795,6 +855,34 @@ int build_tensor_cast_plan(const dora_tensor_field* f, size_t n, const dora_tens
     return bare ? build_tensor_plan(&f[0].tensor, dev, out)
                 : build_tensor_struct_plan(f, n, dev, out);
   return build_record(f, n, dev, bare, nullptr, out, casts);
+}
+
+int build_tensor_convert_plan(const dora_tensor_field* f, size_t n, const dora_tensor_cast* casts,
+                              const dora_tensor_quant* quants, ArrowDeviceType dev,
+                              dora_plan** out) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a conversion has values: at least one field");
+  if (n > kMaxStructFields)
+    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
+                kMaxStructFields, n);
+  const bool bare = n == 1 && !f[0].name;
+  // every entry's own refusals first; no field quantised: what the cast plan is, whatever it is
+  bool quantised = false;
+  for (size_t k = 0; k < n; ++k) {
+    CastDesc cd;
+    const int rc = describe_convert(f[k].tensor, casts ? &casts[k] : nullptr,
+                                    quants ? &quants[k] : nullptr, cd);
+    if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, f[k].name);
+    quantised |= cd.quant();
+  }
+  if (!quantised) {
+    if (casts) return build_tensor_cast_plan(f, n, casts, dev, out);
+    return bare ? build_tensor_plan(&f[0].tensor, dev, out)
+                : build_tensor_struct_plan(f, n, dev, out);
+  }
+  return build_record(f, n, dev, bare, nullptr, out, casts, quants);
 }
 
 namespace {
@@ -1231,6 +1319,12 @@ int dora_gpu_plan_tensor_cast(const dora_tensor_field* fields, size_t n,
                               const dora_tensor_cast* casts, ArrowDeviceType device_type,
                               dora_plan** out) {
   return dora::build_tensor_cast_plan(fields, n, casts, device_type, out);
+}
+
+int dora_gpu_plan_tensor_convert(const dora_tensor_field* fields, size_t n,
+                                 const dora_tensor_cast* casts, const dora_tensor_quant* quants,
+                                 ArrowDeviceType device_type, dora_plan** out) {
+  return dora::build_tensor_convert_plan(fields, n, casts, quants, device_type, out);
 }
 
 int dora_gpu_plan_tensor_take(const dora_tensor_take* take, ArrowDeviceType device_type,

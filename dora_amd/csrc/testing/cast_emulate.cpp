@@ -1,4 +1,4 @@
-// Host emulation of gather_cast_kernel (cast_device.h, and gather_device.h's rows body for the
+// Host emulation of gather_cast_kernel and gather_quant_kernel (cast_device.h, and gather_device.h's rows body for the
 // fields that are not cast), a stand-alone program that tests/test_cast_index_host.py compiles
 // with the host compiler and -fsanitize=address,undefined and runs once per group of cases; it is
 // part of no library.
@@ -24,6 +24,8 @@
 // then per field
 //   cast src_code src_bits dst_bits has_scale scale_bits count elem row src_total dst_bytes lo hi
 //   src_addr off nd shape[nd] stride[nd] source_file
+// `cast` 2: the field is quantised; two more integers follow `cast` at once, `dst_code` (DLPack: 0
+// int, 1 uint) and `zero_point`, and `dst_bits` is 8 or 16 (tests/test_quant_index_host.py).
 // `cast` 1: the field is converted (`src_code` / `src_bits` the DLPack source dtype, `dst_bits` 16
 // or 32, `scale_bits` the float32 factor's bit pattern, `count` elements); `elem`, `row`,
 // `src_total`, [lo, hi], shape and stride describe the source view in source bytes, `dst_bytes` /
@@ -184,12 +186,15 @@ int main(int argc, char** argv) {
     std::vector<EmuMem> mem(static_cast<size_t>(n));
     for (int k = 0; k < n; ++k) {
       uint64_t src = 0;
-      uint32_t on = 0, code = 0, sbits = 0, dbits = 0, has_scale = 0, scale_bits = 0;
+      uint32_t on = 0, code = 0, sbits = 0, dbits = 0, has_scale = 0, scale_bits = 0, dcode = 2;
+      int32_t zp = 0;
       std::string file;
-      in >> on >> code >> sbits >> dbits >> has_scale >> scale_bits >> c[k].count >> g[k].elem >>
+      in >> on;
+      if (on == 2) in >> dcode >> zp;
+      in >> code >> sbits >> dbits >> has_scale >> scale_bits >> c[k].count >> g[k].elem >>
           g[k].view.row >> g[k].view.total >> dst_bytes[k] >> g[k].lo >> g[k].hi >> src >> off[k] >>
           g[k].view.nd;
-      if (!in || g[k].view.nd < 0 || g[k].view.nd > dora::kMaxTensorDims || on > 1) {
+      if (!in || g[k].view.nd < 0 || g[k].view.nd > dora::kMaxTensorDims || on > 2) {
         std::printf("FAIL bad field %d of case %d\n", k, g_case);
         return 2;
       }
@@ -206,7 +211,14 @@ int main(int argc, char** argv) {
       c[k].dst_bits = uint8_t(dbits);
       c[k].has_scale = has_scale;
       c[k].scale = ct::f32_of(scale_bits);
-      if (c[k].on && (ct::src_kind(code, sbits) < 0 || (dbits != 16 && dbits != 32) ||
+      c[k].dst_code = uint8_t(dcode);
+      c[k].zero_point = zp;
+      const bool dst_ok =
+          on == 2 ? ct::dst_kind(dcode, dbits) >= 0 &&
+                        zp >= ct::dst_lo(uint32_t(ct::dst_kind(dcode, dbits))) &&
+                        zp <= ct::dst_hi(uint32_t(ct::dst_kind(dcode, dbits)))
+                  : dbits == 16 || dbits == 32;
+      if (c[k].on && (ct::src_kind(code, sbits) < 0 || !dst_ok ||
                       c[k].count * (dbits / 8) != dst_bytes[k] || sbits / 8 != g[k].elem)) {
         std::printf("FAIL field %d of case %d is no cast\n", k, g_case);
         return 2;

@@ -420,6 +420,19 @@ int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, i
   return DORA_OK;
 }
 
+int dora_gpu_test_plan_quant(const dora_plan* plan, size_t i, int* is_quant, int* dst_code,
+                             int* dst_bits, int* zero_point) {
+  if (!plan || !plan->dev_tensor || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a device plan with a field %zu", i);
+  const dora::CastDesc& c = plan->fields[i].cast;
+  const bool q = plan->cast && c.quant();
+  if (is_quant) *is_quant = q;
+  if (dst_code) *dst_code = q ? c.dst_code : -1;
+  if (dst_bits) *dst_bits = q ? c.dst_bits : 0;
+  if (zero_point) *zero_point = q ? c.zero_point : 0;
+  return DORA_OK;
+}
+
 int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mask, uint64_t* n,
                             int64_t* lo, int64_t* hi, uint64_t* workspace, uint64_t* part_words,
                             int64_t* stride0) {

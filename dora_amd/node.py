@@ -33,6 +33,7 @@ _DL_CPU = 1
 _DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinned)
 from .device import DeviceArray, DeviceBuffer
 from .tensor import Cast as _Cast
+from .tensor import Quantized as _Quantized
 from .tensor import Ragged as _Ragged
 from .tensor import Masked as _Masked
 from .tensor import Taken as _Taken
@@ -236,6 +237,9 @@ class Node:
                                       ctypes.addressof(c.schema), ARROW_DEVICE_CPU, metadata)
         elif hasattr(data, "__dlpack__") and hasattr(data, "__dlpack_device__"):
             rc = self._send_tensor(output_id, data, metadata, f)
+        elif isinstance(data, _Quantized) or (isinstance(data, dict) and any(
+                isinstance(v, _Quantized) for v in data.values())):
+            rc = self._send_tensor_convert(output_id, data, metadata, f)
         elif isinstance(data, _Cast) or (isinstance(data, dict) and
                                          any(isinstance(v, _Cast) for v in data.values())):
             rc = self._send_tensor_cast(output_id, data, metadata, f)
@@ -254,7 +258,7 @@ class Node:
                             "(dora_amd.tensor.take) or selected by a mask "
                             "(dora_amd.tensor.masked), a ragged batch of any of these "
                             "(dora_amd.tensor.ragged) or tensors converted on send "
-                            "(dora_amd.tensor.cast)")
+                            "(dora_amd.tensor.cast, dora_amd.tensor.quantize)")
         if rc:
             _lib.check(rc)
 
@@ -487,6 +491,57 @@ class Node:
             return rc
         return _fast.send_tensor_cast(self.handle, output_id, names, caps, entries, dev, metadata,
                                       flags)
+
+    def _send_tensor_convert(self, output_id: str, data, metadata, flags: int) -> int:
+        """A tensor quantised on send (dora_amd.tensor.quantize), or a dict of tensors of which
+        some are quantised, some perhaps cast and the rest plain, as the tensor or Struct message
+        of the converted values (dora_node_send_output_tensor_convert).  Everything else is
+        `_send_tensor_cast`'s: host tensors converted by the CPU inside the call, tensors on this
+        node's GPU by one kernel launch after the `__dlpack__` handshake."""
+        record = isinstance(data, dict)
+        items = data if record else {None: data}
+        conv = (_Cast, _Quantized)
+        casts = [v if isinstance(v, _Cast) else None for v in items.values()]
+        quants = [v if isinstance(v, _Quantized) else None for v in items.values()]
+        plain = {k: (v.values if isinstance(v, conv) else v) for k, v in items.items()}
+        kind, tensors, names = self._values_kind(plain if record else plain[None])
+        # (a cast entry has three items, a quantise entry four)
+        entries = tuple(v._entry() if isinstance(v, conv) else None for v in items.values())
+        if kind == "device":
+            _require_one_hip_runtime()
+            held = bool(flags & SEND_ASYNC) or self._async_default
+            if held and len(self._async_tensors) + len(tensors) > self._ASYNC_TENSORS_MAX:
+                self.sync()
+            stream = int(self._lib.dora_node_stream(self.handle))
+            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
+            rc = _fast.send_tensor_convert(self.handle, output_id, names, caps, entries,
+                                           ARROW_DEVICE_ROCM, metadata, flags)
+            if held and not rc:
+                self._async_tensors.extend(tensors)
+            return rc
+        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
+        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
+        try:
+            caps = tuple(v.__dlpack__() for v in tensors)
+        except BufferError:
+            # (read-only numpy arrays: every field through its array interface)
+            if not all(hasattr(v, "__array_interface__") for v in tensors):
+                raise
+            from ._lib import Tensor
+            from .tensor import (_describe_array, _describe_casts, _describe_list,
+                                 _describe_quants)
+            described = [_describe_array(v) for v in tensors]
+            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
+                                       ARROW_DEVICE_CPU)
+            carr, qarr = _describe_casts(casts), _describe_quants(quants)
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_convert(
+                self.handle, output_id.encode(), lst.fields, len(tensors), carr, qarr, dev,
+                params, len(params), flags)
+            del keep, described, carr, qarr
+            return rc
+        return _fast.send_tensor_convert(self.handle, output_id, names, caps, entries, dev,
+                                         metadata, flags)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
         """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with

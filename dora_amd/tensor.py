@@ -85,8 +85,28 @@ inf — `from_numpy_cast` states it in numpy and the send is bit-exact against i
 payload of a NaN.  Multiplying by `1 / 255` is not dividing by 255: the two differ in the last bit
 for some inputs.  Host tensors are converted by the CPU inside the send; tensors in this node's
 HBM by the send's one kernel launch, which reads the source once and writes the sample once, no
-`.to(dtype)` and no intermediate tensor.  Not offered: a cast under `ragged` or `take`, integer
-and bfloat16 destinations.
+`.to(dtype)` and no intermediate tensor.  Not offered: a cast under `ragged` or `take`, bfloat16
+destinations; integer destinations are `quantize`.
+
+A tensor of float results that its consumers read as small integers — a mask or heat map in
+[0, 1] as uint8 pixels, depth in metres as uint16 millimetres, activations as int8 — is quantised
+inside the send: `quantize(x, dtype, scale=None, zero_point=0)` stands for "`x` quantised to
+`dtype`" (uint8, int8, uint16 or int16, from the seven cast sources) and is sent as exactly the
+message the quantised tensor would be, bare or as a value of a dict next to plain and `cast`
+fields:
+
+    node.send_output("mask", tensor.quantize(prob.permute(1, 2, 0), "uint8", scale=255))
+    node.send_output("depth", tensor.quantize(metres, "uint16", scale=1000))
+    node.send_output("out", {"mask": tensor.quantize(m, "uint8", 255), "feat": tensor.cast(f, "float32")})
+
+Element by element, `[lo, hi]` the range of `dtype`: `y = float32(x) * float32(scale)` (one
+float32 multiplication), `r = rint(y)` (ties to even), a NaN counts as 0, and
+`q = int32(clip(r, lo - zero_point, hi - zero_point)) + zero_point`, so infinities and anything out
+of range saturate.  `zero_point` is an integer in `[lo, hi]`.  `from_numpy_quantize` states it in
+numpy and every send, from host and from device, is bit-exact against it for every input.  In
+place of `x.mul(255).round().clamp(0, 255).to(torch.uint8)` and its launches and intermediates
+the send's one launch reads the source once and writes a sample a half or a quarter the size.
+Not offered: a quantise under `ragged`, `take` or `masked`; per-channel scales.
 
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
 is copied once, so every source has been read when `send_output` returns.  A tensor in device
@@ -98,7 +118,8 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import Tensor, TensorCast, TensorField, TensorList, TensorMask, TensorTake
+from ._lib import (Tensor, TensorCast, TensorField, TensorList, TensorMask, TensorQuant,
+                   TensorTake)
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -229,9 +250,16 @@ def _has_cast(values):
     return isinstance(values, Cast)
 
 
+def _has_quantized(values):
+    if isinstance(values, dict):
+        return any(isinstance(v, Quantized) for v in values.values())
+    return isinstance(values, Quantized)
+
+
 def _cast_dtype(dtype):
-    """(DLPack code, bits, name) of a cast destination given as a name, a numpy dtype or a torch
-    dtype; the library refuses all but float16 and float32."""
+    """(DLPack code, bits, name) of a cast or quantise destination given as a name, a numpy dtype
+    or a torch dtype; the library refuses all but float16 and float32 (a cast) or uint8, int8,
+    uint16 and int16 (a quantise)."""
     import numpy as np
     if str(dtype).startswith("torch."):
         name = str(dtype)[len("torch."):]
@@ -271,6 +299,9 @@ def cast(values, dtype, scale=None):
     (or the numpy or torch dtype), `scale` an optional finite factor applied in float32 first.
     `send_output` sends it, on its own or as a value of a dict of tensors, as what
     `from_numpy_cast` states."""
+    if isinstance(values, Quantized):
+        raise TypeError("cast of a quantised tensor is not offered: a field is cast or quantised, "
+                        "not both")
     if isinstance(values, (Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("cast converts one tensor: give a dict's fields a cast each; a cast under "
                         "ragged or take is not offered")
@@ -293,6 +324,75 @@ def from_numpy_cast(x, dtype, scale=None, *, bfloat16=False):
         return from_numpy(y.astype(np.dtype(_cast_dtype(dtype)[2])))
 
 
+class Quantized:
+    """A tensor quantised on send: `values`, a tensor, the integer `dtype` it is sent as, the
+    optional `scale` it is multiplied by first and the `zero_point` added last.  It copies and
+    converts nothing itself.  Build one with `quantize`."""
+
+    __slots__ = ("values", "dtype", "scale", "zero_point", "_code", "_bits")
+
+    def __init__(self, values, dtype, scale=None, zero_point=0):
+        import operator
+        self.values = values
+        self._code, self._bits, self.dtype = _cast_dtype(dtype)
+        self.scale = None if scale is None else float(scale)
+        try:
+            self.zero_point = operator.index(zero_point)
+        except TypeError:
+            raise TypeError(f"quantize: the zero point {zero_point!r} is not an integer (per-channel "
+                            "zero points and scales are not offered)") from None
+        if not -2 ** 31 <= self.zero_point < 2 ** 31:
+            raise ValueError(f"quantize: the zero point {self.zero_point} is outside every "
+                             "destination's range")
+
+    def _entry(self):
+        return (self._code, self._bits, self.scale, self.zero_point)
+
+    def __repr__(self):
+        by = "" if self.scale is None else f" * {self.scale!r}"
+        zp = "" if not self.zero_point else f" + {self.zero_point}"
+        return f"Quantized({self.values!r}{by}{zp} -> {self.dtype})"
+
+
+def quantize(values, dtype, scale=None, zero_point=0):
+    """`values` quantised to `dtype` as a message: `values` a tensor of uint8, int8, uint16, int16,
+    float16, bfloat16 or float32 (host memory or this node's HBM), `dtype` "uint8", "int8",
+    "uint16" or "int16" (or the numpy or torch dtype), `scale` an optional finite factor applied in
+    float32 first, `zero_point` an integer in the range of `dtype`.  `send_output` sends it, on its
+    own or as a value of a dict of tensors, as what `from_numpy_quantize` states."""
+    if isinstance(values, (Quantized, Cast, Taken, Masked, Ragged, dict)):
+        raise TypeError("quantize converts one tensor: give a dict's fields a quantize each; a "
+                        "quantise of a cast, or under ragged, take or masked, is not offered")
+    if scale is not None and not isinstance(scale, (int, float)):
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise TypeError("quantize: the scale is one number (per-channel scales are not "
+                            "offered)") from None
+    return Quantized(values, dtype, scale, zero_point)
+
+
+def from_numpy_quantize(x, dtype, scale=None, zero_point=0, *, bfloat16=False):
+    """The nested pyarrow array of `x` quantised to `dtype`, the statement of record of `quantize`:
+    what `send_output(output_id, quantize(x, dtype, scale, zero_point))` puts on the wire.
+    `bfloat16`: `x` holds the bits of bfloat16 values as uint16."""
+    import numpy as np
+    x = np.asarray(x)
+    if bfloat16:
+        x = (x.astype(np.uint32) << 16).view(np.float32)
+    dt = np.dtype(_cast_dtype(dtype)[2])
+    info = np.iinfo(dt)
+    zp = int(zero_point)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        y = x.astype(np.float32)
+        if scale is not None:
+            y = y * np.float32(scale)
+        r = np.rint(y)
+        r = np.where(np.isnan(y), np.float32(0), r)
+        r = np.clip(r, np.float32(info.min - zp), np.float32(info.max - zp))
+        return from_numpy((r.astype(np.int32) + np.int32(zp)).astype(dt))
+
+
 def take(values, index):
     """`values[index]` along dimension 0 as a message: `values` a tensor or a dict of at most 8
     tensors sharing their leading extent N, `index` a 1-D sequence or tensor of K int32 or int64
@@ -303,6 +403,9 @@ def take(values, index):
     if _has_cast(values):
         raise TypeError("cast under take is not offered: convert the taken rows with .to(dtype), "
                         "or send the cast without the take")
+    if _has_quantized(values):
+        raise TypeError("quantize under take is not offered: quantise the taken rows yourself, or "
+                        "send the quantised tensor without the take")
     return Taken(values, index)
 
 
@@ -317,6 +420,9 @@ def masked(values, mask):
     if _has_cast(values):
         raise TypeError("cast under a mask is not offered: convert the values with .to(dtype), or "
                         "send the cast without the mask")
+    if _has_quantized(values):
+        raise TypeError("quantize under a mask is not offered: quantise the values yourself, or "
+                        "send the quantised tensor without the mask")
     return Masked(values, mask)
 
 
@@ -329,6 +435,9 @@ def ragged(values, *, lengths=None, offsets=None):
     if _has_cast(values):
         raise TypeError("cast under ragged is not offered: convert the values with .to(dtype), or "
                         "send the cast without the partition")
+    if _has_quantized(values):
+        raise TypeError("quantize under ragged is not offered: quantise the values yourself, or "
+                        "send the quantised tensor without the partition")
     return Ragged(values, offsets=offsets, lengths=lengths)
 
 
@@ -537,6 +646,20 @@ def _describe_casts(casts) -> "ctypes.Array":
     return arr
 
 
+def _describe_quants(quants) -> "ctypes.Array":
+    """The `dora_tensor_quant` array of `quants`, each a `Quantized` or None (the field is not
+    quantised)."""
+    arr = (TensorQuant * len(quants))()
+    for k, q in enumerate(quants):
+        if q is None:
+            continue
+        arr[k].dtype_code, arr[k].dtype_bits = q._code, q._bits
+        arr[k].has_scale = 0 if q.scale is None else 1
+        arr[k].scale = 0.0 if q.scale is None else q.scale
+        arr[k].zero_point = q.zero_point
+    return arr
+
+
 def _describe_list(names, tensors, partition, form, partition_device) -> tuple:
     """The `dora_tensor_list` over the `Tensor`s of `_describe` (`names` None: the one bare
     tensor) and the partition's `Tensor`, and what the caller keeps alive with it."""
@@ -603,4 +726,4 @@ def _describe_mask(names, tensors, mask, mask_device, partition, form,
 __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_numpy_struct",
            "from_numpy_ragged", "from_numpy_take", "from_numpy_masked", "to_numpy", "to_torch",
            "Ragged", "ragged", "Taken", "take", "Masked", "masked", "Cast", "cast",
-           "from_numpy_cast"]
+           "from_numpy_cast", "Quantized", "quantize", "from_numpy_quantize"]

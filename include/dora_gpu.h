@@ -431,7 +431,8 @@ int dora_gpu_plan_tensor_mask(const dora_tensor_mask* mask, ArrowDeviceType devi
  *   every value of each is exact in float32, so to_f32 never rounds.  int32, int64, float64, bool,
  *   complex and anything else are DORA_ERR_UNSUPPORTED as cast sources, naming the dtype.
  *   Destinations: float16 and float32 (code 2, 16 or 32 bits); anything else is
- *   DORA_ERR_UNSUPPORTED (float-to-integer and bfloat16 destinations are not provided).
+ *   DORA_ERR_UNSUPPORTED (float-to-integer and bfloat16 destinations are not provided by a cast;
+ *   saturating integer destinations are dora_gpu_plan_tensor_convert's quantise, below).
  *   Scale (has_scale != 0): a finite float32; NaN or infinite is DORA_ERR_INVALID.  The product is
  *   one IEEE float32 multiplication, round to nearest even, subnormals kept.  to_dst for float16
  *   is one round-to-nearest-even conversion: overflow gives +-inf, float16 subnormals are produced,
@@ -467,6 +468,52 @@ typedef struct dora_tensor_cast { /* dtype_bits == 0: this field is sent as it i
 int dora_gpu_plan_tensor_cast(const dora_tensor_field* fields, size_t n,
                               const dora_tensor_cast* casts /* n entries */,
                               ArrowDeviceType device_type, dora_plan** out);
+/*
+ * Quantised tensors as one message: field k "quantised to quants[k]'s dtype", next to fields that
+ * are cast (casts[k]) and fields sent as they are, through the same read of the source and the
+ * same write of the sample as dora_gpu_plan_tensor_cast.  `fields` as there; `casts` and `quants`
+ * are each NULL or n entries, and an entry with dtype_bits == 0 leaves its field alone.  On the
+ * wire the message is exactly what planning the quantised tensors gives: type info, sample size
+ * and leaf offsets of tensors of the destination dtypes with the same shapes.  With no quantised
+ * field the call plans exactly as dora_gpu_plan_tensor_cast does (a NULL `casts`: as one whose
+ * entries all have dtype_bits == 0).
+ *
+ * Element by element, [lo, hi] the destination's range:
+ *   y = float32(x) [* float32(scale)]     one IEEE float32 multiplication, as in a cast
+ *   r = rint(y)                           float32, ties to even (exact: no second rounding)
+ *   r = 0 where y is a NaN                a NaN is the real value 0, so it becomes zero_point
+ *   q = int32(clip(r, lo - zero_point, hi - zero_point)) + zero_point        +-inf saturate
+ *   Sources: the seven cast sources; anything else is DORA_ERR_UNSUPPORTED, as in a cast.
+ *   Destinations: uint8, int8, uint16, int16 (DLPack code 1 or 0, 8 or 16 bits); anything else
+ *   (int32, uint32, int64, float, bool ..) is DORA_ERR_UNSUPPORTED, naming the dtype and the field.
+ *   zero_point: an integer in [lo, hi], so both clip bounds are exact in float32; outside it
+ *   DORA_ERR_INVALID.  Scale: a finite float32; NaN or infinite is DORA_ERR_INVALID.
+ *   A field with both a cast and a quantise entry is DORA_ERR_INVALID.  There is no identity rule:
+ *   a quantise is always a conversion (uint8 to uint8 without a scale runs, and changes nothing).
+ *   The statement of record is numpy's: np.rint, np.where(np.isnan ..), np.clip, then
+ *   .astype(int32) + zero_point, then .astype(dst).  Results are bit-exact against it for every
+ *   input: NaNs, infinities, -0.0 and subnormals included.
+ *
+ * Host values: gathered and quantised by the CPU inside this call into the plan's staging buffer;
+ * every source has been read on return.  Device values: never read on the host; any converted
+ * field makes the plan one launch and no segments (gather_quant_kernel, gfx950, when a field is
+ * quantised), each field's reach computed with the source
+ * element size and held against its allocation before anything is launched.  dora_gpu_pack to a
+ * destination where a 16-bit field would start on an odd address is DORA_ERR_INVALID with nothing
+ * launched.
+ * Not provided: a quantise under a ragged batch, a take or a mask; per-channel scales.
+ */
+typedef struct dora_tensor_quant { /* dtype_bits == 0: this field is not quantised */
+  uint8_t dtype_code;
+  uint8_t dtype_bits;
+  uint16_t has_scale;
+  float scale;
+  int32_t zero_point;
+} dora_tensor_quant;
+int dora_gpu_plan_tensor_convert(const dora_tensor_field* fields, size_t n,
+                                 const dora_tensor_cast* casts /* NULL or n entries */,
+                                 const dora_tensor_quant* quants /* NULL or n entries */,
+                                 ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -706,6 +753,15 @@ int dora_node_send_output_tensor_cast(dora_node* node, const char* output_id,
                                       const dora_tensor_field* fields, size_t n,
                                       const dora_tensor_cast* casts, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags);
+/* Send quantised, cast and plain tensors as one message (dora_gpu_plan_tensor_convert: semantics,
+ * wire form, refusals), with the contract of dora_node_send_output_tensor_cast: host values read
+ * and converted on return, device values in one launch on a fill stream. */
+int dora_node_send_output_tensor_convert(dora_node* node, const char* output_id,
+                                         const dora_tensor_field* fields, size_t n,
+                                         const dora_tensor_cast* casts,
+                                         const dora_tensor_quant* quants,
+                                         ArrowDeviceType device_type, const uint8_t* params,
+                                         size_t params_len, uint32_t flags);
 /* Send rows selected by a mask (dora_gpu_plan_tensor_mask: wire form, where the mask lives,
  * refusals), with the contract of the take send: host values with a host mask take every path of
  * a host plan and everything has been read on return; device values with a device mask go where

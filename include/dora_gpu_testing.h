@@ -115,6 +115,13 @@ int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, i
                             int* src_code, int* src_bits, int* dst_code, int* dst_bits,
                             int* has_scale, float* scale, uint64_t* elements,
                             uint64_t* src_bytes, uint64_t* dst_bytes);
+/* Test tool (host only): whether field `i` of a device plan of dora_gpu_plan_tensor_convert is
+ * quantised (*is_quant 1): then *dst_code / *dst_bits the integer destination (DLPack) and
+ * *zero_point; else -1, 0 and 0.  dora_gpu_test_plan_cast reports the rest of such a field as it
+ * does of a cast one — source dtype, scale, element and byte counts, *dst_bits — with *is_cast 1
+ * and *dst_code 2 as for every converted field. */
+int dora_gpu_test_plan_quant(const dora_plan* plan, size_t i, int* is_quant, int* dst_code,
+                             int* dst_bits, int* zero_point);
 /* Test tool (host only): whether `plan` is a mask plan (dora_gpu_plan_tensor_mask; DORA_ERR_INVALID
  * for any other plan) and what it selects by.  *n the rows of the source.  *device 1 if the plan's
  * launches read the mask in HBM: then *mask its bytes, [*lo, *hi] the bytes from *mask that are
