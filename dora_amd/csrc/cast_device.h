@@ -381,28 +381,12 @@ namespace multi {
 // field gets the grid its body would have on its own.
 DORA_HD Args make_cast_args(const GatherDesc* g, const CastDesc* c, const uint64_t* off,
                             const int* tile_c, int n, uint8_t* dst) {
-  Args a{};
-  a.n = static_cast<uint32_t>(n);
-  uint32_t wg = 0;
-  for (int k = 0; k < n; ++k) {
-    a.wg_begin[k] = wg;
-    Field& f = a.f[k];
-    if (c[k].on) {
-      f.kind = kRowsCast;
-      f.cast = cast::make_args(g[k], c[k], dst + off[k]);
-      wg += static_cast<uint32_t>(cast::grid_for(f.cast));
-    } else if (tile_c[k] >= 0) {
-      f.kind = kTile;
-      f.tile = tile::make_args(g[k], dst + off[k], tile_c[k]);
-      wg += static_cast<uint32_t>(tile::grid_for(f.tile));
-    } else {
-      f.kind = kRows;
-      f.rows = gather::make_args(g[k], dst + off[k]);
-      wg += static_cast<uint32_t>(gather::grid_for(f.rows));
-    }
-  }
-  for (int k = n; k <= kMaxFields; ++k) a.wg_begin[k] = wg;
-  return a;
+  return make_args_by(n, dst, nullptr, [&](int k, Field& f) {
+    if (!c[k].on) return place_plain(f, g[k], dst + off[k], tile_c[k]);
+    f.kind = kRowsCast;
+    f.cast = cast::make_args(g[k], c[k], dst + off[k]);
+    return static_cast<uint32_t>(cast::grid_for(f.cast));
+  });
 }
 
 }  // namespace multi

@@ -932,13 +932,13 @@ struct Args {
 };
 static_assert(sizeof(Args) <= 4096, "multi::Args is passed by value: the kernel-argument limit");
 
-// Arguments of the gather of g[0..n) into dst + off[k]; tile_c[k] is the source-contiguous
-// dimension the tile body transposes field k against, or negative for the rows body (the
-// launcher's selection).  With `sc` the launch's first workgroup scans a ragged batch's partition
-// into the offsets at dst + 0 and the fields' workgroups follow it (n may then be 0).  The grid is
-// wg_begin[n]: at most 8 * 2^20 + 1 workgroups.
-DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile_c, int n,
-                       uint8_t* dst, const ScanDesc* sc = nullptr) {
+// What every launch's Args share: with `sc` the launch's first workgroup scans a ragged batch's
+// partition into the offsets at dst + 0 and the fields' workgroups follow it (n may then be 0);
+// field k runs the workgroups behind those of the fields before it — `place(k, f)` sets f.kind
+// and the field's own arguments and returns its grid — and the rest of wg_begin repeats the end.
+// The grid is wg_begin[n]: at most 8 * 2^20 + 1 workgroups.
+template <class Place>
+DORA_HD Args make_args_by(int n, uint8_t* dst, const ScanDesc* sc, Place place) {
   Args a{};
   a.n = static_cast<uint32_t>(n);
   uint32_t wg = 0;
@@ -948,19 +948,31 @@ DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile
   }
   for (int k = 0; k < n; ++k) {
     a.wg_begin[k] = wg;
-    Field& f = a.f[k];
-    if (tile_c[k] >= 0) {
-      f.kind = kTile;
-      f.tile = tile::make_args(g[k], dst + off[k], tile_c[k]);
-      wg += static_cast<uint32_t>(tile::grid_for(f.tile));
-    } else {
-      f.kind = kRows;
-      f.rows = gather::make_args(g[k], dst + off[k]);
-      wg += static_cast<uint32_t>(gather::grid_for(f.rows));
-    }
+    wg += place(k, a.f[k]);
   }
   for (int k = n; k <= kMaxFields; ++k) a.wg_begin[k] = wg;
   return a;
+}
+
+// A field moved as it is: the tile body against its source-contiguous dimension `tile_c`, or the
+// rows body when that is negative (the launcher's selection).
+DORA_HD uint32_t place_plain(Field& f, const GatherDesc& g, uint8_t* dst, int tile_c) {
+  if (tile_c >= 0) {
+    f.kind = kTile;
+    f.tile = tile::make_args(g, dst, tile_c);
+    return static_cast<uint32_t>(tile::grid_for(f.tile));
+  }
+  f.kind = kRows;
+  f.rows = gather::make_args(g, dst);
+  return static_cast<uint32_t>(gather::grid_for(f.rows));
+}
+
+// Arguments of the gather of g[0..n) into dst + off[k], field k by tile_c[k]; `sc` as above.
+DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile_c, int n,
+                       uint8_t* dst, const ScanDesc* sc = nullptr) {
+  return make_args_by(n, dst, sc, [&](int k, Field& f) {
+    return place_plain(f, g[k], dst + off[k], tile_c[k]);
+  });
 }
 
 // Arguments of a take: every field g[k] (dimensions 1.. of its view, stride0[k] its dimension 0)
@@ -969,25 +981,15 @@ DORA_HD Args make_args(const GatherDesc* g, const uint64_t* off, const int* tile
 DORA_HD Args make_taken_args(const GatherDesc* g, const int64_t* stride0, const uint64_t* off,
                              int n, uint8_t* dst, const TakeDesc& tk,
                              const ScanDesc* sc = nullptr) {
-  Args a{};
-  a.n = static_cast<uint32_t>(n);
+  Args a = make_args_by(n, dst, sc, [&](int k, Field& f) {
+    f.kind = kRowsTaken;
+    f.taken = take::make_args(g[k], stride0[k], dst + off[k]);
+    return static_cast<uint32_t>(gather::grid_for(f.taken.g));
+  });
   a.take.src = tk.src;
   a.take.k = tk.count;
   a.take.n = tk.n;
   a.take.wide = tk.wide;
-  uint32_t wg = 0;
-  if (sc) {
-    a.scan = scan::make_args(*sc, dst);
-    wg = 1;
-  }
-  for (int k = 0; k < n; ++k) {
-    a.wg_begin[k] = wg;
-    Field& f = a.f[k];
-    f.kind = kRowsTaken;
-    f.taken = take::make_args(g[k], stride0[k], dst + off[k]);
-    wg += static_cast<uint32_t>(gather::grid_for(f.taken.g));
-  }
-  for (int k = n; k <= kMaxFields; ++k) a.wg_begin[k] = wg;
   return a;
 }
 

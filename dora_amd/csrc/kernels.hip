@@ -684,13 +684,28 @@ int finish_args(A& a, uint8_t* dst, const FillSignal& sig, size_t nseg, uint32_t
   return DORA_OK;
 }
 
+// One kernel launch on `stream`, timed or not: with an event it is the extended launch, whose
+// dispatch packet stamps the kernel's begin into `ev_start` and its end into `ev_stop` (either
+// may be null).
+template <class A>
+int launch_timed(void (*kern)(A), unsigned grid, unsigned block, hipStream_t stream,
+                 hipEvent_t ev_start, hipEvent_t ev_stop, const A& a) {
+  if (ev_start || ev_stop) {
+    hipExtLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream, ev_start, ev_stop, 0, a);
+  } else {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, stream, a);
+  }
+  DORA_HIP(hipGetLastError());
+  return DORA_OK;
+}
+
 }  // namespace
 
 // Launch the pack of `n` segments into `dst` (device).  Copy segments with device sources go
 // to pack_kernel in batches of kMaxSegs, transform segments (compacting plans) to
-// transform_kernel; host sources are DMA'd with hipMemcpyAsync.  With timing events the
-// launches go through hipExtLaunchKernelGGL, whose dispatch packet stamps the first kernel's
-// begin into `ev_start` and the last kernel's end into `ev_stop`.
+// transform_kernel; host sources are DMA'd with hipMemcpyAsync.  With timing events
+// (launch_timed) the first kernel's begin is stamped into `ev_start` and the last kernel's end
+// into `ev_stop`.
 int launch_pack(const Segment* segs_in, size_t n_in, ArrowDeviceType dev, uint8_t* dst,
                 hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
                 const FillSignal* signal, bool* signalled, uint64_t dst_cap) {
@@ -731,13 +746,9 @@ int launch_pack(const Segment* segs_in, size_t n_in, ArrowDeviceType dev, uint8_
                                signals ? Signal::kInKernel : Signal::kNone, m == 1);
     if (rc != DORA_OK) return rc;
     void (*kern)(PackArgs) = signals ? pack_kernel<kUnroll, 2> : pack_kernel<kUnroll, 1>;
-    if (ev_start || ev_stop) {
-      hipExtLaunchKernelGGL(kern, dim3(a.grid), dim3(kThreads), 0, stream,
-                            first ? ev_start : nullptr, last ? ev_stop : nullptr, 0, a);
-    } else {
-      hipLaunchKernelGGL(kern, dim3(a.grid), dim3(kThreads), 0, stream, a);
-    }
-    DORA_HIP(hipGetLastError());
+    const int rl = launch_timed(kern, a.grid, kThreads, stream, first ? ev_start : nullptr,
+                                last ? ev_stop : nullptr, a);
+    if (rl != DORA_OK) return rl;
     if (a.flag && signalled) *signalled = true;
     i += m;
     ++launch;
@@ -757,14 +768,9 @@ int launch_pack(const Segment* segs_in, size_t n_in, ArrowDeviceType dev, uint8_
     }
     x.nseg = static_cast<uint32_t>(m);
     const bool first = launch == 0, last = launch + 1 == n_launch;
-    if (ev_start || ev_stop) {
-      hipExtLaunchKernelGGL(transform_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads),
-                            0, stream, first ? ev_start : nullptr, last ? ev_stop : nullptr, 0, x);
-    } else {
-      hipLaunchKernelGGL(transform_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0,
-                         stream, x);
-    }
-    DORA_HIP(hipGetLastError());
+    const int rl = launch_timed(transform_kernel, static_cast<unsigned>(blocks), kThreads, stream,
+                                first ? ev_start : nullptr, last ? ev_stop : nullptr, x);
+    if (rl != DORA_OK) return rl;
     ++launch;
   }
   return DORA_OK;
@@ -810,42 +816,44 @@ int check_device_range(const GatherDesc& g, int device) {
   return DORA_OK;
 }
 
+namespace {
+
+// check_device_range of one thing a plan reads, a refusal naming it in front.
+int check_named(const GatherDesc& g, int device, const char* what) {
+  const int rc = check_device_range(g, device);
+  if (rc == DORA_OK) return rc;
+  const std::string why = dora_gpu_last_error();
+  return fail(rc, "%s: %s", what, why.c_str());
+}
+
+}  // namespace
+
+// By launch kind, in one order: partition, mask, index, fields, the single view.
 int check_plan_range(const dora_plan& plan, int device) {
-  if (plan.scan_on && plan.scan.count && !(plan.masked && plan.mask.part_words)) {
-    // a ragged batch's partition in HBM: its words like any field (a mask plan's host partition
-    // is in the plan itself: its scan reads the copy in the workspace)
-    const int rc = check_device_range(plan.scan.reach, device);
-    if (rc != DORA_OK) {
-      const std::string why = dora_gpu_last_error();
-      return fail(rc, "partition: %s", why.c_str());
-    }
+  const PlanLaunch kind = plan.launch;
+  if (plan.scan_in_hbm() && plan.scan.count) {  // its words like any field
+    const int rc = check_named(scan_reach(plan.scan), device, "partition");
+    if (rc != DORA_OK) return rc;
   }
-  if (plan.masked) {
-    // a mask in HBM: its N bytes like any field
-    const int rc = check_device_range(mask_reach(plan.mask), device);
-    if (rc != DORA_OK) {
-      const std::string why = dora_gpu_last_error();
-      return fail(rc, "mask: %s", why.c_str());
-    }
+  if (kind == PlanLaunch::kMasked) {  // a mask in HBM: its N bytes like any field
+    const int rc = check_named(mask_reach(plan.mask), device, "mask");
+    if (rc != DORA_OK) return rc;
   }
-  if (plan.take_on && plan.take.count) {
-    // a take's index in HBM: its words like any field
-    const int rc = check_device_range(take_reach(plan.take), device);
-    if (rc != DORA_OK) {
-      const std::string why = dora_gpu_last_error();
-      return fail(rc, "index: %s", why.c_str());
-    }
+  if (kind == PlanLaunch::kTaken && plan.take.count) {  // a take's index in HBM: its words
+    const int rc = check_named(take_reach(plan.take), device, "index");
+    if (rc != DORA_OK) return rc;
     if (plan.take.n == 0) return DORA_OK;  // rows of zeros: no field is read
   }
-  if (plan.fields.empty())
-    return plan.list || plan.taken || plan.masked ? DORA_OK : check_device_range(plan.gd, device);
   for (size_t k = 0; k < plan.fields.size(); ++k) {
     const int rc = check_device_range(plan.fields[k].gd, device);
     if (rc == DORA_OK) continue;
     const std::string why = dora_gpu_last_error();
     return fail(rc, "field %zu `%s`: %s", k, plan.fields[k].name.c_str(), why.c_str());
   }
-  return DORA_OK;
+  // a bare tensor: strided (kView), or dense and copied by `segs`
+  const bool one_view = kind == PlanLaunch::kView ||
+                        (kind == PlanLaunch::kSegments && plan.fields.empty());
+  return one_view ? check_device_range(plan.gd, device) : DORA_OK;
 }
 
 // Which kernel gathers `g` into `dst`, stated once.  The tiled transpose, where it applies
@@ -882,30 +890,32 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEven
                                        : g.elem == 2 ? gather_tile_kernel<uint16_t>
                                        : g.elem == 4 ? gather_tile_kernel<uint32_t>
                                                      : gather_tile_kernel<uint64_t>;
-    const dim3 grid(static_cast<unsigned>(gather::tile::grid_for(a)));
-    if (ev_start || ev_stop) {
-      hipExtLaunchKernelGGL(kern, grid, dim3(gather::kThreads), 0, stream, ev_start, ev_stop, 0, a);
-    } else {
-      hipLaunchKernelGGL(kern, grid, dim3(gather::kThreads), 0, stream, a);
-    }
-    DORA_HIP(hipGetLastError());
-    return DORA_OK;
+    return launch_timed(kern, static_cast<unsigned>(gather::tile::grid_for(a)), gather::kThreads,
+                        stream, ev_start, ev_stop, a);
   }
   const gather::Args a = gather::make_args(g, dst);
-  const dim3 grid(static_cast<unsigned>(gather::grid_for(a)));
-  if (ev_start || ev_stop) {
-    hipExtLaunchKernelGGL(gather_rows_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
-                          ev_stop, 0, a);
-  } else {
-    hipLaunchKernelGGL(gather_rows_kernel, grid, dim3(gather::kThreads), 0, stream, a);
-  }
-  DORA_HIP(hipGetLastError());
-  return DORA_OK;
+  return launch_timed(gather_rows_kernel, static_cast<unsigned>(gather::grid_for(a)),
+                      gather::kThreads, stream, ev_start, ev_stop, a);
 }
 
-int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
-                         hipEvent_t ev_start, hipEvent_t ev_stop, const ScanDesc* scan,
-                         const TakeDesc* take, const uint8_t* lookup) {
+namespace {
+
+// One launch over fields[0..n) of a plan of `kind` into `dst + dst_off`: the fields marshalled
+// into gather::multi::Args and the kernel chosen, here alone.
+//   kFields: each field as it would go on its own (select_tile_dim), gather_struct_kernel.
+//   kCast: the same, a converted field through the cast body; gather_cast_kernel, or
+//     gather_quant_kernel when any field is quantised.  DORA_ERR_INVALID, nothing launched, when
+//     a converted field would not start on a multiple of its destination element size.
+//   kTaken (`take` given): every field through the taken body, never a tile: row i0 of its bytes
+//     is row take->src[i0] of the field, or zeros where that word is not in [0, take->n).
+// With `scan` (a ragged batch's partition in HBM; n may then be 0) one more workgroup of the same
+// launch writes the sample's offsets at dst + 0 (dst a whole number of dwords).  With `lookup` (a
+// mask plan: scan->n + 1 int32 counts in HBM) the scan share stores lookup[o] where it would
+// store the offset o.
+int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* dst,
+                  hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop,
+                  const ScanDesc* scan = nullptr, const TakeDesc* take = nullptr,
+                  const uint8_t* lookup = nullptr) {
   if ((n == 0 && !scan) || n > size_t(gather::multi::kMaxFields))
     return fail(DORA_ERR_INVALID, "gather of %zu struct fields", n);
   if (scan && (scan->count > kMaxScanEntries || (reinterpret_cast<uintptr_t>(dst) & 3) ||
@@ -918,52 +928,22 @@ int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStr
                 "words aligned", static_cast<unsigned long long>(take->count),
                 static_cast<const void*>(take->src));
   GatherDesc g[gather::multi::kMaxFields];
-  uint64_t off[gather::multi::kMaxFields];
-  int tile_c[gather::multi::kMaxFields];
-  int64_t stride0[gather::multi::kMaxFields];
-  for (size_t k = 0; k < n; ++k) {
-    if (!fields[k].bytes) return fail(DORA_ERR_INVALID, "gather of an empty struct field");
-    g[k] = fields[k].gd;
-    off[k] = fields[k].dst_off;
-    stride0[k] = fields[k].stride0;
-    // each field as it would go on its own; a taken field always the rows body
-    tile_c[k] = take ? -1 : select_tile_dim(g[k], dst + off[k]);
-  }
-  gather::multi::Args a =
-      take ? gather::multi::make_taken_args(g, stride0, off, static_cast<int>(n), dst, *take, scan)
-           : gather::multi::make_args(g, off, tile_c, static_cast<int>(n), dst, scan);
-  a.lookup = lookup;
-  const dim3 grid(gather::multi::grid_for(a));
-  if (ev_start || ev_stop) {
-    hipExtLaunchKernelGGL(gather_struct_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
-                          ev_stop, 0, a);
-  } else {
-    hipLaunchKernelGGL(gather_struct_kernel, grid, dim3(gather::kThreads), 0, stream, a);
-  }
-  DORA_HIP(hipGetLastError());
-  return DORA_OK;
-}
-
-int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
-                       hipEvent_t ev_start, hipEvent_t ev_stop) {
-  if (n == 0 || n > size_t(gather::multi::kMaxFields))
-    return fail(DORA_ERR_INVALID, "gather of %zu struct fields", n);
-  GatherDesc g[gather::multi::kMaxFields];
   CastDesc c[gather::multi::kMaxFields];
   uint64_t off[gather::multi::kMaxFields];
   int tile_c[gather::multi::kMaxFields];
+  int64_t stride0[gather::multi::kMaxFields];
+  bool quant = false;
   for (size_t k = 0; k < n; ++k) {
     const PlanField& f = fields[k];
     if (!f.bytes) return fail(DORA_ERR_INVALID, "gather of an empty struct field");
     g[k] = f.gd;
-    c[k] = f.cast;
     off[k] = f.dst_off;
-    tile_c[k] = -1;
-    if (!f.cast.on) {
-      tile_c[k] = select_tile_dim(g[k], dst + off[k]);
-      continue;
-    }
-    // the body's stores are whole elements and whole 16-byte units of them
+    stride0[k] = f.stride0;
+    c[k] = kind == PlanLaunch::kCast ? f.cast : CastDesc{};
+    quant |= c[k].quant();
+    tile_c[k] = take || c[k].on ? -1 : select_tile_dim(g[k], dst + off[k]);
+    if (!c[k].on) continue;
+    // the cast body's stores are whole elements and whole 16-byte units of them
     const unsigned ds = f.cast.dst_bits / 8u;
     const bool dst_ok = f.cast.quant()
                             ? gather::cast::dst_kind(f.cast.dst_code, f.cast.dst_bits) >= 0
@@ -977,25 +957,26 @@ int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStrea
                   "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
                   static_cast<void*>(dst + off[k]), ds);
   }
-  const gather::multi::Args a =
-      gather::multi::make_cast_args(g, c, off, tile_c, static_cast<int>(n), dst);
-  const dim3 grid(gather::multi::grid_for(a));
-  bool quant = false;
-  for (size_t k = 0; k < n; ++k) quant |= c[k].quant();
-  auto* kernel = quant ? gather_quant_kernel : gather_cast_kernel;
-  if (ev_start || ev_stop) {
-    hipExtLaunchKernelGGL(kernel, grid, dim3(gather::kThreads), 0, stream, ev_start, ev_stop, 0, a);
-  } else {
-    hipLaunchKernelGGL(kernel, grid, dim3(gather::kThreads), 0, stream, a);
-  }
-  DORA_HIP(hipGetLastError());
-  return DORA_OK;
+  namespace gm = gather::multi;
+  const int nf = static_cast<int>(n);
+  gm::Args a = take                        ? gm::make_taken_args(g, stride0, off, nf, dst, *take, scan)
+               : kind == PlanLaunch::kCast ? gm::make_cast_args(g, c, off, tile_c, nf, dst)
+                                           : gm::make_args(g, off, tile_c, nf, dst, scan);
+  a.lookup = lookup;
+  void (*kern)(gm::Args) = kind != PlanLaunch::kCast ? gather_struct_kernel
+                           : quant                   ? gather_quant_kernel
+                                                     : gather_cast_kernel;
+  return launch_timed(kern, gm::grid_for(a), gather::kThreads, stream, ev_start, ev_stop, a);
 }
 
+}  // namespace
+
 uint64_t plan_workspace(const dora_plan& plan) {
-  if (!plan.masked || !plan.gather) return 0;
+  if (plan.launch != PlanLaunch::kMasked) return 0;
   return gather::mask::workspace(plan.size, plan.mask.n, plan.mask.part_words).end - plan.size;
 }
+
+namespace {
 
 // A mask plan's three launches on `stream`: count, compact, then the fields through the taken
 // body by the workspace's index (with the scan share when the message has a partition, its words
@@ -1010,16 +991,11 @@ int launch_mask(const dora_plan& plan, uint8_t* dst, hipStream_t stream, hipEven
                 static_cast<unsigned long long>(mk::kMaxRows));
   const mk::Workspace w = mk::workspace(plan.size, md.n, md.part_words);
   const mk::Args a = mk::make_args(md.src, md.n, dst, w, !plan.scan_on);
-  const dim3 grid(static_cast<unsigned>(mk::tiles(a)));
-  if (ev_start) {
-    hipExtLaunchKernelGGL(mask_count_kernel, grid, dim3(gather::kThreads), 0, stream, ev_start,
-                          nullptr, 0, a);
-  } else {
-    hipLaunchKernelGGL(mask_count_kernel, grid, dim3(gather::kThreads), 0, stream, a);
-  }
-  DORA_HIP(hipGetLastError());
-  hipLaunchKernelGGL(mask_compact_kernel, grid, dim3(gather::kThreads), 0, stream, a);
-  DORA_HIP(hipGetLastError());
+  const unsigned grid = static_cast<unsigned>(mk::tiles(a));
+  int rc = launch_timed(mask_count_kernel, grid, gather::kThreads, stream, ev_start, nullptr, a);
+  if (rc != DORA_OK) return rc;
+  rc = launch_timed(mask_compact_kernel, grid, gather::kThreads, stream, nullptr, nullptr, a);
+  if (rc != DORA_OK) return rc;
   TakeDesc take{};
   take.src = a.index;
   take.count = md.n;
@@ -1033,25 +1009,28 @@ int launch_mask(const dora_plan& plan, uint8_t* dst, hipStream_t stream, hipEven
     scan.wide = 0;
     scan.offsets = 1;
   }
-  return launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, nullptr,
-                              ev_stop, plan.scan_on ? &scan : nullptr, &take,
-                              plan.scan_on ? a.counts : nullptr);
+  return launch_fields(PlanLaunch::kTaken, plan.fields.data(), plan.fields.size(), dst, stream,
+                       nullptr, ev_stop, plan.scan_on ? &scan : nullptr, &take,
+                       plan.scan_on ? a.counts : nullptr);
 }
+
+}  // namespace
 
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start, hipEvent_t ev_stop) {
-  if (plan.masked) return launch_mask(plan, dst, stream, ev_start, ev_stop);
-  if (plan.cast)
-    return launch_gather_cast(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
-                              ev_stop);
-  if (plan.list || plan.taken)
-    return launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
-                                ev_stop, plan.scan_on ? &plan.scan : nullptr,
-                                plan.take_on ? &plan.take : nullptr);
-  return plan.fields.empty()
-             ? launch_gather(plan.gd, dst, stream, ev_start, ev_stop)
-             : launch_gather_struct(plan.fields.data(), plan.fields.size(), dst, stream, ev_start,
-                                    ev_stop);
+  const ScanDesc* scan = plan.scan_on ? &plan.scan : nullptr;
+  switch (plan.launch) {
+    case PlanLaunch::kSegments: break;  // launch_pack's
+    case PlanLaunch::kView: return launch_gather(plan.gd, dst, stream, ev_start, ev_stop);
+    case PlanLaunch::kFields:
+    case PlanLaunch::kCast:
+    case PlanLaunch::kTaken:
+      return launch_fields(plan.launch, plan.fields.data(), plan.fields.size(), dst, stream,
+                           ev_start, ev_stop, scan,
+                           plan.launch == PlanLaunch::kTaken ? &plan.take : nullptr);
+    case PlanLaunch::kMasked: return launch_mask(plan, dst, stream, ev_start, ev_stop);
+  }
+  return fail(DORA_ERR_INVALID, "a plan of copy segments has no gather to launch");
 }
 
 int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream) {
@@ -1254,8 +1233,9 @@ int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_
     return dora::fail(DORA_ERR_TOO_SMALL,
                       "target buffer too small (total_len: %zu, required_len: %llu)", dst_len,
                       static_cast<unsigned long long>(plan->size));
-  if (plan->segs.empty() && !plan->gather) return DORA_OK;
-  if (plan->masked && dst_len - plan->size < dora::plan_workspace(*plan))
+  const bool gather = plan->launch != dora::PlanLaunch::kSegments;
+  if (plan->segs.empty() && !gather) return DORA_OK;
+  if (dst_len - plan->size < dora::plan_workspace(*plan))
     return dora::fail(DORA_ERR_INVALID, "a mask plan's target holds the sample and its workspace "
                       "(total_len: %zu, sample: %llu, workspace: %llu): nothing was launched",
                       dst_len, static_cast<unsigned long long>(plan->size),
@@ -1270,7 +1250,7 @@ int dora_gpu_pack(const dora_plan* plan, void* dst, size_t dst_len, dora_stream_
     rc = dora::launch_plan_prefix(*plan, static_cast<uint8_t*>(dst),
                                   static_cast<hipStream_t>(stream));
     if (rc != DORA_OK) return rc;
-    if (plan->gather)
+    if (gather)
       return dora::launch_plan_gather(*plan, static_cast<uint8_t*>(dst),
                                       static_cast<hipStream_t>(stream));
   }

@@ -599,6 +599,7 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
   const uint64_t t0 = mono_ns();
   // a host-resident array below the zero-copy threshold goes inline, as in the reference
   const bool host_src = plan->dev != ARROW_DEVICE_ROCM;
+  const bool gather = plan->launch != PlanLaunch::kSegments;  // a kernel, not `segs`, fills it
   if (plan->dev_tensor && plan->size && n->core->device >= 0) {
     // a device tensor view: its strides are the caller's, so the runtime names the allocation
     // it must lie in before anything is allocated or launched
@@ -613,7 +614,7 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
   const bool host_bound = plan->size && plan->fill_size() == plan->size && !n->host_bound.empty() &&
                           !n->timed.armed && n->core->device >= 0 &&
                           n->host_bound.count(output_id) && !n->bcast_out.count(output_id);
-  if (host_bound && !host_src && !plan->gather && plan->prefix.empty() &&
+  if (host_bound && !host_src && !gather && plan->prefix.empty() &&
       plan->size <= kHostPackMax) {
     // (a gather plan, or one with a host prefix, takes the HBM slot, which such receivers stage
     // as usual)
@@ -661,7 +662,7 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
     // Timed region: packs that signal their own fill stamp their device time into the flag
     // line; only packs that cannot (kernel signal off, transforms) need timing events
     // (nor can a gather: the stream raises its flag)
-    const bool stampable = n->core->fill_done && !plan->compact && !plan->gather;
+    const bool stampable = n->core->fill_done && !plan->compact && !gather;
     if (n->timed.armed && plan->dev != ARROW_DEVICE_CPU) {
       if (!stampable && !n->timed.started && !tp) {  // its start is the fallback's origin
         t_start = n->timed.start;
@@ -687,7 +688,7 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
       rc = launch_plan_prefix(*plan, static_cast<uint8_t*>(s->slot->ptr), st);
     }
     if (rc == DORA_OK)
-      rc = plan->gather
+      rc = gather
                ? gather_sample(n, s, *plan, st, t_start, t_stop, !bcast)
                : fill_sample(n, s, plan->segs.data(), plan->segs.size(), plan->dev, st, t_start,
                              t_stop, !bcast, sync);
@@ -755,6 +756,24 @@ int pack_and_send(dora_node* n, const char* output_id, const dora_plan* plan, co
   n->prof.phase_ns[3] += t4 - t3;
   ++n->prof.phase_count;
   return rc;
+}
+
+// Every tensor send (dora_node_send_output_tensor*): the plan `build` makes, its time counted as
+// SP_SEND_PLAN, owned for the length of the send and sent like any other plan (what each builder
+// turns its arguments into: plan.h).
+template <class Build>
+int send_plan(dora_node* n, const char* output_id, const uint8_t* params, size_t params_len,
+              uint32_t flags, Build build) {
+  DORA_GUARD_BEGIN
+  dora_plan* plan = nullptr;
+  {
+    SubSpan sp(SP_SEND_PLAN);
+    const int rc = build(&plan);
+    if (rc != DORA_OK) return rc;
+  }
+  std::unique_ptr<dora_plan> owner(plan);
+  return pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
+  DORA_GUARD_END
 }
 
 }  // namespace
@@ -1003,20 +1022,9 @@ int dora_node_send_output_tensor(dora_node* n, const char* output_id, const dora
                                  ArrowDeviceType device_type, const uint8_t* params,
                                  size_t params_len, uint32_t flags) {
   if (!n || !output_id || !tensor) return dora::fail(DORA_ERR_INVALID, "NULL argument");
-  DORA_GUARD_BEGIN
-  dora_plan* plan = nullptr;
-  {
-    dora::SubSpan sp(dora::SP_SEND_PLAN);
-    const int rc = dora::build_tensor_plan(tensor, device_type, &plan);
-    if (rc != DORA_OK) return rc;
-  }
-  // a host view is one copy segment, over the caller's memory when dense and over the plan's
-  // staging buffer when strided: a host source, which the send has read when it returns.  A
-  // device view is one copy segment when dense and a gather when strided; the synchronous send
-  // waits until the kernel has read it
-  std::unique_ptr<dora_plan> owner(plan);
-  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
-  DORA_GUARD_END
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_plan(tensor, device_type, plan);
+  });
 }
 
 int dora_node_send_output_tensor_struct(dora_node* n, const char* output_id,
@@ -1024,18 +1032,9 @@ int dora_node_send_output_tensor_struct(dora_node* n, const char* output_id,
                                         ArrowDeviceType device_type, const uint8_t* params,
                                         size_t params_len, uint32_t flags) {
   if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
-  DORA_GUARD_BEGIN
-  dora_plan* plan = nullptr;
-  {
-    dora::SubSpan sp(dora::SP_SEND_PLAN);
-    const int rc = dora::build_tensor_struct_plan(fields, count, device_type, &plan);
-    if (rc != DORA_OK) return rc;
-  }
-  // host fields and all-dense device fields: a multi-segment plan like any other; device fields
-  // of which any is strided: a gather plan, which goes where a single strided tensor's goes
-  std::unique_ptr<dora_plan> owner(plan);
-  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
-  DORA_GUARD_END
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_struct_plan(fields, count, device_type, plan);
+  });
 }
 
 int dora_node_send_output_tensor_cast(dora_node* n, const char* output_id,
@@ -1043,18 +1042,9 @@ int dora_node_send_output_tensor_cast(dora_node* n, const char* output_id,
                                       const dora_tensor_cast* casts, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags) {
   if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
-  DORA_GUARD_BEGIN
-  dora_plan* plan = nullptr;
-  {
-    dora::SubSpan sp(dora::SP_SEND_PLAN);
-    const int rc = dora::build_tensor_cast_plan(fields, count, casts, device_type, &plan);
-    if (rc != DORA_OK) return rc;
-  }
-  // host values: converted in the plan's staging buffer, a host plan like any other; device
-  // values: a gather plan whose one launch converts, which goes where the struct send's goes
-  std::unique_ptr<dora_plan> owner(plan);
-  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
-  DORA_GUARD_END
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_cast_plan(fields, count, casts, device_type, plan);
+  });
 }
 
 int dora_node_send_output_tensor_convert(dora_node* n, const char* output_id,
@@ -1064,74 +1054,36 @@ int dora_node_send_output_tensor_convert(dora_node* n, const char* output_id,
                                          ArrowDeviceType device_type, const uint8_t* params,
                                          size_t params_len, uint32_t flags) {
   if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
-  DORA_GUARD_BEGIN
-  dora_plan* plan = nullptr;
-  {
-    dora::SubSpan sp(dora::SP_SEND_PLAN);
-    const int rc =
-        dora::build_tensor_convert_plan(fields, count, casts, quants, device_type, &plan);
-    if (rc != DORA_OK) return rc;
-  }
-  // (as the cast send: a host plan converted in its staging buffer, or a gather plan of one launch)
-  std::unique_ptr<dora_plan> owner(plan);
-  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
-  DORA_GUARD_END
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_convert_plan(fields, count, casts, quants, device_type, plan);
+  });
 }
 
 int dora_node_send_output_tensor_list(dora_node* n, const char* output_id,
                                       const dora_tensor_list* list, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags) {
   if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
-  DORA_GUARD_BEGIN
-  dora_plan* plan = nullptr;
-  {
-    dora::SubSpan sp(dora::SP_SEND_PLAN);
-    const int rc = dora::build_tensor_list_plan(list, device_type, &plan);
-    if (rc != DORA_OK) return rc;
-  }
-  // host values: a multi-segment host plan whose first segment is the offsets; device values: the
-  // struct send's plan behind the offsets, which a prefix copy or the launch's scan share writes
-  std::unique_ptr<dora_plan> owner(plan);
-  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
-  DORA_GUARD_END
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_list_plan(list, device_type, plan);
+  });
 }
 
 int dora_node_send_output_tensor_take(dora_node* n, const char* output_id,
                                       const dora_tensor_take* take, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags) {
   if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
-  DORA_GUARD_BEGIN
-  dora_plan* plan = nullptr;
-  {
-    dora::SubSpan sp(dora::SP_SEND_PLAN);
-    const int rc = dora::build_tensor_take_plan(take, device_type, &plan);
-    if (rc != DORA_OK) return rc;
-  }
-  // a host index: the taken rows are in the plan's staging buffer, a host plan like any other; a
-  // device index: a gather plan, which goes where the struct and list sends' gathers go, the index
-  // one more source its launch reads
-  std::unique_ptr<dora_plan> owner(plan);
-  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
-  DORA_GUARD_END
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_take_plan(take, device_type, plan);
+  });
 }
 
 int dora_node_send_output_tensor_mask(dora_node* n, const char* output_id,
                                       const dora_tensor_mask* mask, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags) {
   if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
-  DORA_GUARD_BEGIN
-  dora_plan* plan = nullptr;
-  {
-    dora::SubSpan sp(dora::SP_SEND_PLAN);
-    const int rc = dora::build_tensor_mask_plan(mask, device_type, &plan);
-    if (rc != DORA_OK) return rc;
-  }
-  // a host mask: the compacted rows are in the plan's staging buffer, a host plan like any other;
-  // a device mask: a gather plan, which goes where the take's goes, its slot allocated with the
-  // workspace behind the sample
-  std::unique_ptr<dora_plan> owner(plan);
-  return dora::pack_and_send(n, output_id, plan, params, params_len, nullptr, flags);
-  DORA_GUARD_END
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_mask_plan(mask, device_type, plan);
+  });
 }
 
 int dora_node_send_output_bytes(dora_node* n, const char* output_id, const void* data, size_t len,

@@ -133,6 +133,19 @@ struct PlanField {
   CastDesc cast;
 };
 
+// `bytes` dense bytes of `elem`-byte elements from `src` as a view: what a plan reads of an
+// index, a mask or a partition in HBM.
+inline GatherDesc dense_reach(const uint8_t* src, uint64_t bytes, uint32_t elem) {
+  GatherDesc r{};
+  r.view.src = src;
+  r.view.total = bytes;
+  r.view.row = bytes;
+  r.elem = elem;
+  r.lo = 0;
+  r.hi = static_cast<int64_t>(bytes) - 1;
+  return r;
+}
+
 // The index of a take plan when it lives in HBM: `count` (K) dense words of 4 or 8 bytes at `src`,
 // never read on the host; a word outside [0, n) yields a row of zero bytes (gather_device.h
 // take::).  take_reach is what check_plan_range holds against the allocation of `src`.
@@ -142,17 +155,8 @@ struct TakeDesc {
   uint64_t n;      // N: rows of the source
   uint32_t wide;   // 0: int32 words, 1: int64
 };
-static_assert(sizeof(TakeDesc) <= sizeof(GatherDesc), "a plan holds either in one place");
-// The K words as a dense view: bytes [0, K * width) from `src`.
 inline GatherDesc take_reach(const TakeDesc& t) {
-  GatherDesc r{};
-  r.view.src = t.src;
-  r.view.total = t.count * (t.wide ? 8 : 4);
-  r.view.row = r.view.total;
-  r.elem = t.wide ? 8 : 4;
-  r.lo = 0;
-  r.hi = static_cast<int64_t>(r.view.total) - 1;
-  return r;
+  return dense_reach(t.src, t.count * (t.wide ? 8 : 4), t.wide ? 8 : 4);
 }
 
 // The mask of a mask plan (dora_gpu_plan_tensor_mask) when it lives in HBM: `n` dense bytes at
@@ -165,23 +169,13 @@ struct MaskDesc {
   uint64_t n;
   uint64_t part_words;
 };
-static_assert(sizeof(MaskDesc) <= sizeof(GatherDesc), "a plan holds either in one place");
-inline GatherDesc mask_reach(const MaskDesc& m) {
-  GatherDesc r{};
-  r.view.src = m.src;
-  r.view.total = m.n;
-  r.view.row = m.n;
-  r.elem = 1;
-  r.lo = 0;
-  r.hi = static_cast<int64_t>(m.n) - 1;
-  return r;
-}
+inline GatherDesc mask_reach(const MaskDesc& m) { return dense_reach(m.src, m.n, 1); }
 
 // The partition of a ragged-batch plan (dora_gpu_plan_tensor_list) when it lives in HBM: `count`
 // dense words of 4 or 8 bytes at `src` (B lengths, or B + 1 offsets), never read on the host.  One
 // workgroup of the plan's launch scans them into the sample's B + 1 int32 offsets, every one
-// clamped to [0, n] (gather_device.h scan::).  `reach` is what check_plan_range holds against the
-// allocation of `src` before anything is launched.
+// clamped to [0, n] (gather_device.h scan::).  scan_reach is what check_plan_range holds against
+// the allocation of `src` before anything is launched.
 constexpr uint64_t kMaxScanEntries = 1u << 20;
 struct ScanDesc {
   const uint8_t* src;
@@ -189,8 +183,10 @@ struct ScanDesc {
   uint64_t n;       // rows of the values: the clamp
   uint32_t wide;    // 0: int32 words, 1: int64
   uint32_t offsets; // 0: the words are lengths (sum), 1: offsets (running maximum)
-  GatherDesc reach;
 };
+inline GatherDesc scan_reach(const ScanDesc& s) {
+  return dense_reach(s.src, s.count * (s.wide ? 8 : 4), s.wide ? 8 : 4);
+}
 
 // Fill signal written by a pack launch itself (kernels.hip): once every workgroup's stores are
 // complete, a system-scope store of `epoch` into `flag` (device view of a host-registered fill
@@ -242,35 +238,19 @@ int check_plan_range(const dora_plan& plan, int device);
 // timing events, the dispatch stamps its begin into `ev_start` and its end into `ev_stop`.
 int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream,
                   hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-// Launch the gather of every field of a multi-gather struct plan into `dst + dst_off` in one
-// launch of gather_struct_kernel (kernels.hip): each field's bytes as launch_gather writes them,
-// nothing between fields and nothing at or past the last field's end.
-// With `scan` (a ragged-batch plan whose partition is in HBM; n may then be 0) one more workgroup
-// of the same launch writes the sample's offsets at dst + 0 (dst a whole number of dwords).
-// With `take` (a take plan) every field goes through the taken body: row i0 of its bytes is row
-// take->src[i0] of the field, or zeros where that word is not in [0, take->n).
-// With `lookup` (a mask plan: scan->n + 1 int32 counts in HBM) the scan share stores lookup[o]
-// where it would store the offset o.
-int launch_gather_struct(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
-                         hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                         const ScanDesc* scan = nullptr, const TakeDesc* take = nullptr,
-                         const uint8_t* lookup = nullptr);
 // The host-source segments a device plan carries beside what its kernel reads (a ragged batch's
 // offsets computed in the plan): copied into `dst` on `stream`, ahead of the pack or gather that
 // follows on the same stream.  The bytes are pageable memory of the plan: the runtime has staged
 // them when the call returns.
 int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
-// Launch a cast plan's fields in one launch of gather_cast_kernel (kernels.hip;
-// gather_quant_kernel when a field is quantised): the cast fields
-// converted element by element (cast_device.h), the others as launch_gather_struct moves them.
-// DORA_ERR_INVALID, nothing launched, when a cast field would not start on a multiple of its
-// destination element size.
-int launch_gather_cast(const PlanField* fields, size_t n, uint8_t* dst, hipStream_t stream,
-                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-// The gather a gather plan asks for: launch_gather of its view, or launch_gather_struct of its
-// fields (with the scan of a ragged batch's device partition, by the index of a take); for a
-// mask plan the two compaction launches and then the fields by the index they wrote, `dst` then
-// holding the sample and plan_workspace bytes behind it.
+// Everything a plan's launch kind asks for beyond `segs` (PlanLaunch below; never kSegments):
+// launch_gather of its view; one launch over its fields — gather_struct_kernel, with the scan of a
+// ragged batch's device partition and by the index of a take, or gather_cast_kernel /
+// gather_quant_kernel for converted fields — each field's bytes as launch_gather would write
+// them, nothing between fields and nothing at or past the last field's end; for a mask plan the
+// two compaction launches and then the fields by the index they wrote, `dst` then holding the
+// sample and plan_workspace bytes behind it.  DORA_ERR_INVALID, nothing launched, when a
+// converted field would not start on a multiple of its destination element size.
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
@@ -295,21 +275,37 @@ Layout layout_of(const char* format);
 inline Layout layout_of(const std::string& format) { return layout_of(format.c_str()); }
 int build_plan(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                dora_plan** out, bool validity_in_sample = false);
-// A tensor view in host or device memory (dora_gpu_plan_tensor, tensor_plan.cpp).
+// A tensor view in host or device memory (dora_gpu_plan_tensor, tensor_plan.cpp).  A host view is
+// one copy segment, over the caller's memory when dense and over the plan's staging buffer when
+// strided: a host source, which the send has read when it returns.  A device view is one copy
+// segment when dense and a gather when strided; the synchronous send waits until the kernel has
+// read it.
 int build_tensor_plan(const dora_tensor* tensor, ArrowDeviceType dev, dora_plan** out);
-// Named tensors of one leading extent as one Struct message (dora_gpu_plan_tensor_struct).
+// Named tensors of one leading extent as one Struct message (dora_gpu_plan_tensor_struct).  Host
+// fields and all-dense device fields: a multi-segment plan like any other; device fields of which
+// any is strided: a gather plan, which goes where a single strided tensor's goes.
 int build_tensor_struct_plan(const dora_tensor_field* fields, size_t n, ArrowDeviceType dev,
                              dora_plan** out);
 // A ragged batch: the fields' rows cut into lists by a partition (dora_gpu_plan_tensor_list).
+// Host values: a multi-segment host plan whose first segment is the offsets; device values: the
+// struct plan behind the offsets, which a prefix copy or the launch's scan share writes.
 int build_tensor_list_plan(const dora_tensor_list* list, ArrowDeviceType dev, dora_plan** out);
-// Rows taken by an index, as a tensor, a record or a ragged batch (dora_gpu_plan_tensor_take).
+// Rows taken by an index, as a tensor, a record or a ragged batch (dora_gpu_plan_tensor_take).  A
+// host index: the taken rows are in the plan's staging buffer, a host plan like any other; a
+// device index: a gather plan, which goes where the struct and list plans' gathers go, the index
+// one more source its launch reads.
 int build_tensor_take_plan(const dora_tensor_take* take, ArrowDeviceType dev, dora_plan** out);
-// Rows selected by a mask of N bytes, as one List message (dora_gpu_plan_tensor_mask).
+// Rows selected by a mask of N bytes, as one List message (dora_gpu_plan_tensor_mask).  A host
+// mask: the compacted rows are in the plan's staging buffer, a host plan like any other; a device
+// mask: a gather plan, which goes where the take's goes, its slot allocated with the workspace
+// behind the sample.
 int build_tensor_mask_plan(const dora_tensor_mask* mask, ArrowDeviceType dev, dora_plan** out);
 // Bytes a mask plan's launches need behind the sample (dora_gpu_plan_workspace_size); 0 for
 // every other plan (kernels.hip).
 uint64_t plan_workspace(const dora_plan& plan);
 // Tensors converted to float16 / float32 on send, bare or as a record (dora_gpu_plan_tensor_cast).
+// Host values: converted in the plan's staging buffer, a host plan like any other; device values:
+// a gather plan whose one launch converts, which goes where the struct plan's goes.
 int build_tensor_cast_plan(const dora_tensor_field* fields, size_t n, const dora_tensor_cast* casts,
                            ArrowDeviceType dev, dora_plan** out);
 // The same with fields quantised to uint8 / int8 / uint16 / int16 (dora_gpu_plan_tensor_convert).
@@ -318,6 +314,28 @@ int build_tensor_convert_plan(const dora_tensor_field* fields, size_t n,
                               ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
+
+// What fills a plan's sample, said once: the builder that decides sets it, and the range check,
+// the launcher and the send path act on it alone.
+enum class PlanLaunch : uint8_t {
+  kSegments,  // `segs` (every host plan, dense device plans, empty plans)
+  kView,      // launch_gather of `gd`
+  kFields,    // gather_struct_kernel over `fields` (+ scan share when scan_on)
+  kCast,      // gather_cast_kernel / gather_quant_kernel over `fields`
+  kTaken,     // the taken body over `fields` by `take` (+ scan share when scan_on)
+  kMasked     // count, compact, then the taken body by the workspace's index
+};
+
+// What kind of message a tensor plan is, whichever way its bytes move: reported by the test probes
+// (testing.cpp) and read by nothing on the send path.
+struct PlanFacts {
+  bool list = false;    // a List message (ragged batch, mask)
+  bool taken = false;   // rows taken by an index, on the host or by the launch
+  bool masked = false;  // rows kept by a mask, on the host or by the launch
+  uint64_t take_k = 0, take_n = 0;  // a take: K words over N source rows
+  uint32_t take_wide = 0;           // ... of 8 bytes
+  uint64_t mask_n = 0;              // a mask: its N elements
+};
 
 }  // namespace dora
 
@@ -329,42 +347,33 @@ struct dora_plan {
   bool read_device = false;  // planning read bytes of the array (last offsets, bitmaps)
   std::vector<dora::Segment> segs;
   dora::TypeInfoNode root;
-  // tensor plans (tensor_plan.cpp): the row-major copy of a strided host view, which the plan's
-  // one segment then reads
+  // tensor plans (tensor_plan.cpp): the row-major copy of a strided host view — the taken, kept or
+  // converted rows of a host take, mask or cast — which the plan's segments then read
   std::vector<uint8_t> staged;
-  // device tensor plans: what the plan reads (dev_tensor), and whether a gather kernel rather
-  // than `segs` (then empty) reads it
+  // device tensor plans: everything the plan reads in HBM has its range checked before a launch
+  // (check_plan_range), the dense ones that `segs` copies included
   bool dev_tensor = false;
-  bool gather = false;
-  // take plans (tensor_plan.cpp): `take.count` / `take.n` always; with `take_on` a device plan
-  // whose one launch reads every field through the index `take.src` (always a gather, never
-  // segments), else a host plan whose taken rows are already in `staged`
-  bool taken = false;
-  bool take_on = false;
-  // cast plans (tensor_plan.cpp) with device values: a gather whose fields, a bare tensor's one
-  // included, go through gather_cast_kernel or gather_quant_kernel (a host cast plan is converted in `staged`)
-  bool cast = false;
-  // mask plans (tensor_plan.cpp) with device values: a gather without segments whose launches
-  // compact `mask` into a workspace behind the sample and read every field through it (host
-  // values: an ordinary host plan, compacted in `staged`)
-  bool masked = false;
-  // (a plan reads one view, `gd`, or the fields of a record, by the index `take` if it is a take
-  // plan: never both, and a plan of any other kind stays the size it was)
-  union {
-    dora::GatherDesc gd{};
-    dora::TakeDesc take;
-    dora::MaskDesc mask;
-  };
-  // struct-of-tensors plans (dev_tensor): one entry per field instead of `gd`; with `gather`,
-  // gather_struct_kernel reads all of them in one launch (a multi-gather plan), else `segs` does
+  dora::PlanLaunch launch = dora::PlanLaunch::kSegments;
+  // kView, and the dense bare tensor of a kSegments device plan: the one view
+  dora::GatherDesc gd{};
+  // kFields, kCast, kTaken, kMasked, and the dense fields of a kSegments device plan: one entry
+  // per field of the record (a bare tensor's one included)
   std::vector<dora::PlanField> fields;
+  dora::TakeDesc take{};  // kTaken: the index in HBM
+  dora::MaskDesc mask{};  // kMasked: the mask in HBM
   // ragged-batch plans (tensor_plan.cpp): the int32 offsets computed from a host partition, read
   // by a segment — of `segs` in a host plan, of `prefix` in a device plan, whose other bytes a
-  // kernel moves — or, for a partition in HBM, the scan the plan's one launch carries
-  bool list = false;
+  // kernel moves — or, for a partition in HBM, the scan the plan's one launch carries (kFields,
+  // kTaken, kMasked; `scan.count` may be 0)
   std::vector<int32_t> list_offsets;
   std::vector<dora::Segment> prefix;
   bool scan_on = false;
   dora::ScanDesc scan{};
+  dora::PlanFacts about;
   uint64_t fill_size() const { return ext_size > size ? ext_size : size; }
+  // whether the scan share reads the caller's partition in HBM (a mask plan's host partition is
+  // in the plan itself: its scan reads the copy the prefix puts into the workspace)
+  bool scan_in_hbm() const {
+    return scan_on && !(launch == dora::PlanLaunch::kMasked && mask.part_words);
+  }
 };

@@ -499,7 +499,7 @@ int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out
     p->dev_tensor = true;
     p->gd = v.gd;
     if (g.nd == 0) p->segs.push_back({g.src, 0, v.bytes});
-    else p->gather = true;
+    else p->launch = PlanLaunch::kView;
     *out = p.release();
     return DORA_OK;
   }
@@ -647,6 +647,30 @@ void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
   p.fields.clear();  // (device plans keep them for the range check and the gather)
 }
 
+// Device fields (none of them empty), never dereferenced here.  All `dense`: the copy segments
+// of any device plan (every device path, the AQL multi-segment packs included); otherwise no
+// segments and one launch of kind `gather` over every field.  Either way each field's reach is
+// checked first.
+void place_device_fields(dora_plan& p, bool dense, PlanLaunch gather = PlanLaunch::kFields) {
+  p.dev_tensor = true;
+  if (!dense) {
+    p.launch = gather;
+    return;
+  }
+  for (const PlanField& pf : p.fields) p.segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
+}
+
+// What the record-like builders ask of their values before looking at one: at least one field
+// (`noun` is refused by name) and, when `bounded`, no more than a launch carries.
+int check_fields(const void* f, size_t n, const char* noun, const char* has = "values: ",
+                 bool bounded = true) {
+  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "%s has %sat least one field", noun, has);
+  if (bounded && n > kMaxStructFields)
+    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
+                kMaxStructFields, n);
+  return DORA_OK;
+}
+
 // A 1-D dense tensor of int32 or int64 words: the partition of a ragged batch, the index of a
 // take.
 struct Partition {
@@ -673,6 +697,14 @@ struct TakeIn {
   bool device = false;
 };
 
+// The message facts of a take, wherever its rows are taken: K words over `rows` source rows.
+void note_take(dora_plan& p, const TakeIn& tk, uint64_t rows) {
+  p.about.taken = true;
+  p.about.take_k = tk.ix.count;
+  p.about.take_n = rows;
+  p.about.take_wide = tk.ix.wide ? 1 : 0;
+}
+
 // Where the taken fields' bytes come from (none of them empty: K > 0), after layout_fields.
 //   Host: the index is read and checked — the first word outside [0, n) is refused, naming it —
 //   and the CPU gathers row index[i] of every field into the staging buffer, dense fields and an
@@ -681,14 +713,10 @@ struct TakeIn {
 //   the reach check_plan_range holds against its allocation.
 int place_taken(dora_plan& p, const TakeIn& tk, uint64_t rows, uint64_t staged) {
   const uint64_t k = tk.ix.count;
-  p.take.src = tk.ix.src;
-  p.take.count = k;
-  p.take.n = rows;
-  p.take.wide = tk.ix.wide ? 1 : 0;
   if (tk.device) {
     p.dev_tensor = true;
-    p.gather = true;
-    p.take_on = true;
+    p.launch = PlanLaunch::kTaken;
+    p.take = TakeDesc{tk.ix.src, k, rows, tk.ix.wide ? 1u : 0u};
     return DORA_OK;
   }
   for (uint64_t i = 0; i < k; ++i) {
@@ -763,10 +791,9 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
-  p->taken = tk != nullptr;
   FieldLayout lay;
   std::vector<TypeInfoNode> solo;
-  const int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
+  int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
                                tk ? static_cast<int64_t>(tk->ix.count) : -1, casts, quants);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
@@ -783,36 +810,17 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
     p->root.len = tk ? tk->ix.count : static_cast<uint64_t>(f[0].tensor.shape[0]);
   }
   p->size = off;
-  if (tk) {
-    p->take.count = tk->ix.count;
-    p->take.n = static_cast<uint64_t>(f[0].tensor.shape[0]);
-    p->take.wide = tk->ix.wide ? 1 : 0;
-  }
-  if (off == 0) {  // d0 == 0: an empty message, nothing to read
-    p->fields.clear();
-    *out = p.release();
-    return DORA_OK;
-  }
-  if (tk) {
-    const int rt = place_taken(*p, *tk, static_cast<uint64_t>(f[0].tensor.shape[0]), lay.staged);
-    if (rt != DORA_OK) return rt;
-    *out = p.release();
-    return DORA_OK;
-  }
-  if (dev == ARROW_DEVICE_ROCM) {
-    // never dereferenced here.  All dense: the copy segments of any device plan (every device
-    // path, the AQL multi-segment packs included); any strided: no segments, one launch of
-    // gather_struct_kernel over every field; any cast: no segments, one launch of
-    // gather_cast_kernel.  Either way each field's reach is checked first.
-    p->dev_tensor = true;
-    p->cast = lay.cast;
-    p->gather = lay.strided || lay.cast;
-    if (!p->gather)
-      for (const PlanField& pf : p->fields) p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
-    *out = p.release();
-    return DORA_OK;
-  }
-  stage_host_fields(*p, dev, lay.staged);
+  const uint64_t rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
+  if (tk) note_take(*p, *tk, rows);
+  // what fills the sample: nothing (d0 == 0, an empty message); the taken rows; device fields as
+  // segments, a gather when any is strided or a cast launch when any is converted; host fields
+  if (off == 0) p->fields.clear();
+  else if (tk) rc = place_taken(*p, *tk, rows, lay.staged);
+  else if (dev == ARROW_DEVICE_ROCM)
+    place_device_fields(*p, !lay.strided && !lay.cast,
+                        lay.cast ? PlanLaunch::kCast : PlanLaunch::kFields);
+  else stage_host_fields(*p, dev, lay.staged);
+  if (rc != DORA_OK) return rc;
   *out = p.release();
   return DORA_OK;
   DORA_GUARD_END
@@ -825,11 +833,8 @@ int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceTy
   if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a struct of tensors has at least one field");
-  if (n > kMaxStructFields)
-    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
-                kMaxStructFields, n);
-  return build_record(f, n, dev, false, nullptr, out);
+  const int rc = check_fields(f, n, "a struct of tensors", "");
+  return rc != DORA_OK ? rc : build_record(f, n, dev, false, nullptr, out);
 }
 
 int build_tensor_cast_plan(const dora_tensor_field* f, size_t n, const dora_tensor_cast* casts,
@@ -837,11 +842,10 @@ int build_tensor_cast_plan(const dora_tensor_field* f, size_t n, const dora_tens
   if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a cast has values: at least one field");
-  if (!casts) return fail(DORA_ERR_INVALID, "casts is NULL (one entry per field)");
-  if (n > kMaxStructFields)
-    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
-                kMaxStructFields, n);
+  // (ranked behind "no field" and ahead of "too many")
+  if (n && f && !casts) return fail(DORA_ERR_INVALID, "casts is NULL (one entry per field)");
+  const int rf = check_fields(f, n, "a cast");
+  if (rf != DORA_OK) return rf;
   const bool bare = n == 1 && !f[0].name;
   // no field converted at all (after every cast's own refusals): the plain plan, whatever it is
   bool any = false;
@@ -863,10 +867,8 @@ int build_tensor_convert_plan(const dora_tensor_field* f, size_t n, const dora_t
   if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a conversion has values: at least one field");
-  if (n > kMaxStructFields)
-    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
-                kMaxStructFields, n);
+  const int rf = check_fields(f, n, "a conversion");
+  if (rf != DORA_OK) return rf;
   const bool bare = n == 1 && !f[0].name;
   // every entry's own refusals first; no field quantised: what the cast plan is, whatever it is
   bool quantised = false;
@@ -990,10 +992,8 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
                 l->partition_form);
   const size_t n = l->n;
   const dora_tensor_field* f = l->fields;
-  if (n == 0 || !f) return fail(DORA_ERR_INVALID, "a ragged batch has values: at least one field");
-  if (n > kMaxStructFields)
-    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
-                kMaxStructFields, n);
+  int rc = check_fields(f, n, "a ragged batch");
+  if (rc != DORA_OK) return rc;
   const bool bare = n == 1 && !f[0].name;
   const bool offsets_form = l->partition_form == DORA_PARTITION_OFFSETS;
   const bool dev_part = l->partition_device == ARROW_DEVICE_ROCM;
@@ -1002,7 +1002,7 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
                 "with host values pass the partition as a host list (.tolist())");
   DORA_GUARD_BEGIN
   Partition pt;
-  int rc = describe_partition(l->partition, pt);
+  rc = describe_partition(l->partition, pt);
   if (rc != DORA_OK) return rc;
   if (offsets_form && pt.count == 0)
     return fail(DORA_ERR_INVALID, "partition: offsets have at least one entry (B + 1 of them)");
@@ -1019,7 +1019,7 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
   const uint64_t obytes = (lists + 1) * 4;
 
   std::unique_ptr<dora_plan> p(new dora_plan());
-  p->list = true;
+  p->about.list = true;
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
   // the type info: the list node with its offsets buffer, under it the values' node — the
   // tensor's chain, or the struct node over the fields' chains
@@ -1036,11 +1036,8 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
                      tk ? static_cast<int64_t>(tk->ix.count) : mk ? mask_rows : -1);
   if (rc != DORA_OK) return rc;
   if (mk) {
-    // (a host plan, or an empty one, keeps N and no pointer: nothing of it is launched)
-    p->masked = true;
-    p->mask.src = nullptr;
-    p->mask.n = static_cast<uint64_t>(mask_rows);
-    p->mask.part_words = 0;
+    p->about.masked = true;
+    p->about.mask_n = static_cast<uint64_t>(mask_rows);
     if (mk->count != static_cast<uint64_t>(mask_rows))
       return fail(DORA_ERR_INVALID, "mask has %llu elements, the values have %lld rows: one mask "
                   "element per row", static_cast<unsigned long long>(mk->count),
@@ -1060,12 +1057,7 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
   // the rows the partition cuts: the fields' own, or the K taken ones
   const uint64_t rows = tk ? tk->ix.count : static_cast<uint64_t>(f[0].tensor.shape[0]);
   const uint64_t src_rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
-  if (tk) {
-    p->taken = true;
-    p->take.count = rows;
-    p->take.n = src_rows;
-    p->take.wide = tk->ix.wide ? 1 : 0;
-  }
+  if (tk) note_take(*p, *tk, src_rows);
   if (rows >> 31)
     return fail(DORA_ERR_UNSUPPORTED, "a ragged batch over %llu rows needs 64-bit offsets "
                 "(LargeList), which is not produced", static_cast<unsigned long long>(rows));
@@ -1097,93 +1089,60 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
   const bool empty = rows == 0;  // every field is then empty: only the offsets travel
   if (empty) p->fields.clear();
 
+  const bool dev_values = dev == ARROW_DEVICE_ROCM && !empty;
+  // the offsets are known here: a host partition's, checked; or all 0 for a mask over no rows,
+  // whatever its partition in HBM holds, which is then never read
+  const bool host_part = !dev_part || (mk && empty);
   if (!dev_part) {
     rc = host_offsets(pt, offsets_form, rows, p->list_offsets);
     if (rc != DORA_OK) return rc;
-    const Segment oseg{p->list_offsets.data(), 0, obytes};
-    if (dev != ARROW_DEVICE_ROCM || empty) {
-      // host values (or none): an ordinary multi-segment host plan, the offsets its first segment
-      p->dev = ARROW_DEVICE_CPU;
-      p->segs.push_back(oseg);
-      if (!empty) {
-        if (tk) rc = place_taken(*p, *tk, src_rows, lay.staged);
-        else if (mk) place_masked_host(*p, *mk, lay.staged);
-        else stage_host_fields(*p, dev, lay.staged);
-        if (rc != DORA_OK) return rc;
-      }
-      *out = p.release();
-      return DORA_OK;
-    }
-    if (mk) {
-      // a mask in HBM: never read here.  Always the three launches, no segments; the checked
-      // offsets of a partition go ahead into the workspace, where the scan share finds them
-      p->dev_tensor = true;
-      p->gather = true;
-      p->masked = true;
-      p->mask.src = mk->src;
-      p->mask.n = rows;
-      p->mask.part_words = mk->one_list ? 0 : lists + 1;
-      if (!mk->one_list) {
-        p->scan_on = true;
-        p->scan.count = lists + 1;
-        p->scan.n = rows;
-        p->scan.offsets = 1;
-        p->prefix.push_back({p->list_offsets.data(),
-                             gather::mask::workspace(p->size, rows, lists + 1).part, obytes});
-      }
-      *out = p.release();
-      return DORA_OK;
-    }
-    // device values: the offsets go ahead on the pack's stream, the fields as in the struct plan
-    p->prefix.push_back(oseg);
-    if (tk) {  // (always the one launch, dense fields included)
-      rc = place_taken(*p, *tk, src_rows, lay.staged);
-      if (rc != DORA_OK) return rc;
-      *out = p.release();
-      return DORA_OK;
-    }
-    p->dev_tensor = true;
-    p->gather = lay.strided;
-    if (!lay.strided)
-      for (const PlanField& pf : p->fields) p->segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
-    *out = p.release();
-    return DORA_OK;
-  }
-  if (mk && empty) {
-    // no rows: every offset is 0 whatever the partition holds, which is then never read
+  } else if (host_part) {
     p->list_offsets.assign(lists + 1, 0);
+  }
+  const Segment oseg{p->list_offsets.data(), 0, obytes};
+
+  // what fills the sample, decided once
+  if (host_part && !dev_values) {
+    // host values (or none): an ordinary multi-segment host plan, the offsets its first segment
     p->dev = ARROW_DEVICE_CPU;
-    p->segs.push_back({p->list_offsets.data(), 0, obytes});
-    *out = p.release();
-    return DORA_OK;
+    p->segs.push_back(oseg);
+    if (tk && !empty) rc = place_taken(*p, *tk, src_rows, lay.staged);
+    else if (mk && !empty) place_masked_host(*p, *mk, lay.staged);
+    else if (!empty) stage_host_fields(*p, dev, lay.staged);
+  } else if (mk) {
+    // a mask in HBM: never read here.  Always the three launches, no segments.  The checked
+    // offsets of a host partition go ahead into the workspace, where the scan share finds them;
+    // the words of one in HBM are scanned in place; either way they are looked up in the counts
+    // the mask gives.  Without a partition there is no scan: the compaction writes [0, K].
+    p->dev_tensor = true;
+    p->launch = PlanLaunch::kMasked;
+    const uint64_t part_words = host_part && !mk->one_list ? lists + 1 : 0;
+    p->mask = MaskDesc{mk->src, rows, part_words};
+    if (part_words) {
+      p->scan_on = true;
+      p->scan.count = part_words;
+      p->scan.n = rows;
+      p->scan.offsets = 1;
+      p->prefix.push_back({p->list_offsets.data(),
+                           gather::mask::workspace(p->size, rows, part_words).part, obytes});
+    }
+  } else if (host_part) {
+    // device values: the offsets go ahead on the pack's stream, the fields as in the struct plan
+    // (a take always the one launch, dense fields included)
+    p->prefix.push_back(oseg);
+    if (tk) rc = place_taken(*p, *tk, src_rows, lay.staged);
+    else place_device_fields(*p, !lay.strided);
   }
-  // a partition in HBM: never read here.  One launch scans it and gathers every field, dense
-  // ones included.
-  p->dev_tensor = true;
-  p->gather = true;
-  p->scan_on = true;
-  ScanDesc& sc = p->scan;
-  sc.src = pt.src;
-  sc.count = pt.count;
-  sc.n = rows;
-  sc.wide = pt.wide ? 1 : 0;
-  sc.offsets = offsets_form ? 1 : 0;
-  sc.reach.view.src = pt.src;
-  sc.reach.view.total = pt.count * (pt.wide ? 8 : 4);
-  sc.reach.view.row = sc.reach.view.total;
-  sc.reach.elem = pt.wide ? 8 : 4;
-  sc.reach.lo = 0;
-  sc.reach.hi = static_cast<int64_t>(sc.reach.view.total) - 1;
-  if (tk && !empty) {
-    rc = place_taken(*p, *tk, src_rows, lay.staged);
-    if (rc != DORA_OK) return rc;
+  if (!host_part) {
+    // a partition in HBM: never read here.  The plan's one launch (a mask plan's last) scans it
+    // and gathers every field, dense ones included; over no rows it only writes the offsets.
+    p->dev_tensor = true;
+    p->scan_on = true;
+    p->scan = ScanDesc{pt.src, pt.count, rows, pt.wide ? 1u : 0u, offsets_form ? 1u : 0u};
+    if (tk && !empty) rc = place_taken(*p, *tk, src_rows, lay.staged);
+    else if (!mk) p->launch = PlanLaunch::kFields;
   }
-  if (mk) {  // (the scan's words are then looked up in the counts the mask gives)
-    p->masked = true;
-    p->mask.src = mk->src;
-    p->mask.n = rows;
-    p->mask.part_words = 0;
-  }
+  if (rc != DORA_OK) return rc;
   *out = p.release();
   return DORA_OK;
   DORA_GUARD_END
@@ -1205,11 +1164,8 @@ int build_tensor_take_plan(const dora_tensor_take* t, ArrowDeviceType dev, dora_
   if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
   if (!known_device(t->index_device))
     return fail(DORA_ERR_INVALID, "unsupported index_device %d", t->index_device);
-  if (t->n == 0 || !t->fields)
-    return fail(DORA_ERR_INVALID, "a take has values: at least one field");
-  if (t->n > kMaxStructFields)
-    return fail(DORA_ERR_UNSUPPORTED, "a struct of tensors has at most %zu fields (%zu given)",
-                kMaxStructFields, t->n);
+  int rc = check_fields(t->fields, t->n, "a take");
+  if (rc != DORA_OK) return rc;
   TakeIn tk;
   tk.device = t->index_device == ARROW_DEVICE_ROCM;
   if (tk.device != (dev == ARROW_DEVICE_ROCM))
@@ -1218,7 +1174,7 @@ int build_tensor_take_plan(const dora_tensor_take* t, ArrowDeviceType dev, dora_
                 "this node's HBM for device values)", tk.device ? "device" : "host",
                 tk.device ? "host" : "device");
   // (a host index may sit at any address: only a kernel needs its words aligned)
-  const int rc = describe_words(t->index, "index", "row numbers", tk.device, tk.ix);
+  rc = describe_words(t->index, "index", "row numbers", tk.device, tk.ix);
   if (rc != DORA_OK) return rc;
   if (t->partition) {
     if (tk.ix.count >> 31)
@@ -1243,8 +1199,9 @@ int build_tensor_mask_plan(const dora_tensor_mask* m, ArrowDeviceType dev, dora_
   if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
   if (!known_device(m->mask_device))
     return fail(DORA_ERR_INVALID, "unsupported mask_device %d", m->mask_device);
-  if (m->n == 0 || !m->fields)
-    return fail(DORA_ERR_INVALID, "a mask has values: at least one field");
+  // (too many fields: refused by the ragged batch it becomes, behind its partition's refusals)
+  const int rc = check_fields(m->fields, m->n, "a mask", "values: ", false);
+  if (rc != DORA_OK) return rc;
   MaskIn mk;
   mk.device = m->mask_device == ARROW_DEVICE_ROCM;
   if (mk.device != (dev == ARROW_DEVICE_ROCM))

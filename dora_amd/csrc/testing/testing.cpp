@@ -323,7 +323,7 @@ int dora_gpu_test_plan_gather(const dora_plan* plan, int* gather, const void** s
   if (!plan || !plan->dev_tensor || !plan->fields.empty())
     return dora::fail(DORA_ERR_INVALID, "not a device tensor plan");
   const dora::GatherDesc& g = plan->gd;
-  if (gather) *gather = plan->gather;
+  if (gather) *gather = plan->launch != dora::PlanLaunch::kSegments;
   if (src) *src = g.view.src;
   if (nd) *nd = g.view.nd;
   if (row) *row = g.view.row;
@@ -346,10 +346,12 @@ int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, s
   const dora::PlanField& f = plan->fields[i];
   const dora::GatherDesc& g = f.gd;
   if (n_fields) *n_fields = plan->fields.size();
-  if (gather) *gather = plan->gather;
+  if (gather) *gather = plan->launch != dora::PlanLaunch::kSegments;
   if (dst_off) *dst_off = f.dst_off;
   if (bytes) *bytes = f.bytes;
-  if (kind && (plan->take_on || plan->masked)) *kind = -1;
+  const bool taken_body = plan->launch == dora::PlanLaunch::kTaken ||
+                          plan->launch == dora::PlanLaunch::kMasked;
+  if (kind && taken_body) *kind = -1;
   else if (kind) *kind = dora::select_tile_dim(g, static_cast<const uint8_t*>(dst) + f.dst_off);
   if (src) *src = g.view.src;
   if (nd) *nd = g.view.nd;
@@ -367,7 +369,7 @@ int dora_gpu_test_plan_field(const dora_plan* plan, size_t i, const void* dst, s
 int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, uint64_t* count,
                             int* wide, int* offsets_form, uint64_t* rows, int64_t* lo, int64_t* hi,
                             uint64_t* prefix_bytes) {
-  if (!plan || !plan->list) return dora::fail(DORA_ERR_INVALID, "not a ragged-batch plan");
+  if (!plan || !plan->about.list) return dora::fail(DORA_ERR_INVALID, "not a ragged-batch plan");
   const dora::ScanDesc& s = plan->scan;
   if (scan) *scan = plan->scan_on;
   if (src) *src = s.src;
@@ -375,8 +377,9 @@ int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, 
   if (wide) *wide = static_cast<int>(s.wide);
   if (offsets_form) *offsets_form = static_cast<int>(s.offsets);
   if (rows) *rows = s.n;
-  if (lo) *lo = s.reach.lo;
-  if (hi) *hi = s.reach.hi;
+  const bool hbm = plan->scan_in_hbm();
+  if (lo) *lo = hbm ? dora::scan_reach(s).lo : 0;
+  if (hi) *hi = hbm ? dora::scan_reach(s).hi : 0;
   if (prefix_bytes) *prefix_bytes = plan->prefix.empty() ? 0 : plan->prefix[0].len;
   return DORA_OK;
 }
@@ -384,17 +387,18 @@ int dora_gpu_test_plan_list(const dora_plan* plan, int* scan, const void** src, 
 int dora_gpu_test_plan_take(const dora_plan* plan, int* device, const void** index,
                             uint64_t* k, uint64_t* n, int* wide, int64_t* lo, int64_t* hi,
                             int64_t* stride0) {
-  if (!plan || !plan->taken) return dora::fail(DORA_ERR_INVALID, "not a take plan");
+  if (!plan || !plan->about.taken) return dora::fail(DORA_ERR_INVALID, "not a take plan");
+  const bool dev = plan->launch == dora::PlanLaunch::kTaken;
   const dora::TakeDesc& t = plan->take;
-  if (device) *device = plan->take_on;
-  if (index) *index = plan->take_on ? t.src : nullptr;
-  if (k) *k = t.count;
-  if (n) *n = t.n;
-  if (wide) *wide = static_cast<int>(t.wide);
-  if (lo) *lo = plan->take_on ? dora::take_reach(t).lo : 0;
-  if (hi) *hi = plan->take_on ? dora::take_reach(t).hi : -1;
+  if (device) *device = dev;
+  if (index) *index = dev ? t.src : nullptr;
+  if (k) *k = plan->about.take_k;
+  if (n) *n = plan->about.take_n;
+  if (wide) *wide = static_cast<int>(plan->about.take_wide);
+  if (lo) *lo = dev ? dora::take_reach(t).lo : 0;
+  if (hi) *hi = dev ? dora::take_reach(t).hi : -1;
   for (size_t i = 0; stride0 && i < dora::kMaxStructFields; ++i)
-    stride0[i] = plan->take_on && i < plan->fields.size() ? plan->fields[i].stride0 : 0;
+    stride0[i] = dev && i < plan->fields.size() ? plan->fields[i].stride0 : 0;
   return DORA_OK;
 }
 
@@ -407,7 +411,7 @@ int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, i
   const dora::PlanField& f = plan->fields[i];
   const dora::CastDesc& c = f.cast;
   if (n_fields) *n_fields = plan->fields.size();
-  if (is_cast) *is_cast = plan->cast && c.on;
+  if (is_cast) *is_cast = plan->launch == dora::PlanLaunch::kCast && c.on;
   if (src_code) *src_code = c.on ? c.src_code : -1;
   if (src_bits) *src_bits = c.on ? c.src_bits : static_cast<int>(f.gd.elem * 8);
   if (dst_code) *dst_code = c.on ? 2 : -1;
@@ -425,7 +429,7 @@ int dora_gpu_test_plan_quant(const dora_plan* plan, size_t i, int* is_quant, int
   if (!plan || !plan->dev_tensor || i >= plan->fields.size())
     return dora::fail(DORA_ERR_INVALID, "not a device plan with a field %zu", i);
   const dora::CastDesc& c = plan->fields[i].cast;
-  const bool q = plan->cast && c.quant();
+  const bool q = plan->launch == dora::PlanLaunch::kCast && c.quant();
   if (is_quant) *is_quant = q;
   if (dst_code) *dst_code = q ? c.dst_code : -1;
   if (dst_bits) *dst_bits = q ? c.dst_bits : 0;
@@ -436,23 +440,32 @@ int dora_gpu_test_plan_quant(const dora_plan* plan, size_t i, int* is_quant, int
 int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mask, uint64_t* n,
                             int64_t* lo, int64_t* hi, uint64_t* workspace, uint64_t* part_words,
                             int64_t* stride0) {
-  if (!plan || !plan->masked) return dora::fail(DORA_ERR_INVALID, "not a mask plan");
-  const bool dev = plan->gather;
+  if (!plan || !plan->about.masked) return dora::fail(DORA_ERR_INVALID, "not a mask plan");
+  const bool dev = plan->launch == dora::PlanLaunch::kMasked;
   const dora::MaskDesc& m = plan->mask;
   if (device) *device = dev;
   if (mask) *mask = dev ? m.src : nullptr;
-  if (n) *n = m.n;
+  if (n) *n = plan->about.mask_n;
   if (lo) *lo = dev ? dora::mask_reach(m).lo : 0;
   if (hi) *hi = dev ? dora::mask_reach(m).hi : -1;
   if (part_words) *part_words = dev ? m.part_words : 0;
   if (workspace) {
     const dora::gather::mask::Workspace w =
-        dora::gather::mask::workspace(plan->size, m.n, m.part_words);
+        dev ? dora::gather::mask::workspace(plan->size, m.n, m.part_words)
+            : dora::gather::mask::Workspace{};
     const uint64_t at[5] = {w.index, w.counts, w.totals, w.part, w.end};
-    for (int i = 0; i < 5; ++i) workspace[i] = dev ? at[i] : 0;
+    for (int i = 0; i < 5; ++i) workspace[i] = at[i];
   }
   for (size_t i = 0; stride0 && i < dora::kMaxStructFields; ++i)
     stride0[i] = dev && i < plan->fields.size() ? plan->fields[i].stride0 : 0;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_launch(const dora_plan* plan, int* launch, int* scan, int* checked) {
+  if (!plan) return dora::fail(DORA_ERR_INVALID, "plan is NULL");
+  if (launch) *launch = static_cast<int>(plan->launch);
+  if (scan) *scan = plan->scan_on;
+  if (checked) *checked = plan->dev_tensor;
   return DORA_OK;
 }
 

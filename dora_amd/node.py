@@ -266,6 +266,48 @@ class Node:
     # many, the send syncs first (each entry pins a tensor's storage)
     _ASYNC_TENSORS_MAX = 64
 
+    def _device_caps(self, flags: int, tensors, also=(), count=None):
+        """The device side of every tensor send: `tensors`, the values, and `also`, whatever else
+        the launch reads on this node's GPU (an index, a mask, a partition; None entries are
+        skipped).  An asynchronous send is about to hold `count` tensors (default: the values)
+        until `sync()`: past `_ASYNC_TENSORS_MAX` of them the send syncs first.  Every tensor
+        does DLPack's handshake, `__dlpack__(stream=<the node stream>)`, which orders the node
+        stream after the producer's current stream (dora_node_stream: the node then knows its
+        stream is in use, and fills wait on it).  Returns the values' capsules, those of `also`
+        and `done`, which takes the send's status, records what must be held after a successful
+        asynchronous send and returns the status."""
+        _require_one_hip_runtime()
+        held = bool(flags & SEND_ASYNC) or self._async_default
+        need = len(tensors) if count is None else count
+        if held and len(self._async_tensors) + need > self._ASYNC_TENSORS_MAX:
+            self.sync()
+        stream = int(self._lib.dora_node_stream(self.handle))
+        caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
+        acaps = tuple(None if v is None else v.__dlpack__(stream=stream) for v in also)
+
+        def done(rc: int) -> int:
+            if held and not rc:
+                self._async_tensors.extend(tensors)
+                self._async_tensors.extend(v for v in also if v is not None)
+            return rc
+        return caps, acaps, done
+
+    @staticmethod
+    def _host_caps(tensors):
+        """(dev, caps) of host tensors: pinned memory in any of them makes the whole message
+        pinned (copied inside the call).  `caps` is None when numpy refuses to export one of them:
+        a read-only array (np.broadcast_to, an array over a received pyarrow buffer) cannot be an
+        unversioned capsule, which cannot say "read-only"; the send only reads, so the caller
+        then describes every tensor through its array interface."""
+        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
+        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
+        try:
+            return dev, tuple(v.__dlpack__() for v in tensors)
+        except BufferError:
+            if not all(hasattr(v, "__array_interface__") for v in tensors):
+                raise
+            return dev, None
+
     def _send_tensor(self, output_id: str, data, metadata, flags: int) -> int:
         """A DLPack producer (numpy.ndarray, a CPU, pinned or device torch.Tensor), strided views
         included, as the nested FixedSizeList array of its shape (dora_node_send_output_tensor;
@@ -273,13 +315,12 @@ class Node:
         reads asynchronously to the host, is declared as such and copied inside the call.
 
         A device tensor (kDLROCM, on this node's GPU) is read by a kernel: in place when it is
-        dense, gathered into row-major order when it is a strided view.  The producer is asked
-        for the capsule with `__dlpack__(stream=<the node stream>)`, DLPack's own handshake: it
-        orders the node stream after its current stream, and the kernel runs after the node
-        stream.  Without `asynchronous` the call returns once the kernel has read the tensor;
-        with it, once the kernel is queued, and the node holds the tensor until the next
-        `sync()` or `close()` (at most `_ASYNC_TENSORS_MAX` of them: the send then syncs first).
-        The caller must not overwrite it before that `sync()`."""
+        dense, gathered into row-major order when it is a strided view, after the handshake of
+        `_device_caps`: the kernel runs after the node stream.  Without `asynchronous` the call
+        returns once the kernel has read the tensor; with it, once the kernel is queued, and the
+        node holds the tensor until the next `sync()` or `close()` (at most `_ASYNC_TENSORS_MAX`
+        of them: the send then syncs first).  The caller must not overwrite it before that
+        `sync()`."""
         dl_dev = data.__dlpack_device__()
         dev_type = int(dl_dev[0])
         if dev_type == _DL_ROCM:
@@ -287,27 +328,13 @@ class Node:
             if ordinal != self.device:
                 raise TypeError(f"the tensor is on GPU {ordinal}, this node on GPU {self.device}: "
                                 "a node sends tensors of its own GPU")
-            _require_one_hip_runtime()
-            held = bool(flags & SEND_ASYNC) or self._async_default
-            if held and len(self._async_tensors) >= self._ASYNC_TENSORS_MAX:
-                self.sync()
-            # (dora_node_stream: the node then knows its stream is in use, and fills wait on it)
-            cap = data.__dlpack__(stream=int(self._lib.dora_node_stream(self.handle)))
-            rc = _fast.send_tensor(self.handle, output_id, cap, ARROW_DEVICE_ROCM, metadata, flags)
-            if held and not rc:
-                self._async_tensors.append(data)
-            return rc
+            (cap,), _, done = self._device_caps(flags, [data])
+            return done(_fast.send_tensor(self.handle, output_id, cap, ARROW_DEVICE_ROCM, metadata,
+                                          flags))
         if dev_type not in _DL_HOST:
             raise TypeError(f"tensors of DLPack device type {dev_type} cannot be sent")
-        dev = ARROW_DEVICE_CPU if dev_type == _DL_CPU else ARROW_DEVICE_ROCM_HOST
-        try:
-            cap = data.__dlpack__()
-        except BufferError:
-            # numpy refuses to export a read-only array (np.broadcast_to, an array over a received
-            # pyarrow buffer) as an unversioned capsule, which cannot say "read-only"; the send
-            # only reads, so its array interface serves
-            if not hasattr(data, "__array_interface__"):
-                raise
+        dev, caps = self._host_caps([data])
+        if caps is None:
             from .tensor import _describe_array
             t, keep = _describe_array(data)
             params = encode_parameters(metadata)
@@ -315,66 +342,24 @@ class Node:
                                                         dev, params, len(params), flags)
             del keep
             return rc
-        return _fast.send_tensor(self.handle, output_id, cap, dev, metadata, flags)
+        return _fast.send_tensor(self.handle, output_id, caps[0], dev, metadata, flags)
 
     def _send_tensor_struct(self, output_id: str, data: dict, metadata, flags: int) -> int:
         """A dict of DLPack producers as one Struct message with a field per entry, in the dict's
         order (dora_node_send_output_tensor_struct; dora_amd.tensor): every tensor shares
         shape[0], and all are host tensors or all are on this node's GPU.  Host fields have been
-        read on return.  Device fields do the `__dlpack__(stream=<the node stream>)` handshake
-        each and are read by one kernel launch; an asynchronous send holds every one of them until
-        the next `sync()`, as `_send_tensor` holds its one."""
-        if not data:
-            raise TypeError("a struct of tensors has at least one field")
-        kinds = {}
-        for name, v in data.items():
-            if not isinstance(name, str):
-                raise TypeError(f"field names are str, not {type(name).__name__}")
-            if not (hasattr(v, "__dlpack__") and hasattr(v, "__dlpack_device__")):
-                raise TypeError(f"field `{name}` is not a tensor with __dlpack__")
-            dl_dev = v.__dlpack_device__()
-            dev_type = int(dl_dev[0])
-            if dev_type == _DL_ROCM:
-                if int(dl_dev[1]) != self.device:
-                    raise TypeError(f"field `{name}` is on GPU {int(dl_dev[1])}, this node on GPU "
-                                    f"{self.device}: a node sends tensors of its own GPU")
-                kinds[name] = "device"
-            elif dev_type in _DL_HOST:
-                kinds[name] = "host"
-            else:
-                raise TypeError(f"field `{name}`: tensors of DLPack device type {dev_type} "
-                                "cannot be sent")
-        first = next(iter(kinds))
-        for name, kind in kinds.items():
-            if kind != kinds[first]:
-                raise TypeError(f"field `{first}` is a {kinds[first]} tensor and field `{name}` a "
-                                f"{kind} tensor: the fields of one message are all host tensors "
-                                "or all on this node's GPU")
-        names = tuple(data)
-        if kinds[first] == "device":
-            _require_one_hip_runtime()
-            held = bool(flags & SEND_ASYNC) or self._async_default
-            if held and len(self._async_tensors) + len(names) > self._ASYNC_TENSORS_MAX:
-                self.sync()
-            stream = int(self._lib.dora_node_stream(self.handle))
-            caps = tuple(v.__dlpack__(stream=stream) for v in data.values())
-            rc = _fast.send_tensor_struct(self.handle, output_id, names, caps, ARROW_DEVICE_ROCM,
-                                          metadata, flags)
-            if held and not rc:
-                self._async_tensors.extend(data.values())
-            return rc
-        # host fields: pinned memory in any of them makes the whole record pinned (copied inside
-        # the call); a read-only numpy array cannot export a capsule, so then every field goes
-        # through its array interface
-        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in data.values())
-        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
-        try:
-            caps = tuple(v.__dlpack__() for v in data.values())
-        except BufferError:
-            if not all(hasattr(v, "__array_interface__") for v in data.values()):
-                raise
+        read on return.  Device fields do the handshake each and are read by one kernel launch;
+        an asynchronous send holds every one of them until the next `sync()`, as `_send_tensor`
+        holds its one."""
+        kind, tensors, names = self._values_kind(data)
+        if kind == "device":
+            caps, _, done = self._device_caps(flags, tensors)
+            return done(_fast.send_tensor_struct(self.handle, output_id, names, caps,
+                                                 ARROW_DEVICE_ROCM, metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
             from .tensor import _describe_array, _describe_fields
-            described = [_describe_array(v) for v in data.values()]
+            described = [_describe_array(v) for v in tensors]
             fields, keep = _describe_fields(names, [t for t, _ in described])
             params = encode_parameters(metadata)
             rc = self._lib.dora_node_send_output_tensor_struct(
@@ -445,103 +430,52 @@ class Node:
     def _send_tensor_cast(self, output_id: str, data, metadata, flags: int) -> int:
         """A tensor converted on send (dora_amd.tensor.cast), or a dict of tensors of which some
         are, as the tensor or Struct message of the converted values
-        (dora_node_send_output_tensor_cast).  Host tensors are converted by the CPU inside the
-        call and have been read on return.  Tensors on this node's GPU do the
-        `__dlpack__(stream=<the node stream>)` handshake each and are read, converted and written
-        by one kernel launch; an asynchronous send holds them until `sync()`.  A torch bfloat16
-        tensor goes through DLPack like any other (type code 4)."""
-        record = isinstance(data, dict)
-        items = data if record else {None: data}
-        casts = [v if isinstance(v, _Cast) else None for v in items.values()]
-        plain = {k: (v.values if isinstance(v, _Cast) else v) for k, v in items.items()}
-        kind, tensors, names = self._values_kind(plain if record else plain[None])
-        entries = tuple(c._entry() if c is not None else None for c in casts)
-        if kind == "device":
-            _require_one_hip_runtime()
-            held = bool(flags & SEND_ASYNC) or self._async_default
-            if held and len(self._async_tensors) + len(tensors) > self._ASYNC_TENSORS_MAX:
-                self.sync()
-            stream = int(self._lib.dora_node_stream(self.handle))
-            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
-            rc = _fast.send_tensor_cast(self.handle, output_id, names, caps, entries,
-                                        ARROW_DEVICE_ROCM, metadata, flags)
-            if held and not rc:
-                self._async_tensors.extend(tensors)
-            return rc
-        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
-        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
-        try:
-            caps = tuple(v.__dlpack__() for v in tensors)
-        except BufferError:
-            # (read-only numpy arrays: every field through its array interface, as in
-            # _send_tensor_struct)
-            if not all(hasattr(v, "__array_interface__") for v in tensors):
-                raise
-            from ._lib import Tensor
-            from .tensor import _describe_array, _describe_casts, _describe_list
-            described = [_describe_array(v) for v in tensors]
-            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
-                                       ARROW_DEVICE_CPU)
-            carr = _describe_casts(casts)
-            params = encode_parameters(metadata)
-            rc = self._lib.dora_node_send_output_tensor_cast(
-                self.handle, output_id.encode(), lst.fields, len(tensors), carr, dev, params,
-                len(params), flags)
-            del keep, described, carr
-            return rc
-        return _fast.send_tensor_cast(self.handle, output_id, names, caps, entries, dev, metadata,
-                                      flags)
+        (dora_node_send_output_tensor_cast): `_send_tensor_convert` without quantise entries.  A
+        torch bfloat16 tensor goes through DLPack like any other (type code 4)."""
+        return self._send_tensor_convert(output_id, data, metadata, flags, quantise=False)
 
-    def _send_tensor_convert(self, output_id: str, data, metadata, flags: int) -> int:
+    def _send_tensor_convert(self, output_id: str, data, metadata, flags: int,
+                             quantise: bool = True) -> int:
         """A tensor quantised on send (dora_amd.tensor.quantize), or a dict of tensors of which
         some are quantised, some perhaps cast and the rest plain, as the tensor or Struct message
-        of the converted values (dora_node_send_output_tensor_convert).  Everything else is
-        `_send_tensor_cast`'s: host tensors converted by the CPU inside the call, tensors on this
-        node's GPU by one kernel launch after the `__dlpack__` handshake."""
+        of the converted values (dora_node_send_output_tensor_convert; without `quantise`, no
+        entry is a quantise entry and the call is dora_node_send_output_tensor_cast).  Host
+        tensors are converted by the CPU inside the call and have been read on return.  Tensors
+        on this node's GPU do the handshake each and are read, converted and written by one
+        kernel launch; an asynchronous send holds them until `sync()`."""
         record = isinstance(data, dict)
         items = data if record else {None: data}
         conv = (_Cast, _Quantized)
-        casts = [v if isinstance(v, _Cast) else None for v in items.values()]
-        quants = [v if isinstance(v, _Quantized) else None for v in items.values()]
         plain = {k: (v.values if isinstance(v, conv) else v) for k, v in items.items()}
         kind, tensors, names = self._values_kind(plain if record else plain[None])
         # (a cast entry has three items, a quantise entry four)
         entries = tuple(v._entry() if isinstance(v, conv) else None for v in items.values())
+        fast = _fast.send_tensor_convert if quantise else _fast.send_tensor_cast
         if kind == "device":
-            _require_one_hip_runtime()
-            held = bool(flags & SEND_ASYNC) or self._async_default
-            if held and len(self._async_tensors) + len(tensors) > self._ASYNC_TENSORS_MAX:
-                self.sync()
-            stream = int(self._lib.dora_node_stream(self.handle))
-            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
-            rc = _fast.send_tensor_convert(self.handle, output_id, names, caps, entries,
-                                           ARROW_DEVICE_ROCM, metadata, flags)
-            if held and not rc:
-                self._async_tensors.extend(tensors)
-            return rc
-        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
-        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
-        try:
-            caps = tuple(v.__dlpack__() for v in tensors)
-        except BufferError:
-            # (read-only numpy arrays: every field through its array interface)
-            if not all(hasattr(v, "__array_interface__") for v in tensors):
-                raise
+            caps, _, done = self._device_caps(flags, tensors)
+            return done(fast(self.handle, output_id, names, caps, entries, ARROW_DEVICE_ROCM,
+                             metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
             from ._lib import Tensor
             from .tensor import (_describe_array, _describe_casts, _describe_list,
                                  _describe_quants)
             described = [_describe_array(v) for v in tensors]
             lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
                                        ARROW_DEVICE_CPU)
-            carr, qarr = _describe_casts(casts), _describe_quants(quants)
+            carr = _describe_casts([v if isinstance(v, _Cast) else None for v in items.values()])
             params = encode_parameters(metadata)
-            rc = self._lib.dora_node_send_output_tensor_convert(
-                self.handle, output_id.encode(), lst.fields, len(tensors), carr, qarr, dev,
-                params, len(params), flags)
-            del keep, described, carr, qarr
+            head = (self.handle, output_id.encode(), lst.fields, len(tensors), carr)
+            tail = (dev, params, len(params), flags)
+            if quantise:
+                qarr = _describe_quants([v if isinstance(v, _Quantized) else None
+                                         for v in items.values()])
+                rc = self._lib.dora_node_send_output_tensor_convert(*head, qarr, *tail)
+            else:
+                rc = self._lib.dora_node_send_output_tensor_cast(*head, *tail)
+            del keep, described
             return rc
-        return _fast.send_tensor_convert(self.handle, output_id, names, caps, entries, dev,
-                                         metadata, flags)
+        return fast(self.handle, output_id, names, caps, entries, dev, metadata, flags)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
         """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with
@@ -568,36 +502,17 @@ class Node:
         if batch is not None:
             part, form, part_dev = self._partition_of(batch, kind)
         if kind == "device":
-            _require_one_hip_runtime()
-            held = bool(flags & SEND_ASYNC) or self._async_default
-            if held and len(self._async_tensors) + len(tensors) + 2 > self._ASYNC_TENSORS_MAX:
-                self.sync()
-            stream = int(self._lib.dora_node_stream(self.handle))
-            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
-            icap = index.__dlpack__(stream=stream)
-            pcap = None
-            if part is not None:
-                pcap = part.__dlpack__(stream=stream) if part_dev == ARROW_DEVICE_ROCM \
-                    else part.__dlpack__()
-            rc = _fast.send_tensor_take(self.handle, output_id, names, caps, icap,
-                                        ARROW_DEVICE_ROCM, pcap, form, part_dev, ARROW_DEVICE_ROCM,
-                                        metadata, flags)
-            if held and not rc:
-                self._async_tensors.extend(tensors)
-                self._async_tensors.append(index)
-                if part_dev == ARROW_DEVICE_ROCM:
-                    self._async_tensors.append(part)
-            return rc
+            dev_part = part if part_dev == ARROW_DEVICE_ROCM else None
+            caps, (icap, pcap), done = self._device_caps(flags, tensors, (index, dev_part),
+                                                         len(tensors) + 2)
+            if part is not None and dev_part is None:
+                pcap = part.__dlpack__()
+            return done(_fast.send_tensor_take(self.handle, output_id, names, caps, icap,
+                                               ARROW_DEVICE_ROCM, pcap, form, part_dev,
+                                               ARROW_DEVICE_ROCM, metadata, flags))
         index = self._host_words(index, "index")
-        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
-        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
-        try:
-            caps = tuple(v.__dlpack__() for v in tensors)
-        except BufferError:
-            # (read-only numpy arrays: every field through its array interface, as in
-            # _send_tensor_struct)
-            if not all(hasattr(v, "__array_interface__") for v in tensors):
-                raise
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
             from .tensor import _describe_array, _describe_take
             described = [_describe_array(v) for v in tensors]
             it, ikeep = _describe_array(index)
@@ -640,26 +555,14 @@ class Node:
         if batch is not None:
             part, form, part_dev = self._partition_of(batch, kind)
         if kind == "device":
-            _require_one_hip_runtime()
-            held = bool(flags & SEND_ASYNC) or self._async_default
-            if held and len(self._async_tensors) + len(tensors) + 2 > self._ASYNC_TENSORS_MAX:
-                self.sync()
-            stream = int(self._lib.dora_node_stream(self.handle))
-            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
-            mcap = mask.__dlpack__(stream=stream)
-            pcap = None
-            if part is not None:
-                pcap = part.__dlpack__(stream=stream) if part_dev == ARROW_DEVICE_ROCM \
-                    else part.__dlpack__()
-            rc = _fast.send_tensor_masked(self.handle, output_id, names, caps, mcap,
-                                          ARROW_DEVICE_ROCM, pcap, form, part_dev,
-                                          ARROW_DEVICE_ROCM, metadata, flags)
-            if held and not rc:
-                self._async_tensors.extend(tensors)
-                self._async_tensors.append(mask)
-                if part_dev == ARROW_DEVICE_ROCM:
-                    self._async_tensors.append(part)
-            return rc
+            dev_part = part if part_dev == ARROW_DEVICE_ROCM else None
+            caps, (mcap, pcap), done = self._device_caps(flags, tensors, (mask, dev_part),
+                                                         len(tensors) + 2)
+            if part is not None and dev_part is None:
+                pcap = part.__dlpack__()
+            return done(_fast.send_tensor_masked(self.handle, output_id, names, caps, mcap,
+                                                 ARROW_DEVICE_ROCM, pcap, form, part_dev,
+                                                 ARROW_DEVICE_ROCM, metadata, flags))
         # (the mask as it is: the call has read it when it returns, and what it cannot take — a
         # dtype, a shape, a stride — is refused there)
         mask = np.asarray(mask)
@@ -699,30 +602,14 @@ class Node:
         kind, tensors, names = self._values_kind(data.values)
         part, form, part_dev = self._partition_of(data, kind)
         if kind == "device":
-            _require_one_hip_runtime()
-            held = bool(flags & SEND_ASYNC) or self._async_default
-            if held and len(self._async_tensors) + len(tensors) + 1 > self._ASYNC_TENSORS_MAX:
-                self.sync()
-            stream = int(self._lib.dora_node_stream(self.handle))
-            caps = tuple(v.__dlpack__(stream=stream) for v in tensors)
-            pcap = part.__dlpack__(stream=stream) if part_dev == ARROW_DEVICE_ROCM \
-                else part.__dlpack__()
-            rc = _fast.send_tensor_list(self.handle, output_id, names, caps, pcap, form, part_dev,
-                                        ARROW_DEVICE_ROCM, metadata, flags)
-            if held and not rc:
-                self._async_tensors.extend(tensors)
-                if part_dev == ARROW_DEVICE_ROCM:
-                    self._async_tensors.append(part)
-            return rc
-        pinned = any(int(v.__dlpack_device__()[0]) != _DL_CPU for v in tensors)
-        dev = ARROW_DEVICE_ROCM_HOST if pinned else ARROW_DEVICE_CPU
-        try:
-            caps = tuple(v.__dlpack__() for v in tensors)
-        except BufferError:
-            # (read-only numpy arrays: every field through its array interface, as in
-            # _send_tensor_struct)
-            if not all(hasattr(v, "__array_interface__") for v in tensors):
-                raise
+            dev_part = part if part_dev == ARROW_DEVICE_ROCM else None
+            caps, (pcap,), done = self._device_caps(flags, tensors, (dev_part,), len(tensors) + 1)
+            if dev_part is None:
+                pcap = part.__dlpack__()
+            return done(_fast.send_tensor_list(self.handle, output_id, names, caps, pcap, form,
+                                               part_dev, ARROW_DEVICE_ROCM, metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
             from .tensor import _describe_array, _describe_list
             described = [_describe_array(v) for v in tensors]
             pt, pkeep = _describe_array(part)

@@ -134,6 +134,13 @@ int dora_gpu_test_plan_quant(const dora_plan* plan, size_t i, int* is_quant, int
 int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mask, uint64_t* n,
                             int64_t* lo, int64_t* hi, uint64_t* workspace, uint64_t* part_words,
                             int64_t* stride0);
+/* Test tool (host only): what fills the sample of any plan.  *launch 0 its copy segments (every
+ * host plan, dense device plans, empty plans), 1 the gather of its one strided view, 2
+ * gather_struct_kernel over its fields, 3 gather_cast_kernel / gather_quant_kernel, 4 the taken
+ * body by an index in HBM, 5 a mask's count, compact and taken launches; *scan 1 if that launch
+ * also scans a partition in HBM; *checked 1 if the plan reads HBM whose range is checked before
+ * anything is launched. */
+int dora_gpu_test_plan_launch(const dora_plan* plan, int* launch, int* scan, int* checked);
 /* Test and probe tool: which kernel gathers strided device tensor views of this process from now
  * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
  * it applies (short contiguous extents included). */
