@@ -94,6 +94,13 @@ class TensorQuant(ctypes.Structure):
                 ("scale", c_float), ("zero_point", c_int32)]
 
 
+class TensorAffine(ctypes.Structure):
+    """dora_tensor_affine of include/dora_gpu.h: the per-channel scale and bias tables of one
+    converted field (NULL: none), the axis they run along and the optional scalar bias."""
+    _fields_ = [("scale", POINTER(Tensor)), ("bias", POINTER(Tensor)), ("axis", c_int32),
+                ("has_bias", ctypes.c_uint16), ("bias_value", c_float)]
+
+
 class TensorMask(ctypes.Structure):
     """dora_tensor_mask of include/dora_gpu.h: the fields rows are selected from, the mask that
     selects them and, for more than one list, the partition of the N source rows (else NULL)."""
@@ -160,6 +167,11 @@ _SIGS = {
     "dora_node_send_output_tensor_convert": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
                                                      c_void_p, c_void_p, c_int32, c_char_p,
                                                      c_size_t, c_uint32]),
+    "dora_gpu_plan_tensor_affine": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                            c_int32, POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_affine": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
+                                                    c_void_p, c_void_p, c_void_p, c_int32,
+                                                    c_char_p, c_size_t, c_uint32]),
     "dora_gpu_plan_tensor_mask": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_mask": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                                   c_size_t, c_uint32]),
@@ -309,6 +321,11 @@ _TEST_SIGS = {
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "dora_gpu_test_plan_quant": (c_int, [c_void_p, c_size_t, POINTER(c_int), POINTER(c_int),
                                          POINTER(c_int), POINTER(c_int)]),
+    "dora_gpu_test_plan_affine": (c_int, [c_void_p, c_size_t, POINTER(c_int), POINTER(c_void_p),
+                                          POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64),
+                                          POINTER(c_int), POINTER(c_float),
+                                          POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
+    "dora_gpu_test_fields_launches": (c_int, [POINTER(c_uint64)]),
     "dora_gpu_test_plan_take": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int),
                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),

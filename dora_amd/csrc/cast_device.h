@@ -2,7 +2,9 @@
 // elements of a strided view read once as their source type, converted, and written once as
 // float16 or float32 — y = to_dst(to_f32(x) [* scale]), element by element — or, a quantised field,
 // as uint8, int8, uint16 or int16: q = int(clip(rint(y), lo - zp, hi - zp)) + zp with a NaN taken
-// as 0, [lo, hi] the destination's range and zp the zero point inside it.
+// as 0, [lo, hi] the destination's range and zp the zero point inside it.  With the affine step
+// (template flag A, gather_affine_kernel) y = to_f32(x) * S + B first, S and B each a scalar, a
+// per-channel table word or absent, product and sum rounded one after the other.
 //
 // It is gather_device.h's rows body restated per element, in the same style: every address
 // computation is plain C++ in functions that compile for host and device alike, all memory and
@@ -158,6 +160,12 @@ struct HostCvt {
     else return int_to_f32<K>(raw);
   }
   float mul(float x, float s) const { return x * s; }
+  // The sum of the affine step, a rounding of its own: the product is read back through a
+  // volatile so that no compiler contracts the pair into one fused multiply-add.
+  float add(float x, float b) const {
+    volatile float p = x;
+    return p + b;
+  }
   uint32_t to_f16(float y) const { return f32_to_f16_bits(bits_of(y)); }
   uint32_t f32_bits(float y) const { return bits_of(y); }
   int32_t to_int(float y, int32_t lo, int32_t hi, int32_t zp) const {
@@ -197,6 +205,12 @@ DORA_HD Args make_args(const GatherDesc& g, const CastDesc& c, uint8_t* dst) {
   const int dk = c.dst_code == 2 ? int(kDstFloat) : dst_kind(c.dst_code, c.dst_bits);
   a.dst = static_cast<uint32_t>(dk < 0 ? 0 : dk);
   a.zp = c.zero_point;
+  a.stab = c.scale_tab;
+  a.btab = c.bias_tab;
+  a.inner = c.inner;
+  a.channels = c.channels;
+  a.has_bias = c.has_bias;
+  a.bias = c.bias;
   return a;
 }
 
@@ -272,18 +286,61 @@ DORA_HDI void load_unit(const Args& a, uint64_t e, M& m, U16* v) {
   }
 }
 
+// The channel of an output element under the affine step: element e is of channel
+// c = (e / inner) % channels, `rem` = e % inner elements into that channel's run.
+struct Chan {
+  uint64_t rem, c;
+};
+
+// Output element `e` -> Chan: one division and one remainder, 32-bit where the operands allow.
+DORA_HDI void chan_pos(uint64_t inner, uint64_t channels, uint64_t e, Chan& ch) {
+  if ((e | inner | channels) >> 32) {
+    const uint64_t q = e / inner;
+    ch.rem = e - q * inner;
+    ch.c = q % channels;
+  } else {
+    const uint32_t e32 = static_cast<uint32_t>(e), i32 = static_cast<uint32_t>(inner);
+    const uint32_t q = e32 / i32;
+    ch.rem = e32 - q * i32;
+    ch.c = q % static_cast<uint32_t>(channels);
+  }
+}
+
+// The Chan of the next output element: `rem` counts up to inner, then `c` up to channels, so
+// c < channels always and nothing is divided per element.
+DORA_HDI void chan_next(uint64_t inner, uint64_t channels, Chan& ch) {
+  if (++ch.rem < inner) return;
+  ch.rem = 0;
+  if (++ch.c >= channels) ch.c = 0;
+}
+
 // The image's E elements of source type K -> the unit's 16 output bytes: floats of D bytes, or
-// with Q integers of D bytes, each the product quantised into the destination's range.
-template <uint32_t K, int D, bool Q, class M>
-DORA_HDI U16 convert_as(const Args& a, const U16* v, M& m) {
+// with Q integers of D bytes, each the product quantised into the destination's range.  With A
+// (gather_affine_kernel's body) the elements are output elements e, e + 1, .. and each is taken
+// through y * S + B of its channel first, product and sum rounded one after the other; without
+// it `e` is not read and no line of the affine step is compiled.
+template <uint32_t K, int D, bool Q, bool A, class M>
+DORA_HDI U16 convert_as(const Args& a, const U16* v, uint64_t e, M& m) {
   constexpr int E = 16 / D;
   U16 out = {{0, 0, 0, 0}};
   // (the clip bounds less the zero point: exact as integers and as float32)
   const int32_t lo = Q ? dst_lo(a.dst) - a.zp : 0, hi = Q ? dst_hi(a.dst) - a.zp : 0;
+  Chan ch{0, 0};
+  if constexpr (A) {
+    if (a.stab || a.btab) chan_pos(a.inner, a.channels, e, ch);
+  }
 #pragma unroll
   for (int j = 0; j < E; ++j) {
     float y = m.template to_f32<K>(elem_of<kSize<K>>(v, j));
-    if (a.has_scale) y = m.mul(y, a.scale);
+    if constexpr (A) {
+      if (a.stab) y = m.mul(y, m.load_table(a.stab, ch.c));
+      else if (a.has_scale) y = m.mul(y, a.scale);
+      if (a.btab) y = m.add(y, m.load_table(a.btab, ch.c));
+      else if (a.has_bias) y = m.add(y, a.bias);
+      if (a.stab || a.btab) chan_next(a.inner, a.channels, ch);
+    } else {
+      if (a.has_scale) y = m.mul(y, a.scale);
+    }
     if constexpr (Q) {
       const uint32_t q = static_cast<uint32_t>(m.to_int(y, lo, hi, a.zp));
       if constexpr (D == 1) out.w[j / 4] |= (q & 0xffu) << (8 * (j % 4));
@@ -296,31 +353,31 @@ DORA_HDI U16 convert_as(const Args& a, const U16* v, M& m) {
   return out;
 }
 
-template <int D, bool Q, class M>
-DORA_HDI U16 convert_unit(const Args& a, const U16* v, M& m) {
+template <int D, bool Q, bool A, class M>
+DORA_HDI U16 convert_unit(const Args& a, const U16* v, uint64_t e, M& m) {
   switch (a.src) {
-    case kU8: return convert_as<kU8, D, Q>(a, v, m);
-    case kI8: return convert_as<kI8, D, Q>(a, v, m);
-    case kU16: return convert_as<kU16, D, Q>(a, v, m);
-    case kI16: return convert_as<kI16, D, Q>(a, v, m);
-    case kF16: return convert_as<kF16, D, Q>(a, v, m);
-    case kBF16: return convert_as<kBF16, D, Q>(a, v, m);
-    default: return convert_as<kF32, D, Q>(a, v, m);
+    case kU8: return convert_as<kU8, D, Q, A>(a, v, e, m);
+    case kI8: return convert_as<kI8, D, Q, A>(a, v, e, m);
+    case kU16: return convert_as<kU16, D, Q, A>(a, v, e, m);
+    case kI16: return convert_as<kI16, D, Q, A>(a, v, e, m);
+    case kF16: return convert_as<kF16, D, Q, A>(a, v, e, m);
+    case kBF16: return convert_as<kBF16, D, Q, A>(a, v, e, m);
+    default: return convert_as<kF32, D, Q, A>(a, v, e, m);
   }
 }
 
 // Whole unit `u` of the output.
-template <int D, bool Q, class M>
+template <int D, bool Q, bool A, class M>
 DORA_HDI void cast_unit(const Args& a, uint64_t u, M& m) {
   const uint64_t e = a.g.head + static_cast<uint64_t>(16 / D) * u;
   U16 v[kImage<D>];
   load_unit<D>(a, e, m, v);
-  m.store16(e * D, convert_unit<D, Q>(a, v, m));
+  m.store16(e * D, convert_unit<D, Q, A>(a, v, e, m));
 }
 
 // Output element `e` on its own (the elements before the first and after the last whole unit):
 // element 0 of an image that holds nothing else.
-template <int D, bool Q, class M>
+template <int D, bool Q, bool A, class M>
 DORA_HDI void cast_elem(const Args& a, uint64_t e, M& m) {
   const uint32_t ss = a.g.piece;
   uint64_t r, b;
@@ -331,38 +388,38 @@ DORA_HDI void cast_elem(const Args& a, uint64_t e, M& m) {
   U16 v[kImage<D>] = {};
   v[0].w[0] = ss == 1 ? m.template load_elem<1>(s)
                       : ss == 2 ? m.template load_elem<2>(s) : m.template load_elem<4>(s);
-  const U16 y = convert_unit<D, Q>(a, v, m);
+  const U16 y = convert_unit<D, Q, A>(a, v, e, m);
   m.template store_elem<D>(e, D == 1 ? y.w[0] & 0xffu : D == 2 ? y.w[0] & 0xffffu : y.w[0]);
 }
 
 // gather_lane's division of the work: lanes 0..15 a head element each, lanes 16..31 a tail
 // element each (at most E - 1 <= 15 of either: the head ends at the first 16-byte boundary, the
 // tail is less than a unit), and every lane the whole units lane, lane + lanes, ..
-template <int D, bool Q, class M>
+template <int D, bool Q, bool A, class M>
 DORA_HDI void cast_lane_as(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
   constexpr int E = 16 / D;
   static_assert(E - 1 <= 15, "16 lanes each for the head's and the tail's elements");
   if (lane < 16) {
-    if (lane < a.g.head) cast_elem<D, Q>(a, lane, m);
+    if (lane < a.g.head) cast_elem<D, Q, A>(a, lane, m);
   } else if (lane < 32) {
     const uint64_t t0 = a.g.head + static_cast<uint64_t>(E) * a.g.nunits;  // <= total
-    if (lane - 16 < a.g.total - t0) cast_elem<D, Q>(a, t0 + (lane - 16), m);
+    if (lane - 16 < a.g.total - t0) cast_elem<D, Q, A>(a, t0 + (lane - 16), m);
   }
-  for (uint64_t u = lane; u < a.g.nunits; u += lanes) cast_unit<D, Q>(a, u, m);
+  for (uint64_t u = lane; u < a.g.nunits; u += lanes) cast_unit<D, Q, A>(a, u, m);
 }
 
 // Everything lane `lane` of `lanes` does for a field cast to float16 or float32.
-template <class M>
+template <bool A = false, class M>
 DORA_HDI void cast_lane_float(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
-  if (a.dsize == 2) cast_lane_as<2, false>(a, lane, lanes, m);
-  else cast_lane_as<4, false>(a, lane, lanes, m);
+  if (a.dsize == 2) cast_lane_as<2, false, A>(a, lane, lanes, m);
+  else cast_lane_as<4, false, A>(a, lane, lanes, m);
 }
 
 // The same for a quantised field: 8- or 16-bit integers.
-template <class M>
+template <bool A = false, class M>
 DORA_HDI void cast_lane_quant(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
-  if (a.dsize == 1) cast_lane_as<1, true>(a, lane, lanes, m);
-  else cast_lane_as<2, true>(a, lane, lanes, m);
+  if (a.dsize == 1) cast_lane_as<1, true, A>(a, lane, lanes, m);
+  else cast_lane_as<2, true, A>(a, lane, lanes, m);
 }
 
 // Everything lane `lane` of `lanes` does.
@@ -370,6 +427,14 @@ template <class M>
 DORA_HDI void cast_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
   if (a.dst == kDstFloat) cast_lane_float(a, lane, lanes, m);
   else cast_lane_quant(a, lane, lanes, m);
+}
+
+// The same with the affine step (gather_affine_kernel): every converted field of its launch,
+// those without a table or a bias included.
+template <class M>
+DORA_HDI void cast_lane_affine(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+  if (a.dst == kDstFloat) cast_lane_float<true>(a, lane, lanes, m);
+  else cast_lane_quant<true>(a, lane, lanes, m);
 }
 
 }  // namespace cast

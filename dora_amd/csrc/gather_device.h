@@ -871,8 +871,8 @@ DORA_HD void scan_store(const Args& a, uint64_t tile, uint32_t thread, uint32_t 
 }  // namespace mask
 
 // ------------------------------------------------------------------------------------------
-// A field converted on the way (one more field kind, run by gather_cast_kernel and
-// gather_quant_kernel only): the rows
+// A field converted on the way (one more field kind, run by gather_cast_kernel,
+// gather_quant_kernel and gather_affine_kernel only): the rows
 // body restated per element, source elements of one type read, converted and written as float16
 // or float32, or quantised to an 8- or 16-bit integer.  Only the arguments live here, where multi::Field needs them; the body is
 // cast_device.h.
@@ -896,7 +896,17 @@ struct Args {
   float scale;
   uint32_t dst;        // Dst
   int32_t zp;          // a quantised field's zero point, inside the destination's range
+  // the affine step (read by gather_affine_kernel only): per-channel
+  // float32 tables that take the place of `scale` and `bias` where they are not null, output
+  // element e being of channel (e / inner) % channels
+  const uint8_t* stab;
+  const uint8_t* btab;
+  uint64_t inner;
+  uint64_t channels;
+  uint32_t has_bias;
+  float bias;
 };
+static_assert(sizeof(Args) == sizeof(gather::Args) + 64, "the affine arguments fill the union");
 
 }  // namespace cast
 
@@ -904,7 +914,8 @@ namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
 // (a scan share, kScan, is no Field: it has no view; it runs workgroups [0, wg_begin[0]))
-// (kRowsCast fields are run by gather_cast_kernel / gather_quant_kernel only: gather_struct_kernel's launches hold none)
+// (kRowsCast fields are run by gather_cast_kernel / gather_quant_kernel / gather_affine_kernel
+// only: gather_struct_kernel's launches hold none)
 enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4 };
 
 struct Field {

@@ -398,6 +398,19 @@ struct CastMem {
     asm volatile("" : "+v"(y));
     return y;
   }
+  // The sum of the affine step, opaque in the same way and for the same reason: the contract is
+  // a rounded product and then a rounded sum, and left to itself the compiler contracts the pair
+  // into one v_fma_f32 — or, towards float16, a v_fma_mix* — which rounds once.
+  __device__ __forceinline__ float add(float x, float b) const {
+    float y = x + b;
+    asm volatile("" : "+v"(y));
+    return y;
+  }
+  // Word `c` of a per-channel table (c < channels always; the table a whole number of dwords):
+  // a plain cached load, neighbouring lanes read the same few words.
+  __device__ __forceinline__ float load_table(const uint8_t* tab, uint64_t c) const {
+    return reinterpret_cast<const float*>(tab)[c];
+  }
   __device__ __forceinline__ uint32_t to_f16(float y) const {
     return __builtin_bit_cast(uint16_t, static_cast<_Float16>(y));
   }
@@ -442,7 +455,8 @@ struct CastMem {
 static_assert(gather::scan::kLds <= gather::tile::kLds, "the scan's rows fit the tile buffer");
 
 // What a workgroup of a multi-field launch does, for the kernels below.  kCast 0: no cast kind;
-// 1: the cast kind with float destinations only; 2: with the quantised destinations too.  With
+// 1: the cast kind with float destinations only; 2: with the quantised destinations too; 3: both
+// with the affine step.  With
 // kCast the cast kind takes the place of the scan share and the taken kind, which no cast plan has: with all of them
 // in one kernel the compiler no longer follows every read back to the by-value arguments and
 // keeps a copy of the 2.3 KB in scratch.
@@ -480,6 +494,9 @@ __device__ __forceinline__ void struct_share(const gather::multi::Args& a, uint6
       if constexpr (kCast == 1)
         gather::cast::cast_lane_float(c, local * gather::kThreads + threadIdx.x,
                                       share * gather::kThreads, m);
+      else if constexpr (kCast == 3)
+        gather::cast::cast_lane_affine(c, local * gather::kThreads + threadIdx.x,
+                                       share * gather::kThreads, m);
       else
         gather::cast::cast_lane(c, local * gather::kThreads + threadIdx.x,
                                 share * gather::kThreads, m);
@@ -515,6 +532,18 @@ __global__ __launch_bounds__(gather::kThreads) void gather_cast_kernel(gather::m
 __global__ __launch_bounds__(gather::kThreads) void gather_quant_kernel(gather::multi::Args a) {
   __shared__ uint64_t lds[gather::tile::kLds];
   struct_share<2>(a, lds);
+}
+
+// gather_affine_kernel: the same for a plan in which any converted field has a bias or a
+// per-channel table (y = x * S[c] + B[c], cast_device.h): every converted field of such a plan
+// runs the body with the affine step, float and integer destinations alike; the other two
+// kernels hold no line of it.  One kernel, not a float and an integer one as for the plain
+// conversions: it keeps 97 VGPRs, no scratch and four waves a SIMD with 152 SGPRs spilt into
+// VGPR lanes, while the float destinations on their own spilt 85 SGPRs but took 20 bytes of
+// scratch a lane.
+__global__ __launch_bounds__(gather::kThreads) void gather_affine_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  struct_share<3>(a, lds);
 }
 
 // The mask kernels' memory (gather_device.h mask::): the mask with one aligned 16-byte
@@ -845,10 +874,21 @@ int check_plan_range(const dora_plan& plan, int device) {
     if (plan.take.n == 0) return DORA_OK;  // rows of zeros: no field is read
   }
   for (size_t k = 0; k < plan.fields.size(); ++k) {
-    const int rc = check_device_range(plan.fields[k].gd, device);
+    const CastDesc& c = plan.fields[k].cast;
+    int rc = check_device_range(plan.fields[k].gd, device);
+    const char* what = "";
+    // an affine field's tables in HBM: their `channels` words like a take's index
+    if (rc == DORA_OK && kind == PlanLaunch::kCast && c.on && c.scale_tab) {
+      rc = check_device_range(table_reach(c.scale_tab, c.channels), device);
+      what = "scale table: ";
+    }
+    if (rc == DORA_OK && kind == PlanLaunch::kCast && c.on && c.bias_tab) {
+      rc = check_device_range(table_reach(c.bias_tab, c.channels), device);
+      what = "bias table: ";
+    }
     if (rc == DORA_OK) continue;
     const std::string why = dora_gpu_last_error();
-    return fail(rc, "field %zu `%s`: %s", k, plan.fields[k].name.c_str(), why.c_str());
+    return fail(rc, "field %zu `%s`: %s%s", k, plan.fields[k].name.c_str(), what, why.c_str());
   }
   // a bare tensor: strided (kView), or dense and copied by `segs`
   const bool one_view = kind == PlanLaunch::kView ||
@@ -880,6 +920,13 @@ int select_tile_dim(const GatherDesc& g, const uint8_t* dst) {
 
 void gather_force(int mode) { g_gather_force.store(mode, std::memory_order_relaxed); }
 
+// Test hook: launches of this process so far over the fields of a plan, by kernel:
+// gather_struct_kernel, gather_cast_kernel, gather_quant_kernel, gather_affine_kernel.
+std::atomic<uint64_t> g_fields_launches[4];
+void fields_launches(uint64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = g_fields_launches[i].load(std::memory_order_relaxed);
+}
+
 int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEvent_t ev_start,
                   hipEvent_t ev_stop) {
   if (!g.view.total) return DORA_OK;
@@ -904,8 +951,9 @@ namespace {
 // into gather::multi::Args and the kernel chosen, here alone.
 //   kFields: each field as it would go on its own (select_tile_dim), gather_struct_kernel.
 //   kCast: the same, a converted field through the cast body; gather_cast_kernel, or
-//     gather_quant_kernel when any field is quantised.  DORA_ERR_INVALID, nothing launched, when
-//     a converted field would not start on a multiple of its destination element size.
+//     gather_quant_kernel when any field is quantised, or gather_affine_kernel when any has a
+//     bias or a per-channel table.  DORA_ERR_INVALID, nothing launched, when a converted field
+//     would not start on a multiple of its destination element size.
 //   kTaken (`take` given): every field through the taken body, never a tile: row i0 of its bytes
 //     is row take->src[i0] of the field, or zeros where that word is not in [0, take->n).
 // With `scan` (a ragged batch's partition in HBM; n may then be 0) one more workgroup of the same
@@ -932,7 +980,7 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
   uint64_t off[gather::multi::kMaxFields];
   int tile_c[gather::multi::kMaxFields];
   int64_t stride0[gather::multi::kMaxFields];
-  bool quant = false;
+  bool quant = false, affine = false;
   for (size_t k = 0; k < n; ++k) {
     const PlanField& f = fields[k];
     if (!f.bytes) return fail(DORA_ERR_INVALID, "gather of an empty struct field");
@@ -956,6 +1004,13 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
       return fail(DORA_ERR_INVALID, "field %zu `%s`: the converted field would start at %p, not a "
                   "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
                   static_cast<void*>(dst + off[k]), ds);
+    if (!c[k].affine()) continue;
+    affine = true;
+    // the channel stepping never leaves [0, channels) of a table of whole dwords
+    if (!c[k].inner || !c[k].channels ||
+        ((reinterpret_cast<uintptr_t>(c[k].scale_tab) | reinterpret_cast<uintptr_t>(c[k].bias_tab)) & 3))
+      return fail(DORA_ERR_INVALID, "field %zu `%s`: not an affine step this kernel runs", k,
+                  f.name.c_str());
   }
   namespace gm = gather::multi;
   const int nf = static_cast<int>(n);
@@ -963,9 +1018,11 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
                : kind == PlanLaunch::kCast ? gm::make_cast_args(g, c, off, tile_c, nf, dst)
                                            : gm::make_args(g, off, tile_c, nf, dst, scan);
   a.lookup = lookup;
-  void (*kern)(gm::Args) = kind != PlanLaunch::kCast ? gather_struct_kernel
-                           : quant                   ? gather_quant_kernel
-                                                     : gather_cast_kernel;
+  const int which = kind != PlanLaunch::kCast ? 0 : affine ? 3 : quant ? 2 : 1;
+  void (*const kerns[4])(gm::Args) = {gather_struct_kernel, gather_cast_kernel,
+                                      gather_quant_kernel, gather_affine_kernel};
+  void (*kern)(gm::Args) = kerns[which];
+  g_fields_launches[which].fetch_add(1, std::memory_order_relaxed);
   return launch_timed(kern, gm::grid_for(a), gather::kThreads, stream, ev_start, ev_stop, a);
 }
 

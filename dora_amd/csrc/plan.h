@@ -112,7 +112,18 @@ struct CastDesc {
   uint64_t count = 0;
   uint8_t dst_code = 2;  // DL_FLOAT: a cast
   int32_t zero_point = 0;
+  // The affine step (dora_gpu_plan_tensor_affine): y = float32(x) * S + B, two roundings, with
+  // S = scale_tab[c] or the scalar scale or absent, B = bias_tab[c] or the scalar bias or absent,
+  // c = (e / inner) % channels for row-major output element e.  A table is `channels` dense
+  // float32 words where the values live: read by the CPU while a host plan is built and not kept,
+  // read by the launch of a device plan and never on the host (table_reach).
+  const uint8_t* scale_tab = nullptr;
+  const uint8_t* bias_tab = nullptr;
+  uint64_t inner = 1, channels = 1;
+  uint32_t has_bias = 0;
+  float bias = 0.0f;
   bool quant() const { return on && dst_code != 2; }
+  bool affine() const { return on && (has_bias || scale_tab || bias_tab); }
 };
 
 // One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
@@ -144,6 +155,12 @@ inline GatherDesc dense_reach(const uint8_t* src, uint64_t bytes, uint32_t elem)
   r.lo = 0;
   r.hi = static_cast<int64_t>(bytes) - 1;
   return r;
+}
+
+// A per-channel table of an affine field in HBM: what check_plan_range holds against the
+// allocation of `tab`.
+inline GatherDesc table_reach(const uint8_t* tab, uint64_t channels) {
+  return dense_reach(tab, 4 * channels, 4);
 }
 
 // The index of a take plan when it lives in HBM: `count` (K) dense words of 4 or 8 bytes at `src`,
@@ -246,7 +263,7 @@ int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
 // Everything a plan's launch kind asks for beyond `segs` (PlanLaunch below; never kSegments):
 // launch_gather of its view; one launch over its fields — gather_struct_kernel, with the scan of a
 // ragged batch's device partition and by the index of a take, or gather_cast_kernel /
-// gather_quant_kernel for converted fields — each field's bytes as launch_gather would write
+// gather_quant_kernel / gather_affine_kernel for converted fields — each field's bytes as launch_gather would write
 // them, nothing between fields and nothing at or past the last field's end; for a mask plan the
 // two compaction launches and then the fields by the index they wrote, `dst` then holding the
 // sample and plan_workspace bytes behind it.  DORA_ERR_INVALID, nothing launched, when a
@@ -312,6 +329,12 @@ int build_tensor_cast_plan(const dora_tensor_field* fields, size_t n, const dora
 int build_tensor_convert_plan(const dora_tensor_field* fields, size_t n,
                               const dora_tensor_cast* casts, const dora_tensor_quant* quants,
                               ArrowDeviceType dev, dora_plan** out);
+// The same with a per-channel or scalar affine step on converted fields
+// (dora_gpu_plan_tensor_affine); `affines` NULL or all zero: build_tensor_convert_plan's plan.
+int build_tensor_affine_plan(const dora_tensor_field* fields, size_t n,
+                             const dora_tensor_cast* casts, const dora_tensor_quant* quants,
+                             const dora_tensor_affine* affines, ArrowDeviceType dev,
+                             dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -321,7 +344,7 @@ enum class PlanLaunch : uint8_t {
   kSegments,  // `segs` (every host plan, dense device plans, empty plans)
   kView,      // launch_gather of `gd`
   kFields,    // gather_struct_kernel over `fields` (+ scan share when scan_on)
-  kCast,      // gather_cast_kernel / gather_quant_kernel over `fields`
+  kCast,      // gather_cast_kernel / gather_quant_kernel / gather_affine_kernel over `fields`
   kTaken,     // the taken body over `fields` by `take` (+ scan share when scan_on)
   kMasked     // count, compact, then the taken body by the workspace's index
 };

@@ -383,6 +383,9 @@ PyObject* py_send_tensor_struct(PyObject*, PyObject* const* args, Py_ssize_t nar
 // consumes its own.
 // send_tensor_convert takes the same arguments and sends as dora_node_send_output_tensor_convert:
 // an entry may then also be (dtype_code, dtype_bits, scale or None, zero_point), a quantised field.
+// With a ninth argument `affines`, a tuple as long, it sends as
+// dora_node_send_output_tensor_affine: each entry None or (scale table or None, bias table or
+// None, axis, scalar bias or None), a table a "dltensor" capsule that is consumed like a field's.
 PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) {
   const char* usage = convert
       ? "send_tensor_convert(handle, output_id, names, capsules, entries, device_type, metadata, "
@@ -391,7 +394,14 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
       : "send_tensor_cast(handle, output_id, names, capsules, casts, device_type, "
         "metadata, flags): names is None over one capsule or a tuple as long as the "
         "tuple of capsules; casts a tuple as long, of None or (code, bits, scale)";
-  if (nargs != 8 || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
+  // (send_tensor_convert alone: a ninth argument, the affine entries)
+  const bool with_affine = convert && nargs == 9;
+  if (with_affine && !(PyTuple_Check(args[8]) && PyTuple_Check(args[3]) &&
+                       PyTuple_GET_SIZE(args[8]) == PyTuple_GET_SIZE(args[3]))) {
+    PyErr_SetString(PyExc_TypeError, usage);
+    return nullptr;
+  }
+  if ((nargs != 8 && !with_affine) || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
       PyTuple_GET_SIZE(args[4]) != PyTuple_GET_SIZE(args[3]) ||
       !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
                            : PyTuple_Check(args[2]) &&
@@ -471,23 +481,62 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
       c.scale = static_cast<float>(factor);
     }
   }
+  // the affine entries: None, or (scale table capsule or None, bias table capsule or None, axis,
+  // scalar bias or None); the tables' capsules are consumed with the fields'
+  std::vector<dora_tensor_affine> affines(with_affine ? static_cast<size_t>(n) : 0);
+  std::vector<dora_tensor> tables(with_affine ? 2 * static_cast<size_t>(n) : 0);
+  std::vector<std::pair<PyObject*, size_t>> table_caps;  // (capsule, index into `tables`)
+  for (Py_ssize_t k = 0; with_affine && k < n; ++k) {
+    affines[size_t(k)] = dora_tensor_affine{};
+    PyObject* entry = PyTuple_GET_ITEM(args[8], k);
+    if (entry == Py_None) continue;
+    if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 4) {
+      PyErr_Format(PyExc_TypeError, "field %zd: an affine entry is None or (scale table, bias "
+                                    "table, axis, bias)", k);
+      return nullptr;
+    }
+    for (int w = 0; w < 2; ++w) {
+      PyObject* cap = PyTuple_GET_ITEM(entry, w);
+      if (cap == Py_None) continue;
+      if (!PyCapsule_IsValid(cap, "dltensor")) {
+        PyErr_Format(PyExc_TypeError, "field %zd: a table is a DLPack capsule named \"dltensor\" "
+                                      "(an unused, unversioned one)", k);
+        return nullptr;
+      }
+      for (const auto& seen : table_caps)
+        if (seen.first == cap) {
+          PyErr_Format(PyExc_TypeError, "field %zd: two tables share one capsule", k);
+          return nullptr;
+        }
+      for (Py_ssize_t j = 0; j < n; ++j)
+        if (PyTuple_GET_ITEM(args[3], j) == cap) {
+          PyErr_Format(PyExc_TypeError, "field %zd: a table shares a field's capsule", k);
+          return nullptr;
+        }
+      table_caps.emplace_back(cap, 2 * size_t(k) + size_t(w));
+    }
+    const long axis = PyLong_AsLong(PyTuple_GET_ITEM(entry, 2));
+    if (axis == -1 && PyErr_Occurred()) return nullptr;
+    if (axis < INT32_MIN || axis > INT32_MAX) {
+      PyErr_Format(PyExc_TypeError, "field %zd: axis %ld", k, axis);
+      return nullptr;
+    }
+    affines[size_t(k)].axis = static_cast<int32_t>(axis);
+    PyObject* bias = PyTuple_GET_ITEM(entry, 3);
+    if (bias != Py_None) {
+      const double b = PyFloat_AsDouble(bias);
+      if (b == -1.0 && PyErr_Occurred()) return nullptr;
+      affines[size_t(k)].has_bias = 1;
+      affines[size_t(k)].bias_value = static_cast<float>(b);
+    }
+  }
   const long dev = PyLong_AsLong(args[5]);
   if (dev == -1 && PyErr_Occurred()) return nullptr;
   const unsigned long flags = PyLong_AsUnsignedLong(args[7]);
   if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
   std::string& params = t_params;
   if (!encode(args[6], params)) return nullptr;
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
-    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
-      // (cannot happen after the checks above; the capsules renamed so far are released)
-      for (Py_ssize_t j = 0; j < k; ++j)
-        if (managed[size_t(j)]->deleter) managed[size_t(j)]->deleter(managed[size_t(j)]);
-      return nullptr;
-    }
-    managed[size_t(k)] = m;
-    dora_tensor& t = fields[size_t(k)].tensor;
+  auto describe = [](const DlManaged* m, dora_tensor& t) {
     t = dora_tensor{};
     t.data = m->t.data;
     t.byte_offset = m->t.byte_offset;
@@ -497,10 +546,35 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
     t.ndim = m->t.ndim;
     t.shape = m->t.shape;
     t.strides = m->t.strides;
+  };
+  for (Py_ssize_t k = 0; k < n + static_cast<Py_ssize_t>(table_caps.size()); ++k) {
+    PyObject* cap = k < n ? PyTuple_GET_ITEM(args[3], k) : table_caps[size_t(k - n)].first;
+    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
+    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
+      // (cannot happen after the checks above; the capsules renamed so far are released)
+      for (DlManaged* r : managed)
+        if (r && r->deleter) r->deleter(r);
+      return nullptr;
+    }
+    if (k < n) {
+      managed[size_t(k)] = m;
+      describe(m, fields[size_t(k)].tensor);
+      continue;
+    }
+    managed.push_back(m);
+    const size_t at = table_caps[size_t(k - n)].second;
+    describe(m, tables[at]);
+    (at % 2 ? affines[at / 2].bias : affines[at / 2].scale) = &tables[at];
   }
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  if (convert)
+  if (with_affine)
+    rc = dora_node_send_output_tensor_affine(static_cast<dora_node*>(h), oid, fields.data(),
+                                             fields.size(), casts.data(), quants.data(),
+                                             affines.data(), static_cast<ArrowDeviceType>(dev),
+                                             reinterpret_cast<const uint8_t*>(params.data()),
+                                             params.size(), static_cast<uint32_t>(flags));
+  else if (convert)
     rc = dora_node_send_output_tensor_convert(static_cast<dora_node*>(h), oid, fields.data(),
                                               fields.size(), casts.data(), quants.data(),
                                               static_cast<ArrowDeviceType>(dev),

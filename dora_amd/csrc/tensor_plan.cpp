@@ -28,6 +28,9 @@
 // dora_gpu_plan_tensor_convert) are a tensor or a record laid out for the
 // destination dtypes: a cast or quantised field is validated and viewed as its source, and converted on the way
 // — by the CPU here for host values, by the plan's one launch for device values (cast_device.h).
+// With an affine entry (dora_gpu_plan_tensor_affine) a converted field is taken through
+// y = x * S + B first, S and B each a scalar or a per-channel table along one axis: host tables
+// are read and checked here, tables in HBM never, their reach kept for check_plan_range.
 #include <cstring>
 #include <memory>
 #include <string>
@@ -333,7 +336,9 @@ std::string dtype_name(unsigned code, unsigned bits, unsigned lanes) {
 
 // Whether `c` converts `t` at all: dtype_bits == 0 and a destination equal to the source without
 // a scale do not.  The cast's own refusals otherwise (UNSUPPORTED naming the dtype, INVALID).
-int describe_cast(const dora_tensor& t, const dora_tensor_cast& c, CastDesc& out) {
+// (`force`: the field has an affine entry, so a destination equal to the source converts too)
+int describe_cast(const dora_tensor& t, const dora_tensor_cast& c, CastDesc& out,
+                  bool force = false) {
   out = CastDesc{};
   if (c.dtype_bits == 0) return DORA_OK;
   if (c.dtype_code != DL_FLOAT || (c.dtype_bits != 16 && c.dtype_bits != 32))
@@ -347,7 +352,8 @@ int describe_cast(const dora_tensor& t, const dora_tensor_cast& c, CastDesc& out
     return fail(DORA_ERR_UNSUPPORTED, "cast source dtype %s is not supported: uint8, int8, uint16, "
                 "int16, float16, bfloat16 and float32 are",
                 dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
-  if (!c.has_scale && t.dtype_code == c.dtype_code && t.dtype_bits == c.dtype_bits) return DORA_OK;
+  if (!c.has_scale && !force && t.dtype_code == c.dtype_code && t.dtype_bits == c.dtype_bits)
+    return DORA_OK;
   out.on = true;
   out.src_code = t.dtype_code;
   out.src_bits = t.dtype_bits;
@@ -392,29 +398,115 @@ int describe_quant(const dora_tensor& t, const dora_tensor_quant& q, CastDesc& o
 // What converts field `t`: its cast entry, its quantise entry, or neither (`c`, `q` may be NULL).
 // A field with both is INVALID.
 int describe_convert(const dora_tensor& t, const dora_tensor_cast* c, const dora_tensor_quant* q,
-                     CastDesc& out) {
+                     CastDesc& out, bool force = false) {
   out = CastDesc{};
   if (c && q && c->dtype_bits && q->dtype_bits)
     return fail(DORA_ERR_INVALID, "the field is both cast and quantised: one conversion a field");
   if (q && q->dtype_bits) return describe_quant(t, *q, out);
-  return c ? describe_cast(t, *c, out) : DORA_OK;
+  return c ? describe_cast(t, *c, out, force) : DORA_OK;
+}
+
+// Whether an affine entry adds anything to its field (all zero: it does not).
+bool affine_on(const dora_tensor_affine& a) { return a.scale || a.bias || a.has_bias; }
+
+// A per-channel table of the affine step over axis `axis` of `t`: 1-D dense float32 of
+// shape[axis] words on a multiple of 4, where the values live.  A host table is read here and
+// every value must be finite; one in HBM is never read.
+int describe_table(const dora_tensor& tab, const char* what, const dora_tensor& t, int axis,
+                   ArrowDeviceType dev, const uint8_t** out) {
+  if (tab.dtype_code != DL_FLOAT || tab.dtype_bits != 32 || tab.dtype_lanes != 1)
+    return fail(DORA_ERR_UNSUPPORTED, "%s table dtype %s is not supported: float32 is", what,
+                dtype_name(tab.dtype_code, tab.dtype_bits, tab.dtype_lanes).c_str());
+  if (tab.ndim != 1 || !tab.shape)
+    return fail(DORA_ERR_INVALID, "%s table has %d dimensions (a 1-D tensor of the %lld values "
+                "along axis %d)", what, tab.ndim, static_cast<long long>(t.shape[axis]), axis);
+  if (tab.shape[0] != t.shape[axis])
+    return fail(DORA_ERR_INVALID, "%s table has %lld elements, the tensor has %lld along axis %d",
+                what, static_cast<long long>(tab.shape[0]), static_cast<long long>(t.shape[axis]),
+                axis);
+  if (tab.strides && tab.shape[0] > 1 && tab.strides[0] != 1)
+    return fail(DORA_ERR_INVALID, "%s table stride %lld: the table is dense", what,
+                static_cast<long long>(tab.strides[0]));
+  if (!tab.data && tab.shape[0]) return fail(DORA_ERR_INVALID, "%s table data is NULL", what);
+  const uint8_t* p = static_cast<const uint8_t*>(tab.data) + tab.byte_offset;
+  if (reinterpret_cast<uintptr_t>(p) & 3)
+    return fail(DORA_ERR_INVALID, "%s table data %p (data + byte_offset) is not a multiple of 4",
+                what, static_cast<const void*>(p));
+  if (dev != ARROW_DEVICE_ROCM) {
+    for (int64_t i = 0; i < tab.shape[0]; ++i) {
+      float v;
+      std::memcpy(&v, p + 4 * i, 4);
+      if (!std::isfinite(v))
+        return fail(DORA_ERR_INVALID, "%s table: value %lld is %f, not finite", what,
+                    static_cast<long long>(i), static_cast<double>(v));
+    }
+  }
+  *out = p;
+  return DORA_OK;
+}
+
+// The affine step of a field `t` (validated) that `cd` converts or not, by the entry `af`
+// (affine_on): its refusals, else `cd` with the tables, the axis' geometry and the bias.
+int describe_affine(const dora_tensor& t, ArrowDeviceType dev, const dora_tensor_affine& af,
+                    CastDesc& cd) {
+  if (!cd.on)
+    return fail(DORA_ERR_INVALID, "an affine entry on a field that is neither cast nor quantised "
+                "(give it a cast to its own dtype)");
+  if (af.scale && cd.has_scale)
+    return fail(DORA_ERR_INVALID, "a scale table together with a scalar scale (has_scale): one "
+                "scale a field");
+  if (af.bias && af.has_bias)
+    return fail(DORA_ERR_INVALID, "a bias table together with a scalar bias (has_bias): one bias "
+                "a field");
+  if (af.scale || af.bias) {
+    if (af.axis < 0 || af.axis >= t.ndim)
+      return fail(DORA_ERR_INVALID, "affine axis %d is outside the tensor's %d dimensions",
+                  af.axis, t.ndim);
+    int rc = af.scale ? describe_table(*af.scale, "scale", t, af.axis, dev, &cd.scale_tab)
+                      : DORA_OK;
+    if (rc == DORA_OK && af.bias)
+      rc = describe_table(*af.bias, "bias", t, af.axis, dev, &cd.bias_tab);
+    if (rc != DORA_OK) return rc;
+    cd.channels = static_cast<uint64_t>(t.shape[af.axis]);
+    cd.inner = 1;  // (a factor of the element count, which fits 64 bits)
+    for (int i = af.axis + 1; i < t.ndim; ++i) cd.inner *= static_cast<uint64_t>(t.shape[i]);
+  }
+  if (af.has_bias && !std::isfinite(af.bias_value))
+    return fail(DORA_ERR_INVALID, "affine bias %f is not finite",
+                static_cast<double>(af.bias_value));
+  cd.has_bias = af.has_bias ? 1 : 0;
+  cd.bias = af.has_bias ? af.bias_value : 0.0f;
+  return DORA_OK;
 }
 
 // The CPU's conversion of a cast field: the view's rows in row-major order, each element through
 // the integer routines of cast_device.h, into `dst` (any alignment).
+// `ch`: the channel of the row's first element under an affine step, stepped on to that of the
+// element behind the row (the rows come in output order, so one Chan walks the whole field).
 template <uint32_t K>
-void cast_row(const uint8_t* src, uint64_t n, const CastDesc& c, uint8_t* dst) {
+void cast_row(const uint8_t* src, uint64_t n, const CastDesc& c, uint8_t* dst,
+              gather::cast::Chan& ch) {
   constexpr int S = gather::cast::kSize<K>;
   const gather::cast::HostCvt cv;
   const bool quant = c.quant();
   const int dk = quant ? gather::cast::dst_kind(c.dst_code, c.dst_bits) : 0;
   const int32_t lo = quant ? gather::cast::dst_lo(uint32_t(dk)) - c.zero_point : 0,
                 hi = quant ? gather::cast::dst_hi(uint32_t(dk)) - c.zero_point : 0;
+  const bool tables = c.scale_tab || c.bias_tab;
+  auto word = [&](const uint8_t* tab) {
+    float v;
+    std::memcpy(&v, tab + 4 * ch.c, 4);
+    return v;
+  };
   for (uint64_t i = 0; i < n; ++i) {
     uint32_t raw = 0;
     std::memcpy(&raw, src + i * S, S);  // (little-endian)
     float y = cv.to_f32<K>(raw);
-    if (c.has_scale) y = cv.mul(y, c.scale);
+    if (c.scale_tab) y = cv.mul(y, word(c.scale_tab));
+    else if (c.has_scale) y = cv.mul(y, c.scale);
+    if (c.bias_tab) y = cv.add(y, word(c.bias_tab));
+    else if (c.has_bias) y = cv.add(y, c.bias);
+    if (tables) gather::cast::chan_next(c.inner, c.channels, ch);
     if (quant) {
       const uint32_t q = static_cast<uint32_t>(cv.to_int(y, lo, hi, c.zero_point));
       std::memcpy(dst + (c.dst_bits / 8u) * i, &q, c.dst_bits / 8u);  // (little-endian)
@@ -430,7 +522,7 @@ void cast_row(const uint8_t* src, uint64_t n, const CastDesc& c, uint8_t* dst) {
 void cast_host(const StridedView& g, const CastDesc& c, uint8_t* dst) {
   namespace gc = gather::cast;
   const uint64_t ss = c.src_bits / 8u, ds = c.dst_bits / 8u, n = g.row / ss;
-  void (*row)(const uint8_t*, uint64_t, const CastDesc&, uint8_t*) = nullptr;
+  void (*row)(const uint8_t*, uint64_t, const CastDesc&, uint8_t*, gc::Chan&) = nullptr;
   switch (gc::src_kind(c.src_code, c.src_bits)) {
     case gc::kU8: row = cast_row<gc::kU8>; break;
     case gc::kI8: row = cast_row<gc::kI8>; break;
@@ -442,8 +534,9 @@ void cast_host(const StridedView& g, const CastDesc& c, uint8_t* dst) {
   }
   int64_t idx[kMaxTensorDims] = {0};
   int64_t off = 0;
+  gc::Chan ch{0, 0};
   for (uint64_t done = 0; done < c.count; done += n) {
-    row(g.src + off, n, c, dst + done * ds);
+    row(g.src + off, n, c, dst + done * ds, ch);
     for (int k = g.nd - 1; k >= 0; --k) {
       off += g.stride[k];
       if (++idx[k] < g.shape[k]) break;
@@ -539,7 +632,8 @@ struct FieldLayout {
 int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                   const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
                   FieldLayout& lay, int64_t taken = -1, const dora_tensor_cast* casts = nullptr,
-                  const dora_tensor_quant* quants = nullptr) {
+                  const dora_tensor_quant* quants = nullptr,
+                  const dora_tensor_affine* affines = nullptr) {
   p.fields.resize(n);
   lay.chains.resize(n);
   lay.kids.resize(n);
@@ -558,8 +652,15 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     TensorView v;
     int64_t stride0 = 0;
     CastDesc cd;
-    int rc = describe_convert(t, casts ? &casts[k] : nullptr, quants ? &quants[k] : nullptr, cd);
+    const bool affine = affines && affine_on(affines[k]);
+    int rc = describe_convert(t, casts ? &casts[k] : nullptr, quants ? &quants[k] : nullptr, cd,
+                              affine);
     if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
+    if (affine && !cd.on) {
+      rc = describe_tensor(&t, dev, v);  // (the tensor's own refusals first)
+      if (rc == DORA_OK) rc = describe_affine(t, dev, affines[k], cd);
+      return bare ? rc : field_fail(rc, k, name);
+    }
     if (cd.on) {
       // the view of the source: any accepted dtype of its width describes it (Arrow has no
       // bfloat16, and the leaf is the destination's anyway)
@@ -571,6 +672,7 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
         rc = fail(DORA_ERR_INVALID, "cast source data %p (data + byte_offset) is not a multiple "
                   "of its %u-byte elements", static_cast<const void*>(v.gd.view.src),
                   cd.src_bits / 8u);
+      if (rc == DORA_OK && affine) rc = describe_affine(t, dev, affines[k], cd);
       if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
       cd.count = v.bytes / (cd.src_bits / 8u);
       if (cd.quant())
@@ -787,14 +889,16 @@ void place_masked_host(dora_plan& p, const MaskIn& mk, uint64_t staged) {
 // the rows of it that the index takes.
 int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                  const TakeIn* tk, dora_plan** out, const dora_tensor_cast* casts = nullptr,
-                 const dora_tensor_quant* quants = nullptr) {
+                 const dora_tensor_quant* quants = nullptr,
+                 const dora_tensor_affine* affines = nullptr) {
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
   FieldLayout lay;
   std::vector<TypeInfoNode> solo;
   int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
-                               tk ? static_cast<int64_t>(tk->ix.count) : -1, casts, quants);
+                               tk ? static_cast<int64_t>(tk->ix.count) : -1, casts, quants,
+                               affines);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
   if (bare) {
@@ -885,6 +989,22 @@ int build_tensor_convert_plan(const dora_tensor_field* f, size_t n, const dora_t
                 : build_tensor_struct_plan(f, n, dev, out);
   }
   return build_record(f, n, dev, bare, nullptr, out, casts, quants);
+}
+
+int build_tensor_affine_plan(const dora_tensor_field* f, size_t n, const dora_tensor_cast* casts,
+                             const dora_tensor_quant* quants, const dora_tensor_affine* affines,
+                             ArrowDeviceType dev, dora_plan** out) {
+  bool any = false;
+  for (size_t k = 0; affines && f && k < n; ++k) any |= affine_on(affines[k]);
+  // no affine step at all: the conversion's plan, whatever it is, refusals included
+  if (!any) return build_tensor_convert_plan(f, n, casts, quants, dev, out);
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  const int rf = check_fields(f, n, "a conversion");
+  if (rf != DORA_OK) return rf;
+  // every field's own refusals, then its affine entry's, as the fields are laid out
+  return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, casts, quants, affines);
 }
 
 namespace {
@@ -1282,6 +1402,13 @@ int dora_gpu_plan_tensor_convert(const dora_tensor_field* fields, size_t n,
                                  const dora_tensor_cast* casts, const dora_tensor_quant* quants,
                                  ArrowDeviceType device_type, dora_plan** out) {
   return dora::build_tensor_convert_plan(fields, n, casts, quants, device_type, out);
+}
+
+int dora_gpu_plan_tensor_affine(const dora_tensor_field* fields, size_t n,
+                                const dora_tensor_cast* casts, const dora_tensor_quant* quants,
+                                const dora_tensor_affine* affines, ArrowDeviceType device_type,
+                                dora_plan** out) {
+  return dora::build_tensor_affine_plan(fields, n, casts, quants, affines, device_type, out);
 }
 
 int dora_gpu_plan_tensor_take(const dora_tensor_take* take, ArrowDeviceType device_type,

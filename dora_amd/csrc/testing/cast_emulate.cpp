@@ -32,7 +32,16 @@
 // `off` the field's bytes in the sample.  `source_file` holds the hi - lo + 1 bytes of
 // [src + lo, src + hi].  `dst_addr` / `src_addr` are the addresses the kernel would see (only
 // their alignment matters; neither is dereferenced).
-// Exit status 0 and "ok" when every check held in every case.
+// `cast` 3: the field has an affine step (tests/test_affine_index_host.py) and its case is
+// gather_affine_kernel's launch; these follow `cast` at once:
+//   base inner channels has_bias bias_bits scale_addr bias_addr scale_file bias_file
+// `base` 1 or 2, after which the field goes on as such a field does (2: `dst_code zero_point`);
+// `inner` / `channels` the geometry of the axis, `bias_bits` the scalar bias' bit pattern,
+// `scale_addr` / `bias_addr` the addresses the kernel would see of the tables (0: none, the file
+// name is then ignored) and the files their `channels` float32 words.  Besides (a)-(f) every table
+// load must have an index inside [0, channels) and a naturally aligned address.
+// Exit status 0 and "ok" when every check held in every case; after cases with an affine step a
+// second line counts them and their table loads.
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -117,6 +126,18 @@ struct EmuMem : ct::HostCvt {
     if ((s->addr + at + e * D) % D) die(field, "element store not aligned", int64_t(e), D);
     for (int i = 0; i < D; ++i) s->write(field, at + e * D + uint64_t(i), uint8_t(bits >> (8 * i)));
   }
+  // the affine step: word `c` of the table the kernel would see at `tab`
+  std::vector<float> stab, btab;
+  uint64_t stab_addr = 0, btab_addr = 0, channels = 0, table_loads = 0;
+  float load_table(const uint8_t* tab, uint64_t c) {
+    const uint64_t addr = reinterpret_cast<uintptr_t>(tab);
+    if (!addr || (addr != stab_addr && addr != btab_addr)) die(field, "load from no table", int64_t(addr), 0);
+    if (c >= channels) die(field, "table index outside [0, C)", int64_t(c), int64_t(channels));
+    if ((addr + 4 * c) & 3) die(field, "table load not naturally aligned", int64_t(addr), int64_t(c));
+    ++table_loads;
+    // (the same address for both: the same words)
+    return addr == stab_addr ? stab[size_t(c)] : btab[size_t(c)];
+  }
   // the rows body
   U16 load16(int64_t o) {
     src_check(o, 16, 4);
@@ -167,7 +188,7 @@ int main(int argc, char** argv) {
     std::printf("FAIL output file\n");
     return 2;
   }
-  uint64_t loads = 0, vec_loads = 0, grid_sum = 0;
+  uint64_t loads = 0, vec_loads = 0, grid_sum = 0, table_loads = 0, affine_cases = 0;
   int64_t n = 0;
   while (in >> n) {
     uint64_t dst_addr = 0, size = 0;
@@ -184,12 +205,25 @@ int main(int argc, char** argv) {
     Sample s{size, dst_addr, std::vector<int8_t>(size, -1), std::vector<uint8_t>(size, 0xA5),
              std::vector<uint8_t>(size, 0)};
     std::vector<EmuMem> mem(static_cast<size_t>(n));
+    bool any_affine = false;
     for (int k = 0; k < n; ++k) {
       uint64_t src = 0;
       uint32_t on = 0, code = 0, sbits = 0, dbits = 0, has_scale = 0, scale_bits = 0, dcode = 2;
       int32_t zp = 0;
-      std::string file;
+      std::string file, stab_file, btab_file;
+      uint64_t stab_addr = 0, btab_addr = 0;
+      uint32_t has_bias = 0, bias_bits = 0;
+      bool affine = false;
       in >> on;
+      if (on == 3) {
+        affine = any_affine = true;
+        in >> on >> c[k].inner >> c[k].channels >> has_bias >> bias_bits >> stab_addr >>
+            btab_addr >> stab_file >> btab_file;
+        if (!in || (on != 1 && on != 2) || !c[k].inner || !c[k].channels) {
+          std::printf("FAIL bad affine field %d of case %d\n", k, g_case);
+          return 2;
+        }
+      }
       if (on == 2) in >> dcode >> zp;
       in >> code >> sbits >> dbits >> has_scale >> scale_bits >> c[k].count >> g[k].elem >>
           g[k].view.row >> g[k].view.total >> dst_bytes[k] >> g[k].lo >> g[k].hi >> src >> off[k] >>
@@ -239,6 +273,26 @@ int main(int argc, char** argv) {
         std::printf("FAIL source file of field %d of case %d\n", k, g_case);
         return 2;
       }
+      if (affine) {
+        c[k].has_bias = has_bias;
+        c[k].bias = ct::f32_of(bias_bits);
+        c[k].scale_tab = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(stab_addr));
+        c[k].bias_tab = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(btab_addr));
+        m.stab_addr = stab_addr;
+        m.btab_addr = btab_addr;
+        m.channels = c[k].channels;
+        std::vector<uint8_t> raw;
+        for (int t = 0; t < 2; ++t) {
+          if (!(t ? btab_addr : stab_addr)) continue;
+          if (!read_file(t ? btab_file : stab_file, raw, 4 * c[k].channels)) {
+            std::printf("FAIL table file of field %d of case %d\n", k, g_case);
+            return 2;
+          }
+          std::vector<float>& tab = t ? m.btab : m.stab;
+          tab.resize(size_t(c[k].channels));
+          std::memcpy(tab.data(), raw.data(), raw.size());
+        }
+      }
     }
     const mt::Args a = mt::make_cast_args(g, c, off, tile_c, int(n), dst);
     const uint32_t grid = mt::grid_for(a);
@@ -257,7 +311,10 @@ int main(int argc, char** argv) {
       EmuMem& m = mem[size_t(k)];
       for (uint32_t th = 0; th < uint32_t(dora::gather::kThreads); ++th) {
         const uint64_t lane = local * dora::gather::kThreads + th;
-        if (c[k].on) ct::cast_lane(a.f[k].cast, lane, share * dora::gather::kThreads, m);
+        // (a case with an affine field is gather_affine_kernel's: all its converted fields)
+        if (c[k].on && any_affine)
+          ct::cast_lane_affine(a.f[k].cast, lane, share * dora::gather::kThreads, m);
+        else if (c[k].on) ct::cast_lane(a.f[k].cast, lane, share * dora::gather::kThreads, m);
         else dora::gather::gather_lane(a.f[k].rows, lane, share * dora::gather::kThreads, m);
       }
     }
@@ -271,7 +328,9 @@ int main(int argc, char** argv) {
     for (const EmuMem& m : mem) {
       loads += m.loads;
       vec_loads += m.vec_loads;
+      table_loads += m.table_loads;
     }
+    affine_cases += any_affine;
     grid_sum += grid;
     ++g_case;
   }
@@ -282,5 +341,7 @@ int main(int argc, char** argv) {
   }
   std::printf("ok cases=%d grid=%" PRIu64 " loads=%" PRIu64 " vector_loads=%" PRIu64 "\n", g_case,
               grid_sum, loads, vec_loads);
+  if (affine_cases)
+    std::printf("affine cases=%" PRIu64 " table_loads=%" PRIu64 "\n", affine_cases, table_loads);
   return 0;
 }

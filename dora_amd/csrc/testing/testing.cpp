@@ -33,6 +33,7 @@ namespace dora {
 int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t cap,
                          uint32_t* grid);
 void gather_force(int mode);
+void fields_launches(uint64_t out[4]);
 int select_tile_dim(const GatherDesc& g, const uint8_t* dst);
 }  // namespace dora
 
@@ -434,6 +435,33 @@ int dora_gpu_test_plan_quant(const dora_plan* plan, size_t i, int* is_quant, int
   if (dst_code) *dst_code = q ? c.dst_code : -1;
   if (dst_bits) *dst_bits = q ? c.dst_bits : 0;
   if (zero_point) *zero_point = q ? c.zero_point : 0;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_affine(const dora_plan* plan, size_t i, int* is_affine,
+                              const void** scale_table, const void** bias_table, uint64_t* inner,
+                              uint64_t* channels, int* has_bias, float* bias, int64_t* lo,
+                              int64_t* hi) {
+  if (!plan || !plan->dev_tensor || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a device plan with a field %zu", i);
+  const dora::CastDesc& c = plan->fields[i].cast;
+  const bool on = plan->launch == dora::PlanLaunch::kCast && c.affine();
+  const bool tables = on && (c.scale_tab || c.bias_tab);
+  if (is_affine) *is_affine = on;
+  if (scale_table) *scale_table = on ? c.scale_tab : nullptr;
+  if (bias_table) *bias_table = on ? c.bias_tab : nullptr;
+  if (inner) *inner = tables ? c.inner : 0;
+  if (channels) *channels = tables ? c.channels : 0;
+  if (has_bias) *has_bias = on && c.has_bias;
+  if (bias) *bias = on ? c.bias : 0.0f;
+  if (lo) *lo = tables ? dora::table_reach(nullptr, c.channels).lo : 0;
+  if (hi) *hi = tables ? dora::table_reach(nullptr, c.channels).hi : -1;
+  return DORA_OK;
+}
+
+int dora_gpu_test_fields_launches(uint64_t* counts) {
+  if (!counts) return dora::fail(DORA_ERR_INVALID, "counts is NULL");
+  dora::fields_launches(counts);
   return DORA_OK;
 }
 

@@ -450,6 +450,10 @@ class Node:
         kind, tensors, names = self._values_kind(plain if record else plain[None])
         # (a cast entry has three items, a quantise entry four)
         entries = tuple(v._entry() if isinstance(v, conv) else None for v in items.values())
+        affines = [v._affine() if isinstance(v, conv) else None for v in items.values()]
+        if any(a is not None for a in affines):
+            return self._send_tensor_affine(output_id, items, kind, tensors, names, entries,
+                                            affines, metadata, flags)
         fast = _fast.send_tensor_convert if quantise else _fast.send_tensor_cast
         if kind == "device":
             caps, _, done = self._device_caps(flags, tensors)
@@ -476,6 +480,70 @@ class Node:
             del keep, described
             return rc
         return fast(self.handle, output_id, names, caps, entries, dev, metadata, flags)
+
+    def _send_tensor_affine(self, output_id: str, items, kind, tensors, names, entries, affines,
+                            metadata, flags: int) -> int:
+        """`_send_tensor_convert` when a field has a bias or a per-channel table
+        (dora_node_send_output_tensor_affine): `affines` holds, per field, None or (scale table,
+        bias table, axis, scalar bias).
+
+        Tables live where the values live.  With host values a table is a sequence, a numpy
+        array or a CPU tensor: it is converted to float32 here and checked inside the call — its
+        length, every value finite — else the call raises and nothing is sent.  With values on
+        this node's GPU a table is a float32 tensor there: it does the
+        `__dlpack__(stream=<the node stream>)` handshake like every field, is never read on the
+        host, and an asynchronous send holds it with the values until `sync()`."""
+        import numpy as np
+        tabs = [t for a in affines if a is not None for t in a[:2] if t is not None]
+        for t in tabs:
+            on_device = hasattr(t, "__dlpack_device__") and \
+                int(t.__dlpack_device__()[0]) not in _DL_HOST
+            if on_device:
+                self._tensor_kind(t, "a per-channel table")
+            if kind == "device" and not on_device:
+                raise TypeError("a per-channel table in host memory over values on this node's "
+                                "GPU: make the table once on the device (a float32 tensor) and "
+                                "send with that")
+            if kind != "device" and on_device:
+                raise TypeError("a per-channel table in device memory over host values: move the "
+                                "table next to the values (.tolist())")
+        if kind == "device":
+            caps, tcaps, done = self._device_caps(flags, tensors, tabs, len(tensors) + len(tabs))
+            tcaps = iter(tcaps)
+            aff = tuple(None if a is None else
+                        (None if a[0] is None else next(tcaps),
+                         None if a[1] is None else next(tcaps), a[2], a[3]) for a in affines)
+            return done(_fast.send_tensor_convert(self.handle, output_id, names, caps, entries,
+                                                  ARROW_DEVICE_ROCM, metadata, flags, aff))
+        host = {id(t): np.ascontiguousarray(np.asarray(t, dtype=np.float32)) for t in tabs}
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
+            from ._lib import Tensor
+            from .tensor import (_describe_affines, _describe_array, _describe_casts,
+                                 _describe_list, _describe_quants)
+            described = [_describe_array(v) for v in tensors]
+            tdesc = {k: _describe_array(a) for k, a in host.items()}
+            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
+                                       ARROW_DEVICE_CPU)
+            carr = _describe_casts([v if isinstance(v, _Cast) else None for v in items.values()])
+            qarr = _describe_quants([v if isinstance(v, _Quantized) else None
+                                     for v in items.values()])
+            aarr, akeep = _describe_affines([
+                None if a is None else (None if a[0] is None else tdesc[id(a[0])][0],
+                                        None if a[1] is None else tdesc[id(a[1])][0], a[2], a[3])
+                for a in affines])
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_affine(
+                self.handle, output_id.encode(), lst.fields, len(tensors), carr, qarr, aarr, dev,
+                params, len(params), flags)
+            del keep, described, tdesc, akeep
+            return rc
+        aff = tuple(None if a is None else
+                    (None if a[0] is None else host[id(a[0])].__dlpack__(),
+                     None if a[1] is None else host[id(a[1])].__dlpack__(), a[2], a[3])
+                    for a in affines)
+        return _fast.send_tensor_convert(self.handle, output_id, names, caps, entries, dev,
+                                         metadata, flags, aff)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
         """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with

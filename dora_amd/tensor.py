@@ -106,7 +106,35 @@ of range saturate.  `zero_point` is an integer in `[lo, hi]`.  `from_numpy_quant
 numpy and every send, from host and from device, is bit-exact against it for every input.  In
 place of `x.mul(255).round().clamp(0, 255).to(torch.uint8)` and its launches and intermediates
 the send's one launch reads the source once and writes a sample a half or a quarter the size.
-Not offered: a quantise under `ragged`, `take` or `masked`; per-channel scales.
+Not offered: a quantise under `ragged`, `take` or `masked`; per-channel zero points.
+
+Both take a bias and per-channel values, which is what normalisation and per-channel quantisation
+need: `cast(x, dtype, scale=None, *, bias=None, axis=None)` and `quantize(x, dtype, scale=None,
+zero_point=0, *, bias=None, axis=None)`, `scale` and `bias` each one number or a 1-D table of one
+value per channel along `axis`, a dimension of `x` as given (after any `permute`; negative: from
+the back):
+
+    s, b = 1 / (255 * std), -mean / std                    # (x / 255 - mean[c]) / std[c] = x * s[c] + b[c]
+    node.send_output("image", tensor.cast(frame.permute(2, 0, 1), "float16", scale=s, bias=b, axis=0))
+    node.send_output("act", tensor.quantize(feat, "int8", scale=per_channel, axis=1))
+    node.send_output("out", {"image": tensor.cast(img, "float16", scale=s, bias=b, axis=-1), "conf": conf})
+
+With C the extent of `axis` and `inner` the product of the extents behind it, output element `e`
+(row-major) has channel `c = (e / inner) % C` and `y = float32(x) * S + B`: two float32
+operations, the product rounded and then the sum, never one fused multiply-add; `S` is
+`scale[c]`, the scalar scale or absent (no multiplication), `B` is `bias[c]`, the scalar bias or
+absent (no addition, so a zero product keeps its sign).  Then the cast or the quantise as above.
+`from_numpy_cast` and `from_numpy_quantize` state it in numpy with `bias=` and `axis=`, and every
+send is bit-exact against them but for a NaN's payload in a float destination.  A scalar and a
+table may be mixed; a table needs `axis`, and `axis` needs a table.  Tables live where the values
+live.  With host values a table is a sequence, a numpy array or a CPU tensor, converted to float32
+and checked inside the send: length C, every value finite, else the send raises and nothing
+leaves.  With values in this node's HBM a table is a float32 tensor in this node's HBM, 1-D, dense,
+of C elements; it is never read on the host, so whatever it holds the result is the formula (a
+NaN or an infinity propagates, and under a quantise saturates or becomes `zero_point`), and no
+word outside the table is read.  A host table over device values raises: make the table once on
+the device.  Not offered: per-channel zero points, a host table over device values, a conversion
+under `ragged`, `take` or `masked`, bfloat16 destinations.
 
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
 is copied once, so every source has been read when `send_output` returns.  A tensor in device
@@ -118,8 +146,8 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import (Tensor, TensorCast, TensorField, TensorList, TensorMask, TensorQuant,
-                   TensorTake)
+from ._lib import (Tensor, TensorAffine, TensorCast, TensorField, TensorList, TensorMask,
+                   TensorQuant, TensorTake)
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -273,74 +301,168 @@ def _cast_dtype(dtype):
     return _DL_CODES.get(dt.kind, 255), dt.itemsize * 8, dt.name
 
 
-class Cast:
+def _is_table(v):
+    """Whether `v` (a scale or a bias) is a per-channel table and not one number."""
+    if v is None or isinstance(v, (int, float)):
+        return False
+    if getattr(v, "ndim", None) == 0:
+        return False
+    return hasattr(v, "__len__") or hasattr(v, "__dlpack__")
+
+
+class _Affine:
+    """What `Cast` and `Quantized` share of the affine step `x * S + B`: `scale` and `bias` the
+    scalars (None: absent or a table), `scale_table` and `bias_table` the per-channel tables as
+    given (None: absent or a scalar), `axis` the dimension of `values` they run along, counted
+    from the front (None: no table)."""
+
+    __slots__ = ()
+
+    def _set_affine(self, what, scale, bias, axis):
+        import operator
+        self.scale = self.bias = self.scale_table = self.bias_table = self.axis = None
+        if axis is None:
+            for name, v in (("scale", scale), ("bias", bias)):
+                if _is_table(v) and not (name == "scale" and bias is None and what == "cast"):
+                    # (a cast without bias and axis refuses a table as float() does, as before)
+                    try:
+                        v = float(v)
+                    except (TypeError, ValueError):
+                        raise TypeError(f"{what}: the {name} is one number; a per-channel {name} "
+                                        "(a 1-D table) needs axis=") from None
+                if v is not None:
+                    setattr(self, name, float(v))
+            return
+        if not (_is_table(scale) or _is_table(bias)):
+            raise TypeError(f"{what}: axis= goes with a per-channel scale or bias (a 1-D table); "
+                            "with numbers alone leave it out")
+        shape = getattr(self.values, "shape", None)
+        if shape is None:
+            raise TypeError(f"{what}: the values have no shape to count axis= in")
+        axis = operator.index(axis)
+        self.axis = axis + len(shape) if axis < 0 else axis  # (out of range: the send refuses it)
+        for name, v in (("scale", scale), ("bias", bias)):
+            if _is_table(v):
+                setattr(self, name + "_table", v)
+            elif v is not None:
+                setattr(self, name, float(v))
+
+    def _affine(self):
+        """None, or the send's affine entry before its tables are described: (scale table or
+        None, bias table or None, axis, scalar bias or None)."""
+        if self.bias is None and self.scale_table is None and self.bias_table is None:
+            return None
+        return (self.scale_table, self.bias_table, self.axis or 0, self.bias)
+
+    def _affine_repr(self):
+        by = " * table" if self.scale_table is not None else \
+            "" if self.scale is None else f" * {self.scale!r}"
+        plus = " + table" if self.bias_table is not None else \
+            "" if self.bias is None else f" + {self.bias!r}"
+        return by + plus + ("" if self.axis is None else f" along axis {self.axis}")
+
+
+class Cast(_Affine):
     """A tensor converted on send: `values`, a tensor, and the `dtype` it is sent as, after one
-    optional multiplication by `scale`.  It copies and converts nothing itself.  Build one with
+    optional multiplication by `scale` and one optional addition of `bias`, each a number or a
+    per-channel table along `axis`.  It copies and converts nothing itself.  Build one with
     `cast`."""
 
-    __slots__ = ("values", "dtype", "scale", "_code", "_bits")
+    __slots__ = ("values", "dtype", "scale", "bias", "scale_table", "bias_table", "axis", "_code",
+                 "_bits")
 
-    def __init__(self, values, dtype, scale=None):
+    def __init__(self, values, dtype, scale=None, bias=None, axis=None):
         self.values = values
         self._code, self._bits, self.dtype = _cast_dtype(dtype)
-        self.scale = None if scale is None else float(scale)
+        self._set_affine("cast", scale, bias, axis)
 
     def _entry(self):
         return (self._code, self._bits, self.scale)
 
     def __repr__(self):
-        by = "" if self.scale is None else f" * {self.scale!r}"
-        return f"Cast({self.values!r}{by} -> {self.dtype})"
+        return f"Cast({self.values!r}{self._affine_repr()} -> {self.dtype})"
 
 
-def cast(values, dtype, scale=None):
+def cast(values, dtype, scale=None, *, bias=None, axis=None):
     """`values` converted to `dtype` as a message: `values` a tensor of uint8, int8, uint16, int16,
     float16, bfloat16 or float32 (host memory or this node's HBM), `dtype` "float16" or "float32"
-    (or the numpy or torch dtype), `scale` an optional finite factor applied in float32 first.
-    `send_output` sends it, on its own or as a value of a dict of tensors, as what
-    `from_numpy_cast` states."""
+    (or the numpy or torch dtype), `scale` an optional finite factor applied in float32 first and
+    `bias` an optional finite term added after it.  Either may be a 1-D table of one value per
+    channel along `axis`, a dimension of `values` as given (negative: from the back), next to the
+    values: a sequence, numpy array or CPU tensor with host values, a float32 tensor in this
+    node's HBM with device values.  `send_output` sends it, on its own or as a value of a dict of
+    tensors, as what `from_numpy_cast` states."""
     if isinstance(values, Quantized):
         raise TypeError("cast of a quantised tensor is not offered: a field is cast or quantised, "
                         "not both")
     if isinstance(values, (Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("cast converts one tensor: give a dict's fields a cast each; a cast under "
                         "ragged or take is not offered")
-    return Cast(values, dtype, scale)
+    return Cast(values, dtype, scale, bias, axis)
 
 
-def from_numpy_cast(x, dtype, scale=None, *, bfloat16=False):
-    """The nested pyarrow array of `(x.astype(float32) * float32(scale)).astype(dtype)`, the
-    statement of record of `cast` and the counterpart of `from_numpy`: what
-    `send_output(output_id, cast(x, dtype, scale))` puts on the wire.  `bfloat16`: `x` holds the
-    bits of bfloat16 values as uint16 (numpy has no such dtype)."""
+def _numpy_affine(y, scale, bias, axis):
+    """`y * s32 + b32` in float32, the product rounded and then the sum: `scale` and `bias` None,
+    a number or a 1-D table reshaped to broadcast along `axis` of `y`."""
+    import numpy as np
+
+    def term(v, name):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float32)
+        if a.ndim == 0:
+            return np.float32(a)
+        if axis is None:
+            raise TypeError(f"a per-channel {name} (a 1-D table) needs axis=")
+        if a.ndim != 1 or len(a) != y.shape[axis]:
+            raise ValueError(f"the {name} table has shape {a.shape}, the values have "
+                             f"{y.shape[axis]} along axis {axis}")
+        shape = [1] * y.ndim
+        shape[axis] = len(a)
+        return a.reshape(shape)
+    s, b = term(scale, "scale"), term(bias, "bias")
+    if s is not None:
+        y = y * s
+    if b is not None:
+        y = y + b
+    return y
+
+
+def from_numpy_cast(x, dtype, scale=None, *, bfloat16=False, bias=None, axis=None):
+    """The nested pyarrow array of `(x.astype(float32) * s32 + b32).astype(dtype)`, the statement
+    of record of `cast` and the counterpart of `from_numpy`: what
+    `send_output(output_id, cast(x, dtype, scale, bias=bias, axis=axis))` puts on the wire.  `s32`
+    and `b32` are `scale` and `bias` as float32, a 1-D table reshaped to broadcast along `axis`;
+    the product is rounded to float32, then the sum; an absent term is not applied.  `bfloat16`:
+    `x` holds the bits of bfloat16 values as uint16 (numpy has no such dtype)."""
     import numpy as np
     x = np.asarray(x)
     if bfloat16:
         x = (x.astype(np.uint32) << 16).view(np.float32)
-    y = x.astype(np.float32)
-    if scale is not None:
-        y = y * np.float32(scale)
-    with np.errstate(over="ignore"):
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        y = _numpy_affine(x.astype(np.float32), scale, bias, axis)
         return from_numpy(y.astype(np.dtype(_cast_dtype(dtype)[2])))
 
 
-class Quantized:
+class Quantized(_Affine):
     """A tensor quantised on send: `values`, a tensor, the integer `dtype` it is sent as, the
-    optional `scale` it is multiplied by first and the `zero_point` added last.  It copies and
+    optional `scale` it is multiplied by first, the optional `bias` added to the product (each a
+    number or a per-channel table along `axis`) and the `zero_point` added last.  It copies and
     converts nothing itself.  Build one with `quantize`."""
 
-    __slots__ = ("values", "dtype", "scale", "zero_point", "_code", "_bits")
+    __slots__ = ("values", "dtype", "scale", "bias", "scale_table", "bias_table", "axis",
+                 "zero_point", "_code", "_bits")
 
-    def __init__(self, values, dtype, scale=None, zero_point=0):
+    def __init__(self, values, dtype, scale=None, zero_point=0, bias=None, axis=None):
         import operator
         self.values = values
         self._code, self._bits, self.dtype = _cast_dtype(dtype)
-        self.scale = None if scale is None else float(scale)
+        self._set_affine("quantize", scale, bias, axis)
         try:
             self.zero_point = operator.index(zero_point)
         except TypeError:
             raise TypeError(f"quantize: the zero point {zero_point!r} is not an integer (per-channel "
-                            "zero points and scales are not offered)") from None
+                            "zero points are not offered)") from None
         if not -2 ** 31 <= self.zero_point < 2 ** 31:
             raise ValueError(f"quantize: the zero point {self.zero_point} is outside every "
                              "destination's range")
@@ -349,33 +471,30 @@ class Quantized:
         return (self._code, self._bits, self.scale, self.zero_point)
 
     def __repr__(self):
-        by = "" if self.scale is None else f" * {self.scale!r}"
         zp = "" if not self.zero_point else f" + {self.zero_point}"
-        return f"Quantized({self.values!r}{by}{zp} -> {self.dtype})"
+        return f"Quantized({self.values!r}{self._affine_repr()}{zp} -> {self.dtype})"
 
 
-def quantize(values, dtype, scale=None, zero_point=0):
+def quantize(values, dtype, scale=None, zero_point=0, *, bias=None, axis=None):
     """`values` quantised to `dtype` as a message: `values` a tensor of uint8, int8, uint16, int16,
     float16, bfloat16 or float32 (host memory or this node's HBM), `dtype` "uint8", "int8",
     "uint16" or "int16" (or the numpy or torch dtype), `scale` an optional finite factor applied in
-    float32 first, `zero_point` an integer in the range of `dtype`.  `send_output` sends it, on its
-    own or as a value of a dict of tensors, as what `from_numpy_quantize` states."""
+    float32 first, `bias` an optional finite term added after it — either may be a 1-D table of one
+    value per channel along `axis`, as in `cast` — and `zero_point` one integer in the range of
+    `dtype`.  `send_output` sends it, on its own or as a value of a dict of tensors, as what
+    `from_numpy_quantize` states."""
     if isinstance(values, (Quantized, Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("quantize converts one tensor: give a dict's fields a quantize each; a "
                         "quantise of a cast, or under ragged, take or masked, is not offered")
-    if scale is not None and not isinstance(scale, (int, float)):
-        try:
-            scale = float(scale)
-        except (TypeError, ValueError):
-            raise TypeError("quantize: the scale is one number (per-channel scales are not "
-                            "offered)") from None
-    return Quantized(values, dtype, scale, zero_point)
+    return Quantized(values, dtype, scale, zero_point, bias, axis)
 
 
-def from_numpy_quantize(x, dtype, scale=None, zero_point=0, *, bfloat16=False):
+def from_numpy_quantize(x, dtype, scale=None, zero_point=0, *, bfloat16=False, bias=None,
+                        axis=None):
     """The nested pyarrow array of `x` quantised to `dtype`, the statement of record of `quantize`:
-    what `send_output(output_id, quantize(x, dtype, scale, zero_point))` puts on the wire.
-    `bfloat16`: `x` holds the bits of bfloat16 values as uint16."""
+    what `send_output(output_id, quantize(x, dtype, scale, zero_point, bias=bias, axis=axis))`
+    puts on the wire, `y = x.astype(float32) * s32 + b32` as in `from_numpy_cast`.  `bfloat16`:
+    `x` holds the bits of bfloat16 values as uint16."""
     import numpy as np
     x = np.asarray(x)
     if bfloat16:
@@ -384,9 +503,7 @@ def from_numpy_quantize(x, dtype, scale=None, zero_point=0, *, bfloat16=False):
     info = np.iinfo(dt)
     zp = int(zero_point)
     with np.errstate(over="ignore", under="ignore", invalid="ignore"):
-        y = x.astype(np.float32)
-        if scale is not None:
-            y = y * np.float32(scale)
+        y = _numpy_affine(x.astype(np.float32), scale, bias, axis)
         r = np.rint(y)
         r = np.where(np.isnan(y), np.float32(0), r)
         r = np.clip(r, np.float32(info.min - zp), np.float32(info.max - zp))
@@ -658,6 +775,28 @@ def _describe_quants(quants) -> "ctypes.Array":
         arr[k].scale = 0.0 if q.scale is None else q.scale
         arr[k].zero_point = q.zero_point
     return arr
+
+
+def _describe_affines(entries) -> tuple:
+    """The `dora_tensor_affine` array of `entries`, each None (no affine step) or (scale table,
+    bias table, axis, scalar bias) with a table a `Tensor` of `_describe` or None, and what the
+    caller keeps alive with it."""
+    from ctypes import pointer
+    arr = (TensorAffine * len(entries))()
+    keep = []
+    for k, e in enumerate(entries):
+        if e is None:
+            continue
+        s, b, axis, bias = e
+        if s is not None:
+            arr[k].scale = pointer(s)
+        if b is not None:
+            arr[k].bias = pointer(b)
+        arr[k].axis = axis
+        arr[k].has_bias = 0 if bias is None else 1
+        arr[k].bias_value = 0.0 if bias is None else bias
+        keep.append((s, b))
+    return arr, keep
 
 
 def _describe_list(names, tensors, partition, form, partition_device) -> tuple:

@@ -501,7 +501,8 @@ int dora_gpu_plan_tensor_cast(const dora_tensor_field* fields, size_t n,
  * element size and held against its allocation before anything is launched.  dora_gpu_pack to a
  * destination where a 16-bit field would start on an odd address is DORA_ERR_INVALID with nothing
  * launched.
- * Not provided: a quantise under a ragged batch, a take or a mask; per-channel scales.
+ * Not provided: a quantise under a ragged batch, a take or a mask; per-channel zero points
+ * (per-channel scales and biases are dora_gpu_plan_tensor_affine's, below).
  */
 typedef struct dora_tensor_quant { /* dtype_bits == 0: this field is not quantised */
   uint8_t dtype_code;
@@ -514,6 +515,59 @@ int dora_gpu_plan_tensor_convert(const dora_tensor_field* fields, size_t n,
                                  const dora_tensor_cast* casts /* NULL or n entries */,
                                  const dora_tensor_quant* quants /* NULL or n entries */,
                                  ArrowDeviceType device_type, dora_plan** out);
+/*
+ * Normalised tensors as one message: the conversions of dora_gpu_plan_tensor_convert with an
+ * affine step in front, a scale and a bias that are each one number or one value per channel —
+ * (x / 255 - mean[c]) / std[c] as x * s[c] + b[c], per-channel int8 quantisation — in the same
+ * read of the source and the same write of the sample.  `fields`, `casts` and `quants` as there;
+ * `affines` is NULL or n entries, and an entry that is all zero adds nothing to its field.  With
+ * `affines` NULL or all entries zero the call plans exactly as dora_gpu_plan_tensor_convert does.
+ * The wire form — type info, sample size, leaf offsets — never depends on the affine step.
+ *
+ * `axis` names a dimension of the field as given (shape[axis] = C values along it), `inner` is the
+ * product of the extents behind it, and for the output element with row-major index e,
+ * c = (e / inner) % C and
+ *   y = float32(x) * S + B      two IEEE float32 operations, each round to nearest even: the
+ *                               product is rounded, then the sum; never one fused multiply-add
+ *   S = scale[c], or the entry's scalar scale (casts[k] / quants[k]), or absent: no multiplication
+ *   B = bias[c], or bias_value (has_bias), or absent: no addition, a zero product keeps its sign
+ * and then the field's own conversion of y: to float16 / float32 (a cast) or rounded, clamped and
+ * moved by zero_point (a quantise), exactly as above.  Subnormal products and sums are kept,
+ * (-0) + (+0) is +0.  The statement of record is numpy's x.astype(float32) * s32 + b32 with the
+ * tables reshaped to broadcast along `axis`; results are bit-exact against it, from host and from
+ * device values, except for the payload of a NaN in a float destination.  A cast to the source's
+ * own dtype is a conversion once it has an affine entry.
+ *
+ * Tables live where the values live.  Host values: a table is C float32 words in host memory,
+ * read inside this call; a value that is not finite is DORA_ERR_INVALID.  Device values: a table
+ * is C float32 words in HBM, never read on the host; whatever it holds the result is the formula
+ * (a NaN or an infinity propagates, and under a quantise saturates or becomes zero_point), and
+ * since c < C always no word outside the table is read.  Each table's 4 * C bytes are held against
+ * its allocation before anything is launched, like a take's index; a refusal says which table.
+ * Any field with a bias or a table makes a device plan one launch of gather_affine_kernel (gfx950).
+ * A field with d0 == 0 (C == 0 included) is the empty message and nothing is launched.
+ *
+ * DORA_ERR_INVALID naming the field, on top of dora_gpu_plan_tensor_convert's refusals: an affine
+ * entry on a field that is neither cast nor quantised; a table scale together with the entry's
+ * has_scale; a table bias together with has_bias; `axis` outside the field's dimensions; a table
+ * that is not 1-D, not of shape[axis] elements or not dense; a table whose data + byte_offset is
+ * not a multiple of 4; a scalar bias or a host table's value that is not finite.  A table that is
+ * not float32 is DORA_ERR_UNSUPPORTED, naming the dtype.
+ * Not provided: per-channel zero points; a conversion under a ragged batch, a take or a mask;
+ * bfloat16 destinations.
+ */
+typedef struct dora_tensor_affine { /* all zero: no affine step beyond the entry's own scalar scale */
+  const dora_tensor* scale; /* NULL, or C float32 values along `axis`: takes the place of the scalar scale */
+  const dora_tensor* bias;  /* NULL, or C float32 values along `axis` */
+  int32_t axis;             /* 0 <= axis < ndim of the field; read only when a table is given */
+  uint16_t has_bias;        /* a scalar bias */
+  float bias_value;
+} dora_tensor_affine;
+int dora_gpu_plan_tensor_affine(const dora_tensor_field* fields, size_t n,
+                                const dora_tensor_cast* casts /* NULL or n entries */,
+                                const dora_tensor_quant* quants /* NULL or n entries */,
+                                const dora_tensor_affine* affines /* NULL or n entries */,
+                                ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -762,6 +816,18 @@ int dora_node_send_output_tensor_convert(dora_node* node, const char* output_id,
                                          const dora_tensor_quant* quants,
                                          ArrowDeviceType device_type, const uint8_t* params,
                                          size_t params_len, uint32_t flags);
+/* Send normalised tensors (dora_gpu_plan_tensor_affine: semantics, where the tables live,
+ * refusals), with the contract of dora_node_send_output_tensor_convert: host values and host
+ * tables read on return, device values and device tables in one launch on a fill stream; with
+ * DORA_SEND_ASYNC the caller keeps the tables alive and unwritten with the fields until
+ * dora_node_sync. */
+int dora_node_send_output_tensor_affine(dora_node* node, const char* output_id,
+                                        const dora_tensor_field* fields, size_t n,
+                                        const dora_tensor_cast* casts,
+                                        const dora_tensor_quant* quants,
+                                        const dora_tensor_affine* affines,
+                                        ArrowDeviceType device_type, const uint8_t* params,
+                                        size_t params_len, uint32_t flags);
 /* Send rows selected by a mask (dora_gpu_plan_tensor_mask: wire form, where the mask lives,
  * refusals), with the contract of the take send: host values with a host mask take every path of
  * a host plan and everything has been read on return; device values with a device mask go where

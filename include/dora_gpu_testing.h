@@ -122,6 +122,19 @@ int dora_gpu_test_plan_cast(const dora_plan* plan, size_t i, size_t* n_fields, i
  * and *dst_code 2 as for every converted field. */
 int dora_gpu_test_plan_quant(const dora_plan* plan, size_t i, int* is_quant, int* dst_code,
                              int* dst_bits, int* zero_point);
+/* Test tool (host only): whether field `i` of a device plan of dora_gpu_plan_tensor_affine has an
+ * affine step (*is_affine 1: its launch is gather_affine_kernel): then *scale_table / *bias_table
+ * the tables in HBM (NULL: none), *inner and *channels the geometry of the axis they run along and
+ * [*lo, *hi] the bytes from either table that are checked against its allocation (0, 0, 0, -1
+ * without a table), *has_bias and *bias the scalar bias.  dora_gpu_test_plan_cast and
+ * dora_gpu_test_plan_quant report the rest of the field. */
+int dora_gpu_test_plan_affine(const dora_plan* plan, size_t i, int* is_affine,
+                              const void** scale_table, const void** bias_table, uint64_t* inner,
+                              uint64_t* channels, int* has_bias, float* bias, int64_t* lo,
+                              int64_t* hi);
+/* Test tool: counts[4], the launches of this process so far over the fields of a plan, by kernel:
+ * gather_struct_kernel, gather_cast_kernel, gather_quant_kernel, gather_affine_kernel. */
+int dora_gpu_test_fields_launches(uint64_t* counts);
 /* Test tool (host only): whether `plan` is a mask plan (dora_gpu_plan_tensor_mask; DORA_ERR_INVALID
  * for any other plan) and what it selects by.  *n the rows of the source.  *device 1 if the plan's
  * launches read the mask in HBM: then *mask its bytes, [*lo, *hi] the bytes from *mask that are
