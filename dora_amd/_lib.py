@@ -101,6 +101,16 @@ class TensorAffine(ctypes.Structure):
                 ("has_bias", ctypes.c_uint16), ("bias_value", c_float)]
 
 
+class TensorReduce(ctypes.Structure):
+    """dora_tensor_reduce of include/dora_gpu.h: the reduction of one field (op 0: none), its
+    axis and the index dtype."""
+    _fields_ = [("op", c_uint32), ("axis", c_int32), ("dtype_code", c_uint8),
+                ("dtype_bits", c_uint8)]
+
+
+REDUCE_ARGMAX = 1
+
+
 class TensorMask(ctypes.Structure):
     """dora_tensor_mask of include/dora_gpu.h: the fields rows are selected from, the mask that
     selects them and, for more than one list, the partition of the N source rows (else NULL)."""
@@ -172,6 +182,11 @@ _SIGS = {
     "dora_node_send_output_tensor_affine": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
                                                     c_void_p, c_void_p, c_void_p, c_int32,
                                                     c_char_p, c_size_t, c_uint32]),
+    "dora_gpu_plan_tensor_reduce": (c_int, [c_void_p, c_size_t, c_void_p, c_int32,
+                                            POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_reduce": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
+                                                    c_void_p, c_int32, c_char_p, c_size_t,
+                                                    c_uint32]),
     "dora_gpu_plan_tensor_mask": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_mask": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                                   c_size_t, c_uint32]),
@@ -326,6 +341,11 @@ _TEST_SIGS = {
                                           POINTER(c_int), POINTER(c_float),
                                           POINTER(ctypes.c_int64), POINTER(ctypes.c_int64)]),
     "dora_gpu_test_fields_launches": (c_int, [POINTER(c_uint64)]),
+    "dora_gpu_test_plan_reduce": (c_int, [c_void_p, c_size_t, c_void_p, POINTER(c_int),
+                                          POINTER(c_uint64), POINTER(ctypes.c_int64),
+                                          POINTER(c_uint64), POINTER(c_int), POINTER(c_int),
+                                          POINTER(c_uint64), POINTER(c_uint64)]),
+    "dora_gpu_test_reduce_body": (c_int, [c_int]),
     "dora_gpu_test_plan_take": (c_int, [c_void_p, POINTER(c_int), POINTER(c_void_p),
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_int),
                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),

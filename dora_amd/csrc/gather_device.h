@@ -910,13 +910,37 @@ static_assert(sizeof(Args) == sizeof(gather::Args) + 64, "the affine arguments f
 
 }  // namespace cast
 
+// ------------------------------------------------------------------------------------------
+// A field reduced on the way (two more field kinds, run by gather_reduce_kernel only): the index
+// of the maximum along one axis of the source, one index per element of the kept dimensions.
+// Only the arguments live here, where multi::Field needs them; the bodies are reduce_device.h.
+// ------------------------------------------------------------------------------------------
+namespace reduce {
+
+struct Args {
+  // the view of the kept dimensions with rows counted in elements, as cast::Args has it: `total`
+  // output elements, `row` contiguous source elements per row, `head` elements before the first
+  // whole 16-byte unit of the output, `nunits` whole units, `piece` the source element size;
+  // shape[] / stride[] in source bytes and [lo, hi] over all `c` steps of the reduced axis
+  gather::Args g;
+  uint64_t c;        // candidates per output element, >= 1
+  int64_t cstride;   // bytes per step of the reduced axis (signed, 0 allowed)
+  uint32_t src;      // cast::Src
+  uint32_t dsize;    // index element size: 1, 2, 4 or 8
+};
+
+}  // namespace reduce
+
 namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
 // (a scan share, kScan, is no Field: it has no view; it runs workgroups [0, wg_begin[0]))
 // (kRowsCast fields are run by gather_cast_kernel / gather_quant_kernel / gather_affine_kernel
 // only: gather_struct_kernel's launches hold none)
-enum Kind : uint32_t { kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4 };
+// (kReduceLane and kReduceWave fields are run by gather_reduce_kernel only)
+enum Kind : uint32_t {
+  kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4, kReduceLane = 5, kReduceWave = 6
+};
 
 struct Field {
   uint32_t kind;
@@ -926,10 +950,12 @@ struct Field {
     tile::Args tile;
     take::Args taken;
     cast::Args cast;
+    reduce::Args reduce;
   };
 };
 static_assert(sizeof(take::Args) <= sizeof(tile::Args), "a taken field does not grow Field");
 static_assert(sizeof(cast::Args) <= sizeof(tile::Args), "a cast field does not grow Field");
+static_assert(sizeof(reduce::Args) <= sizeof(tile::Args), "a reduced field does not grow Field");
 
 struct Args {
   uint32_t n;

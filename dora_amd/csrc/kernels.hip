@@ -17,6 +17,7 @@
 #include "aql.h"
 #include "common.h"
 #include "cast_device.h"
+#include "reduce_device.h"
 #include "gather_device.h"
 #include "pack_device.h"
 #include "plan.h"
@@ -546,6 +547,78 @@ __global__ __launch_bounds__(gather::kThreads) void gather_affine_kernel(gather:
   struct_share<3>(a, lds);
 }
 
+// The reduce bodies' memory, conversions and lane exchange (reduce_device.h): the cast body's
+// policy — a unit's contiguous candidates in naturally aligned non-temporal vector loads,
+// elements of permuted lines with plain cached loads, the sample with the pack's write-through
+// stores — plus the wave body's coalesced element loads, non-temporal like the vector loads (each
+// candidate is read once), index elements of 8 bytes, and the butterfly's exchange: the pair of
+// lane l ^ d, three 32-bit lane permutes.
+struct ReduceMem : CastMem {
+  template <int S>
+  __device__ __forceinline__ uint32_t load_stream(int64_t s) const {
+    const uint8_t* p = src + s;
+    if constexpr (S == 4) return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p));
+    else if constexpr (S == 2) return __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p));
+    else return __builtin_nontemporal_load(p);
+  }
+  template <int D>
+  __device__ __forceinline__ void store_index(uint64_t e, uint64_t i) const {
+    if constexpr (D == 8) {
+      __builtin_nontemporal_store(i, reinterpret_cast<uint64_t*>(dst) + e);
+    } else {
+      store_elem<D>(e, static_cast<uint32_t>(i));
+    }
+  }
+  __device__ __forceinline__ gather::reduce::Pair lane_xor(const gather::reduce::Pair& p,
+                                                           int d) const {
+    gather::reduce::Pair o;
+    o.v = __shfl_xor(p.v, d, gather::reduce::kWave);
+    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(p.i), d, gather::reduce::kWave);
+    const uint32_t hi = __shfl_xor(static_cast<uint32_t>(p.i >> 32), d, gather::reduce::kWave);
+    o.i = (static_cast<uint64_t>(hi) << 32) | lo;
+    return o;
+  }
+};
+
+// What a workgroup of gather_reduce_kernel does: struct_share's walk to its field, then the
+// field's body over the field's share of the grid: the rows or the tile body of a plain field, the
+// lane or the wave body of a reduced one (a branch uniform over the workgroup; the wave body's
+// lanes are numbered so that a wave is 64 consecutive ones).  No scan, taken or cast share.
+__device__ __forceinline__ void reduce_share(const gather::multi::Args& a, uint64_t* lds) {
+  const uint32_t w = blockIdx.x;
+  const int k = gather::multi::field_of(a, w);
+  const gather::multi::Field& f = a.f[k];
+  const uint64_t local = w - a.wg_begin[k], share = a.wg_begin[k + 1] - a.wg_begin[k];
+  const uint64_t lane = local * gather::kThreads + threadIdx.x, lanes = share * gather::kThreads;
+  if (f.kind == gather::multi::kRows) {
+    GatherMem m{f.rows.src, f.rows.dst};
+    gather::gather_lane(f.rows, lane, lanes, m);
+    return;
+  }
+  if (f.kind == gather::multi::kReduceLane || f.kind == gather::multi::kReduceWave) {
+    // (a copy of its own, as the cast body's arguments are)
+    const gather::reduce::Args r = f.reduce;
+    ReduceMem m{{r.g.src, r.g.dst}};
+    if (f.kind == gather::multi::kReduceLane) gather::reduce::reduce_lane(r, lane, lanes, m);
+    else gather::reduce::reduce_wave(r, lane, lanes, m);
+    return;
+  }
+  switch (f.tile.elem) {
+    case 1: tile_loop(f.tile, local, share, reinterpret_cast<uint8_t*>(lds)); break;
+    case 2: tile_loop(f.tile, local, share, reinterpret_cast<uint16_t*>(lds)); break;
+    case 4: tile_loop(f.tile, local, share, reinterpret_cast<uint32_t*>(lds)); break;
+    default: tile_loop(f.tile, local, share, lds); break;
+  }
+}
+
+// gather_reduce_kernel: the fields of a reduce plan in one launch: reduced fields through the
+// lane or the wave body (reduce_device.h), plain ones through their usual rows or tile body.
+// Chosen per plan, so the other kernels hold no line of it.
+__global__ __launch_bounds__(gather::kThreads) void gather_reduce_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  reduce_share(a, lds);
+}
+
 // The mask kernels' memory (gather_device.h mask::): the mask with one aligned 16-byte
 // non-temporal load per thread (each byte is read once by each kernel) or byte by byte at its
 // head and tail; the thread counts in LDS; the workspace's index, counts and totals with plain
@@ -922,6 +995,19 @@ void gather_force(int mode) { g_gather_force.store(mode, std::memory_order_relax
 
 // Test hook: launches of this process so far over the fields of a plan, by kernel:
 // gather_struct_kernel, gather_cast_kernel, gather_quant_kernel, gather_affine_kernel.
+std::atomic<int> g_reduce_force{0};  // test hook: 1 the lane body, 2 the wave body wherever it applies
+void reduce_force(int mode) { g_reduce_force.store(mode, std::memory_order_relaxed); }
+
+// Which body reduces field `g` by `r`, stated once: the wave body where the reduced axis is the
+// source-contiguous dimension and at least reduce::kWaveMinC long, the lane body for everything
+// else.
+bool select_reduce_wave(const GatherDesc& g, const ReduceDesc& r) {
+  const int force = g_reduce_force.load(std::memory_order_relaxed);
+  if (force == 1) return false;
+  if (force == 2) return gather::reduce::wave_applies(g, r);
+  return gather::reduce::wave_chosen(g, r);
+}
+
 std::atomic<uint64_t> g_fields_launches[4];
 void fields_launches(uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = g_fields_launches[i].load(std::memory_order_relaxed);
@@ -954,6 +1040,9 @@ namespace {
 //     gather_quant_kernel when any field is quantised, or gather_affine_kernel when any has a
 //     bias or a per-channel table.  DORA_ERR_INVALID, nothing launched, when a converted field
 //     would not start on a multiple of its destination element size.
+//   kReduce: the same, a reduced field through the lane or the wave body (select_reduce_wave);
+//     gather_reduce_kernel.  DORA_ERR_INVALID, nothing launched, when a reduced field would not
+//     start on a multiple of its index element size.
 //   kTaken (`take` given): every field through the taken body, never a tile: row i0 of its bytes
 //     is row take->src[i0] of the field, or zeros where that word is not in [0, take->n).
 // With `scan` (a ragged batch's partition in HBM; n may then be 0) one more workgroup of the same
@@ -980,6 +1069,8 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
   uint64_t off[gather::multi::kMaxFields];
   int tile_c[gather::multi::kMaxFields];
   int64_t stride0[gather::multi::kMaxFields];
+  ReduceDesc rd[gather::multi::kMaxFields];
+  bool wave[gather::multi::kMaxFields];
   bool quant = false, affine = false;
   for (size_t k = 0; k < n; ++k) {
     const PlanField& f = fields[k];
@@ -988,8 +1079,25 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
     off[k] = f.dst_off;
     stride0[k] = f.stride0;
     c[k] = kind == PlanLaunch::kCast ? f.cast : CastDesc{};
+    rd[k] = kind == PlanLaunch::kReduce ? f.reduce : ReduceDesc{};
+    wave[k] = false;
     quant |= c[k].quant();
-    tile_c[k] = take || c[k].on ? -1 : select_tile_dim(g[k], dst + off[k]);
+    tile_c[k] = take || c[k].on || rd[k].on ? -1 : select_tile_dim(g[k], dst + off[k]);
+    if (rd[k].on) {
+      // the bodies' loads are whole source elements, their stores whole index elements
+      const unsigned ds = gather::reduce::index_size(rd[k].idx_code, rd[k].idx_bits);
+      if (gather::cast::src_kind(rd[k].src_code, rd[k].src_bits) < 0 || !ds || !rd[k].c ||
+          ((reinterpret_cast<uintptr_t>(f.gd.view.src) | static_cast<uintptr_t>(rd[k].cstride)) &
+           (f.gd.elem - 1)))
+        return fail(DORA_ERR_INVALID, "field %zu `%s`: not a reduction this kernel runs", k,
+                    f.name.c_str());
+      if (reinterpret_cast<uintptr_t>(dst + off[k]) & (ds - 1))
+        return fail(DORA_ERR_INVALID, "field %zu `%s`: the reduced field would start at %p, not a "
+                    "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
+                    static_cast<void*>(dst + off[k]), ds);
+      wave[k] = select_reduce_wave(g[k], rd[k]);
+      continue;
+    }
     if (!c[k].on) continue;
     // the cast body's stores are whole elements and whole 16-byte units of them
     const unsigned ds = f.cast.dst_bits / 8u;
@@ -1016,8 +1124,13 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
   const int nf = static_cast<int>(n);
   gm::Args a = take                        ? gm::make_taken_args(g, stride0, off, nf, dst, *take, scan)
                : kind == PlanLaunch::kCast ? gm::make_cast_args(g, c, off, tile_c, nf, dst)
-                                           : gm::make_args(g, off, tile_c, nf, dst, scan);
+               : kind == PlanLaunch::kReduce
+                   ? gm::make_reduce_args(g, rd, wave, off, tile_c, nf, dst)
+                   : gm::make_args(g, off, tile_c, nf, dst, scan);
   a.lookup = lookup;
+  if (kind == PlanLaunch::kReduce)
+    return launch_timed(gather_reduce_kernel, gm::grid_for(a), gather::kThreads, stream, ev_start,
+                        ev_stop, a);
   const int which = kind != PlanLaunch::kCast ? 0 : affine ? 3 : quant ? 2 : 1;
   void (*const kerns[4])(gm::Args) = {gather_struct_kernel, gather_cast_kernel,
                                       gather_quant_kernel, gather_affine_kernel};
@@ -1081,6 +1194,7 @@ int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
     case PlanLaunch::kView: return launch_gather(plan.gd, dst, stream, ev_start, ev_stop);
     case PlanLaunch::kFields:
     case PlanLaunch::kCast:
+    case PlanLaunch::kReduce:
     case PlanLaunch::kTaken:
       return launch_fields(plan.launch, plan.fields.data(), plan.fields.size(), dst, stream,
                            ev_start, ev_stop, scan,

@@ -126,6 +126,18 @@ struct CastDesc {
   bool affine() const { return on && (has_bias || scale_tab || bias_tab); }
 };
 
+// A field reduced on send (dora_gpu_plan_tensor_reduce): the index of the maximum along one axis
+// of the source.  `c` candidates per output element, `cstride` bytes apart (signed, 0 allowed),
+// of the source dtype (a cast source); `count` output elements of the index type, DL_UINT of 8 or
+// 16 bits or DL_INT of 32 or 64.  `on` false: the field is sent as it is.
+struct ReduceDesc {
+  bool on = false;
+  uint8_t src_code = 0, src_bits = 0, idx_code = 0, idx_bits = 0;
+  uint64_t c = 0;
+  int64_t cstride = 0;
+  uint64_t count = 0;
+};
+
 // One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
 // own tensor plan would describe it (dense: nd == 0), where its row-major values start in the
 // sample and how many bytes they are.  Fields follow one another in destination order.
@@ -142,6 +154,11 @@ struct PlanField {
   // a cast plan (dora_gpu_plan_tensor_cast), `cast.on`: `gd` is the source view in source bytes
   // (elem the source element size, view.total the source bytes), `bytes` the converted bytes
   CastDesc cast;
+  // a reduce plan (dora_gpu_plan_tensor_reduce), `reduce.on`: `gd` is the view of the kept
+  // dimensions in source bytes (elem the source element size, view.total the source bytes of one
+  // candidate per output element), its [lo, hi] over all `reduce.c` steps of the reduced axis;
+  // `bytes` the index bytes
+  ReduceDesc reduce;
 };
 
 // `bytes` dense bytes of `elem`-byte elements from `src` as a view: what a plan reads of an
@@ -263,11 +280,12 @@ int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
 // Everything a plan's launch kind asks for beyond `segs` (PlanLaunch below; never kSegments):
 // launch_gather of its view; one launch over its fields — gather_struct_kernel, with the scan of a
 // ragged batch's device partition and by the index of a take, or gather_cast_kernel /
-// gather_quant_kernel / gather_affine_kernel for converted fields — each field's bytes as launch_gather would write
+// gather_quant_kernel / gather_affine_kernel for converted fields, or gather_reduce_kernel for
+// reduced ones — each field's bytes as launch_gather would write
 // them, nothing between fields and nothing at or past the last field's end; for a mask plan the
 // two compaction launches and then the fields by the index they wrote, `dst` then holding the
 // sample and plan_workspace bytes behind it.  DORA_ERR_INVALID, nothing launched, when a
-// converted field would not start on a multiple of its destination element size.
+// converted or reduced field would not start on a multiple of its destination element size.
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
@@ -335,6 +353,14 @@ int build_tensor_affine_plan(const dora_tensor_field* fields, size_t n,
                              const dora_tensor_cast* casts, const dora_tensor_quant* quants,
                              const dora_tensor_affine* affines, ArrowDeviceType dev,
                              dora_plan** out);
+// Tensors reduced on send, bare or as a record (dora_gpu_plan_tensor_reduce): a field with an
+// argmax entry is the index tensor of its maximum along one axis.  Host values: reduced in the
+// plan's staging buffer, a host plan like any other; device values: a gather plan whose one launch
+// reduces (gather_reduce_kernel).  `reduces` NULL or every op 0: build_tensor_plan's (bare) or
+// build_tensor_struct_plan's plan.
+int build_tensor_reduce_plan(const dora_tensor_field* fields, size_t n,
+                             const dora_tensor_reduce* reduces, ArrowDeviceType dev,
+                             dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -346,7 +372,8 @@ enum class PlanLaunch : uint8_t {
   kFields,    // gather_struct_kernel over `fields` (+ scan share when scan_on)
   kCast,      // gather_cast_kernel / gather_quant_kernel / gather_affine_kernel over `fields`
   kTaken,     // the taken body over `fields` by `take` (+ scan share when scan_on)
-  kMasked     // count, compact, then the taken body by the workspace's index
+  kMasked,    // count, compact, then the taken body by the workspace's index
+  kReduce     // gather_reduce_kernel over `fields`
 };
 
 // What kind of message a tensor plan is, whichever way its bytes move: reported by the test probes

@@ -31,6 +31,12 @@
 // With an affine entry (dora_gpu_plan_tensor_affine) a converted field is taken through
 // y = x * S + B first, S and B each a scalar or a per-channel table along one axis: host tables
 // are read and checked here, tables in HBM never, their reach kept for check_plan_range.
+//
+// Reduced tensors (dora_gpu_plan_tensor_reduce) are a tensor or a record in which a field with an
+// argmax entry is laid out as the index tensor of its maximum along one axis: the field is
+// validated and viewed over its kept dimensions, the reduced axis kept apart as an extent and a
+// byte stride, its reach over all the axis' steps — reduced by the CPU here for host values, by
+// the plan's one launch for device values (reduce_device.h).
 #include <cstring>
 #include <memory>
 #include <string>
@@ -39,6 +45,7 @@
 #include <cmath>
 
 #include "cast_device.h"
+#include "reduce_device.h"
 #include "common.h"
 #include "plan.h"
 
@@ -546,6 +553,149 @@ void cast_host(const StridedView& g, const CastDesc& c, uint8_t* dst) {
   }
 }
 
+// The index of the maximum of the `c` candidates `cstride` bytes apart from `src`, of type K:
+// reduce_device.h's rule, the first NaN or else the first maximum.
+template <uint32_t K>
+uint64_t argmax_at(const uint8_t* src, uint64_t c, int64_t cstride) {
+  constexpr int S = gather::cast::kSize<K>;
+  const gather::cast::HostCvt cv;
+  auto at = [&](uint64_t i) {
+    uint32_t raw = 0;
+    std::memcpy(&raw, src + static_cast<int64_t>(i) * cstride, S);  // (little-endian)
+    return cv.to_f32<K>(raw);
+  };
+  float best = at(0);
+  uint64_t bi = 0;
+  for (uint64_t i = 1; i < c; ++i) {
+    const float v = at(i);
+    if (gather::reduce::better(v, best)) {
+      best = v;
+      bi = i;
+    }
+  }
+  return bi;
+}
+
+// The CPU's reduction of a reduce field: the elements of the view of the kept dimensions in
+// row-major order, each the argmax of its candidates, into `dst` (any alignment).
+void reduce_host(const StridedView& g, const ReduceDesc& r, uint8_t* dst) {
+  namespace gc = gather::cast;
+  const uint64_t ss = r.src_bits / 8u, ds = r.idx_bits / 8u, n = g.row / ss;
+  uint64_t (*one)(const uint8_t*, uint64_t, int64_t) = nullptr;
+  switch (gc::src_kind(r.src_code, r.src_bits)) {
+    case gc::kU8: one = argmax_at<gc::kU8>; break;
+    case gc::kI8: one = argmax_at<gc::kI8>; break;
+    case gc::kU16: one = argmax_at<gc::kU16>; break;
+    case gc::kI16: one = argmax_at<gc::kI16>; break;
+    case gc::kF16: one = argmax_at<gc::kF16>; break;
+    case gc::kBF16: one = argmax_at<gc::kBF16>; break;
+    default: one = argmax_at<gc::kF32>; break;
+  }
+  int64_t idx[kMaxTensorDims] = {0};
+  int64_t off = 0;
+  for (uint64_t done = 0; done < r.count; done += n) {
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint64_t w = one(g.src + off + static_cast<int64_t>(i * ss), r.c, r.cstride);
+      std::memcpy(dst + (done + i) * ds, &w, ds);  // (little-endian)
+    }
+    for (int k = g.nd - 1; k >= 0; --k) {
+      off += g.stride[k];
+      if (++idx[k] < g.shape[k]) break;
+      off -= g.stride[k] * g.shape[k];
+      idx[k] = 0;
+    }
+  }
+}
+
+// What reduces `t` (dora_gpu_plan_tensor_reduce, `r.op` != 0): the entry's and the tensor's
+// refusals, else `rd`, the view `v` of the kept dimensions — validated and canonicalised as a
+// tensor of its own, its reach over all C steps of the reduced axis, its leaf and byte count the
+// index tensor's — and `kshape`, the shape of the message.
+int describe_reduce(const dora_tensor& t, const dora_tensor_reduce& r, ArrowDeviceType dev,
+                    ReduceDesc& rd, TensorView& v, std::vector<int64_t>& kshape) {
+  rd = ReduceDesc{};
+  if (r.op != DORA_REDUCE_ARGMAX)
+    return fail(DORA_ERR_UNSUPPORTED, "reduce op %u is not supported: DORA_REDUCE_ARGMAX (%u) is",
+                r.op, DORA_REDUCE_ARGMAX);
+  const unsigned ib = gather::reduce::index_size(r.dtype_code, r.dtype_bits);
+  if (!ib)
+    return fail(DORA_ERR_UNSUPPORTED, "argmax index dtype %s is not supported: uint8, uint16, "
+                "int32 and int64 are", dtype_name(r.dtype_code, r.dtype_bits, 1).c_str());
+  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
+    return fail(DORA_ERR_UNSUPPORTED, "argmax source dtype %s is not supported: uint8, int8, "
+                "uint16, int16, float16, bfloat16 and float32 are",
+                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  if (t.ndim < 2)
+    return fail(DORA_ERR_INVALID, "argmax of a tensor of %d dimensions (at least 2: the reduced "
+                "axis and one that is kept)", t.ndim);
+  if (!t.shape) return fail(DORA_ERR_INVALID, "tensor shape is NULL");
+  if (r.axis < 0 || r.axis >= t.ndim)
+    return fail(DORA_ERR_INVALID, "argmax axis %d is outside the tensor's %d dimensions", r.axis,
+                t.ndim);
+  const int64_t c = t.shape[r.axis];
+  if (c < 0)
+    return fail(DORA_ERR_INVALID, "tensor extent %lld in dimension %d is negative",
+                static_cast<long long>(c), r.axis);
+  if (c == 0)
+    return fail(DORA_ERR_INVALID, "argmax along axis %d of extent 0: there is no candidate",
+                r.axis);
+  if ((r.dtype_bits == 8 && c > 256) || (r.dtype_bits == 16 && c > 65536) ||
+      (r.dtype_bits == 32 && c > (int64_t(1) << 31)))
+    return fail(DORA_ERR_INVALID, "argmax along axis %d of extent %lld: the index %lld does not "
+                "fit %s", r.axis, static_cast<long long>(c), static_cast<long long>(c - 1),
+                dtype_name(r.dtype_code, r.dtype_bits, 1).c_str());
+  // the strides in elements, the caller's or row-major
+  std::vector<int64_t> strides(static_cast<size_t>(t.ndim));
+  int64_t rm = 1;
+  for (int i = t.ndim - 1; i >= 0; --i) {
+    strides[size_t(i)] = t.strides ? t.strides[i] : rm;
+    if (!t.strides && __builtin_mul_overflow(rm, t.shape[i] > 0 ? t.shape[i] : 1, &rm))
+      return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
+  }
+  kshape.clear();
+  std::vector<int64_t> kstrides;
+  for (int i = 0; i < t.ndim; ++i) {
+    if (i == r.axis) continue;
+    kshape.push_back(t.shape[i]);
+    kstrides.push_back(strides[size_t(i)]);
+  }
+  // the view of the kept dimensions: any accepted dtype of the source's width describes it
+  dora_tensor kept = t;
+  kept.dtype_code = DL_UINT;
+  kept.ndim = t.ndim - 1;
+  kept.shape = kshape.data();
+  kept.strides = kstrides.data();
+  const int rc = describe_tensor(&kept, dev, v);
+  if (rc != DORA_OK) return rc;
+  const int64_t ss = t.dtype_bits / 8;
+  if (v.bytes && (reinterpret_cast<uintptr_t>(v.gd.view.src) & static_cast<uintptr_t>(ss - 1)))
+    return fail(DORA_ERR_INVALID, "argmax source data %p (data + byte_offset) is not a multiple "
+                "of its %lld-byte elements", static_cast<const void*>(v.gd.view.src),
+                static_cast<long long>(ss));
+  rd.on = true;
+  rd.src_code = t.dtype_code;
+  rd.src_bits = t.dtype_bits;
+  rd.idx_code = r.dtype_code;
+  rd.idx_bits = r.dtype_bits;
+  rd.c = static_cast<uint64_t>(c);
+  rd.count = v.bytes / static_cast<uint64_t>(ss);
+  if (__builtin_mul_overflow(strides[size_t(r.axis)], ss, &rd.cstride))
+    return fail(DORA_ERR_INVALID, "tensor stride %d overflows 64 bits", r.axis);
+  if (v.bytes && dev == ARROW_DEVICE_ROCM) {  // all C steps, held against the allocation later
+    int64_t span, width;
+    GatherDesc& g = v.gd;
+    if (__builtin_mul_overflow(c - 1, rd.cstride, &span) ||
+        __builtin_add_overflow(span < 0 ? g.lo : g.hi, span, span < 0 ? &g.lo : &g.hi) ||
+        __builtin_sub_overflow(g.hi, g.lo, &width))
+      return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
+                  "stride, summed over its dimensions)");
+  }
+  v.leaf = ib == 1 ? "C" : ib == 2 ? "S" : ib == 4 ? "i" : "l";
+  if (__builtin_mul_overflow(rd.count, static_cast<uint64_t>(ib), &v.bytes) || v.bytes >> 63)
+    return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
+  return DORA_OK;
+}
+
 bool known_device(ArrowDeviceType dev) {
   return dev == ARROW_DEVICE_CPU || dev == ARROW_DEVICE_ROCM_HOST || dev == ARROW_DEVICE_ROCM;
 }
@@ -618,6 +768,8 @@ struct FieldLayout {
   uint64_t staged = 0;  // bytes of host fields that are gathered or copied now
   bool strided = false;
   bool cast = false;    // any field is converted (layout_fields with `casts`)
+  bool reduce = false;  // any field is reduced (layout_fields with `reduces`)
+  uint64_t lead = 0;    // out: the leading extent the fields share, as sent
 };
 
 // Validation, view and type info of every field of `f[0..n)`, each leaf at the running offset
@@ -629,11 +781,15 @@ struct FieldLayout {
 // or quantised by quants[k] (describe_convert) is
 // validated and viewed as its source — the view and its reach in source bytes — while its leaf,
 // byte count and padding are the destination dtype's.
+// `reduces` (n entries or NULL, never with `taken` or a conversion): field k with an op is viewed
+// over its kept dimensions (describe_reduce) while its shape, leaf, byte count and padding are the
+// index tensor's; the fields then share the leading extent of the shapes they are sent with.
 int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                   const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
                   FieldLayout& lay, int64_t taken = -1, const dora_tensor_cast* casts = nullptr,
                   const dora_tensor_quant* quants = nullptr,
-                  const dora_tensor_affine* affines = nullptr) {
+                  const dora_tensor_affine* affines = nullptr,
+                  const dora_tensor_reduce* reduces = nullptr) {
   p.fields.resize(n);
   lay.chains.resize(n);
   lay.kids.resize(n);
@@ -661,7 +817,13 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
       if (rc == DORA_OK) rc = describe_affine(t, dev, affines[k], cd);
       return bare ? rc : field_fail(rc, k, name);
     }
-    if (cd.on) {
+    ReduceDesc rd;
+    std::vector<int64_t> rshape;  // a reduced field's shape as sent
+    if (reduces && reduces[k].op) {
+      rc = describe_reduce(t, reduces[k], dev, rd, v, rshape);
+      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
+      lay.reduce = true;
+    } else if (cd.on) {
       // the view of the source: any accepted dtype of its width describes it (Arrow has no
       // bfloat16, and the leaf is the destination's anyway)
       dora_tensor src = t;
@@ -691,13 +853,15 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
                      : describe_taken(t, dev, static_cast<uint64_t>(taken), v, &stride0);
       if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
     }
-    if (t.shape[0] != f[0].tensor.shape[0])
+    const int64_t lead = rd.on ? rshape[0] : t.shape[0];
+    if (k == 0) lay.lead = static_cast<uint64_t>(lead);
+    if (static_cast<uint64_t>(lead) != lay.lead)
       return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
                   "%lld: the fields of a struct share shape[0] (give tensors of unrelated shapes "
-                  "a leading extent of 1)", k, name, static_cast<long long>(t.shape[0]),
-                  f[0].name, static_cast<long long>(f[0].tensor.shape[0]));
+                  "a leading extent of 1)", k, name, static_cast<long long>(lead),
+                  f[0].name, static_cast<long long>(lay.lead));
     // the running offset padded to the leaf's element size (a power of two)
-    const uint64_t elem = cd.on ? cd.dst_bits / 8u : t.dtype_bits / 8u;
+    const uint64_t elem = rd.on ? rd.idx_bits / 8u : cd.on ? cd.dst_bits / 8u : t.dtype_bits / 8u;
     uint64_t padded, end;
     if (__builtin_add_overflow(off, elem - 1, &padded) ||
         __builtin_add_overflow(padded & ~(elem - 1), v.bytes, &end) || end >> 63)
@@ -711,18 +875,24 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     pf.bytes = v.bytes;
     pf.stride0 = stride0;
     pf.cast = cd;
+    pf.reduce = rd;
     const int64_t* shape = t.shape;  // as sent
+    int ndim = t.ndim;
     std::vector<int64_t> kshape;
     if (taken >= 0) {
       kshape.assign(t.shape, t.shape + t.ndim);
       kshape[0] = taken;
       shape = kshape.data();
     }
-    lay.chains[k].reset(new TypeChain(v.leaf, shape, t.ndim, name));
+    if (rd.on) {
+      shape = rshape.data();
+      ndim = t.ndim - 1;
+    }
+    lay.chains[k].reset(new TypeChain(v.leaf, shape, ndim, name));
     lay.kids[k] = &lay.chains[k]->sch[0];
-    tensor_type_info(*lay.chains[k], shape, t.ndim, off, v.bytes, nodes[k]);
+    tensor_type_info(*lay.chains[k], shape, ndim, off, v.bytes, nodes[k]);
     off = end;
-    const bool stage = taken >= 0 || cd.on || dev == ARROW_DEVICE_ROCM_HOST ||
+    const bool stage = taken >= 0 || cd.on || rd.on || dev == ARROW_DEVICE_ROCM_HOST ||
                        (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
     if (stage) lay.staged += v.bytes;  // (<= off)
     lay.strided |= v.gd.view.nd != 0;
@@ -737,11 +907,12 @@ void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
   p.staged.resize(staged);
   uint64_t at = 0;
   for (const PlanField& pf : p.fields) {
-    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0 && !pf.cast.on) {
+    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0 && !pf.cast.on && !pf.reduce.on) {
       p.segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
       continue;
     }
-    if (pf.cast.on) cast_host(pf.gd.view, pf.cast, p.staged.data() + at);
+    if (pf.reduce.on) reduce_host(pf.gd.view, pf.reduce, p.staged.data() + at);
+    else if (pf.cast.on) cast_host(pf.gd.view, pf.cast, p.staged.data() + at);
     else gather_host(pf.gd.view, p.staged.data() + at);
     p.segs.push_back({p.staged.data() + at, pf.dst_off, pf.bytes});
     at += pf.bytes;
@@ -890,7 +1061,8 @@ void place_masked_host(dora_plan& p, const MaskIn& mk, uint64_t staged) {
 int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                  const TakeIn* tk, dora_plan** out, const dora_tensor_cast* casts = nullptr,
                  const dora_tensor_quant* quants = nullptr,
-                 const dora_tensor_affine* affines = nullptr) {
+                 const dora_tensor_affine* affines = nullptr,
+                 const dora_tensor_reduce* reduces = nullptr) {
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
@@ -898,7 +1070,7 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   std::vector<TypeInfoNode> solo;
   int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
                                tk ? static_cast<int64_t>(tk->ix.count) : -1, casts, quants,
-                               affines);
+                               affines, reduces);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
   if (bare) {
@@ -911,18 +1083,20 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
     top.children = lay.kids.data();
     top.n_children = static_cast<int64_t>(n);
     serialize_schema(&top, true, p->root.schema);
-    p->root.len = tk ? tk->ix.count : static_cast<uint64_t>(f[0].tensor.shape[0]);
+    p->root.len = tk ? tk->ix.count : lay.lead;
   }
   p->size = off;
   const uint64_t rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
   if (tk) note_take(*p, *tk, rows);
   // what fills the sample: nothing (d0 == 0, an empty message); the taken rows; device fields as
-  // segments, a gather when any is strided or a cast launch when any is converted; host fields
+  // segments, a gather when any is strided, a cast launch when any is converted or a reduce
+  // launch when any is reduced; host fields
   if (off == 0) p->fields.clear();
   else if (tk) rc = place_taken(*p, *tk, rows, lay.staged);
   else if (dev == ARROW_DEVICE_ROCM)
-    place_device_fields(*p, !lay.strided && !lay.cast,
-                        lay.cast ? PlanLaunch::kCast : PlanLaunch::kFields);
+    place_device_fields(*p, !lay.strided && !lay.cast && !lay.reduce,
+                        lay.reduce ? PlanLaunch::kReduce
+                                   : lay.cast ? PlanLaunch::kCast : PlanLaunch::kFields);
   else stage_host_fields(*p, dev, lay.staged);
   if (rc != DORA_OK) return rc;
   *out = p.release();
@@ -1005,6 +1179,25 @@ int build_tensor_affine_plan(const dora_tensor_field* f, size_t n, const dora_te
   if (rf != DORA_OK) return rf;
   // every field's own refusals, then its affine entry's, as the fields are laid out
   return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, casts, quants, affines);
+}
+
+int build_tensor_reduce_plan(const dora_tensor_field* f, size_t n,
+                             const dora_tensor_reduce* reduces, ArrowDeviceType dev,
+                             dora_plan** out) {
+  bool any = false;
+  for (size_t k = 0; reduces && f && k < n; ++k) any |= reduces[k].op != 0;
+  // no reduction at all: the plain plan, whatever it is, refusals included
+  if (!any) {
+    if (f && n == 1 && !f[0].name) return build_tensor_plan(&f[0].tensor, dev, out);
+    return build_tensor_struct_plan(f, n, dev, out);
+  }
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  const int rf = check_fields(f, n, "a reduction");
+  if (rf != DORA_OK) return rf;
+  return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, nullptr, nullptr, nullptr,
+                      reduces);
 }
 
 namespace {
@@ -1402,6 +1595,12 @@ int dora_gpu_plan_tensor_convert(const dora_tensor_field* fields, size_t n,
                                  const dora_tensor_cast* casts, const dora_tensor_quant* quants,
                                  ArrowDeviceType device_type, dora_plan** out) {
   return dora::build_tensor_convert_plan(fields, n, casts, quants, device_type, out);
+}
+
+int dora_gpu_plan_tensor_reduce(const dora_tensor_field* fields, size_t n,
+                                const dora_tensor_reduce* reduces, ArrowDeviceType device_type,
+                                dora_plan** out) {
+  return dora::build_tensor_reduce_plan(fields, n, reduces, device_type, out);
 }
 
 int dora_gpu_plan_tensor_affine(const dora_tensor_field* fields, size_t n,

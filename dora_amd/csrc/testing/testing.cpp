@@ -25,6 +25,7 @@
 #include "dora_gpu_testing.h"
 #include "fence_probes.h"
 #include "gather_device.h"
+#include "reduce_device.h"
 #include "plan.h"
 #include "shm.h"
 
@@ -33,6 +34,8 @@ namespace dora {
 int build_aql_batch_args(const BatchItem* items, size_t n, uint8_t* out, size_t cap,
                          uint32_t* grid);
 void gather_force(int mode);
+void reduce_force(int mode);
+bool select_reduce_wave(const GatherDesc& g, const ReduceDesc& r);
 void fields_launches(uint64_t out[4]);
 int select_tile_dim(const GatherDesc& g, const uint8_t* dst);
 }  // namespace dora
@@ -456,6 +459,49 @@ int dora_gpu_test_plan_affine(const dora_plan* plan, size_t i, int* is_affine,
   if (bias) *bias = on ? c.bias : 0.0f;
   if (lo) *lo = tables ? dora::table_reach(nullptr, c.channels).lo : 0;
   if (hi) *hi = tables ? dora::table_reach(nullptr, c.channels).hi : -1;
+  return DORA_OK;
+}
+
+int dora_gpu_test_reduce_body(int mode) {
+  if (mode < 0 || mode > 2) return dora::fail(DORA_ERR_INVALID, "reduce body mode %d", mode);
+  dora::reduce_force(mode);
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_reduce(const dora_plan* plan, size_t i, const void* dst, int* op,
+                              uint64_t* c, int64_t* axis_stride, uint64_t* outputs,
+                              int* index_bits, int* body, uint64_t* vector_units,
+                              uint64_t* element_units) {
+  if (!plan || !plan->dev_tensor || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a device plan with a field %zu", i);
+  namespace rd = dora::gather::reduce;
+  const dora::PlanField& f = plan->fields[i];
+  const dora::ReduceDesc& r = f.reduce;
+  const bool on = plan->launch == dora::PlanLaunch::kReduce && r.on;
+  const bool wave = on && dora::select_reduce_wave(f.gd, r);
+  if (op) *op = on ? int(DORA_REDUCE_ARGMAX) : 0;
+  if (c) *c = on ? r.c : 0;
+  if (axis_stride) *axis_stride = on ? r.cstride : 0;
+  if (outputs) *outputs = on ? r.count : 0;
+  if (index_bits) *index_bits = on ? r.idx_bits : 0;
+  if (body) *body = !on ? 0 : wave ? 2 : 1;
+  uint64_t vec = 0, elem = 0;
+  if (on && !wave) {
+    // the lane body's units by the path each takes into a sample at `dst`
+    const rd::Args a = rd::make_args(
+        f.gd, r, const_cast<uint8_t*>(static_cast<const uint8_t*>(dst)) + f.dst_off);
+    for (uint64_t u = 0; u < a.g.nunits; ++u) {
+      rd::Start st;
+      rd::start_of(a, a.g.head + (16 / a.dsize) * u, st);
+      const bool v = a.dsize == 1   ? rd::unit_is_vector<1>(a, st)
+                     : a.dsize == 2 ? rd::unit_is_vector<2>(a, st)
+                     : a.dsize == 4 ? rd::unit_is_vector<4>(a, st)
+                                    : rd::unit_is_vector<8>(a, st);
+      ++(v ? vec : elem);
+    }
+  }
+  if (vector_units) *vector_units = vec;
+  if (element_units) *element_units = elem;
   return DORA_OK;
 }
 

@@ -32,6 +32,7 @@ _DL_ROCM = 10          # DLPack device types: kDLROCM
 _DL_CPU = 1
 _DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinned)
 from .device import DeviceArray, DeviceBuffer
+from .tensor import Argmax as _Argmax
 from .tensor import Cast as _Cast
 from .tensor import Quantized as _Quantized
 from .tensor import Ragged as _Ragged
@@ -237,6 +238,9 @@ class Node:
                                       ctypes.addressof(c.schema), ARROW_DEVICE_CPU, metadata)
         elif hasattr(data, "__dlpack__") and hasattr(data, "__dlpack_device__"):
             rc = self._send_tensor(output_id, data, metadata, f)
+        elif isinstance(data, _Argmax) or (isinstance(data, dict) and any(
+                isinstance(v, _Argmax) for v in data.values())):
+            rc = self._send_tensor_reduce(output_id, data, metadata, f)
         elif isinstance(data, _Quantized) or (isinstance(data, dict) and any(
                 isinstance(v, _Quantized) for v in data.values())):
             rc = self._send_tensor_convert(output_id, data, metadata, f)
@@ -257,8 +261,9 @@ class Node:
                             "a dict of such tensors, rows of either taken by an index "
                             "(dora_amd.tensor.take) or selected by a mask "
                             "(dora_amd.tensor.masked), a ragged batch of any of these "
-                            "(dora_amd.tensor.ragged) or tensors converted on send "
-                            "(dora_amd.tensor.cast, dora_amd.tensor.quantize)")
+                            "(dora_amd.tensor.ragged) or tensors converted or reduced on send "
+                            "(dora_amd.tensor.cast, dora_amd.tensor.quantize, "
+                            "dora_amd.tensor.argmax)")
         if rc:
             _lib.check(rc)
 
@@ -544,6 +549,46 @@ class Node:
                     for a in affines)
         return _fast.send_tensor_convert(self.handle, output_id, names, caps, entries, dev,
                                          metadata, flags, aff)
+
+    def _send_tensor_reduce(self, output_id: str, data, metadata, flags: int) -> int:
+        """A tensor reduced on send (dora_amd.tensor.argmax), or a dict of tensors of which some
+        are reduced and the rest plain, as the tensor or Struct message of the index tensors and
+        the plain values (dora_node_send_output_tensor_reduce).  Host tensors are reduced by the
+        CPU inside the call and have been read on return.  Tensors on this node's GPU do the
+        handshake each and are read, reduced and written by one kernel launch; an asynchronous
+        send holds them until `sync()`.  A dict that also holds a cast or a quantised field is not
+        offered: nothing is sent."""
+        record = isinstance(data, dict)
+        items = data if record else {None: data}
+        for name, v in items.items():
+            if isinstance(v, (_Cast, _Quantized)):
+                raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion beside an argmax in "
+                                               "one message is not offered (send the converted "
+                                               "field in a message of its own)")
+        plain = {k: (v.values if isinstance(v, _Argmax) else v) for k, v in items.items()}
+        kind, tensors, names = self._values_kind(plain if record else plain[None])
+        entries = tuple(v._entry() if isinstance(v, _Argmax) else None for v in items.values())
+        if kind == "device":
+            caps, _, done = self._device_caps(flags, tensors)
+            return done(_fast.send_tensor_reduce(self.handle, output_id, names, caps, entries,
+                                                 ARROW_DEVICE_ROCM, metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
+            from ._lib import Tensor
+            from .tensor import _describe_array, _describe_list, _describe_reduces
+            described = [_describe_array(v) for v in tensors]
+            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
+                                       ARROW_DEVICE_CPU)
+            rarr = _describe_reduces([v if isinstance(v, _Argmax) else None
+                                      for v in items.values()])
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_reduce(
+                self.handle, output_id.encode(), lst.fields, len(tensors), rarr, dev, params,
+                len(params), flags)
+            del keep, described
+            return rc
+        return _fast.send_tensor_reduce(self.handle, output_id, names, caps, entries, dev, metadata,
+                                        flags)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
         """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with

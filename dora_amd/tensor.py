@@ -136,6 +136,29 @@ word outside the table is read.  A host table over device values raises: make th
 the device.  Not offered: per-channel zero points, a host table over device values, a conversion
 under `ragged`, `take` or `masked`, bfloat16 destinations.
 
+A class map — what a segmentation head or a classifier ends in — is reduced inside the send:
+`argmax(x, axis, dtype="int64")` stands for "the index of the maximum of `x` along `axis`" (`x` a
+tensor of one of the seven cast sources with at least two dimensions, any strided view; `axis` a
+dimension of `x` as given, after any `permute`, negative: from the back; `dtype` uint8, uint16,
+int32 or int64) and is sent as exactly the message the index tensor would be, `x`'s shape without
+`axis`, bare or as a value of a dict next to plain fields and other `argmax` fields, which share
+the leading extent of their *output* shapes:
+
+    node.send_output("cls", tensor.argmax(logits, 0, "uint8"))            # (C, H, W) -> (H, W)
+    node.send_output("top1", tensor.argmax(bf16_logits, -1, "int32"))     # (B, 1000) -> (B,)
+    node.send_output("out", {"cls": tensor.argmax(seg, 1, "uint8"), "depth": depth[:, ::2]})
+
+For each output element with candidates `v[0..C)` in view order the result is the smallest `c`
+such that `v[c]` is a NaN, or without a NaN the smallest `c` with `v[c] >= v[k]` for all `k`:
+numpy's and torch's rule, `-0.0` and `+0.0` tie.  Nothing is rounded, so every send, from host
+memory or HBM, equals `from_numpy_argmax` exactly.  In place of `logits.argmax(0).to(torch.uint8)`
+with its reduction launch, 8-byte indices, cast launch and two intermediates, the send's one launch
+reads the logits once and writes only the message; it takes bfloat16 logits, which no plain send
+accepts.  Refused, nothing leaving the node: fewer than two dimensions, an axis outside them, an
+axis of extent 0, an extent whose last index does not fit `dtype` (uint8 with C > 256, ..), another
+source or index dtype.  Not offered: `argmin`, the maximum's value, a reduction beside a conversion
+in one dict, a reduction under `ragged`, `take` or `masked`, more than one axis.
+
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
 is copied once, so every source has been read when `send_output` returns.  A tensor in device
 memory is read by a kernel: in place when dense, gathered by the gfx950 gather kernel when it is a
@@ -146,8 +169,8 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import (Tensor, TensorAffine, TensorCast, TensorField, TensorList, TensorMask,
-                   TensorQuant, TensorTake)
+from ._lib import (REDUCE_ARGMAX, Tensor, TensorAffine, TensorCast, TensorField, TensorList,
+                   TensorMask, TensorQuant, TensorReduce, TensorTake)
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -284,6 +307,12 @@ def _has_quantized(values):
     return isinstance(values, Quantized)
 
 
+def _has_argmax(values):
+    if isinstance(values, dict):
+        return any(isinstance(v, Argmax) for v in values.values())
+    return isinstance(values, Argmax)
+
+
 def _cast_dtype(dtype):
     """(DLPack code, bits, name) of a cast or quantise destination given as a name, a numpy dtype
     or a torch dtype; the library refuses all but float16 and float32 (a cast) or uint8, int8,
@@ -395,6 +424,8 @@ def cast(values, dtype, scale=None, *, bias=None, axis=None):
     if isinstance(values, Quantized):
         raise TypeError("cast of a quantised tensor is not offered: a field is cast or quantised, "
                         "not both")
+    if isinstance(values, Argmax):
+        raise TypeError("cast of an argmax is not offered: give argmax the index dtype to send")
     if isinstance(values, (Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("cast converts one tensor: give a dict's fields a cast each; a cast under "
                         "ragged or take is not offered")
@@ -483,6 +514,9 @@ def quantize(values, dtype, scale=None, zero_point=0, *, bias=None, axis=None):
     value per channel along `axis`, as in `cast` — and `zero_point` one integer in the range of
     `dtype`.  `send_output` sends it, on its own or as a value of a dict of tensors, as what
     `from_numpy_quantize` states."""
+    if isinstance(values, Argmax):
+        raise TypeError("quantize of an argmax is not offered: give argmax the index dtype to "
+                        "send")
     if isinstance(values, (Quantized, Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("quantize converts one tensor: give a dict's fields a quantize each; a "
                         "quantise of a cast, or under ragged, take or masked, is not offered")
@@ -510,6 +544,62 @@ def from_numpy_quantize(x, dtype, scale=None, zero_point=0, *, bfloat16=False, b
         return from_numpy((r.astype(np.int32) + np.int32(zp)).astype(dt))
 
 
+class Argmax:
+    """A tensor reduced on send: `values`, a tensor, the `axis` whose maximum's index is sent
+    (counted from the front) and the index `dtype`.  It reads and reduces nothing itself.  Build
+    one with `argmax`."""
+
+    __slots__ = ("values", "axis", "dtype", "_code", "_bits")
+
+    def __init__(self, values, axis, dtype="int64"):
+        import operator
+        self.values = values
+        self._code, self._bits, self.dtype = _cast_dtype(dtype)
+        axis = operator.index(axis)
+        shape = getattr(values, "shape", None)
+        if shape is None:
+            raise TypeError("argmax: the values have no shape to count axis in")
+        self.axis = axis + len(shape) if axis < 0 else axis  # (out of range: the send refuses it)
+        if not -2 ** 31 <= self.axis < 2 ** 31:
+            raise ValueError(f"argmax: axis {axis}")
+
+    def _entry(self):
+        return (REDUCE_ARGMAX, self.axis, self._code, self._bits)
+
+    def __repr__(self):
+        return f"Argmax({self.values!r} along axis {self.axis} -> {self.dtype})"
+
+
+def argmax(values, axis, dtype="int64"):
+    """The index of the maximum of `values` along `axis` as a message: `values` a tensor of uint8,
+    int8, uint16, int16, float16, bfloat16 or float32 with at least two dimensions (host memory or
+    this node's HBM, any strided view), `axis` one of its dimensions as given (negative: from the
+    back), `dtype` "uint8", "uint16", "int32" or "int64" (or the numpy or torch dtype).
+    `send_output` sends it, on its own or as a value of a dict of tensors, as what
+    `from_numpy_argmax` states."""
+    if isinstance(values, (Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
+        raise TypeError("argmax reduces one tensor: give a dict's fields an argmax each; an argmax "
+                        "of a cast, a quantise, a take, a mask or a ragged batch is not offered")
+    return Argmax(values, axis, dtype)
+
+
+def from_numpy_argmax(x, axis, dtype="int64", *, bfloat16=False):
+    """The nested pyarrow array of `np.argmax(x32, axis).astype(dtype)`, the statement of record
+    of `argmax`: what `send_output(output_id, argmax(x, axis, dtype))` puts on the wire.  `x32` is
+    `x` widened to float32, exact for every source; the first NaN wins, else the first maximum.
+    `bfloat16`: `x` holds the bits of bfloat16 values as uint16 (numpy has no such dtype)."""
+    import numpy as np
+    x = np.asarray(x)
+    if bfloat16:
+        x = (x.astype(np.uint32) << 16).view(np.float32)
+    if x.ndim < 2:
+        raise ValueError("an argmax message reduces a tensor of at least two dimensions")
+    dt = np.dtype(_cast_dtype(dtype)[2])
+    if x.shape[axis] - 1 > np.iinfo(dt).max:
+        raise ValueError(f"the index {x.shape[axis] - 1} does not fit {dt.name}")
+    return from_numpy(np.argmax(x.astype(np.float32), axis).astype(dt))
+
+
 def take(values, index):
     """`values[index]` along dimension 0 as a message: `values` a tensor or a dict of at most 8
     tensors sharing their leading extent N, `index` a 1-D sequence or tensor of K int32 or int64
@@ -523,6 +613,9 @@ def take(values, index):
     if _has_quantized(values):
         raise TypeError("quantize under take is not offered: quantise the taken rows yourself, or "
                         "send the quantised tensor without the take")
+    if _has_argmax(values):
+        raise TypeError("argmax under take is not offered: reduce the taken rows yourself, or "
+                        "send the argmax without the take")
     return Taken(values, index)
 
 
@@ -540,6 +633,9 @@ def masked(values, mask):
     if _has_quantized(values):
         raise TypeError("quantize under a mask is not offered: quantise the values yourself, or "
                         "send the quantised tensor without the mask")
+    if _has_argmax(values):
+        raise TypeError("argmax under a mask is not offered: reduce the values yourself, or send "
+                        "the argmax without the mask")
     return Masked(values, mask)
 
 
@@ -555,6 +651,9 @@ def ragged(values, *, lengths=None, offsets=None):
     if _has_quantized(values):
         raise TypeError("quantize under ragged is not offered: quantise the values yourself, or "
                         "send the quantised tensor without the partition")
+    if _has_argmax(values):
+        raise TypeError("argmax under ragged is not offered: reduce the values yourself, or send "
+                        "the argmax without the partition")
     return Ragged(values, offsets=offsets, lengths=lengths)
 
 
@@ -799,6 +898,17 @@ def _describe_affines(entries) -> tuple:
     return arr, keep
 
 
+def _describe_reduces(reduces) -> "ctypes.Array":
+    """The `dora_tensor_reduce` array of `reduces`, each an `Argmax` or None (the field is sent as
+    it is)."""
+    arr = (TensorReduce * len(reduces))()
+    for k, r in enumerate(reduces):
+        if r is None:
+            continue
+        arr[k].op, arr[k].axis, arr[k].dtype_code, arr[k].dtype_bits = r._entry()
+    return arr
+
+
 def _describe_list(names, tensors, partition, form, partition_device) -> tuple:
     """The `dora_tensor_list` over the `Tensor`s of `_describe` (`names` None: the one bare
     tensor) and the partition's `Tensor`, and what the caller keeps alive with it."""
@@ -865,4 +975,5 @@ def _describe_mask(names, tensors, mask, mask_device, partition, form,
 __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_numpy_struct",
            "from_numpy_ragged", "from_numpy_take", "from_numpy_masked", "to_numpy", "to_torch",
            "Ragged", "ragged", "Taken", "take", "Masked", "masked", "Cast", "cast",
-           "from_numpy_cast", "Quantized", "quantize", "from_numpy_quantize"]
+           "from_numpy_cast", "Quantized", "quantize", "from_numpy_quantize", "Argmax", "argmax",
+           "from_numpy_argmax"]

@@ -568,6 +568,49 @@ int dora_gpu_plan_tensor_affine(const dora_tensor_field* fields, size_t n,
                                 const dora_tensor_quant* quants /* NULL or n entries */,
                                 const dora_tensor_affine* affines /* NULL or n entries */,
                                 ArrowDeviceType device_type, dora_plan** out);
+/*
+ * Class maps as one message: a field with an argmax entry is sent as the index of its maximum
+ * along one axis — logits.argmax(0) of (C, H, W), logits.argmax(-1) of (B, 1000) — reduced in the
+ * same read of the source, so only the index tensor is written.  `fields` as
+ * dora_gpu_plan_tensor_struct takes them (one field with a NULL name: a bare tensor); `reduces` is
+ * NULL or n entries, and an entry with op 0 leaves its field as it is.  With `reduces` NULL or
+ * every op 0 the call plans exactly as dora_gpu_plan_tensor (bare) or dora_gpu_plan_tensor_struct
+ * does, refusals included.
+ *
+ * A reduced field is a tensor of one of the seven cast sources (uint8, int8, uint16, int16,
+ * float16, bfloat16, float32), any strided view of at least two dimensions; `axis` names a
+ * dimension of it as given, of extent C >= 1.  Its wire form — type info, size, leaf offset and
+ * padding — is that of the tensor of the index type (uint8, uint16, int32 or int64) whose shape
+ * is the field's without `axis`; the fields of a record share the leading extent of these output
+ * shapes.  For each output element with candidates v[0..C) in view order the result is the
+ * smallest c such that v[c] is a NaN, or without a NaN the smallest c with v[c] >= v[k] for all k:
+ * numpy's and torch's argmax of the values widened to float32 (exact for every source); -0.0 and
+ * +0.0 tie.  Nothing is rounded: every send equals the statement exactly.
+ *
+ * Host values are reduced by the CPU inside this call (a host plan like any other, ROCM_HOST
+ * sources too).  Device values are never read on the host: the field's reach over all C steps is
+ * held against its allocation before anything is launched, and the plan is one launch of
+ * gather_reduce_kernel (gfx950), plain fields through their usual bodies.  An empty leading
+ * extent is the empty message and nothing is launched.
+ *
+ * Refusals, each naming the field in a record: fewer than two dimensions, `axis` outside them or
+ * C == 0 (DORA_ERR_INVALID); C - 1 not representable in the index type — uint8 with C > 256,
+ * uint16 with C > 65536, int32 with C > 2^31 (DORA_ERR_INVALID); a source that is not one of the
+ * seven, an index type that is not one of the four, an `op` other than DORA_REDUCE_ARGMAX
+ * (DORA_ERR_UNSUPPORTED, naming it).
+ * Not provided: argmin, the maximum's value, a reduction beside a conversion in one record, a
+ * reduction under a ragged batch, a take or a mask, more than one axis.
+ */
+#define DORA_REDUCE_ARGMAX 1u
+typedef struct dora_tensor_reduce { /* op == 0: this field is sent as it is */
+  uint32_t op;        /* DORA_REDUCE_ARGMAX */
+  int32_t axis;       /* 0 <= axis < ndim of the field as given */
+  uint8_t dtype_code; /* the index type (DLPack): uint 8/16, int 32/64 */
+  uint8_t dtype_bits;
+} dora_tensor_reduce;
+int dora_gpu_plan_tensor_reduce(const dora_tensor_field* fields, size_t n,
+                                const dora_tensor_reduce* reduces /* NULL or n entries */,
+                                ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -826,6 +869,14 @@ int dora_node_send_output_tensor_affine(dora_node* node, const char* output_id,
                                         const dora_tensor_cast* casts,
                                         const dora_tensor_quant* quants,
                                         const dora_tensor_affine* affines,
+                                        ArrowDeviceType device_type, const uint8_t* params,
+                                        size_t params_len, uint32_t flags);
+/* Send class maps (dora_gpu_plan_tensor_reduce: semantics, refusals), with the contract of
+ * dora_node_send_output_tensor_convert: host values are read and reduced on return, device values
+ * are read by one launch on a fill stream, and the synchronous send waits for the read. */
+int dora_node_send_output_tensor_reduce(dora_node* node, const char* output_id,
+                                        const dora_tensor_field* fields, size_t n,
+                                        const dora_tensor_reduce* reduces,
                                         ArrowDeviceType device_type, const uint8_t* params,
                                         size_t params_len, uint32_t flags);
 /* Send rows selected by a mask (dora_gpu_plan_tensor_mask: wire form, where the mask lives,

@@ -132,6 +132,23 @@ int dora_gpu_test_plan_affine(const dora_plan* plan, size_t i, int* is_affine,
                               const void** scale_table, const void** bias_table, uint64_t* inner,
                               uint64_t* channels, int* has_bias, float* bias, int64_t* lo,
                               int64_t* hi);
+/* Test tool (host only): whether field `i` of a device plan of dora_gpu_plan_tensor_reduce is
+ * reduced (*op DORA_REDUCE_ARGMAX; 0 for a field sent as it is and for any other device plan that
+ * keeps its fields): then *c the candidates per output element, *axis_stride the bytes between
+ * them, *outputs the output elements, *index_bits the index type's width, and *body which body of
+ * gather_reduce_kernel reduces it under the current selection (dora_gpu_test_reduce_body): 1 the
+ * lane body, 2 the wave body (0: not reduced).  For the lane body *vector_units and *element_units
+ * count the whole 16-byte units of a sample at address `dst` by the load path each takes (0 and 0
+ * for the wave body, which has no units).  dora_gpu_test_plan_field keeps reporting the view of
+ * the kept dimensions and the reach over all *c steps. */
+int dora_gpu_test_plan_reduce(const dora_plan* plan, size_t i, const void* dst, int* op,
+                              uint64_t* c, int64_t* axis_stride, uint64_t* outputs,
+                              int* index_bits, int* body, uint64_t* vector_units,
+                              uint64_t* element_units);
+/* Test and probe tool: which body reduces the fields of this process' reduce plans from now on:
+ * 0 the library's own selection, 1 the lane body always, 2 the wave body wherever it applies (a
+ * source-contiguous reduced axis of at least two candidates). */
+int dora_gpu_test_reduce_body(int mode);
 /* Test tool: counts[4], the launches of this process so far over the fields of a plan, by kernel:
  * gather_struct_kernel, gather_cast_kernel, gather_quant_kernel, gather_affine_kernel. */
 int dora_gpu_test_fields_launches(uint64_t* counts);
@@ -150,7 +167,7 @@ int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mas
 /* Test tool (host only): what fills the sample of any plan.  *launch 0 its copy segments (every
  * host plan, dense device plans, empty plans), 1 the gather of its one strided view, 2
  * gather_struct_kernel over its fields, 3 gather_cast_kernel / gather_quant_kernel, 4 the taken
- * body by an index in HBM, 5 a mask's count, compact and taken launches; *scan 1 if that launch
+ * body by an index in HBM, 5 a mask's count, compact and taken launches, 6 gather_reduce_kernel; *scan 1 if that launch
  * also scans a partition in HBM; *checked 1 if the plan reads HBM whose range is checked before
  * anything is launched. */
 int dora_gpu_test_plan_launch(const dora_plan* plan, int* launch, int* scan, int* checked);
