@@ -931,15 +931,44 @@ struct Args {
 
 }  // namespace reduce
 
+// ------------------------------------------------------------------------------------------
+// A field resized on the way (one more field kind, run by gather_resize_kernel only): two
+// dimensions of the source take new extents by nearest or bilinear taps.  Only the arguments live
+// here, where multi::Field needs them; the body is resize_device.h.
+// ------------------------------------------------------------------------------------------
+namespace resize {
+
+struct Args {
+  // the output counted in elements: `total` output elements, `row` 1 (every element a row of the
+  // odometer, whose shape[] is the output's), `head` elements before the first whole 16-byte unit
+  // of the output, `nunits` whole units, `piece` the source element size; stride[] in source
+  // bytes with 0 at the two resized dimensions, whose steps are sa[] below; [lo, hi] the reach of
+  // the whole source view
+  gather::Args g;
+  int64_t sa[2];     // source bytes per step of the resized dimensions (signed, 0 allowed)
+  uint32_t in[2];    // their source extents, 1 .. 32768
+  uint32_t out[2];   // their output extents, 1 .. 32768 (shape[] at ax[])
+  uint8_t ax[2];    // their places in shape[], in the order of the caller's axes
+  uint8_t mode;      // DORA_RESIZE_NEAREST or DORA_RESIZE_BILINEAR
+  uint8_t src;       // cast::Src
+  uint8_t dst;       // cast::Dst
+  uint8_t dsize;     // destination element size: 1, 2 or 4
+  uint8_t pad[2];
+};
+
+}  // namespace resize
+
 namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
 // (a scan share, kScan, is no Field: it has no view; it runs workgroups [0, wg_begin[0]))
 // (kRowsCast fields are run by gather_cast_kernel / gather_quant_kernel / gather_affine_kernel
 // only: gather_struct_kernel's launches hold none)
-// (kReduceLane and kReduceWave fields are run by gather_reduce_kernel only)
+// (kReduceLane and kReduceWave fields are run by gather_reduce_kernel only, kResize fields by
+// gather_resize_kernel only)
 enum Kind : uint32_t {
-  kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4, kReduceLane = 5, kReduceWave = 6
+  kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4, kReduceLane = 5, kReduceWave = 6,
+  kResize = 7
 };
 
 struct Field {
@@ -951,11 +980,13 @@ struct Field {
     take::Args taken;
     cast::Args cast;
     reduce::Args reduce;
+    resize::Args resize;
   };
 };
 static_assert(sizeof(take::Args) <= sizeof(tile::Args), "a taken field does not grow Field");
 static_assert(sizeof(cast::Args) <= sizeof(tile::Args), "a cast field does not grow Field");
 static_assert(sizeof(reduce::Args) <= sizeof(tile::Args), "a reduced field does not grow Field");
+static_assert(sizeof(resize::Args) <= sizeof(tile::Args), "a resized field does not grow Field");
 
 struct Args {
   uint32_t n;

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "cast_device.h"
 #include "reduce_device.h"
+#include "resize_device.h"
 #include "gather_device.h"
 #include "pack_device.h"
 #include "plan.h"
@@ -619,6 +620,55 @@ __global__ __launch_bounds__(gather::kThreads) void gather_reduce_kernel(gather:
   reduce_share(a, lds);
 }
 
+// The resize body's memory and arithmetic (resize_device.h): the cast body's policy — taps with
+// plain cached loads, one naturally aligned element each (neighbouring outputs read the same taps
+// again), products and sums opaque so that none is contracted, the sample with the pack's
+// write-through stores — plus a weight: the quotient of two exact integers, the compiler's
+// correctly rounded float32 division (no build flag relaxes it).
+struct ResizeMem : CastMem {
+  __device__ __forceinline__ float ratio(uint32_t r, uint32_t d) const {
+    return static_cast<float>(r) / static_cast<float>(d);
+  }
+};
+
+// What a workgroup of gather_resize_kernel does: struct_share's walk to its field, then the
+// field's body over the field's share of the grid: the rows or the tile body of a plain field, the
+// resize body of a resized one (a branch uniform over the workgroup).  No scan, taken, cast or
+// reduce share.
+__device__ __forceinline__ void resize_share(const gather::multi::Args& a, uint64_t* lds) {
+  const uint32_t w = blockIdx.x;
+  const int k = gather::multi::field_of(a, w);
+  const gather::multi::Field& f = a.f[k];
+  const uint64_t local = w - a.wg_begin[k], share = a.wg_begin[k + 1] - a.wg_begin[k];
+  const uint64_t lane = local * gather::kThreads + threadIdx.x, lanes = share * gather::kThreads;
+  if (f.kind == gather::multi::kRows) {
+    GatherMem m{f.rows.src, f.rows.dst};
+    gather::gather_lane(f.rows, lane, lanes, m);
+    return;
+  }
+  if (f.kind == gather::multi::kResize) {
+    // (a copy of its own, as the cast body's arguments are)
+    const gather::resize::Args r = f.resize;
+    ResizeMem m{{r.g.src, r.g.dst}};
+    gather::resize::resize_lane(r, lane, lanes, m);
+    return;
+  }
+  switch (f.tile.elem) {
+    case 1: tile_loop(f.tile, local, share, reinterpret_cast<uint8_t*>(lds)); break;
+    case 2: tile_loop(f.tile, local, share, reinterpret_cast<uint16_t*>(lds)); break;
+    case 4: tile_loop(f.tile, local, share, reinterpret_cast<uint32_t*>(lds)); break;
+    default: tile_loop(f.tile, local, share, lds); break;
+  }
+}
+
+// gather_resize_kernel: the fields of a resize plan in one launch: resized fields through the
+// resize body (resize_device.h), plain ones through their usual rows or tile body.  Chosen per
+// plan, so the other kernels hold no line of it.
+__global__ __launch_bounds__(gather::kThreads) void gather_resize_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  resize_share(a, lds);
+}
+
 // The mask kernels' memory (gather_device.h mask::): the mask with one aligned 16-byte
 // non-temporal load per thread (each byte is read once by each kernel) or byte by byte at its
 // head and tail; the thread counts in LDS; the workspace's index, counts and totals with plain
@@ -1043,6 +1093,9 @@ namespace {
 //   kReduce: the same, a reduced field through the lane or the wave body (select_reduce_wave);
 //     gather_reduce_kernel.  DORA_ERR_INVALID, nothing launched, when a reduced field would not
 //     start on a multiple of its index element size.
+//   kResize: the same, a resized field through the resize body; gather_resize_kernel.
+//     DORA_ERR_INVALID, nothing launched, when a resized field would not start on a multiple of
+//     its destination element size.
 //   kTaken (`take` given): every field through the taken body, never a tile: row i0 of its bytes
 //     is row take->src[i0] of the field, or zeros where that word is not in [0, take->n).
 // With `scan` (a ragged batch's partition in HBM; n may then be 0) one more workgroup of the same
@@ -1071,6 +1124,7 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
   int64_t stride0[gather::multi::kMaxFields];
   ReduceDesc rd[gather::multi::kMaxFields];
   bool wave[gather::multi::kMaxFields];
+  ResizeDesc rs[gather::multi::kMaxFields];
   bool quant = false, affine = false;
   for (size_t k = 0; k < n; ++k) {
     const PlanField& f = fields[k];
@@ -1082,7 +1136,35 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
     rd[k] = kind == PlanLaunch::kReduce ? f.reduce : ReduceDesc{};
     wave[k] = false;
     quant |= c[k].quant();
-    tile_c[k] = take || c[k].on || rd[k].on ? -1 : select_tile_dim(g[k], dst + off[k]);
+    rs[k] = kind == PlanLaunch::kResize ? f.resize : ResizeDesc{};
+    tile_c[k] = take || c[k].on || rd[k].on || rs[k].on ? -1
+                                                         : select_tile_dim(g[k], dst + off[k]);
+    if (rs[k].on) {
+      // the body's loads are whole source elements, its stores whole destination elements; every
+      // extent it divides by or multiplies fits the statement's 32-bit arithmetic
+      const ResizeDesc& r = rs[k];
+      const unsigned ds = r.dst_bits / 8u;
+      const bool dst_ok = r.dst_code == 2 ? ds == 2 || ds == 4
+                                          : gather::cast::dst_kind(r.dst_code, r.dst_bits) >= 0;
+      bool ok = gather::cast::src_kind(r.src_code, r.src_bits) >= 0 && dst_ok &&
+                (r.mode == DORA_RESIZE_NEAREST || r.mode == DORA_RESIZE_BILINEAR) && r.nd >= 2 &&
+                r.nd <= gather::kDims && r.ax[0] != r.ax[1] &&
+                !(reinterpret_cast<uintptr_t>(f.gd.view.src) & (f.gd.elem - 1));
+      for (int j = 0; ok && j < 2; ++j)
+        ok = r.ax[j] >= 0 && r.ax[j] < r.nd && r.in[j] >= 1 &&
+             r.in[j] <= int64_t(gather::resize::kMaxExtent) && r.shape[r.ax[j]] >= 1 &&
+             r.shape[r.ax[j]] <= int64_t(gather::resize::kMaxExtent);
+      for (int i = 0; ok && i < r.nd; ++i)
+        ok = !(static_cast<uintptr_t>(r.stride[i]) & (f.gd.elem - 1));
+      if (!ok)
+        return fail(DORA_ERR_INVALID, "field %zu `%s`: not a resize this kernel runs", k,
+                    f.name.c_str());
+      if (reinterpret_cast<uintptr_t>(dst + off[k]) & (ds - 1))
+        return fail(DORA_ERR_INVALID, "field %zu `%s`: the resized field would start at %p, not a "
+                    "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
+                    static_cast<void*>(dst + off[k]), ds);
+      continue;
+    }
     if (rd[k].on) {
       // the bodies' loads are whole source elements, their stores whole index elements
       const unsigned ds = gather::reduce::index_size(rd[k].idx_code, rd[k].idx_bits);
@@ -1126,8 +1208,13 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
                : kind == PlanLaunch::kCast ? gm::make_cast_args(g, c, off, tile_c, nf, dst)
                : kind == PlanLaunch::kReduce
                    ? gm::make_reduce_args(g, rd, wave, off, tile_c, nf, dst)
+               : kind == PlanLaunch::kResize
+                   ? gm::make_resize_args(g, rs, off, tile_c, nf, dst)
                    : gm::make_args(g, off, tile_c, nf, dst, scan);
   a.lookup = lookup;
+  if (kind == PlanLaunch::kResize)
+    return launch_timed(gather_resize_kernel, gm::grid_for(a), gather::kThreads, stream, ev_start,
+                        ev_stop, a);
   if (kind == PlanLaunch::kReduce)
     return launch_timed(gather_reduce_kernel, gm::grid_for(a), gather::kThreads, stream, ev_start,
                         ev_stop, a);
@@ -1195,6 +1282,7 @@ int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
     case PlanLaunch::kFields:
     case PlanLaunch::kCast:
     case PlanLaunch::kReduce:
+    case PlanLaunch::kResize:
     case PlanLaunch::kTaken:
       return launch_fields(plan.launch, plan.fields.data(), plan.fields.size(), dst, stream,
                            ev_start, ev_stop, scan,

@@ -138,6 +138,23 @@ struct ReduceDesc {
   uint64_t count = 0;
 };
 
+// A field resized on send (dora_gpu_plan_tensor_resize): two dimensions of the source take new
+// extents by nearest or bilinear taps (resize_device.h).  `nd` dimensions as given: `shape[]` the
+// output's extents, `stride[]` the source's byte strides (signed, 0 allowed), `ax[]` the two
+// resized dimensions in the order of the caller's axes and `in[]` their source extents; `count`
+// output elements of the destination dtype (float16, float32, or uint8, int8, uint16, int16).
+// `on` false: the field is sent as it is.
+struct ResizeDesc {
+  bool on = false;
+  uint8_t mode = 0, src_code = 0, src_bits = 0, dst_code = 0, dst_bits = 0;
+  int nd = 0;
+  int ax[2] = {0, 0};
+  int64_t in[2] = {0, 0};
+  int64_t shape[kMaxTensorDims] = {0};
+  int64_t stride[kMaxTensorDims] = {0};
+  uint64_t count = 0;
+};
+
 // One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
 // own tensor plan would describe it (dense: nd == 0), where its row-major values start in the
 // sample and how many bytes they are.  Fields follow one another in destination order.
@@ -159,6 +176,10 @@ struct PlanField {
   // candidate per output element), its [lo, hi] over all `reduce.c` steps of the reduced axis;
   // `bytes` the index bytes
   ReduceDesc reduce;
+  // a resize plan (dora_gpu_plan_tensor_resize), `resize.on`: `gd` is the whole source view in
+  // source bytes — any element of it may be a tap, so its [lo, hi] is the field's reach — and
+  // `resize` the dimensions as given; `bytes` the resized bytes
+  ResizeDesc resize;
 };
 
 // `bytes` dense bytes of `elem`-byte elements from `src` as a view: what a plan reads of an
@@ -280,12 +301,13 @@ int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
 // Everything a plan's launch kind asks for beyond `segs` (PlanLaunch below; never kSegments):
 // launch_gather of its view; one launch over its fields — gather_struct_kernel, with the scan of a
 // ragged batch's device partition and by the index of a take, or gather_cast_kernel /
-// gather_quant_kernel / gather_affine_kernel for converted fields, or gather_reduce_kernel for
-// reduced ones — each field's bytes as launch_gather would write
+// gather_quant_kernel / gather_affine_kernel for converted fields, gather_reduce_kernel for
+// reduced ones or gather_resize_kernel for resized ones — each field's bytes as launch_gather would write
 // them, nothing between fields and nothing at or past the last field's end; for a mask plan the
 // two compaction launches and then the fields by the index they wrote, `dst` then holding the
 // sample and plan_workspace bytes behind it.  DORA_ERR_INVALID, nothing launched, when a
-// converted or reduced field would not start on a multiple of its destination element size.
+// converted, reduced or resized field would not start on a multiple of its destination element
+// size.
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 
@@ -361,6 +383,14 @@ int build_tensor_affine_plan(const dora_tensor_field* fields, size_t n,
 int build_tensor_reduce_plan(const dora_tensor_field* fields, size_t n,
                              const dora_tensor_reduce* reduces, ArrowDeviceType dev,
                              dora_plan** out);
+// Tensors resized on send, bare or as a record (dora_gpu_plan_tensor_resize): a field with a
+// resize entry is the tensor of its two new extents, nearest or bilinear.  Host values: resized
+// in the plan's staging buffer, a host plan like any other; device values: a gather plan whose one
+// launch resizes (gather_resize_kernel).  `resizes` NULL or every mode 0: build_tensor_plan's
+// (bare) or build_tensor_struct_plan's plan.
+int build_tensor_resize_plan(const dora_tensor_field* fields, size_t n,
+                             const dora_tensor_resize* resizes, ArrowDeviceType dev,
+                             dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -373,7 +403,8 @@ enum class PlanLaunch : uint8_t {
   kCast,      // gather_cast_kernel / gather_quant_kernel / gather_affine_kernel over `fields`
   kTaken,     // the taken body over `fields` by `take` (+ scan share when scan_on)
   kMasked,    // count, compact, then the taken body by the workspace's index
-  kReduce     // gather_reduce_kernel over `fields`
+  kReduce,    // gather_reduce_kernel over `fields`
+  kResize     // gather_resize_kernel over `fields`
 };
 
 // What kind of message a tensor plan is, whichever way its bytes move: reported by the test probes

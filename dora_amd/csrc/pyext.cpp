@@ -708,6 +708,116 @@ PyObject* py_send_tensor_reduce(PyObject*, PyObject* const* args, Py_ssize_t nar
   return PyLong_FromLong(rc);
 }
 
+// send_tensor_resize(handle, output_id, names, capsules, resizes, device_type, metadata, flags)
+// -> status: tensors resized on send as dora_node_send_output_tensor_resize.  `names` / `capsules`
+// as send_tensor_cast takes them; `resizes` a tuple as long, each entry None (the field is sent as
+// it is) or (mode, axis0, axis1, size0, size1, dtype_code, dtype_bits).  Every capsule is consumed as send_tensor_struct
+// consumes its own.
+PyObject* py_send_tensor_resize(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  const char* usage =
+      "send_tensor_resize(handle, output_id, names, capsules, resizes, device_type, metadata, "
+      "flags): names is None over one capsule or a tuple as long as the tuple of capsules; "
+      "resizes a tuple as long, of None or (mode, axis0, axis1, size0, size1, code, bits)";
+  if (nargs != 8 || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
+      PyTuple_GET_SIZE(args[4]) != PyTuple_GET_SIZE(args[3]) ||
+      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
+                           : PyTuple_Check(args[2]) &&
+                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+    PyErr_SetString(PyExc_TypeError, usage);
+    return nullptr;
+  }
+  void* h = nullptr;
+  if (!as_ptr(args[0], &h)) return nullptr;
+  const char* oid = as_cstr(args[1]);
+  if (!oid) return nullptr;
+  const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
+  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
+  std::vector<dora_tensor_resize> resizes(static_cast<size_t>(n));
+  std::vector<DlManaged*> managed(static_cast<size_t>(n));
+  for (Py_ssize_t k = 0; k < n; ++k) {
+    fields[size_t(k)].name = nullptr;
+    if (args[2] != Py_None) {
+      fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
+      if (!fields[size_t(k)].name) return nullptr;
+    }
+    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
+    if (!PyCapsule_IsValid(cap, "dltensor")) {
+      PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
+                                    "unused, unversioned one)", k);
+      return nullptr;
+    }
+    for (Py_ssize_t j = 0; j < k; ++j)
+      if (PyTuple_GET_ITEM(args[3], j) == cap) {
+        PyErr_Format(PyExc_TypeError, "fields %zd and %zd share one capsule", j, k);
+        return nullptr;
+      }
+    dora_tensor_resize& r = resizes[size_t(k)];
+    r = dora_tensor_resize{};
+    PyObject* entry = PyTuple_GET_ITEM(args[4], k);
+    if (entry == Py_None) continue;
+    if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 7) {
+      PyErr_SetString(PyExc_TypeError, usage);
+      return nullptr;
+    }
+    long long w[7];
+    for (int j = 0; j < 7; ++j) w[j] = PyLong_AsLongLong(PyTuple_GET_ITEM(entry, j));
+    if (PyErr_Occurred()) return nullptr;
+    if (w[0] < 1 || w[0] > INT32_MAX || w[1] < INT32_MIN || w[1] > INT32_MAX ||
+        w[2] < INT32_MIN || w[2] > INT32_MAX || w[5] < 0 || w[5] > 255 || w[6] < 0 ||
+        w[6] > 255) {
+      PyErr_Format(PyExc_TypeError, "field %zd: resize entry (mode %lld, axes %lld and %lld, "
+                                    "code %lld, %lld bits)", k, w[0], w[1], w[2], w[5], w[6]);
+      return nullptr;
+    }
+    r.mode = static_cast<uint32_t>(w[0]);
+    r.axis[0] = static_cast<int32_t>(w[1]);
+    r.axis[1] = static_cast<int32_t>(w[2]);
+    r.size[0] = static_cast<int64_t>(w[3]);
+    r.size[1] = static_cast<int64_t>(w[4]);
+    r.dtype_code = static_cast<uint8_t>(w[5]);
+    r.dtype_bits = static_cast<uint8_t>(w[6]);
+  }
+  const long dev = PyLong_AsLong(args[5]);
+  if (dev == -1 && PyErr_Occurred()) return nullptr;
+  const unsigned long flags = PyLong_AsUnsignedLong(args[7]);
+  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
+  std::string& params = t_params;
+  if (!encode(args[6], params)) return nullptr;
+  for (Py_ssize_t k = 0; k < n; ++k) {
+    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
+    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
+    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
+      // (cannot happen after the checks above; the capsules renamed so far are released)
+      for (Py_ssize_t j = 0; j < k; ++j)
+        if (managed[size_t(j)]->deleter) managed[size_t(j)]->deleter(managed[size_t(j)]);
+      return nullptr;
+    }
+    managed[size_t(k)] = m;
+    dora_tensor& t = fields[size_t(k)].tensor;
+    t = dora_tensor{};
+    t.data = m->t.data;
+    t.byte_offset = m->t.byte_offset;
+    t.dtype_code = m->t.code;
+    t.dtype_bits = m->t.bits;
+    t.dtype_lanes = m->t.lanes;
+    t.ndim = m->t.ndim;
+    t.shape = m->t.shape;
+    t.strides = m->t.strides;
+  }
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor_resize(static_cast<dora_node*>(h), oid, fields.data(),
+                                           fields.size(), resizes.data(),
+                                           static_cast<ArrowDeviceType>(dev),
+                                           reinterpret_cast<const uint8_t*>(params.data()),
+                                           params.size(), static_cast<uint32_t>(flags));
+  Py_END_ALLOW_THREADS
+  // (deleters under the GIL and after the status has been taken, as in send_tensor)
+  for (DlManaged* m : managed)
+    if (m->deleter) m->deleter(m);
+  return PyLong_FromLong(rc);
+}
+
 // send_tensor_list(handle, output_id, names, capsules, partition, form, partition_device,
 // device_type, metadata, flags) -> status: a ragged batch as dora_node_send_output_tensor_list.
 // `names` is a tuple of str over the tuple `capsules`, or None over a tuple of one capsule (a bare
@@ -1406,6 +1516,9 @@ PyMethodDef methods[] = {
     {"send_tensor_reduce",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_reduce)),
      METH_FASTCALL, "dora_node_send_output_tensor_reduce of DLPack capsules, which it consumes."},
+    {"send_tensor_resize",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_resize)),
+     METH_FASTCALL, "dora_node_send_output_tensor_resize of DLPack capsules, which it consumes."},
     {"send_tensor_take",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_take)),
      METH_FASTCALL, "dora_node_send_output_tensor_take of DLPack capsules, which it consumes."},

@@ -37,6 +37,12 @@
 // validated and viewed over its kept dimensions, the reduced axis kept apart as an extent and a
 // byte stride, its reach over all the axis' steps — reduced by the CPU here for host values, by
 // the plan's one launch for device values (reduce_device.h).
+//
+// Resized tensors (dora_gpu_plan_tensor_resize) are a tensor or a record in which a field with a
+// resize entry is laid out as the tensor of its two new extents and its destination dtype: the
+// field is validated and viewed as its whole source, whose reach is the field's since any element
+// may be a tap, its dimensions kept as given beside it — resized by the CPU here for host values,
+// by the plan's one launch for device values (resize_device.h).
 #include <cstring>
 #include <memory>
 #include <string>
@@ -46,6 +52,7 @@
 
 #include "cast_device.h"
 #include "reduce_device.h"
+#include "resize_device.h"
 #include "common.h"
 #include "plan.h"
 
@@ -696,6 +703,145 @@ int describe_reduce(const dora_tensor& t, const dora_tensor_reduce& r, ArrowDevi
   return DORA_OK;
 }
 
+// The CPU's resize of a resize field: the output's elements in row-major order through
+// resize_device.h's own walk, taps and blend, with cast_device.h's plain-integer conversions, into
+// `dst` (any alignment).
+struct ResizeHostMem : gather::resize::HostArith {
+  const uint8_t* src;
+  template <int S>
+  uint32_t load_elem(int64_t s) const {
+    uint32_t raw = 0;
+    std::memcpy(&raw, src + s, S);  // (little-endian)
+    return raw;
+  }
+};
+
+template <uint32_t K>
+void resize_all(const gather::resize::Args& a, uint8_t* dst) {
+  namespace rs = gather::resize;
+  ResizeHostMem m{{}, a.g.src};
+  rs::Walk w;
+  rs::walk_start(a, 0, w, m);
+  for (uint64_t e = 0; e < a.g.total; ++e) {
+    const float y = rs::value_at<K>(a, w, m);
+    const uint32_t q = a.dsize == 1   ? rs::to_dst<1>(a, y, m)
+                       : a.dsize == 2 ? rs::to_dst<2>(a, y, m)
+                                      : rs::to_dst<4>(a, y, m);
+    std::memcpy(dst + e * a.dsize, &q, a.dsize);  // (little-endian)
+    if (e + 1 < a.g.total) rs::walk_next(a, w, m);
+  }
+}
+
+void resize_host(const GatherDesc& g, const ResizeDesc& r, uint8_t* dst) {
+  namespace gc = gather::cast;
+  const gather::resize::Args a = gather::resize::make_args(g, r, dst);
+  switch (a.src) {
+    case gc::kU8: resize_all<gc::kU8>(a, dst); break;
+    case gc::kI8: resize_all<gc::kI8>(a, dst); break;
+    case gc::kU16: resize_all<gc::kU16>(a, dst); break;
+    case gc::kI16: resize_all<gc::kI16>(a, dst); break;
+    case gc::kF16: resize_all<gc::kF16>(a, dst); break;
+    case gc::kBF16: resize_all<gc::kBF16>(a, dst); break;
+    default: resize_all<gc::kF32>(a, dst); break;
+  }
+}
+
+// What resizes `t` (dora_gpu_plan_tensor_resize, `r.mode` != 0): the entry's and the tensor's
+// refusals, else `rs`, the view `v` of the whole source — validated and canonicalised as a tensor
+// of its own, its reach the field's; its leaf and byte count the resized tensor's — and `oshape`,
+// the shape of the message.
+int describe_resize(const dora_tensor& t, const dora_tensor_resize& r, ArrowDeviceType dev,
+                    ResizeDesc& rs, TensorView& v, std::vector<int64_t>& oshape) {
+  rs = ResizeDesc{};
+  if (r.mode != DORA_RESIZE_NEAREST && r.mode != DORA_RESIZE_BILINEAR)
+    return fail(DORA_ERR_UNSUPPORTED, "resize mode %u is not supported: DORA_RESIZE_NEAREST (%u) "
+                "and DORA_RESIZE_BILINEAR (%u) are", r.mode, DORA_RESIZE_NEAREST,
+                DORA_RESIZE_BILINEAR);
+  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
+    return fail(DORA_ERR_UNSUPPORTED, "resize source dtype %s is not supported: uint8, int8, "
+                "uint16, int16, float16, bfloat16 and float32 are",
+                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  const unsigned dcode = r.dtype_bits ? r.dtype_code : t.dtype_code;
+  const unsigned dbits = r.dtype_bits ? r.dtype_bits : t.dtype_bits;
+  if (!r.dtype_bits && t.dtype_code == DL_BFLOAT)
+    return fail(DORA_ERR_UNSUPPORTED, "resize of a bfloat16 source without a destination dtype: "
+                "Arrow has no bfloat16 (float16, float32, uint8, int8, uint16 and int16 are "
+                "the destinations)");
+  const bool dst_float = dcode == DL_FLOAT && (dbits == 16 || dbits == 32);
+  if (!dst_float && gather::cast::dst_kind(dcode, dbits) < 0)
+    return fail(DORA_ERR_UNSUPPORTED, "resize destination dtype %s is not supported: float16, "
+                "float32, uint8, int8, uint16 and int16 are", dtype_name(dcode, dbits, 1).c_str());
+  if (t.ndim < 2)
+    return fail(DORA_ERR_INVALID, "resize of a tensor of %d dimensions (at least 2: the two "
+                "resized axes)", t.ndim);
+  if (t.ndim > kMaxTensorDims)
+    return fail(DORA_ERR_UNSUPPORTED, "resize of a tensor of %d dimensions (at most %d)", t.ndim,
+                kMaxTensorDims);
+  if (!t.shape) return fail(DORA_ERR_INVALID, "tensor shape is NULL");
+  for (int j = 0; j < 2; ++j)
+    if (r.axis[j] < 0 || r.axis[j] >= t.ndim)
+      return fail(DORA_ERR_INVALID, "resize axis %d is outside the tensor's %d dimensions",
+                  r.axis[j], t.ndim);
+  if (r.axis[0] == r.axis[1])
+    return fail(DORA_ERR_INVALID, "resize axes %d and %d are the same dimension", r.axis[0],
+                r.axis[1]);
+  constexpr int64_t kMax = gather::resize::kMaxExtent;
+  for (int j = 0; j < 2; ++j) {
+    const int64_t in = t.shape[r.axis[j]];
+    if (in < 1 || in > kMax)
+      return fail(DORA_ERR_INVALID, "resize along axis %d of source extent %lld: 1 to %lld are "
+                  "resized", r.axis[j], static_cast<long long>(in), static_cast<long long>(kMax));
+    if (r.size[j] < 1 || r.size[j] > kMax)
+      return fail(DORA_ERR_INVALID, "resize along axis %d to extent %lld: 1 to %lld are offered",
+                  r.axis[j], static_cast<long long>(r.size[j]), static_cast<long long>(kMax));
+  }
+  // the view of the whole source: any accepted dtype of the source's width describes it
+  dora_tensor src = t;
+  src.dtype_code = DL_UINT;
+  const int rc = describe_tensor(&src, dev, v);
+  if (rc != DORA_OK) return rc;
+  const int64_t ss = t.dtype_bits / 8;
+  if (v.bytes && (reinterpret_cast<uintptr_t>(v.gd.view.src) & static_cast<uintptr_t>(ss - 1)))
+    return fail(DORA_ERR_INVALID, "resize source data %p (data + byte_offset) is not a multiple "
+                "of its %lld-byte elements", static_cast<const void*>(v.gd.view.src),
+                static_cast<long long>(ss));
+  rs.on = true;
+  rs.mode = static_cast<uint8_t>(r.mode);
+  rs.src_code = t.dtype_code;
+  rs.src_bits = t.dtype_bits;
+  rs.dst_code = static_cast<uint8_t>(dcode);
+  rs.dst_bits = static_cast<uint8_t>(dbits);
+  rs.nd = t.ndim;
+  oshape.assign(t.shape, t.shape + t.ndim);
+  int64_t rm = ss;  // the byte strides, the caller's or row-major
+  for (int i = t.ndim - 1; i >= 0; --i) {
+    if (t.strides) {
+      if (__builtin_mul_overflow(t.strides[i], ss, &rs.stride[i]))
+        return fail(DORA_ERR_INVALID, "tensor stride %d overflows 64 bits", i);
+    } else {
+      rs.stride[i] = rm;
+      rm *= t.shape[i] ? t.shape[i] : 1;  // (describe_tensor found the byte count to fit)
+    }
+  }
+  for (int j = 0; j < 2; ++j) {
+    rs.ax[j] = r.axis[j];
+    rs.in[j] = t.shape[r.axis[j]];
+    oshape[size_t(r.axis[j])] = r.size[j];
+  }
+  // the resized element count: the source's, which fits, over two extents >= 1 times two <= 2^15
+  uint64_t count = v.bytes / static_cast<uint64_t>(ss);
+  count = count / static_cast<uint64_t>(rs.in[0]) / static_cast<uint64_t>(rs.in[1]);
+  if (__builtin_mul_overflow(count, static_cast<uint64_t>(r.size[0]), &count) ||
+      __builtin_mul_overflow(count, static_cast<uint64_t>(r.size[1]), &count) ||
+      __builtin_mul_overflow(count, static_cast<uint64_t>(dbits / 8u), &v.bytes) || v.bytes >> 63)
+    return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
+  rs.count = count;
+  for (int i = 0; i < t.ndim; ++i) rs.shape[i] = oshape[size_t(i)];
+  v.leaf = dst_float ? (dbits == 16 ? "e" : "f")
+           : dcode == DL_UINT ? (dbits == 8 ? "C" : "S") : (dbits == 8 ? "c" : "s");
+  return DORA_OK;
+}
+
 bool known_device(ArrowDeviceType dev) {
   return dev == ARROW_DEVICE_CPU || dev == ARROW_DEVICE_ROCM_HOST || dev == ARROW_DEVICE_ROCM;
 }
@@ -769,6 +915,7 @@ struct FieldLayout {
   bool strided = false;
   bool cast = false;    // any field is converted (layout_fields with `casts`)
   bool reduce = false;  // any field is reduced (layout_fields with `reduces`)
+  bool resize = false;  // any field is resized (layout_fields with `resizes`)
   uint64_t lead = 0;    // out: the leading extent the fields share, as sent
 };
 
@@ -784,12 +931,16 @@ struct FieldLayout {
 // `reduces` (n entries or NULL, never with `taken` or a conversion): field k with an op is viewed
 // over its kept dimensions (describe_reduce) while its shape, leaf, byte count and padding are the
 // index tensor's; the fields then share the leading extent of the shapes they are sent with.
+// `resizes` (n entries or NULL, never with any of the others): field k with a mode is viewed as
+// its whole source (describe_resize) while its shape, leaf, byte count and padding are the resized
+// tensor's; the leading extents shared are again those of the shapes as sent.
 int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
                   const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
                   FieldLayout& lay, int64_t taken = -1, const dora_tensor_cast* casts = nullptr,
                   const dora_tensor_quant* quants = nullptr,
                   const dora_tensor_affine* affines = nullptr,
-                  const dora_tensor_reduce* reduces = nullptr) {
+                  const dora_tensor_reduce* reduces = nullptr,
+                  const dora_tensor_resize* resizes = nullptr) {
   p.fields.resize(n);
   lay.chains.resize(n);
   lay.kids.resize(n);
@@ -818,8 +969,13 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
       return bare ? rc : field_fail(rc, k, name);
     }
     ReduceDesc rd;
-    std::vector<int64_t> rshape;  // a reduced field's shape as sent
-    if (reduces && reduces[k].op) {
+    ResizeDesc rs;
+    std::vector<int64_t> rshape;  // a reduced or resized field's shape as sent
+    if (resizes && resizes[k].mode) {
+      rc = describe_resize(t, resizes[k], dev, rs, v, rshape);
+      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
+      lay.resize = true;
+    } else if (reduces && reduces[k].op) {
       rc = describe_reduce(t, reduces[k], dev, rd, v, rshape);
       if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
       lay.reduce = true;
@@ -853,7 +1009,7 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
                      : describe_taken(t, dev, static_cast<uint64_t>(taken), v, &stride0);
       if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
     }
-    const int64_t lead = rd.on ? rshape[0] : t.shape[0];
+    const int64_t lead = rd.on || rs.on ? rshape[0] : t.shape[0];
     if (k == 0) lay.lead = static_cast<uint64_t>(lead);
     if (static_cast<uint64_t>(lead) != lay.lead)
       return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
@@ -861,7 +1017,10 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
                   "a leading extent of 1)", k, name, static_cast<long long>(lead),
                   f[0].name, static_cast<long long>(lay.lead));
     // the running offset padded to the leaf's element size (a power of two)
-    const uint64_t elem = rd.on ? rd.idx_bits / 8u : cd.on ? cd.dst_bits / 8u : t.dtype_bits / 8u;
+    const uint64_t elem = rs.on   ? rs.dst_bits / 8u
+                          : rd.on ? rd.idx_bits / 8u
+                          : cd.on ? cd.dst_bits / 8u
+                                  : t.dtype_bits / 8u;
     uint64_t padded, end;
     if (__builtin_add_overflow(off, elem - 1, &padded) ||
         __builtin_add_overflow(padded & ~(elem - 1), v.bytes, &end) || end >> 63)
@@ -876,6 +1035,7 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
     pf.stride0 = stride0;
     pf.cast = cd;
     pf.reduce = rd;
+    pf.resize = rs;
     const int64_t* shape = t.shape;  // as sent
     int ndim = t.ndim;
     std::vector<int64_t> kshape;
@@ -888,11 +1048,12 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
       shape = rshape.data();
       ndim = t.ndim - 1;
     }
+    if (rs.on) shape = rshape.data();
     lay.chains[k].reset(new TypeChain(v.leaf, shape, ndim, name));
     lay.kids[k] = &lay.chains[k]->sch[0];
     tensor_type_info(*lay.chains[k], shape, ndim, off, v.bytes, nodes[k]);
     off = end;
-    const bool stage = taken >= 0 || cd.on || rd.on || dev == ARROW_DEVICE_ROCM_HOST ||
+    const bool stage = taken >= 0 || cd.on || rd.on || rs.on || dev == ARROW_DEVICE_ROCM_HOST ||
                        (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
     if (stage) lay.staged += v.bytes;  // (<= off)
     lay.strided |= v.gd.view.nd != 0;
@@ -907,11 +1068,13 @@ void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
   p.staged.resize(staged);
   uint64_t at = 0;
   for (const PlanField& pf : p.fields) {
-    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0 && !pf.cast.on && !pf.reduce.on) {
+    if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0 && !pf.cast.on && !pf.reduce.on &&
+        !pf.resize.on) {
       p.segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
       continue;
     }
-    if (pf.reduce.on) reduce_host(pf.gd.view, pf.reduce, p.staged.data() + at);
+    if (pf.resize.on) resize_host(pf.gd, pf.resize, p.staged.data() + at);
+    else if (pf.reduce.on) reduce_host(pf.gd.view, pf.reduce, p.staged.data() + at);
     else if (pf.cast.on) cast_host(pf.gd.view, pf.cast, p.staged.data() + at);
     else gather_host(pf.gd.view, p.staged.data() + at);
     p.segs.push_back({p.staged.data() + at, pf.dst_off, pf.bytes});
@@ -1062,7 +1225,8 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
                  const TakeIn* tk, dora_plan** out, const dora_tensor_cast* casts = nullptr,
                  const dora_tensor_quant* quants = nullptr,
                  const dora_tensor_affine* affines = nullptr,
-                 const dora_tensor_reduce* reduces = nullptr) {
+                 const dora_tensor_reduce* reduces = nullptr,
+                 const dora_tensor_resize* resizes = nullptr) {
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
@@ -1070,7 +1234,7 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   std::vector<TypeInfoNode> solo;
   int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
                                tk ? static_cast<int64_t>(tk->ix.count) : -1, casts, quants,
-                               affines, reduces);
+                               affines, reduces, resizes);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
   if (bare) {
@@ -1090,12 +1254,13 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   if (tk) note_take(*p, *tk, rows);
   // what fills the sample: nothing (d0 == 0, an empty message); the taken rows; device fields as
   // segments, a gather when any is strided, a cast launch when any is converted or a reduce
-  // launch when any is reduced; host fields
+  // launch when any is reduced, a resize launch when any is resized; host fields
   if (off == 0) p->fields.clear();
   else if (tk) rc = place_taken(*p, *tk, rows, lay.staged);
   else if (dev == ARROW_DEVICE_ROCM)
-    place_device_fields(*p, !lay.strided && !lay.cast && !lay.reduce,
-                        lay.reduce ? PlanLaunch::kReduce
+    place_device_fields(*p, !lay.strided && !lay.cast && !lay.reduce && !lay.resize,
+                        lay.resize   ? PlanLaunch::kResize
+                        : lay.reduce ? PlanLaunch::kReduce
                                    : lay.cast ? PlanLaunch::kCast : PlanLaunch::kFields);
   else stage_host_fields(*p, dev, lay.staged);
   if (rc != DORA_OK) return rc;
@@ -1198,6 +1363,25 @@ int build_tensor_reduce_plan(const dora_tensor_field* f, size_t n,
   if (rf != DORA_OK) return rf;
   return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, nullptr, nullptr, nullptr,
                       reduces);
+}
+
+int build_tensor_resize_plan(const dora_tensor_field* f, size_t n,
+                             const dora_tensor_resize* resizes, ArrowDeviceType dev,
+                             dora_plan** out) {
+  bool any = false;
+  for (size_t k = 0; resizes && f && k < n; ++k) any |= resizes[k].mode != 0;
+  // no resize at all: the plain plan, whatever it is, refusals included
+  if (!any) {
+    if (f && n == 1 && !f[0].name) return build_tensor_plan(&f[0].tensor, dev, out);
+    return build_tensor_struct_plan(f, n, dev, out);
+  }
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  const int rf = check_fields(f, n, "a resize");
+  if (rf != DORA_OK) return rf;
+  return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, nullptr, nullptr, nullptr,
+                      nullptr, resizes);
 }
 
 namespace {
@@ -1601,6 +1785,12 @@ int dora_gpu_plan_tensor_reduce(const dora_tensor_field* fields, size_t n,
                                 const dora_tensor_reduce* reduces, ArrowDeviceType device_type,
                                 dora_plan** out) {
   return dora::build_tensor_reduce_plan(fields, n, reduces, device_type, out);
+}
+
+int dora_gpu_plan_tensor_resize(const dora_tensor_field* fields, size_t n,
+                                const dora_tensor_resize* resizes, ArrowDeviceType device_type,
+                                dora_plan** out) {
+  return dora::build_tensor_resize_plan(fields, n, resizes, device_type, out);
 }
 
 int dora_gpu_plan_tensor_affine(const dora_tensor_field* fields, size_t n,

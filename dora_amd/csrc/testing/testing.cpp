@@ -26,6 +26,7 @@
 #include "fence_probes.h"
 #include "gather_device.h"
 #include "reduce_device.h"
+#include "resize_device.h"
 #include "plan.h"
 #include "shm.h"
 
@@ -502,6 +503,39 @@ int dora_gpu_test_plan_reduce(const dora_plan* plan, size_t i, const void* dst, 
   }
   if (vector_units) *vector_units = vec;
   if (element_units) *element_units = elem;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_resize(const dora_plan* plan, size_t i, const void* dst, int* mode,
+                              uint64_t* outputs, int* dst_bits, int64_t* in_extent,
+                              int64_t* out_extent, int64_t* axis_stride, uint64_t* head_elements,
+                              uint64_t* units, uint64_t* tail_elements) {
+  if (!plan || !plan->dev_tensor || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a device plan with a field %zu", i);
+  namespace rs = dora::gather::resize;
+  const dora::PlanField& f = plan->fields[i];
+  const dora::ResizeDesc& r = f.resize;
+  const bool on = plan->launch == dora::PlanLaunch::kResize && r.on;
+  if (mode) *mode = on ? int(r.mode) : 0;
+  if (outputs) *outputs = on ? r.count : 0;
+  if (dst_bits) *dst_bits = on ? r.dst_bits : 0;
+  for (int j = 0; j < 2; ++j) {
+    if (in_extent) in_extent[j] = on ? r.in[j] : 0;
+    if (out_extent) out_extent[j] = on ? r.shape[r.ax[j]] : 0;
+    if (axis_stride) axis_stride[j] = on ? r.stride[r.ax[j]] : 0;
+  }
+  uint64_t head = 0, nunits = 0, tail = 0;
+  if (on) {
+    // the body's division of a sample at `dst`: single elements, whole units, single elements
+    const rs::Args a = rs::make_args(
+        f.gd, r, const_cast<uint8_t*>(static_cast<const uint8_t*>(dst)) + f.dst_off);
+    head = a.g.head;
+    nunits = a.g.nunits;
+    tail = a.g.total - head - (16u / a.dsize) * nunits;
+  }
+  if (head_elements) *head_elements = head;
+  if (units) *units = nunits;
+  if (tail_elements) *tail_elements = tail;
   return DORA_OK;
 }
 

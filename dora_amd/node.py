@@ -36,6 +36,7 @@ from .tensor import Argmax as _Argmax
 from .tensor import Cast as _Cast
 from .tensor import Quantized as _Quantized
 from .tensor import Ragged as _Ragged
+from .tensor import Resized as _Resized
 from .tensor import Masked as _Masked
 from .tensor import Taken as _Taken
 from .type_info import decode
@@ -238,6 +239,9 @@ class Node:
                                       ctypes.addressof(c.schema), ARROW_DEVICE_CPU, metadata)
         elif hasattr(data, "__dlpack__") and hasattr(data, "__dlpack_device__"):
             rc = self._send_tensor(output_id, data, metadata, f)
+        elif isinstance(data, _Resized) or (isinstance(data, dict) and any(
+                isinstance(v, _Resized) for v in data.values())):
+            rc = self._send_tensor_resize(output_id, data, metadata, f)
         elif isinstance(data, _Argmax) or (isinstance(data, dict) and any(
                 isinstance(v, _Argmax) for v in data.values())):
             rc = self._send_tensor_reduce(output_id, data, metadata, f)
@@ -261,9 +265,9 @@ class Node:
                             "a dict of such tensors, rows of either taken by an index "
                             "(dora_amd.tensor.take) or selected by a mask "
                             "(dora_amd.tensor.masked), a ragged batch of any of these "
-                            "(dora_amd.tensor.ragged) or tensors converted or reduced on send "
-                            "(dora_amd.tensor.cast, dora_amd.tensor.quantize, "
-                            "dora_amd.tensor.argmax)")
+                            "(dora_amd.tensor.ragged) or tensors converted, reduced or resized "
+                            "on send (dora_amd.tensor.cast, dora_amd.tensor.quantize, "
+                            "dora_amd.tensor.argmax, dora_amd.tensor.resize)")
         if rc:
             _lib.check(rc)
 
@@ -588,6 +592,46 @@ class Node:
             del keep, described
             return rc
         return _fast.send_tensor_reduce(self.handle, output_id, names, caps, entries, dev, metadata,
+                                        flags)
+
+    def _send_tensor_resize(self, output_id: str, data, metadata, flags: int) -> int:
+        """A tensor resized on send (dora_amd.tensor.resize), or a dict of tensors of which some
+        are resized and the rest plain, as the tensor or Struct message of the resized tensors and
+        the plain values (dora_node_send_output_tensor_resize).  Host tensors are resized by the
+        CPU inside the call and have been read on return.  Tensors on this node's GPU do the
+        handshake each and are read, resized and written by one kernel launch; an asynchronous
+        send holds them until `sync()`.  A dict that also holds a cast, a quantised or an argmax
+        field is not offered: nothing is sent."""
+        record = isinstance(data, dict)
+        items = data if record else {None: data}
+        for name, v in items.items():
+            if isinstance(v, (_Cast, _Quantized, _Argmax)):
+                raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion or an argmax beside "
+                                               "a resize in one message is not offered (send the "
+                                               "field in a message of its own)")
+        plain = {k: (v.values if isinstance(v, _Resized) else v) for k, v in items.items()}
+        kind, tensors, names = self._values_kind(plain if record else plain[None])
+        entries = tuple(v._entry() if isinstance(v, _Resized) else None for v in items.values())
+        if kind == "device":
+            caps, _, done = self._device_caps(flags, tensors)
+            return done(_fast.send_tensor_resize(self.handle, output_id, names, caps, entries,
+                                                 ARROW_DEVICE_ROCM, metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
+            from ._lib import Tensor
+            from .tensor import _describe_array, _describe_list, _describe_resizes
+            described = [_describe_array(v) for v in tensors]
+            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
+                                       ARROW_DEVICE_CPU)
+            rarr = _describe_resizes([v if isinstance(v, _Resized) else None
+                                      for v in items.values()])
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_resize(
+                self.handle, output_id.encode(), lst.fields, len(tensors), rarr, dev, params,
+                len(params), flags)
+            del keep, described
+            return rc
+        return _fast.send_tensor_resize(self.handle, output_id, names, caps, entries, dev, metadata,
                                         flags)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:

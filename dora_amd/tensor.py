@@ -159,6 +159,39 @@ axis of extent 0, an extent whose last index does not fit `dtype` (uint8 with C 
 source or index dtype.  Not offered: `argmin`, the maximum's value, a reduction beside a conversion
 in one dict, a reduction under `ragged`, `take` or `masked`, more than one axis.
 
+A resized frame — what every vision dataflow starts with — is resized inside the send:
+`resize(x, size, axes=(-2, -1), mode="nearest", dtype=None)` stands for "`x` with the two
+dimensions `axes` at the new extents `size`" (`x` a tensor of one of the seven cast sources with 2
+to 8 dimensions, any strided view; `axes` two different dimensions of `x` as given, after any
+`permute`, negative: from the back; `mode` "nearest" or "bilinear"; `dtype` float16, float32,
+uint8, int8, uint16 or int16, by default the source's own, which a bfloat16 source cannot keep) and
+is sent as exactly the message the resized tensor would be, bare or as a value of a dict next to
+plain fields and other `resize` fields, which share the leading extent of their *output* shapes:
+
+    node.send_output("image", tensor.resize(frame, (640, 640), axes=(0, 1), mode="bilinear"))
+    node.send_output("image", tensor.resize(frame.permute(2, 0, 1), (320, 320), mode="bilinear",
+                                            dtype="float16"))
+    node.send_output("out", {"thumb": tensor.resize(frames, (90, 160), axes=(1, 2)), "stamp": t})
+
+An axis of source extent I and output extent O, both 1 to 32768, reads at output coordinate o the
+tap `(o * I) // O` (nearest: OpenCV's INTER_NEAREST, torch's "nearest") or, bilinear with
+half-pixel centres and no antialiasing, with `d = 2 * O`, `n = max((2 * o + 1) * I - O, 0)` and
+`q = n // d`, the taps `q` and `q + 1` with weights `float32(d - n % d) / float32(d)` and
+`float32(n % d) / float32(d)`, or the last element alone where `q >= I - 1`.  Every source element
+is widened to float32; the four taps are blended along the second of `axes`, then along the first,
+every product rounded to float32 and then every sum, never fused; the result is rounded to `dtype`
+as `cast` does (floats) or as `quantize` does without a scale (integers: ties to even, saturated,
+a NaN as 0).  Every send, from host memory or HBM, equals `from_numpy_resize` bit for bit but for
+the payload of a NaN; torch's `interpolate` computes its weights from a float32 scale factor and
+differs in the last bits.  In place of `permute`, `float()`, `interpolate`, `round`, `clamp`,
+`to(uint8)`, `permute` and `contiguous` with their full-size intermediates, the send's one launch
+reads only the taps it needs and writes only the small message.  Refused, nothing leaving the
+node: fewer than two dimensions, an axis outside them, the two axes equal, an extent outside 1 to
+32768, another source, destination or mode.  Not offered: bicubic, area and antialiased modes,
+`align_corners=True`, one axis alone or more than two, a resize beside a conversion or an argmax
+in one dict, a resize of or under `cast`, `quantize`, `argmax`, `ragged`, `take` or `masked`,
+bfloat16 destinations.
+
 A strided host view is gathered into row-major order by the CPU inside the send; pinned memory
 is copied once, so every source has been read when `send_output` returns.  A tensor in device
 memory is read by a kernel: in place when dense, gathered by the gfx950 gather kernel when it is a
@@ -169,8 +202,9 @@ from __future__ import annotations
 
 from ctypes import c_int64
 
-from ._lib import (REDUCE_ARGMAX, Tensor, TensorAffine, TensorCast, TensorField, TensorList,
-                   TensorMask, TensorQuant, TensorReduce, TensorTake)
+from ._lib import (REDUCE_ARGMAX, RESIZE_BILINEAR, RESIZE_NEAREST, Tensor, TensorAffine,
+                   TensorCast, TensorField, TensorList, TensorMask, TensorQuant, TensorReduce,
+                   TensorResize, TensorTake)
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -313,6 +347,12 @@ def _has_argmax(values):
     return isinstance(values, Argmax)
 
 
+def _has_resized(values):
+    if isinstance(values, dict):
+        return any(isinstance(v, Resized) for v in values.values())
+    return isinstance(values, Resized)
+
+
 def _cast_dtype(dtype):
     """(DLPack code, bits, name) of a cast or quantise destination given as a name, a numpy dtype
     or a torch dtype; the library refuses all but float16 and float32 (a cast) or uint8, int8,
@@ -426,6 +466,8 @@ def cast(values, dtype, scale=None, *, bias=None, axis=None):
                         "not both")
     if isinstance(values, Argmax):
         raise TypeError("cast of an argmax is not offered: give argmax the index dtype to send")
+    if isinstance(values, Resized):
+        raise TypeError("cast of a resize is not offered: give resize the dtype to send")
     if isinstance(values, (Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("cast converts one tensor: give a dict's fields a cast each; a cast under "
                         "ragged or take is not offered")
@@ -517,6 +559,8 @@ def quantize(values, dtype, scale=None, zero_point=0, *, bias=None, axis=None):
     if isinstance(values, Argmax):
         raise TypeError("quantize of an argmax is not offered: give argmax the index dtype to "
                         "send")
+    if isinstance(values, Resized):
+        raise TypeError("quantize of a resize is not offered: give resize the dtype to send")
     if isinstance(values, (Quantized, Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("quantize converts one tensor: give a dict's fields a quantize each; a "
                         "quantise of a cast, or under ragged, take or masked, is not offered")
@@ -577,6 +621,9 @@ def argmax(values, axis, dtype="int64"):
     back), `dtype` "uint8", "uint16", "int32" or "int64" (or the numpy or torch dtype).
     `send_output` sends it, on its own or as a value of a dict of tensors, as what
     `from_numpy_argmax` states."""
+    if isinstance(values, Resized):
+        raise TypeError("argmax of a resize is not offered: reduce the resized tensor yourself, or "
+                        "send the two in messages of their own")
     if isinstance(values, (Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
         raise TypeError("argmax reduces one tensor: give a dict's fields an argmax each; an argmax "
                         "of a cast, a quantise, a take, a mask or a ragged batch is not offered")
@@ -600,6 +647,146 @@ def from_numpy_argmax(x, axis, dtype="int64", *, bfloat16=False):
     return from_numpy(np.argmax(x.astype(np.float32), axis).astype(dt))
 
 
+_RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR}
+
+
+class Resized:
+    """A tensor resized on send: `values`, a tensor, the two `axes` resized (counted from the
+    front), their new extents `size`, the `mode` and the destination `dtype` (None: the source's
+    own).  It reads and resizes nothing itself.  Build one with `resize`."""
+
+    __slots__ = ("values", "size", "axes", "mode", "dtype", "_mode", "_code", "_bits")
+
+    def __init__(self, values, size, axes=(-2, -1), mode="nearest", dtype=None):
+        import operator
+        self.values = values
+        shape = getattr(values, "shape", None)
+        if shape is None:
+            raise TypeError("resize: the values have no shape to count axes in")
+        try:
+            size = tuple(operator.index(v) for v in size)
+            axes = tuple(operator.index(v) for v in axes)
+        except TypeError:
+            raise TypeError("resize: size and axes are two integers each") from None
+        if len(size) != 2 or len(axes) != 2:
+            raise TypeError("resize: size and axes are two integers each")
+        if mode not in _RESIZE_MODES:
+            raise ValueError(f"resize: mode {mode!r} is not offered: 'nearest' and 'bilinear' are")
+        self.size = size
+        # (out of range or equal: the send refuses them)
+        self.axes = tuple(a + len(shape) if a < 0 else a for a in axes)
+        if not all(-2 ** 31 <= a < 2 ** 31 for a in self.axes) or \
+                not all(-2 ** 63 <= v < 2 ** 63 for v in size):
+            raise ValueError(f"resize: axes {axes}, size {size}")
+        self.mode, self._mode = mode, _RESIZE_MODES[mode]
+        if dtype is None:
+            self._code, self._bits, self.dtype = 0, 0, None
+        else:
+            self._code, self._bits, self.dtype = _cast_dtype(dtype)
+
+    def _entry(self):
+        return (self._mode, self.axes[0], self.axes[1], self.size[0], self.size[1], self._code,
+                self._bits)
+
+    def __repr__(self):
+        return (f"Resized({self.values!r} axes {self.axes} -> {self.size}, {self.mode}"
+                f"{'' if self.dtype is None else ' -> ' + self.dtype})")
+
+
+def resize(values, size, *, axes=(-2, -1), mode="nearest", dtype=None):
+    """`values` with its two dimensions `axes` at the new extents `size` as a message: `values` a
+    tensor of uint8, int8, uint16, int16, float16, bfloat16 or float32 with 2 to 8 dimensions (host
+    memory or this node's HBM, any strided view), `axes` two of its dimensions as given (negative:
+    from the back), `size` their new extents in that order, `mode` "nearest" or "bilinear"
+    (half-pixel centres, no antialiasing), `dtype` "float16", "float32", "uint8", "int8", "uint16"
+    or "int16" (or the numpy or torch dtype; None: the source's own).  `send_output` sends it, on
+    its own or as a value of a dict of tensors, as what `from_numpy_resize` states."""
+    if isinstance(values, (Resized, Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
+        raise TypeError("resize resizes one tensor: give a dict's fields a resize each; a resize "
+                        "of a cast, a quantise, an argmax, a take, a mask or a ragged batch is not "
+                        "offered")
+    return Resized(values, size, axes, mode, dtype)
+
+
+def _resize_taps(n_in, n_out, mode):
+    """(i0, i1, w0, w1) of every output coordinate of an axis of `n_in` source and `n_out` output
+    steps: the statement's integer arithmetic and its two float32 divisions."""
+    import numpy as np
+    o = np.arange(n_out, dtype=np.int64)
+    if mode == "nearest":
+        i = (o * n_in) // n_out
+        return i, i, None, None
+    d = 2 * n_out
+    n = np.maximum((2 * o + 1) * n_in - n_out, 0)
+    q = n // d
+    last = q >= n_in - 1
+    i0 = np.where(last, n_in - 1, q)
+    i1 = np.where(last, n_in - 1, q + 1)
+    r = np.where(last, 0, n % d)
+    w1 = r.astype(np.float32) / np.float32(d)
+    w0 = (d - r).astype(np.float32) / np.float32(d)
+    return i0, i1, w0, w1
+
+
+def from_numpy_resize(x, size, *, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=False):
+    """The nested pyarrow array of `x` resized, the statement of record of `resize`: what
+    `send_output(output_id, resize(x, size, axes=axes, mode=mode, dtype=dtype))` puts on the wire.
+    Every element is widened to float32; an axis of I source and O output steps reads at o the tap
+    `(o * I) // O` (nearest) or blends the taps `q`, `q + 1` of `n = max((2 * o + 1) * I - O, 0)`,
+    `q = n // (2 * O)` by `float32(n % (2 * O)) / float32(2 * O)` and its complement (bilinear; the
+    last element alone where `q >= I - 1`), along the second of `axes` first, every product
+    rounded to float32 and then every sum; the result goes to `dtype` as `from_numpy_cast` or
+    `from_numpy_quantize` (no scale, zero point 0) takes it.  `bfloat16`: `x` holds the bits of
+    bfloat16 values as uint16 (numpy has no such dtype) and `dtype` must be given."""
+    return from_numpy(_numpy_resize(x, size, axes, mode, dtype, bfloat16))
+
+
+def _numpy_resize(x, size, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=False):
+    """`from_numpy_resize`'s values as a numpy array."""
+    import numpy as np
+    x = np.asarray(x)
+    if bfloat16:
+        if dtype is None:
+            raise ValueError("a bfloat16 source names its destination dtype")
+        x = (x.astype(np.uint32) << 16).view(np.float32)
+    if mode not in _RESIZE_MODES:
+        raise ValueError(f"mode {mode!r}")
+    if not 2 <= x.ndim <= 8:
+        raise ValueError("a resize message resizes a tensor of 2 to 8 dimensions")
+    a, b = (ax + x.ndim if ax < 0 else ax for ax in axes)
+    if a == b or not (0 <= a < x.ndim and 0 <= b < x.ndim):
+        raise ValueError(f"axes {tuple(axes)} of {x.ndim} dimensions")
+    for n in (x.shape[a], x.shape[b], size[0], size[1]):
+        if not 1 <= n <= 32768:
+            raise ValueError(f"extent {n}: 1 to 32768 are resized")
+    dt = x.dtype if dtype is None else np.dtype(_cast_dtype(dtype)[2])
+    v = x.astype(np.float32)
+    a0, a1, wa0, wa1 = _resize_taps(x.shape[a], size[0], mode)
+    b0, b1, wb0, wb1 = _resize_taps(x.shape[b], size[1], mode)
+
+    def along(ax, w):  # a weight vector broadcast along axis `ax`
+        shape = [1] * x.ndim
+        shape[ax] = -1
+        return w.reshape(shape)
+
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        if mode == "nearest":
+            y = np.take(np.take(v, a0, axis=a), b0, axis=b)
+        else:
+            va0, va1 = np.take(v, a0, axis=a), np.take(v, a1, axis=a)
+            wb0, wb1, wa0, wa1 = along(b, wb0), along(b, wb1), along(a, wa0), along(a, wa1)
+            top = np.take(va0, b0, axis=b) * wb0 + np.take(va0, b1, axis=b) * wb1
+            bot = np.take(va1, b0, axis=b) * wb0 + np.take(va1, b1, axis=b) * wb1
+            y = top * wa0 + bot * wa1
+        assert y.dtype == np.float32
+        if dt.kind == "f":
+            return y.astype(dt)
+        info = np.iinfo(dt)
+        r = np.where(np.isnan(y), np.float32(0), np.rint(y))
+        r = np.clip(r, np.float32(info.min), np.float32(info.max))
+        return r.astype(np.int32).astype(dt)
+
+
 def take(values, index):
     """`values[index]` along dimension 0 as a message: `values` a tensor or a dict of at most 8
     tensors sharing their leading extent N, `index` a 1-D sequence or tensor of K int32 or int64
@@ -616,6 +803,9 @@ def take(values, index):
     if _has_argmax(values):
         raise TypeError("argmax under take is not offered: reduce the taken rows yourself, or "
                         "send the argmax without the take")
+    if _has_resized(values):
+        raise TypeError("resize under take is not offered: resize the taken rows yourself, or "
+                        "send the resize without the take")
     return Taken(values, index)
 
 
@@ -636,6 +826,9 @@ def masked(values, mask):
     if _has_argmax(values):
         raise TypeError("argmax under a mask is not offered: reduce the values yourself, or send "
                         "the argmax without the mask")
+    if _has_resized(values):
+        raise TypeError("resize under a mask is not offered: resize the values yourself, or send "
+                        "the resize without the mask")
     return Masked(values, mask)
 
 
@@ -654,6 +847,9 @@ def ragged(values, *, lengths=None, offsets=None):
     if _has_argmax(values):
         raise TypeError("argmax under ragged is not offered: reduce the values yourself, or send "
                         "the argmax without the partition")
+    if _has_resized(values):
+        raise TypeError("resize under ragged is not offered: resize the values yourself, or send "
+                        "the resize without the partition")
     return Ragged(values, offsets=offsets, lengths=lengths)
 
 
@@ -909,6 +1105,18 @@ def _describe_reduces(reduces) -> "ctypes.Array":
     return arr
 
 
+def _describe_resizes(resizes) -> "ctypes.Array":
+    """The `dora_tensor_resize` array of `resizes`, each a `Resized` or None (the field is sent as
+    it is)."""
+    arr = (TensorResize * len(resizes))()
+    for k, r in enumerate(resizes):
+        if r is None:
+            continue
+        (arr[k].mode, arr[k].axis[0], arr[k].axis[1], arr[k].size[0], arr[k].size[1],
+         arr[k].dtype_code, arr[k].dtype_bits) = r._entry()
+    return arr
+
+
 def _describe_list(names, tensors, partition, form, partition_device) -> tuple:
     """The `dora_tensor_list` over the `Tensor`s of `_describe` (`names` None: the one bare
     tensor) and the partition's `Tensor`, and what the caller keeps alive with it."""
@@ -976,4 +1184,4 @@ __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_nump
            "from_numpy_ragged", "from_numpy_take", "from_numpy_masked", "to_numpy", "to_torch",
            "Ragged", "ragged", "Taken", "take", "Masked", "masked", "Cast", "cast",
            "from_numpy_cast", "Quantized", "quantize", "from_numpy_quantize", "Argmax", "argmax",
-           "from_numpy_argmax"]
+           "from_numpy_argmax", "Resized", "resize", "from_numpy_resize"]

@@ -611,6 +611,67 @@ typedef struct dora_tensor_reduce { /* op == 0: this field is sent as it is */
 int dora_gpu_plan_tensor_reduce(const dora_tensor_field* fields, size_t n,
                                 const dora_tensor_reduce* reduces /* NULL or n entries */,
                                 ArrowDeviceType device_type, dora_plan** out);
+/*
+ * Resized frames as one message: a field with a resize entry is sent with two of its dimensions
+ * at new extents — a 1080x1920x3 camera frame as the 640x640x3 a detector reads — the taps read
+ * from the source in place, so only the small tensor is written.  `fields` as
+ * dora_gpu_plan_tensor_struct takes them (one field with a NULL name: a bare tensor); `resizes`
+ * is NULL or n entries, and an entry with mode 0 leaves its field as it is.  With `resizes` NULL
+ * or every mode 0 the call plans exactly as dora_gpu_plan_tensor (bare) or
+ * dora_gpu_plan_tensor_struct does, refusals included.
+ *
+ * A resized field is a tensor of one of the seven cast sources (uint8, int8, uint16, int16,
+ * float16, bfloat16, float32), any strided view of 2 to 8 dimensions; axis[0] and axis[1] name two
+ * different dimensions of it as given and size[0], size[1] their new extents.  Its wire form —
+ * type info, size, leaf offset and padding — is that of the tensor of the destination dtype
+ * (dtype_bits 0: the source's own; else float16 or float32, or uint8, int8, uint16 or int16)
+ * whose shape is the field's with those two extents replaced; the fields of a record share the
+ * leading extent of these output shapes.
+ *
+ * The statement.  Each resized axis has source extent I and output extent O, both in [1, 32768].
+ * Nearest: output coordinate o reads the one tap i = (o * I) / O (integer division).  Bilinear
+ * (half-pixel centres, no antialiasing): d = 2 * O, n = max((2 * o + 1) * I - O, 0), q = n / d; if
+ * q >= I - 1 then i0 = i1 = I - 1, w0 = 1, w1 = 0; else i0 = q, i1 = q + 1, r = n % d,
+ * w1 = float32(r) / float32(d), w0 = float32(d - r) / float32(d), each one correctly rounded
+ * float32 division of two exact integers.  Every source element is widened to float32 (exact).
+ * Nearest: the value is the one tap.  Bilinear, a = axis[0], b = axis[1], v[ia][ib] the four taps:
+ *   top = v[a0][b0] * wb0 + v[a0][b1] * wb1
+ *   bot = v[a1][b0] * wb0 + v[a1][b1] * wb1
+ *   y   = top * wa0 + bot * wa1
+ * every product rounded to float32, then every sum; never a fused multiply-add.  y goes to the
+ * destination as dora_gpu_plan_tensor_cast does (float16, float32: round to nearest even,
+ * subnormals kept, overflow to infinity) or as dora_gpu_plan_tensor_convert does without a scale
+ * and with zero point 0 (integers: nearest, ties to even, a NaN as 0, saturated).  Non-finite
+ * sources give what the formula gives (inf * 0 is a NaN).  Nearest to the source's own dtype moves
+ * elements unchanged.  Every send is bit-exact against this statement but for the payload of a
+ * NaN in a float destination.
+ *
+ * Host values are resized by the CPU inside this call (a host plan like any other, ROCM_HOST
+ * sources too).  Device values are never read on the host: the field's reach is that of its whole
+ * view, held against its allocation before anything is launched, and the plan is one launch of
+ * gather_resize_kernel (gfx950), plain fields through their usual bodies.  An empty kept leading
+ * dimension is the empty message and nothing is launched.
+ *
+ * Refusals, each naming the field in a record: fewer than two dimensions, an axis outside them,
+ * the two axes equal, I or O outside [1, 32768] (DORA_ERR_INVALID); a source that is not one of
+ * the seven, a destination that is not one of the six, a bfloat16 source without a destination, a
+ * mode other than the two (DORA_ERR_UNSUPPORTED, naming it).
+ * Not provided: bicubic, area and antialiased modes, align_corners, one axis alone or more than
+ * two, a resize beside a conversion or a reduction in one record, a resize under a ragged batch,
+ * a take or a mask, bfloat16 destinations.
+ */
+#define DORA_RESIZE_NEAREST 1u
+#define DORA_RESIZE_BILINEAR 2u
+typedef struct dora_tensor_resize { /* mode == 0: this field is sent as it is */
+  uint32_t mode;      /* DORA_RESIZE_NEAREST or DORA_RESIZE_BILINEAR */
+  int32_t axis[2];    /* 0 <= axis < ndim of the field as given, different */
+  int64_t size[2];    /* the new extents, in the order of axis */
+  uint8_t dtype_code; /* the destination (DLPack); dtype_bits 0: the source's own dtype */
+  uint8_t dtype_bits;
+} dora_tensor_resize;
+int dora_gpu_plan_tensor_resize(const dora_tensor_field* fields, size_t n,
+                                const dora_tensor_resize* resizes /* NULL or n entries */,
+                                ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -877,6 +938,14 @@ int dora_node_send_output_tensor_affine(dora_node* node, const char* output_id,
 int dora_node_send_output_tensor_reduce(dora_node* node, const char* output_id,
                                         const dora_tensor_field* fields, size_t n,
                                         const dora_tensor_reduce* reduces,
+                                        ArrowDeviceType device_type, const uint8_t* params,
+                                        size_t params_len, uint32_t flags);
+/* Send resized frames (dora_gpu_plan_tensor_resize: the statement, refusals), with the contract
+ * of dora_node_send_output_tensor_reduce: host values are read and resized on return, device
+ * values are read by one launch on a fill stream, and the synchronous send waits for the read. */
+int dora_node_send_output_tensor_resize(dora_node* node, const char* output_id,
+                                        const dora_tensor_field* fields, size_t n,
+                                        const dora_tensor_resize* resizes,
                                         ArrowDeviceType device_type, const uint8_t* params,
                                         size_t params_len, uint32_t flags);
 /* Send rows selected by a mask (dora_gpu_plan_tensor_mask: wire form, where the mask lives,

@@ -21,7 +21,8 @@ SIZED = {"dora_fill_ticket"}
 # plain structs the caller fills in, declared field by field from the header (struct_decl)
 STRUCTS = {"dora_tensor", "dora_tensor_cast", "dora_tensor_quant", "dora_tensor_field",
            "dora_tensor_list",
-           "dora_tensor_take", "dora_tensor_mask", "dora_tensor_affine", "dora_tensor_reduce"}
+           "dora_tensor_take", "dora_tensor_mask", "dora_tensor_affine", "dora_tensor_reduce",
+           "dora_tensor_resize"}
 SCALAR = {"uint16_t": "u16", "int": "c_int", "int64_t": "i64", "uint64_t": "u64", "uint32_t": "u32",
           "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64",
           "uint8_t": "u8", "char": "c_char", "void": "c_void", "ArrowDeviceType": "ArrowDeviceType",
@@ -116,8 +117,11 @@ def struct_decl(name, text):
         decl = " ".join(decl.split())
         if not decl:
             continue
-        fm = re.match(r"(.*?)(\b\w+)$", decl)
-        out.append(f"    pub {fm.group(2)}: {rust_type(fm.group(1))},")
+        fm = re.match(r"(.*?)(\b\w+)(?:\[(\d+)\])?$", decl)
+        t = rust_type(fm.group(1))
+        if fm.group(3):  # a fixed array member
+            t = f"[{t}; {fm.group(3)}]"
+        out.append(f"    pub {fm.group(2)}: {t},")
     out.append("}")
     return out
 
