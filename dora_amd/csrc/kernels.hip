@@ -1083,19 +1083,65 @@ int launch_gather(const GatherDesc& g, uint8_t* dst, hipStream_t stream, hipEven
 
 namespace {
 
+// What a launch of `kind` does to field `k`, `f`, held against what the kernel's body takes for
+// granted — its loads whole source elements, its stores whole destination elements, every extent
+// within its arithmetic.  Returns the size of the elements stored, with `*noun` what the field
+// then is ("converted", "reduced", "resized"); 0 with `*noun` NULL for a field that goes as it is;
+// -1 after recording that this is not an op the kernel runs.  A new op is one more branch here.
+int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** noun) {
+  namespace gc = gather::cast;
+  const uintptr_t src = reinterpret_cast<uintptr_t>(f.gd.view.src), elem_mask = f.gd.elem - 1;
+  const char* op = nullptr;
+  unsigned ds = 0;
+  bool ok = true;
+  *noun = nullptr;
+  if (kind == PlanLaunch::kResize && f.resize.on) {
+    const ResizeDesc& r = f.resize;
+    op = "a resize";
+    *noun = "resized";
+    ds = r.dst_bits / 8u;
+    const bool dst_ok = r.dst_code == 2 ? ds == 2 || ds == 4
+                                        : gc::dst_kind(r.dst_code, r.dst_bits) >= 0;
+    ok = gc::src_kind(r.src_code, r.src_bits) >= 0 && dst_ok &&
+         (r.mode == DORA_RESIZE_NEAREST || r.mode == DORA_RESIZE_BILINEAR) && r.nd >= 2 &&
+         r.nd <= gather::kDims && r.ax[0] != r.ax[1] && !(src & elem_mask);
+    for (int j = 0; ok && j < 2; ++j)
+      ok = r.ax[j] >= 0 && r.ax[j] < r.nd && r.in[j] >= 1 &&
+           r.in[j] <= int64_t(gather::resize::kMaxExtent) && r.shape[r.ax[j]] >= 1 &&
+           r.shape[r.ax[j]] <= int64_t(gather::resize::kMaxExtent);
+    for (int i = 0; ok && i < r.nd; ++i) ok = !(static_cast<uintptr_t>(r.stride[i]) & elem_mask);
+  } else if (kind == PlanLaunch::kReduce && f.reduce.on) {
+    const ReduceDesc& r = f.reduce;
+    op = "a reduction";
+    *noun = "reduced";
+    ds = gather::reduce::index_size(r.idx_code, r.idx_bits);
+    ok = gc::src_kind(r.src_code, r.src_bits) >= 0 && ds && r.c &&
+         !((src | static_cast<uintptr_t>(r.cstride)) & elem_mask);
+  } else if (kind == PlanLaunch::kCast && f.cast.on) {
+    // (the cast body's stores are whole elements and whole 16-byte units of them)
+    const CastDesc& c = f.cast;
+    op = "a cast";
+    *noun = "converted";
+    ds = c.dst_bits / 8u;
+    const bool dst_ok = c.quant() ? gc::dst_kind(c.dst_code, c.dst_bits) >= 0 : ds == 2 || ds == 4;
+    ok = gc::src_kind(c.src_code, c.src_bits) >= 0 && dst_ok && !(src & elem_mask);
+  }
+  if (ok) return static_cast<int>(ds);
+  fail(DORA_ERR_INVALID, "field %zu `%s`: not %s this kernel runs", k, f.name.c_str(), op);
+  return -1;
+}
+
 // One launch over fields[0..n) of a plan of `kind` into `dst + dst_off`: the fields marshalled
 // into gather::multi::Args and the kernel chosen, here alone.
 //   kFields: each field as it would go on its own (select_tile_dim), gather_struct_kernel.
 //   kCast: the same, a converted field through the cast body; gather_cast_kernel, or
 //     gather_quant_kernel when any field is quantised, or gather_affine_kernel when any has a
-//     bias or a per-channel table.  DORA_ERR_INVALID, nothing launched, when a converted field
-//     would not start on a multiple of its destination element size.
+//     bias or a per-channel table.
 //   kReduce: the same, a reduced field through the lane or the wave body (select_reduce_wave);
-//     gather_reduce_kernel.  DORA_ERR_INVALID, nothing launched, when a reduced field would not
-//     start on a multiple of its index element size.
+//     gather_reduce_kernel.
 //   kResize: the same, a resized field through the resize body; gather_resize_kernel.
-//     DORA_ERR_INVALID, nothing launched, when a resized field would not start on a multiple of
-//     its destination element size.
+//   (these three: DORA_ERR_INVALID, nothing launched, when a field with an op, field_op_size,
+//   would not start on a multiple of the size of the elements stored)
 //   kTaken (`take` given): every field through the taken body, never a tile: row i0 of its bytes
 //     is row take->src[i0] of the field, or zeros where that word is not in [0, take->n).
 // With `scan` (a ragged batch's partition in HBM; n may then be 0) one more workgroup of the same
@@ -1134,66 +1180,17 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
     stride0[k] = f.stride0;
     c[k] = kind == PlanLaunch::kCast ? f.cast : CastDesc{};
     rd[k] = kind == PlanLaunch::kReduce ? f.reduce : ReduceDesc{};
-    wave[k] = false;
-    quant |= c[k].quant();
     rs[k] = kind == PlanLaunch::kResize ? f.resize : ResizeDesc{};
-    tile_c[k] = take || c[k].on || rd[k].on || rs[k].on ? -1
-                                                         : select_tile_dim(g[k], dst + off[k]);
-    if (rs[k].on) {
-      // the body's loads are whole source elements, its stores whole destination elements; every
-      // extent it divides by or multiplies fits the statement's 32-bit arithmetic
-      const ResizeDesc& r = rs[k];
-      const unsigned ds = r.dst_bits / 8u;
-      const bool dst_ok = r.dst_code == 2 ? ds == 2 || ds == 4
-                                          : gather::cast::dst_kind(r.dst_code, r.dst_bits) >= 0;
-      bool ok = gather::cast::src_kind(r.src_code, r.src_bits) >= 0 && dst_ok &&
-                (r.mode == DORA_RESIZE_NEAREST || r.mode == DORA_RESIZE_BILINEAR) && r.nd >= 2 &&
-                r.nd <= gather::kDims && r.ax[0] != r.ax[1] &&
-                !(reinterpret_cast<uintptr_t>(f.gd.view.src) & (f.gd.elem - 1));
-      for (int j = 0; ok && j < 2; ++j)
-        ok = r.ax[j] >= 0 && r.ax[j] < r.nd && r.in[j] >= 1 &&
-             r.in[j] <= int64_t(gather::resize::kMaxExtent) && r.shape[r.ax[j]] >= 1 &&
-             r.shape[r.ax[j]] <= int64_t(gather::resize::kMaxExtent);
-      for (int i = 0; ok && i < r.nd; ++i)
-        ok = !(static_cast<uintptr_t>(r.stride[i]) & (f.gd.elem - 1));
-      if (!ok)
-        return fail(DORA_ERR_INVALID, "field %zu `%s`: not a resize this kernel runs", k,
-                    f.name.c_str());
-      if (reinterpret_cast<uintptr_t>(dst + off[k]) & (ds - 1))
-        return fail(DORA_ERR_INVALID, "field %zu `%s`: the resized field would start at %p, not a "
-                    "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
-                    static_cast<void*>(dst + off[k]), ds);
-      continue;
-    }
-    if (rd[k].on) {
-      // the bodies' loads are whole source elements, their stores whole index elements
-      const unsigned ds = gather::reduce::index_size(rd[k].idx_code, rd[k].idx_bits);
-      if (gather::cast::src_kind(rd[k].src_code, rd[k].src_bits) < 0 || !ds || !rd[k].c ||
-          ((reinterpret_cast<uintptr_t>(f.gd.view.src) | static_cast<uintptr_t>(rd[k].cstride)) &
-           (f.gd.elem - 1)))
-        return fail(DORA_ERR_INVALID, "field %zu `%s`: not a reduction this kernel runs", k,
-                    f.name.c_str());
-      if (reinterpret_cast<uintptr_t>(dst + off[k]) & (ds - 1))
-        return fail(DORA_ERR_INVALID, "field %zu `%s`: the reduced field would start at %p, not a "
-                    "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
-                    static_cast<void*>(dst + off[k]), ds);
-      wave[k] = select_reduce_wave(g[k], rd[k]);
-      continue;
-    }
-    if (!c[k].on) continue;
-    // the cast body's stores are whole elements and whole 16-byte units of them
-    const unsigned ds = f.cast.dst_bits / 8u;
-    const bool dst_ok = f.cast.quant()
-                            ? gather::cast::dst_kind(f.cast.dst_code, f.cast.dst_bits) >= 0
-                            : ds == 2 || ds == 4;
-    if (gather::cast::src_kind(f.cast.src_code, f.cast.src_bits) < 0 || !dst_ok ||
-        (reinterpret_cast<uintptr_t>(f.gd.view.src) & (f.gd.elem - 1)))
-      return fail(DORA_ERR_INVALID, "field %zu `%s`: not a cast this kernel runs", k,
-                  f.name.c_str());
-    if (reinterpret_cast<uintptr_t>(dst + off[k]) & (ds - 1))
-      return fail(DORA_ERR_INVALID, "field %zu `%s`: the converted field would start at %p, not a "
-                  "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(),
-                  static_cast<void*>(dst + off[k]), ds);
+    quant |= c[k].quant();
+    const char* noun = nullptr;
+    const int ds = field_op_size(kind, f, k, &noun);
+    if (ds < 0) return DORA_ERR_INVALID;
+    tile_c[k] = take || noun ? -1 : select_tile_dim(g[k], dst + off[k]);
+    if (noun && (reinterpret_cast<uintptr_t>(dst + off[k]) & (static_cast<unsigned>(ds) - 1)))
+      return fail(DORA_ERR_INVALID, "field %zu `%s`: the %s field would start at %p, not a "
+                  "multiple of its %u-byte elements: nothing was launched", k, f.name.c_str(), noun,
+                  static_cast<void*>(dst + off[k]), static_cast<unsigned>(ds));
+    wave[k] = rd[k].on && select_reduce_wave(g[k], rd[k]);
     if (!c[k].affine()) continue;
     affine = true;
     // the channel stepping never leaves [0, channels) of a table of whole dwords

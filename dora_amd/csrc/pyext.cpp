@@ -251,128 +251,211 @@ struct DlManaged {
   void (*deleter)(DlManaged*);
 };
 
+void to_tensor(const DlTensor& d, dora_tensor& t) {
+  t = dora_tensor{};
+  t.data = d.data;
+  t.byte_offset = d.byte_offset;
+  t.dtype_code = d.code;
+  t.dtype_bits = d.bits;
+  t.dtype_lanes = d.lanes;
+  t.ndim = d.ndim;
+  t.shape = d.shape;
+  t.strides = d.strides;
+}
+
+const char* const kUnused = "a DLPack capsule named \"dltensor\" (an unused, unversioned one)";
+
+// The "dltensor" capsules of one tensor send and what becomes of them, as DLPack prescribes.
+// First every capsule is taken and checked — the fields' (`take`), then whatever else travels
+// with the call (`also`: a partition, an index, a mask; `table`: an affine table), each against
+// all taken before it.  Nothing is touched yet: a call refused for any argument leaves its
+// capsules as they were.  Then `consume` renames each "used_dltensor" and describes its tensor
+// where the taker said.  The destructor runs the deleter of every capsule consumed, once: under
+// the GIL and after the status has been taken, since it runs as the send function returns (a
+// deleter may run Python code: numpy's and torch's drop a reference; it does not disturb the
+// thread's error message, which the caller reads only when the status is not 0 and deleters do
+// not call the library).
+class Capsules {
+ public:
+  std::vector<dora_tensor_field> fields;
+
+  Capsules() = default;
+  Capsules(const Capsules&) = delete;
+  Capsules& operator=(const Capsules&) = delete;
+  ~Capsules() {
+    for (const Item& it : items_)
+      if (it.consumed && it.consumed->deleter) it.consumed->deleter(it.consumed);
+  }
+
+  // The fields: `names` a tuple of str as long as the tuple `caps`, or — `bare_ok` — None over a
+  // tuple of one capsule (a bare tensor: no name); anything else is refused with `usage`.
+  // `numbered`: the call has more capsules than fields, and two that are one are refused by their
+  // numbers among all of them.
+  bool take(PyObject* names, PyObject* caps, const char* usage, bool bare_ok, bool numbered) {
+    if (!PyTuple_Check(caps) ||
+        !(names == Py_None ? bare_ok && PyTuple_GET_SIZE(caps) == 1
+                           : PyTuple_Check(names) &&
+                                 PyTuple_GET_SIZE(names) == PyTuple_GET_SIZE(caps))) {
+      PyErr_SetString(PyExc_TypeError, usage);
+      return false;
+    }
+    const Py_ssize_t n = PyTuple_GET_SIZE(caps);
+    fields.assign(static_cast<size_t>(n), dora_tensor_field{});
+    items_.reserve(static_cast<size_t>(n) + 2);
+    for (Py_ssize_t k = 0; k < n; ++k) {
+      dora_tensor_field& f = fields[size_t(k)];
+      if (names != Py_None && !(f.name = as_cstr(PyTuple_GET_ITEM(names, k)))) return false;
+      PyObject* cap = PyTuple_GET_ITEM(caps, k);
+      if (!PyCapsule_IsValid(cap, "dltensor")) {
+        PyErr_Format(PyExc_TypeError, "field %zd: expected %s", k, kUnused);
+        return false;
+      }
+      if (const Py_ssize_t j = find(cap); j >= 0) {
+        PyErr_Format(PyExc_TypeError, numbered ? "capsules %zd and %zd are one capsule"
+                                               : "fields %zd and %zd share one capsule", j, k);
+        return false;
+      }
+      items_.push_back({cap, &f.tensor, nullptr});
+    }
+    return true;
+  }
+
+  // One more capsule, its tensor described into `*into`; `what` names it in a refusal (NULL: the
+  // one tensor of send_tensor).
+  bool also(PyObject* cap, dora_tensor* into, const char* what) {
+    if (!PyCapsule_IsValid(cap, "dltensor")) {
+      if (what) PyErr_Format(PyExc_TypeError, "%s: expected %s", what, kUnused);
+      else PyErr_Format(PyExc_TypeError, "expected %s", kUnused);
+      return false;
+    }
+    if (const Py_ssize_t j = find(cap); j >= 0) {
+      PyErr_Format(PyExc_TypeError, "capsules %zd and %zd are one capsule", j,
+                   static_cast<Py_ssize_t>(items_.size()));
+      return false;
+    }
+    items_.push_back({cap, into, nullptr});
+    return true;
+  }
+
+  // A per-channel table of field `k`.
+  bool table(PyObject* cap, dora_tensor* into, Py_ssize_t k) {
+    if (!PyCapsule_IsValid(cap, "dltensor")) {
+      PyErr_Format(PyExc_TypeError, "field %zd: a table is %s", k, kUnused);
+      return false;
+    }
+    if (const Py_ssize_t j = find(cap); j >= 0) {
+      PyErr_Format(PyExc_TypeError, size_t(j) < fields.size()
+                                        ? "field %zd: a table shares a field's capsule"
+                                        : "field %zd: two tables share one capsule", k);
+      return false;
+    }
+    items_.push_back({cap, into, nullptr});
+    return true;
+  }
+
+  bool consume() {
+    for (Item& it : items_) {
+      auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(it.cap, "dltensor"));
+      // (cannot fail after the checks above; the capsules renamed so far are released as all are)
+      if (!m || PyCapsule_SetName(it.cap, "used_dltensor") != 0) return false;
+      it.consumed = m;
+      to_tensor(m->t, *it.into);
+    }
+    return true;
+  }
+
+ private:
+  struct Item {
+    PyObject* cap;
+    dora_tensor* into;
+    DlManaged* consumed;  // set once the capsule is renamed: its deleter is then ours to call
+  };
+  Py_ssize_t find(PyObject* cap) const {
+    for (size_t j = 0; j < items_.size(); ++j)
+      if (items_[j].cap == cap) return static_cast<Py_ssize_t>(j);
+    return -1;
+  }
+  std::vector<Item> items_;
+};
+
+// What every tensor send takes beside its tensors: the node, the output id, the device type of
+// the values, the metadata (encoded into t_params) and the flags.
+struct Frame {
+  dora_node* node;
+  const char* oid;
+  ArrowDeviceType dev;
+  const uint8_t* params;
+  size_t params_len;
+  uint32_t flags;
+
+  bool take(PyObject* handle, PyObject* output_id, PyObject* device_type, PyObject* metadata,
+            PyObject* send_flags) {
+    void* h = nullptr;
+    if (!as_ptr(handle, &h) || !(oid = as_cstr(output_id))) return false;
+    node = static_cast<dora_node*>(h);
+    const long d = PyLong_AsLong(device_type);
+    if (d == -1 && PyErr_Occurred()) return false;
+    dev = static_cast<ArrowDeviceType>(d);
+    const unsigned long f = PyLong_AsUnsignedLong(send_flags);
+    if (f == static_cast<unsigned long>(-1) && PyErr_Occurred()) return false;
+    flags = static_cast<uint32_t>(f);
+    if (!encode(metadata, t_params)) return false;
+    params = reinterpret_cast<const uint8_t*>(t_params.data());
+    params_len = t_params.size();
+    return true;
+  }
+};
+
+// Whether `entries` is a tuple as long as the tuple `caps`.
+bool as_long(PyObject* entries, PyObject* caps) {
+  return PyTuple_Check(entries) && PyTuple_Check(caps) &&
+         PyTuple_GET_SIZE(entries) == PyTuple_GET_SIZE(caps);
+}
+
 // send_tensor(handle, output_id, capsule, device_type, metadata, flags) -> status: the tensor of
 // a "dltensor" capsule (an object's __dlpack__()) as dora_node_send_output_tensor.  The capsule
-// is consumed as DLPack prescribes: renamed "used_dltensor", its deleter called once the call
-// has returned (a host source has then been read).
+// is consumed (Capsules): renamed "used_dltensor", its deleter called once the call has returned
+// (a host source has then been read).
 PyObject* py_send_tensor(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   if (nargs != 6) {
     PyErr_SetString(PyExc_TypeError,
                     "send_tensor(handle, output_id, capsule, device_type, metadata, flags)");
     return nullptr;
   }
-  void* h = nullptr;
-  if (!as_ptr(args[0], &h)) return nullptr;
-  const char* oid = as_cstr(args[1]);
-  if (!oid) return nullptr;
-  if (!PyCapsule_IsValid(args[2], "dltensor")) {
-    PyErr_SetString(PyExc_TypeError, "expected a DLPack capsule named \"dltensor\" (an unused, "
-                                     "unversioned one)");
+  Capsules caps;
+  Frame f;
+  dora_tensor t;
+  if (!caps.also(args[2], &t, nullptr) || !f.take(args[0], args[1], args[3], args[4], args[5]) ||
+      !caps.consume())
     return nullptr;
-  }
-  const long dev = PyLong_AsLong(args[3]);
-  if (dev == -1 && PyErr_Occurred()) return nullptr;
-  const unsigned long flags = PyLong_AsUnsignedLong(args[5]);
-  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
-  std::string& params = t_params;
-  if (!encode(args[4], params)) return nullptr;
-  auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(args[2], "dltensor"));
-  if (!m || PyCapsule_SetName(args[2], "used_dltensor") != 0) return nullptr;
-  dora_tensor t{};
-  t.data = m->t.data;
-  t.byte_offset = m->t.byte_offset;
-  t.dtype_code = m->t.code;
-  t.dtype_bits = m->t.bits;
-  t.dtype_lanes = m->t.lanes;
-  t.ndim = m->t.ndim;
-  t.shape = m->t.shape;
-  t.strides = m->t.strides;
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  rc = dora_node_send_output_tensor(static_cast<dora_node*>(h), oid, &t,
-                                    static_cast<ArrowDeviceType>(dev),
-                                    reinterpret_cast<const uint8_t*>(params.data()), params.size(),
-                                    static_cast<uint32_t>(flags));
+  rc = dora_node_send_output_tensor(f.node, f.oid, &t, f.dev, f.params, f.params_len, f.flags);
   Py_END_ALLOW_THREADS
-  // the deleter may run Python code (numpy's, torch's drop a reference): under the GIL, and
-  // after the status has been taken (it must not disturb the thread's error message either:
-  // the caller reads dora_gpu_last_error only when rc != 0, and deleters do not call the library)
-  if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 
 // send_tensor_struct(handle, output_id, names, capsules, device_type, metadata, flags) -> status:
 // the tensors of a tuple of "dltensor" capsules under a tuple of names as
 // dora_node_send_output_tensor_struct.  Every capsule is consumed the way send_tensor consumes
-// its one: all are checked first (a refused argument leaves them untouched), then renamed, and
-// their deleters run once the call has returned.
+// its one.
 PyObject* py_send_tensor_struct(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
-  if (nargs != 7 || !PyTuple_Check(args[2]) || !PyTuple_Check(args[3]) ||
-      PyTuple_GET_SIZE(args[2]) != PyTuple_GET_SIZE(args[3])) {
-    PyErr_SetString(PyExc_TypeError, "send_tensor_struct(handle, output_id, names, capsules, "
-                                     "device_type, metadata, flags): names and capsules are "
-                                     "tuples of one length");
+  const char* usage = "send_tensor_struct(handle, output_id, names, capsules, device_type, "
+                      "metadata, flags): names and capsules are tuples of one length";
+  if (nargs != 7) {
+    PyErr_SetString(PyExc_TypeError, usage);
     return nullptr;
   }
-  void* h = nullptr;
-  if (!as_ptr(args[0], &h)) return nullptr;
-  const char* oid = as_cstr(args[1]);
-  if (!oid) return nullptr;
-  const Py_ssize_t n = PyTuple_GET_SIZE(args[2]);
-  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
-  std::vector<DlManaged*> managed(static_cast<size_t>(n));
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
-    if (!fields[size_t(k)].name) return nullptr;
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    if (!PyCapsule_IsValid(cap, "dltensor")) {
-      PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
-                                    "unused, unversioned one)", k);
-      return nullptr;
-    }
-    for (Py_ssize_t j = 0; j < k; ++j)
-      if (PyTuple_GET_ITEM(args[3], j) == cap) {
-        PyErr_Format(PyExc_TypeError, "fields %zd and %zd share one capsule", j, k);
-        return nullptr;
-      }
-  }
-  const long dev = PyLong_AsLong(args[4]);
-  if (dev == -1 && PyErr_Occurred()) return nullptr;
-  const unsigned long flags = PyLong_AsUnsignedLong(args[6]);
-  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
-  std::string& params = t_params;
-  if (!encode(args[5], params)) return nullptr;
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
-    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
-      // (cannot happen after the checks above; the capsules renamed so far are released)
-      for (Py_ssize_t j = 0; j < k; ++j)
-        if (managed[size_t(j)]->deleter) managed[size_t(j)]->deleter(managed[size_t(j)]);
-      return nullptr;
-    }
-    managed[size_t(k)] = m;
-    dora_tensor& t = fields[size_t(k)].tensor;
-    t = dora_tensor{};
-    t.data = m->t.data;
-    t.byte_offset = m->t.byte_offset;
-    t.dtype_code = m->t.code;
-    t.dtype_bits = m->t.bits;
-    t.dtype_lanes = m->t.lanes;
-    t.ndim = m->t.ndim;
-    t.shape = m->t.shape;
-    t.strides = m->t.strides;
-  }
+  Capsules caps;
+  Frame f;
+  if (!caps.take(args[2], args[3], usage, false, false) ||
+      !f.take(args[0], args[1], args[4], args[5], args[6]) || !caps.consume())
+    return nullptr;
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  rc = dora_node_send_output_tensor_struct(static_cast<dora_node*>(h), oid, fields.data(),
-                                           fields.size(), static_cast<ArrowDeviceType>(dev),
-                                           reinterpret_cast<const uint8_t*>(params.data()),
-                                           params.size(), static_cast<uint32_t>(flags));
+  rc = dora_node_send_output_tensor_struct(f.node, f.oid, caps.fields.data(), caps.fields.size(),
+                                           f.dev, f.params, f.params_len, f.flags);
   Py_END_ALLOW_THREADS
-  // (deleters under the GIL and after the status has been taken, as in send_tensor)
-  for (DlManaged* m : managed)
-    if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 
@@ -396,48 +479,18 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
         "tuple of capsules; casts a tuple as long, of None or (code, bits, scale)";
   // (send_tensor_convert alone: a ninth argument, the affine entries)
   const bool with_affine = convert && nargs == 9;
-  if (with_affine && !(PyTuple_Check(args[8]) && PyTuple_Check(args[3]) &&
-                       PyTuple_GET_SIZE(args[8]) == PyTuple_GET_SIZE(args[3]))) {
+  if ((nargs != 8 && !with_affine) || !as_long(args[4], args[3]) ||
+      (with_affine && !as_long(args[8], args[3]))) {
     PyErr_SetString(PyExc_TypeError, usage);
     return nullptr;
   }
-  if ((nargs != 8 && !with_affine) || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
-      PyTuple_GET_SIZE(args[4]) != PyTuple_GET_SIZE(args[3]) ||
-      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
-                           : PyTuple_Check(args[2]) &&
-                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
-    PyErr_SetString(PyExc_TypeError, usage);
-    return nullptr;
-  }
-  void* h = nullptr;
-  if (!as_ptr(args[0], &h)) return nullptr;
-  const char* oid = as_cstr(args[1]);
-  if (!oid) return nullptr;
-  const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
-  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
-  std::vector<dora_tensor_cast> casts(static_cast<size_t>(n));
-  std::vector<dora_tensor_quant> quants(convert ? static_cast<size_t>(n) : 0);
-  std::vector<DlManaged*> managed(static_cast<size_t>(n));
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    fields[size_t(k)].name = nullptr;
-    if (args[2] != Py_None) {
-      fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
-      if (!fields[size_t(k)].name) return nullptr;
-    }
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    if (!PyCapsule_IsValid(cap, "dltensor")) {
-      PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
-                                    "unused, unversioned one)", k);
-      return nullptr;
-    }
-    for (Py_ssize_t j = 0; j < k; ++j)
-      if (PyTuple_GET_ITEM(args[3], j) == cap) {
-        PyErr_Format(PyExc_TypeError, "fields %zd and %zd share one capsule", j, k);
-        return nullptr;
-      }
-    dora_tensor_cast& c = casts[size_t(k)];
-    c = dora_tensor_cast{};
-    PyObject* entry = PyTuple_GET_ITEM(args[4], k);
+  Capsules caps;
+  if (!caps.take(args[2], args[3], usage, true, false)) return nullptr;
+  const size_t n = caps.fields.size();
+  std::vector<dora_tensor_cast> casts(n);
+  std::vector<dora_tensor_quant> quants(convert ? n : 0);
+  for (size_t k = 0; k < n; ++k) {
+    PyObject* entry = PyTuple_GET_ITEM(args[4], Py_ssize_t(k));
     if (entry == Py_None) continue;
     if (!PyTuple_Check(entry) ||
         !(PyTuple_GET_SIZE(entry) == 3 || (convert && PyTuple_GET_SIZE(entry) == 4))) {
@@ -449,7 +502,7 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
     const long bits = PyLong_AsLong(PyTuple_GET_ITEM(entry, 1));
     if (PyErr_Occurred()) return nullptr;
     if (code < 0 || code > 255 || bits < 1 || bits > 255) {
-      PyErr_Format(PyExc_TypeError, "field %zd: cast dtype (code %ld, %ld bits)", k, code, bits);
+      PyErr_Format(PyExc_TypeError, "field %zu: cast dtype (code %ld, %ld bits)", k, code, bits);
       return nullptr;
     }
     PyObject* scale = PyTuple_GET_ITEM(entry, 2);
@@ -462,11 +515,10 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
       const long zp = PyLong_AsLong(PyTuple_GET_ITEM(entry, 3));
       if (zp == -1 && PyErr_Occurred()) return nullptr;
       if (zp < INT32_MIN || zp > INT32_MAX) {
-        PyErr_Format(PyExc_TypeError, "field %zd: zero point %ld", k, zp);
+        PyErr_Format(PyExc_TypeError, "field %zu: zero point %ld", k, zp);
         return nullptr;
       }
-      dora_tensor_quant& q = quants[size_t(k)];
-      q = dora_tensor_quant{};
+      dora_tensor_quant& q = quants[k];
       q.dtype_code = static_cast<uint8_t>(code);
       q.dtype_bits = static_cast<uint8_t>(bits);
       q.has_scale = scale != Py_None;
@@ -474,6 +526,7 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
       q.zero_point = static_cast<int32_t>(zp);
       continue;
     }
+    dora_tensor_cast& c = casts[k];
     c.dtype_code = static_cast<uint8_t>(code);
     c.dtype_bits = static_cast<uint8_t>(bits);
     if (scale != Py_None) {
@@ -483,113 +536,54 @@ PyObject* send_converted(PyObject* const* args, Py_ssize_t nargs, bool convert) 
   }
   // the affine entries: None, or (scale table capsule or None, bias table capsule or None, axis,
   // scalar bias or None); the tables' capsules are consumed with the fields'
-  std::vector<dora_tensor_affine> affines(with_affine ? static_cast<size_t>(n) : 0);
-  std::vector<dora_tensor> tables(with_affine ? 2 * static_cast<size_t>(n) : 0);
-  std::vector<std::pair<PyObject*, size_t>> table_caps;  // (capsule, index into `tables`)
-  for (Py_ssize_t k = 0; with_affine && k < n; ++k) {
-    affines[size_t(k)] = dora_tensor_affine{};
-    PyObject* entry = PyTuple_GET_ITEM(args[8], k);
+  std::vector<dora_tensor_affine> affines(with_affine ? n : 0);
+  std::vector<dora_tensor> tables(with_affine ? 2 * n : 0);  // field k's scale, then its bias
+  for (size_t k = 0; with_affine && k < n; ++k) {
+    PyObject* entry = PyTuple_GET_ITEM(args[8], Py_ssize_t(k));
     if (entry == Py_None) continue;
     if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 4) {
-      PyErr_Format(PyExc_TypeError, "field %zd: an affine entry is None or (scale table, bias "
+      PyErr_Format(PyExc_TypeError, "field %zu: an affine entry is None or (scale table, bias "
                                     "table, axis, bias)", k);
       return nullptr;
     }
-    for (int w = 0; w < 2; ++w) {
-      PyObject* cap = PyTuple_GET_ITEM(entry, w);
+    dora_tensor_affine& a = affines[k];
+    for (size_t w = 0; w < 2; ++w) {
+      PyObject* cap = PyTuple_GET_ITEM(entry, Py_ssize_t(w));
       if (cap == Py_None) continue;
-      if (!PyCapsule_IsValid(cap, "dltensor")) {
-        PyErr_Format(PyExc_TypeError, "field %zd: a table is a DLPack capsule named \"dltensor\" "
-                                      "(an unused, unversioned one)", k);
-        return nullptr;
-      }
-      for (const auto& seen : table_caps)
-        if (seen.first == cap) {
-          PyErr_Format(PyExc_TypeError, "field %zd: two tables share one capsule", k);
-          return nullptr;
-        }
-      for (Py_ssize_t j = 0; j < n; ++j)
-        if (PyTuple_GET_ITEM(args[3], j) == cap) {
-          PyErr_Format(PyExc_TypeError, "field %zd: a table shares a field's capsule", k);
-          return nullptr;
-        }
-      table_caps.emplace_back(cap, 2 * size_t(k) + size_t(w));
+      if (!caps.table(cap, &tables[2 * k + w], Py_ssize_t(k))) return nullptr;
+      (w ? a.bias : a.scale) = &tables[2 * k + w];
     }
     const long axis = PyLong_AsLong(PyTuple_GET_ITEM(entry, 2));
     if (axis == -1 && PyErr_Occurred()) return nullptr;
     if (axis < INT32_MIN || axis > INT32_MAX) {
-      PyErr_Format(PyExc_TypeError, "field %zd: axis %ld", k, axis);
+      PyErr_Format(PyExc_TypeError, "field %zu: axis %ld", k, axis);
       return nullptr;
     }
-    affines[size_t(k)].axis = static_cast<int32_t>(axis);
+    a.axis = static_cast<int32_t>(axis);
     PyObject* bias = PyTuple_GET_ITEM(entry, 3);
     if (bias != Py_None) {
       const double b = PyFloat_AsDouble(bias);
       if (b == -1.0 && PyErr_Occurred()) return nullptr;
-      affines[size_t(k)].has_bias = 1;
-      affines[size_t(k)].bias_value = static_cast<float>(b);
+      a.has_bias = 1;
+      a.bias_value = static_cast<float>(b);
     }
   }
-  const long dev = PyLong_AsLong(args[5]);
-  if (dev == -1 && PyErr_Occurred()) return nullptr;
-  const unsigned long flags = PyLong_AsUnsignedLong(args[7]);
-  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
-  std::string& params = t_params;
-  if (!encode(args[6], params)) return nullptr;
-  auto describe = [](const DlManaged* m, dora_tensor& t) {
-    t = dora_tensor{};
-    t.data = m->t.data;
-    t.byte_offset = m->t.byte_offset;
-    t.dtype_code = m->t.code;
-    t.dtype_bits = m->t.bits;
-    t.dtype_lanes = m->t.lanes;
-    t.ndim = m->t.ndim;
-    t.shape = m->t.shape;
-    t.strides = m->t.strides;
-  };
-  for (Py_ssize_t k = 0; k < n + static_cast<Py_ssize_t>(table_caps.size()); ++k) {
-    PyObject* cap = k < n ? PyTuple_GET_ITEM(args[3], k) : table_caps[size_t(k - n)].first;
-    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
-    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
-      // (cannot happen after the checks above; the capsules renamed so far are released)
-      for (DlManaged* r : managed)
-        if (r && r->deleter) r->deleter(r);
-      return nullptr;
-    }
-    if (k < n) {
-      managed[size_t(k)] = m;
-      describe(m, fields[size_t(k)].tensor);
-      continue;
-    }
-    managed.push_back(m);
-    const size_t at = table_caps[size_t(k - n)].second;
-    describe(m, tables[at]);
-    (at % 2 ? affines[at / 2].bias : affines[at / 2].scale) = &tables[at];
-  }
+  Frame f;
+  if (!f.take(args[0], args[1], args[5], args[6], args[7]) || !caps.consume()) return nullptr;
   int rc;
   Py_BEGIN_ALLOW_THREADS
   if (with_affine)
-    rc = dora_node_send_output_tensor_affine(static_cast<dora_node*>(h), oid, fields.data(),
-                                             fields.size(), casts.data(), quants.data(),
-                                             affines.data(), static_cast<ArrowDeviceType>(dev),
-                                             reinterpret_cast<const uint8_t*>(params.data()),
-                                             params.size(), static_cast<uint32_t>(flags));
+    rc = dora_node_send_output_tensor_affine(f.node, f.oid, caps.fields.data(), n, casts.data(),
+                                             quants.data(), affines.data(), f.dev, f.params,
+                                             f.params_len, f.flags);
   else if (convert)
-    rc = dora_node_send_output_tensor_convert(static_cast<dora_node*>(h), oid, fields.data(),
-                                              fields.size(), casts.data(), quants.data(),
-                                              static_cast<ArrowDeviceType>(dev),
-                                              reinterpret_cast<const uint8_t*>(params.data()),
-                                              params.size(), static_cast<uint32_t>(flags));
+    rc = dora_node_send_output_tensor_convert(f.node, f.oid, caps.fields.data(), n, casts.data(),
+                                              quants.data(), f.dev, f.params, f.params_len,
+                                              f.flags);
   else
-    rc = dora_node_send_output_tensor_cast(static_cast<dora_node*>(h), oid, fields.data(),
-                                           fields.size(), casts.data(),
-                                           static_cast<ArrowDeviceType>(dev),
-                                           reinterpret_cast<const uint8_t*>(params.data()),
-                                           params.size(), static_cast<uint32_t>(flags));
+    rc = dora_node_send_output_tensor_cast(f.node, f.oid, caps.fields.data(), n, casts.data(),
+                                           f.dev, f.params, f.params_len, f.flags);
   Py_END_ALLOW_THREADS
-  // (deleters under the GIL and after the status has been taken, as in send_tensor)
-  for (DlManaged* m : managed)
-    if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 
@@ -610,42 +604,16 @@ PyObject* py_send_tensor_reduce(PyObject*, PyObject* const* args, Py_ssize_t nar
       "send_tensor_reduce(handle, output_id, names, capsules, reduces, device_type, metadata, "
       "flags): names is None over one capsule or a tuple as long as the tuple of capsules; "
       "reduces a tuple as long, of None or (op, axis, code, bits)";
-  if (nargs != 8 || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
-      PyTuple_GET_SIZE(args[4]) != PyTuple_GET_SIZE(args[3]) ||
-      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
-                           : PyTuple_Check(args[2]) &&
-                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+  if (nargs != 8 || !as_long(args[4], args[3])) {
     PyErr_SetString(PyExc_TypeError, usage);
     return nullptr;
   }
-  void* h = nullptr;
-  if (!as_ptr(args[0], &h)) return nullptr;
-  const char* oid = as_cstr(args[1]);
-  if (!oid) return nullptr;
-  const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
-  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
-  std::vector<dora_tensor_reduce> reduces(static_cast<size_t>(n));
-  std::vector<DlManaged*> managed(static_cast<size_t>(n));
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    fields[size_t(k)].name = nullptr;
-    if (args[2] != Py_None) {
-      fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
-      if (!fields[size_t(k)].name) return nullptr;
-    }
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    if (!PyCapsule_IsValid(cap, "dltensor")) {
-      PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
-                                    "unused, unversioned one)", k);
-      return nullptr;
-    }
-    for (Py_ssize_t j = 0; j < k; ++j)
-      if (PyTuple_GET_ITEM(args[3], j) == cap) {
-        PyErr_Format(PyExc_TypeError, "fields %zd and %zd share one capsule", j, k);
-        return nullptr;
-      }
-    dora_tensor_reduce& r = reduces[size_t(k)];
-    r = dora_tensor_reduce{};
-    PyObject* entry = PyTuple_GET_ITEM(args[4], k);
+  Capsules caps;
+  if (!caps.take(args[2], args[3], usage, true, false)) return nullptr;
+  const size_t n = caps.fields.size();
+  std::vector<dora_tensor_reduce> reduces(n);
+  for (size_t k = 0; k < n; ++k) {
+    PyObject* entry = PyTuple_GET_ITEM(args[4], Py_ssize_t(k));
     if (entry == Py_None) continue;
     if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 4) {
       PyErr_SetString(PyExc_TypeError, usage);
@@ -658,102 +626,46 @@ PyObject* py_send_tensor_reduce(PyObject*, PyObject* const* args, Py_ssize_t nar
     if (PyErr_Occurred()) return nullptr;
     if (op < 1 || op > INT32_MAX || axis < INT32_MIN || axis > INT32_MAX || code < 0 ||
         code > 255 || bits < 1 || bits > 255) {
-      PyErr_Format(PyExc_TypeError, "field %zd: reduce entry (op %ld, axis %ld, code %ld, %ld "
+      PyErr_Format(PyExc_TypeError, "field %zu: reduce entry (op %ld, axis %ld, code %ld, %ld "
                                     "bits)", k, op, axis, code, bits);
       return nullptr;
     }
+    dora_tensor_reduce& r = reduces[k];
     r.op = static_cast<uint32_t>(op);
     r.axis = static_cast<int32_t>(axis);
     r.dtype_code = static_cast<uint8_t>(code);
     r.dtype_bits = static_cast<uint8_t>(bits);
   }
-  const long dev = PyLong_AsLong(args[5]);
-  if (dev == -1 && PyErr_Occurred()) return nullptr;
-  const unsigned long flags = PyLong_AsUnsignedLong(args[7]);
-  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
-  std::string& params = t_params;
-  if (!encode(args[6], params)) return nullptr;
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
-    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
-      // (cannot happen after the checks above; the capsules renamed so far are released)
-      for (Py_ssize_t j = 0; j < k; ++j)
-        if (managed[size_t(j)]->deleter) managed[size_t(j)]->deleter(managed[size_t(j)]);
-      return nullptr;
-    }
-    managed[size_t(k)] = m;
-    dora_tensor& t = fields[size_t(k)].tensor;
-    t = dora_tensor{};
-    t.data = m->t.data;
-    t.byte_offset = m->t.byte_offset;
-    t.dtype_code = m->t.code;
-    t.dtype_bits = m->t.bits;
-    t.dtype_lanes = m->t.lanes;
-    t.ndim = m->t.ndim;
-    t.shape = m->t.shape;
-    t.strides = m->t.strides;
-  }
+  Frame f;
+  if (!f.take(args[0], args[1], args[5], args[6], args[7]) || !caps.consume()) return nullptr;
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  rc = dora_node_send_output_tensor_reduce(static_cast<dora_node*>(h), oid, fields.data(),
-                                           fields.size(), reduces.data(),
-                                           static_cast<ArrowDeviceType>(dev),
-                                           reinterpret_cast<const uint8_t*>(params.data()),
-                                           params.size(), static_cast<uint32_t>(flags));
+  rc = dora_node_send_output_tensor_reduce(f.node, f.oid, caps.fields.data(), n, reduces.data(),
+                                           f.dev, f.params, f.params_len, f.flags);
   Py_END_ALLOW_THREADS
-  // (deleters under the GIL and after the status has been taken, as in send_tensor)
-  for (DlManaged* m : managed)
-    if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 
 // send_tensor_resize(handle, output_id, names, capsules, resizes, device_type, metadata, flags)
 // -> status: tensors resized on send as dora_node_send_output_tensor_resize.  `names` / `capsules`
 // as send_tensor_cast takes them; `resizes` a tuple as long, each entry None (the field is sent as
-// it is) or (mode, axis0, axis1, size0, size1, dtype_code, dtype_bits).  Every capsule is consumed as send_tensor_struct
-// consumes its own.
+// it is) or (mode, axis0, axis1, size0, size1, dtype_code, dtype_bits).  Every capsule is consumed
+// as send_tensor_struct consumes its own.
 PyObject* py_send_tensor_resize(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   const char* usage =
       "send_tensor_resize(handle, output_id, names, capsules, resizes, device_type, metadata, "
       "flags): names is None over one capsule or a tuple as long as the tuple of capsules; "
       "resizes a tuple as long, of None or (mode, axis0, axis1, size0, size1, code, bits)";
-  if (nargs != 8 || !PyTuple_Check(args[3]) || !PyTuple_Check(args[4]) ||
-      PyTuple_GET_SIZE(args[4]) != PyTuple_GET_SIZE(args[3]) ||
-      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
-                           : PyTuple_Check(args[2]) &&
-                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+  if (nargs != 8 || !as_long(args[4], args[3])) {
     PyErr_SetString(PyExc_TypeError, usage);
     return nullptr;
   }
-  void* h = nullptr;
-  if (!as_ptr(args[0], &h)) return nullptr;
-  const char* oid = as_cstr(args[1]);
-  if (!oid) return nullptr;
-  const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
-  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
-  std::vector<dora_tensor_resize> resizes(static_cast<size_t>(n));
-  std::vector<DlManaged*> managed(static_cast<size_t>(n));
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    fields[size_t(k)].name = nullptr;
-    if (args[2] != Py_None) {
-      fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
-      if (!fields[size_t(k)].name) return nullptr;
-    }
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    if (!PyCapsule_IsValid(cap, "dltensor")) {
-      PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
-                                    "unused, unversioned one)", k);
-      return nullptr;
-    }
-    for (Py_ssize_t j = 0; j < k; ++j)
-      if (PyTuple_GET_ITEM(args[3], j) == cap) {
-        PyErr_Format(PyExc_TypeError, "fields %zd and %zd share one capsule", j, k);
-        return nullptr;
-      }
-    dora_tensor_resize& r = resizes[size_t(k)];
-    r = dora_tensor_resize{};
-    PyObject* entry = PyTuple_GET_ITEM(args[4], k);
+  Capsules caps;
+  if (!caps.take(args[2], args[3], usage, true, false)) return nullptr;
+  const size_t n = caps.fields.size();
+  std::vector<dora_tensor_resize> resizes(n);
+  for (size_t k = 0; k < n; ++k) {
+    PyObject* entry = PyTuple_GET_ITEM(args[4], Py_ssize_t(k));
     if (entry == Py_None) continue;
     if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 7) {
       PyErr_SetString(PyExc_TypeError, usage);
@@ -765,10 +677,11 @@ PyObject* py_send_tensor_resize(PyObject*, PyObject* const* args, Py_ssize_t nar
     if (w[0] < 1 || w[0] > INT32_MAX || w[1] < INT32_MIN || w[1] > INT32_MAX ||
         w[2] < INT32_MIN || w[2] > INT32_MAX || w[5] < 0 || w[5] > 255 || w[6] < 0 ||
         w[6] > 255) {
-      PyErr_Format(PyExc_TypeError, "field %zd: resize entry (mode %lld, axes %lld and %lld, "
+      PyErr_Format(PyExc_TypeError, "field %zu: resize entry (mode %lld, axes %lld and %lld, "
                                     "code %lld, %lld bits)", k, w[0], w[1], w[2], w[5], w[6]);
       return nullptr;
     }
+    dora_tensor_resize& r = resizes[k];
     r.mode = static_cast<uint32_t>(w[0]);
     r.axis[0] = static_cast<int32_t>(w[1]);
     r.axis[1] = static_cast<int32_t>(w[2]);
@@ -777,44 +690,13 @@ PyObject* py_send_tensor_resize(PyObject*, PyObject* const* args, Py_ssize_t nar
     r.dtype_code = static_cast<uint8_t>(w[5]);
     r.dtype_bits = static_cast<uint8_t>(w[6]);
   }
-  const long dev = PyLong_AsLong(args[5]);
-  if (dev == -1 && PyErr_Occurred()) return nullptr;
-  const unsigned long flags = PyLong_AsUnsignedLong(args[7]);
-  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
-  std::string& params = t_params;
-  if (!encode(args[6], params)) return nullptr;
-  for (Py_ssize_t k = 0; k < n; ++k) {
-    PyObject* cap = PyTuple_GET_ITEM(args[3], k);
-    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(cap, "dltensor"));
-    if (!m || PyCapsule_SetName(cap, "used_dltensor") != 0) {
-      // (cannot happen after the checks above; the capsules renamed so far are released)
-      for (Py_ssize_t j = 0; j < k; ++j)
-        if (managed[size_t(j)]->deleter) managed[size_t(j)]->deleter(managed[size_t(j)]);
-      return nullptr;
-    }
-    managed[size_t(k)] = m;
-    dora_tensor& t = fields[size_t(k)].tensor;
-    t = dora_tensor{};
-    t.data = m->t.data;
-    t.byte_offset = m->t.byte_offset;
-    t.dtype_code = m->t.code;
-    t.dtype_bits = m->t.bits;
-    t.dtype_lanes = m->t.lanes;
-    t.ndim = m->t.ndim;
-    t.shape = m->t.shape;
-    t.strides = m->t.strides;
-  }
+  Frame f;
+  if (!f.take(args[0], args[1], args[5], args[6], args[7]) || !caps.consume()) return nullptr;
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  rc = dora_node_send_output_tensor_resize(static_cast<dora_node*>(h), oid, fields.data(),
-                                           fields.size(), resizes.data(),
-                                           static_cast<ArrowDeviceType>(dev),
-                                           reinterpret_cast<const uint8_t*>(params.data()),
-                                           params.size(), static_cast<uint32_t>(flags));
+  rc = dora_node_send_output_tensor_resize(f.node, f.oid, caps.fields.data(), n, resizes.data(),
+                                           f.dev, f.params, f.params_len, f.flags);
   Py_END_ALLOW_THREADS
-  // (deleters under the GIL and after the status has been taken, as in send_tensor)
-  for (DlManaged* m : managed)
-    if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 
@@ -822,97 +704,35 @@ PyObject* py_send_tensor_resize(PyObject*, PyObject* const* args, Py_ssize_t nar
 // device_type, metadata, flags) -> status: a ragged batch as dora_node_send_output_tensor_list.
 // `names` is a tuple of str over the tuple `capsules`, or None over a tuple of one capsule (a bare
 // tensor); `partition` a "dltensor" capsule of the 1-D lengths or offsets.  Every capsule, the
-// partition's included, is consumed as send_tensor_struct consumes its own: all checked first,
-// then renamed, their deleters run once the call has returned.
+// partition's included, is consumed as send_tensor_struct consumes its own.
 PyObject* py_send_tensor_list(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   const char* usage = "send_tensor_list(handle, output_id, names, capsules, partition, form, "
                       "partition_device, device_type, metadata, flags): names is None over one "
                       "capsule or a tuple as long as the tuple of capsules";
-  if (nargs != 10 || !PyTuple_Check(args[3]) ||
-      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
-                           : PyTuple_Check(args[2]) &&
-                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+  if (nargs != 10) {
     PyErr_SetString(PyExc_TypeError, usage);
     return nullptr;
   }
-  void* h = nullptr;
-  if (!as_ptr(args[0], &h)) return nullptr;
-  const char* oid = as_cstr(args[1]);
-  if (!oid) return nullptr;
-  const Py_ssize_t n = PyTuple_GET_SIZE(args[3]);
-  std::vector<dora_tensor_field> fields(static_cast<size_t>(n));
-  std::vector<PyObject*> caps(static_cast<size_t>(n) + 1);
-  for (Py_ssize_t k = 0; k <= n; ++k) {
-    PyObject* cap = k < n ? PyTuple_GET_ITEM(args[3], k) : args[4];
-    if (k < n) {
-      fields[size_t(k)].name = nullptr;
-      if (args[2] != Py_None) {
-        fields[size_t(k)].name = as_cstr(PyTuple_GET_ITEM(args[2], k));
-        if (!fields[size_t(k)].name) return nullptr;
-      }
-    }
-    if (!PyCapsule_IsValid(cap, "dltensor")) {
-      if (k < n)
-        PyErr_Format(PyExc_TypeError, "field %zd: expected a DLPack capsule named \"dltensor\" (an "
-                                      "unused, unversioned one)", k);
-      else
-        PyErr_SetString(PyExc_TypeError, "partition: expected a DLPack capsule named \"dltensor\" "
-                                         "(an unused, unversioned one)");
-      return nullptr;
-    }
-    for (Py_ssize_t j = 0; j < k; ++j)
-      if (caps[size_t(j)] == cap) {
-        PyErr_Format(PyExc_TypeError, "capsules %zd and %zd are one capsule", j, k);
-        return nullptr;
-      }
-    caps[size_t(k)] = cap;
-  }
+  Capsules caps;
+  dora_tensor_list list{};
+  if (!caps.take(args[2], args[3], usage, true, true) ||
+      !caps.also(args[4], &list.partition, "partition"))
+    return nullptr;
   const long form = PyLong_AsLong(args[5]);
   if (form == -1 && PyErr_Occurred()) return nullptr;
   const long pdev = PyLong_AsLong(args[6]);
   if (pdev == -1 && PyErr_Occurred()) return nullptr;
-  const long dev = PyLong_AsLong(args[7]);
-  if (dev == -1 && PyErr_Occurred()) return nullptr;
-  const unsigned long flags = PyLong_AsUnsignedLong(args[9]);
-  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
-  std::string& params = t_params;
-  if (!encode(args[8], params)) return nullptr;
-  dora_tensor_list list{};
-  std::vector<DlManaged*> managed(caps.size());
-  for (size_t k = 0; k < caps.size(); ++k) {
-    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(caps[k], "dltensor"));
-    if (!m || PyCapsule_SetName(caps[k], "used_dltensor") != 0) {
-      // (cannot happen after the checks above; the capsules renamed so far are released)
-      for (size_t j = 0; j < k; ++j)
-        if (managed[j]->deleter) managed[j]->deleter(managed[j]);
-      return nullptr;
-    }
-    managed[k] = m;
-    dora_tensor& t = k + 1 < caps.size() ? fields[k].tensor : list.partition;
-    t = dora_tensor{};
-    t.data = m->t.data;
-    t.byte_offset = m->t.byte_offset;
-    t.dtype_code = m->t.code;
-    t.dtype_bits = m->t.bits;
-    t.dtype_lanes = m->t.lanes;
-    t.ndim = m->t.ndim;
-    t.shape = m->t.shape;
-    t.strides = m->t.strides;
-  }
-  list.fields = fields.data();
-  list.n = fields.size();
+  Frame f;
+  if (!f.take(args[0], args[1], args[7], args[8], args[9]) || !caps.consume()) return nullptr;
+  list.fields = caps.fields.data();
+  list.n = caps.fields.size();
   list.partition_form = static_cast<uint32_t>(form);
   list.partition_device = static_cast<ArrowDeviceType>(pdev);
   int rc;
   Py_BEGIN_ALLOW_THREADS
-  rc = dora_node_send_output_tensor_list(static_cast<dora_node*>(h), oid, &list,
-                                         static_cast<ArrowDeviceType>(dev),
-                                         reinterpret_cast<const uint8_t*>(params.data()),
-                                         params.size(), static_cast<uint32_t>(flags));
+  rc = dora_node_send_output_tensor_list(f.node, f.oid, &list, f.dev, f.params, f.params_len,
+                                         f.flags);
   Py_END_ALLOW_THREADS
-  // (deleters under the GIL and after the status has been taken, as in send_tensor)
-  for (DlManaged* m : managed)
-    if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 
@@ -933,88 +753,34 @@ PyObject* send_selected(PyObject* const* args, Py_ssize_t nargs, bool masked) {
       : "send_tensor_take(handle, output_id, names, capsules, index, index_device, "
         "partition, form, partition_device, device_type, metadata, flags): names is "
         "None over one capsule or a tuple as long as the tuple of capsules";
-  if (nargs != 12 || !PyTuple_Check(args[3]) ||
-      !(args[2] == Py_None ? PyTuple_GET_SIZE(args[3]) == 1
-                           : PyTuple_Check(args[2]) &&
-                                 PyTuple_GET_SIZE(args[2]) == PyTuple_GET_SIZE(args[3]))) {
+  if (nargs != 12) {
     PyErr_SetString(PyExc_TypeError, usage);
     return nullptr;
   }
-  void* h = nullptr;
-  if (!as_ptr(args[0], &h)) return nullptr;
-  const char* oid = as_cstr(args[1]);
-  if (!oid) return nullptr;
-  const size_t n = static_cast<size_t>(PyTuple_GET_SIZE(args[3]));
   const bool lists = args[6] != Py_None;
-  std::vector<dora_tensor_field> fields(n);
-  std::vector<PyObject*> caps(n + 1 + (lists ? 1 : 0));  // the fields', the index's, the partition's
-  for (size_t k = 0; k < caps.size(); ++k) {
-    PyObject* cap = k < n ? PyTuple_GET_ITEM(args[3], Py_ssize_t(k)) : k == n ? args[4] : args[6];
-    if (k < n) {
-      fields[k].name = nullptr;
-      if (args[2] != Py_None) {
-        fields[k].name = as_cstr(PyTuple_GET_ITEM(args[2], Py_ssize_t(k)));
-        if (!fields[k].name) return nullptr;
-      }
-    }
-    if (!PyCapsule_IsValid(cap, "dltensor")) {
-      if (k < n)
-        PyErr_Format(PyExc_TypeError, "field %zu: expected a DLPack capsule named \"dltensor\" (an "
-                                      "unused, unversioned one)", k);
-      else
-        PyErr_Format(PyExc_TypeError, "%s: expected a DLPack capsule named \"dltensor\" (an "
-                                      "unused, unversioned one)", k == n ? (masked ? "mask" : "index") : "partition");
-      return nullptr;
-    }
-    for (size_t j = 0; j < k; ++j)
-      if (caps[j] == cap) {
-        PyErr_Format(PyExc_TypeError, "capsules %zu and %zu are one capsule", j, k);
-        return nullptr;
-      }
-    caps[k] = cap;
-  }
-  long num[4];  // index_device, form, partition_device, device_type
-  const int where[4] = {5, 7, 8, 9};
-  for (int i = 0; i < 4; ++i) {
-    num[i] = PyLong_AsLong(args[where[i]]);
-    if (num[i] == -1 && PyErr_Occurred()) return nullptr;
-  }
-  const unsigned long flags = PyLong_AsUnsignedLong(args[11]);
-  if (flags == static_cast<unsigned long>(-1) && PyErr_Occurred()) return nullptr;
-  std::string& params = t_params;
-  if (!encode(args[10], params)) return nullptr;
+  Capsules caps;
   dora_tensor_take take{};
   dora_tensor_mask mask{};
   dora_tensor partition{};
-  std::vector<DlManaged*> managed(caps.size());
-  for (size_t k = 0; k < caps.size(); ++k) {
-    auto* m = static_cast<DlManaged*>(PyCapsule_GetPointer(caps[k], "dltensor"));
-    if (!m || PyCapsule_SetName(caps[k], "used_dltensor") != 0) {
-      // (cannot happen after the checks above; the capsules renamed so far are released)
-      for (size_t j = 0; j < k; ++j)
-        if (managed[j]->deleter) managed[j]->deleter(managed[j]);
-      return nullptr;
-    }
-    managed[k] = m;
-    dora_tensor& t = k < n ? fields[k].tensor : k == n ? (masked ? mask.mask : take.index) : partition;
-    t = dora_tensor{};
-    t.data = m->t.data;
-    t.byte_offset = m->t.byte_offset;
-    t.dtype_code = m->t.code;
-    t.dtype_bits = m->t.bits;
-    t.dtype_lanes = m->t.lanes;
-    t.ndim = m->t.ndim;
-    t.shape = m->t.shape;
-    t.strides = m->t.strides;
+  if (!caps.take(args[2], args[3], usage, true, true) ||
+      !(masked ? caps.also(args[4], &mask.mask, "mask") : caps.also(args[4], &take.index, "index")) ||
+      (lists && !caps.also(args[6], &partition, "partition")))
+    return nullptr;
+  long num[3];  // index_device, form, partition_device
+  for (int i = 0; i < 3; ++i) {
+    num[i] = PyLong_AsLong(args[i ? 6 + i : 5]);
+    if (num[i] == -1 && PyErr_Occurred()) return nullptr;
   }
-  take.fields = fields.data();
-  take.n = n;
+  Frame f;
+  if (!f.take(args[0], args[1], args[9], args[10], args[11]) || !caps.consume()) return nullptr;
+  take.fields = caps.fields.data();
+  take.n = caps.fields.size();
   take.index_device = static_cast<ArrowDeviceType>(num[0]);
   take.partition = lists ? &partition : nullptr;
   take.partition_form = static_cast<uint32_t>(num[1]);
   take.partition_device = static_cast<ArrowDeviceType>(num[2]);
-  mask.fields = fields.data();
-  mask.n = n;
+  mask.fields = take.fields;
+  mask.n = take.n;
   mask.mask_device = take.index_device;
   mask.partition = take.partition;
   mask.partition_form = take.partition_form;
@@ -1022,19 +788,12 @@ PyObject* send_selected(PyObject* const* args, Py_ssize_t nargs, bool masked) {
   int rc;
   Py_BEGIN_ALLOW_THREADS
   if (masked)
-    rc = dora_node_send_output_tensor_mask(static_cast<dora_node*>(h), oid, &mask,
-                                           static_cast<ArrowDeviceType>(num[3]),
-                                           reinterpret_cast<const uint8_t*>(params.data()),
-                                           params.size(), static_cast<uint32_t>(flags));
+    rc = dora_node_send_output_tensor_mask(f.node, f.oid, &mask, f.dev, f.params, f.params_len,
+                                           f.flags);
   else
-    rc = dora_node_send_output_tensor_take(static_cast<dora_node*>(h), oid, &take,
-                                           static_cast<ArrowDeviceType>(num[3]),
-                                           reinterpret_cast<const uint8_t*>(params.data()),
-                                           params.size(), static_cast<uint32_t>(flags));
+    rc = dora_node_send_output_tensor_take(f.node, f.oid, &take, f.dev, f.params, f.params_len,
+                                           f.flags);
   Py_END_ALLOW_THREADS
-  // (deleters under the GIL and after the status has been taken, as in send_tensor)
-  for (DlManaged* m : managed)
-    if (m->deleter) m->deleter(m);
   return PyLong_FromLong(rc);
 }
 

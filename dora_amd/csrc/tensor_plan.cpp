@@ -46,6 +46,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <cmath>
@@ -60,13 +61,15 @@ namespace dora {
 
 namespace {
 
-// Row-major walk of the view: one memcpy per row, an odometer over the dimensions.  The source
-// position is kept as an offset from `src` (a negative stride steps below it and back).
-void gather_host(const StridedView& g, uint8_t* dst) {
+// Row-major walk of the view, an odometer over the dimensions: `row(off, done)` once per row,
+// `off` the row's position as an offset from `src` (a negative stride steps below it and back),
+// `done` what the rows before it came to, `step` a row, of `total` in all.
+template <class Row>
+void walk_rows(const StridedView& g, uint64_t total, uint64_t step, Row&& row) {
   int64_t idx[kMaxTensorDims] = {0};
   int64_t off = 0;
-  for (uint64_t done = 0; done < g.total; done += g.row) {
-    std::memcpy(dst + done, g.src + off, g.row);
+  for (uint64_t done = 0; done < total; done += step) {
+    row(off, done);
     for (int k = g.nd - 1; k >= 0; --k) {
       off += g.stride[k];
       if (++idx[k] < g.shape[k]) break;
@@ -76,8 +79,50 @@ void gather_host(const StridedView& g, uint8_t* dst) {
   }
 }
 
+// The view's bytes in row-major order: one memcpy per row.
+void gather_host(const StridedView& g, uint8_t* dst) {
+  walk_rows(g, g.total, g.row,
+            [&](int64_t off, uint64_t done) { std::memcpy(dst + done, g.src + off, g.row); });
+}
+
+// `f(K)` with the source kind `kind` (gather::cast::src_kind, never -1 here) as the compile-time
+// constant `decltype(K)::value`.
+template <class F>
+void with_src_kind(int kind, F&& f) {
+  namespace gc = gather::cast;
+  switch (kind) {
+    case gc::kU8: f(std::integral_constant<uint32_t, gc::kU8>{}); break;
+    case gc::kI8: f(std::integral_constant<uint32_t, gc::kI8>{}); break;
+    case gc::kU16: f(std::integral_constant<uint32_t, gc::kU16>{}); break;
+    case gc::kI16: f(std::integral_constant<uint32_t, gc::kI16>{}); break;
+    case gc::kF16: f(std::integral_constant<uint32_t, gc::kF16>{}); break;
+    case gc::kBF16: f(std::integral_constant<uint32_t, gc::kBF16>{}); break;
+    default: f(std::integral_constant<uint32_t, gc::kF32>{}); break;
+  }
+}
+
 // DLPack type codes (dlpack.h, DLDataTypeCode)
 enum { DL_INT = 0, DL_UINT = 1, DL_FLOAT = 2, DL_BFLOAT = 4, DL_COMPLEX = 5, DL_BOOL = 6 };
+
+// Arrow C format of a leaf of int, uint or float `code` and `bits`; NULL when Arrow has none.
+const char* leaf_of(unsigned code, unsigned bits) {
+  if (code == DL_INT || code == DL_UINT) {
+    const bool u = code == DL_UINT;
+    switch (bits) {
+      case 8: return u ? "C" : "c";
+      case 16: return u ? "S" : "s";
+      case 32: return u ? "I" : "i";
+      case 64: return u ? "L" : "l";
+    }
+  } else if (code == DL_FLOAT) {
+    switch (bits) {
+      case 16: return "e";
+      case 32: return "f";
+      case 64: return "g";
+    }
+  }
+  return nullptr;
+}
 
 // Arrow C format of an accepted dtype; NULL after recording why it is refused.
 const char* leaf_format(const dora_tensor& t) {
@@ -102,21 +147,7 @@ const char* leaf_format(const dora_tensor& t) {
               "as pairs of floats)", bits);
     return nullptr;
   }
-  if (code == DL_INT || code == DL_UINT) {
-    const bool u = code == DL_UINT;
-    switch (bits) {
-      case 8: return u ? "C" : "c";
-      case 16: return u ? "S" : "s";
-      case 32: return u ? "I" : "i";
-      case 64: return u ? "L" : "l";
-    }
-  } else if (code == DL_FLOAT) {
-    switch (bits) {
-      case 16: return "e";
-      case 32: return "f";
-      case 64: return "g";
-    }
-  }
+  if (const char* leaf = leaf_of(code, bits)) return leaf;
   set_error("tensor dtype (code %u, %u bits) is not supported: int and uint of 8/16/32/64 bits "
             "and float of 16/32/64 bits are", code, bits);
   return nullptr;
@@ -286,6 +317,18 @@ int describe_tensor(const dora_tensor* t, ArrowDeviceType dev, TensorView& out,
   return DORA_OK;
 }
 
+// The reach of `g` over `steps` more positions `stride` bytes apart along one more axis (the
+// rows of a take, the candidates of a reduction); refused when it leaves int64, as `reach` does.
+int extend_reach(GatherDesc& g, int64_t steps, int64_t stride) {
+  int64_t span, width;
+  if (__builtin_mul_overflow(steps, stride, &span) ||
+      __builtin_add_overflow(span < 0 ? g.lo : g.hi, span, span < 0 ? &g.lo : &g.hi) ||
+      __builtin_sub_overflow(g.hi, g.lo, &width))
+    return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
+                "stride, summed over its dimensions)");
+  return DORA_OK;
+}
+
 // A field of a take (dora_gpu_plan_tensor_take): `k` rows taken along dimension 0 of `t`.
 // Dimensions 1.. are described as a tensor of their own — validated, canonicalised, an innermost
 // unit stride folded into the row — while dimension 0 keeps its entry, extent N and `*stride0`
@@ -329,14 +372,7 @@ int describe_taken(const dora_tensor& t, ArrowDeviceType dev, uint64_t k, Tensor
     out.gd.hi = -1;
     return DORA_OK;
   }
-  int64_t span, width;
-  GatherDesc& g = out.gd;
-  if (__builtin_mul_overflow(rows - 1, *stride0, &span) ||
-      __builtin_add_overflow(span < 0 ? g.lo : g.hi, span, span < 0 ? &g.lo : &g.hi) ||
-      __builtin_sub_overflow(g.hi, g.lo, &width))
-    return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
-                "stride, summed over its dimensions)");
-  return DORA_OK;
+  return extend_reach(out.gd, rows - 1, *stride0);
 }
 
 // A dtype by name, for refusals.
@@ -346,6 +382,32 @@ std::string dtype_name(unsigned code, unsigned bits, unsigned lanes) {
   if (code != DL_BOOL) s += std::to_string(bits);
   if (lanes != 1) s += "x" + std::to_string(lanes);
   return s;
+}
+
+// Whether an op (`noun`: cast, quantise, argmax, resize) reads elements of `t`'s dtype; the
+// refusal naming it otherwise.  Every op ranks it among its entry's own refusals, so it stands
+// apart from describe_source.
+int check_source_dtype(const dora_tensor& t, const char* noun) {
+  if (t.dtype_lanes == 1 && gather::cast::src_kind(t.dtype_code, t.dtype_bits) >= 0)
+    return DORA_OK;
+  return fail(DORA_ERR_UNSUPPORTED, "%s source dtype %s is not supported: uint8, int8, uint16, "
+              "int16, float16, bfloat16 and float32 are", noun,
+              dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+}
+
+// The view `v` of what an op (`noun`) reads of `t`, a tensor of an accepted source dtype: any
+// accepted dtype of the source's width describes it (Arrow has no bfloat16, and the leaf is the
+// destination's anyway), and the op's loads are whole elements.
+int describe_source(const dora_tensor& t, const char* noun, ArrowDeviceType dev, TensorView& v) {
+  dora_tensor src = t;
+  src.dtype_code = DL_UINT;
+  const int rc = describe_tensor(&src, dev, v);
+  if (rc != DORA_OK) return rc;
+  const unsigned ss = t.dtype_bits / 8u;
+  if (v.bytes && (reinterpret_cast<uintptr_t>(v.gd.view.src) & (ss - 1)))
+    return fail(DORA_ERR_INVALID, "%s source data %p (data + byte_offset) is not a multiple of "
+                "its %u-byte elements", noun, static_cast<const void*>(v.gd.view.src), ss);
+  return DORA_OK;
 }
 
 // Whether `c` converts `t` at all: dtype_bits == 0 and a destination equal to the source without
@@ -362,10 +424,7 @@ int describe_cast(const dora_tensor& t, const dora_tensor_cast& c, CastDesc& out
                 dtype_name(c.dtype_code, c.dtype_bits, 1).c_str());
   if (c.has_scale && !std::isfinite(c.scale))
     return fail(DORA_ERR_INVALID, "cast scale %f is not finite", static_cast<double>(c.scale));
-  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
-    return fail(DORA_ERR_UNSUPPORTED, "cast source dtype %s is not supported: uint8, int8, uint16, "
-                "int16, float16, bfloat16 and float32 are",
-                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  if (const int rc = check_source_dtype(t, "cast"); rc != DORA_OK) return rc;
   if (!c.has_scale && !force && t.dtype_code == c.dtype_code && t.dtype_bits == c.dtype_bits)
     return DORA_OK;
   out.on = true;
@@ -394,10 +453,7 @@ int describe_quant(const dora_tensor& t, const dora_tensor_quant& q, CastDesc& o
                 q.zero_point, lo, hi, dtype_name(q.dtype_code, q.dtype_bits, 1).c_str());
   if (q.has_scale && !std::isfinite(q.scale))
     return fail(DORA_ERR_INVALID, "quantise scale %f is not finite", static_cast<double>(q.scale));
-  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
-    return fail(DORA_ERR_UNSUPPORTED, "quantise source dtype %s is not supported: uint8, int8, "
-                "uint16, int16, float16, bfloat16 and float32 are",
-                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  if (const int rc = check_source_dtype(t, "quantise"); rc != DORA_OK) return rc;
   out.on = true;
   out.src_code = t.dtype_code;
   out.src_bits = t.dtype_bits;
@@ -536,28 +592,12 @@ void cast_row(const uint8_t* src, uint64_t n, const CastDesc& c, uint8_t* dst,
 void cast_host(const StridedView& g, const CastDesc& c, uint8_t* dst) {
   namespace gc = gather::cast;
   const uint64_t ss = c.src_bits / 8u, ds = c.dst_bits / 8u, n = g.row / ss;
-  void (*row)(const uint8_t*, uint64_t, const CastDesc&, uint8_t*, gc::Chan&) = nullptr;
-  switch (gc::src_kind(c.src_code, c.src_bits)) {
-    case gc::kU8: row = cast_row<gc::kU8>; break;
-    case gc::kI8: row = cast_row<gc::kI8>; break;
-    case gc::kU16: row = cast_row<gc::kU16>; break;
-    case gc::kI16: row = cast_row<gc::kI16>; break;
-    case gc::kF16: row = cast_row<gc::kF16>; break;
-    case gc::kBF16: row = cast_row<gc::kBF16>; break;
-    default: row = cast_row<gc::kF32>; break;
-  }
-  int64_t idx[kMaxTensorDims] = {0};
-  int64_t off = 0;
   gc::Chan ch{0, 0};
-  for (uint64_t done = 0; done < c.count; done += n) {
-    row(g.src + off, n, c, dst + done * ds, ch);
-    for (int k = g.nd - 1; k >= 0; --k) {
-      off += g.stride[k];
-      if (++idx[k] < g.shape[k]) break;
-      off -= g.stride[k] * g.shape[k];
-      idx[k] = 0;
-    }
-  }
+  with_src_kind(gc::src_kind(c.src_code, c.src_bits), [&](auto K) {
+    walk_rows(g, c.count, n, [&](int64_t off, uint64_t done) {
+      cast_row<decltype(K)::value>(g.src + off, n, c, dst + done * ds, ch);
+    });
+  });
 }
 
 // The index of the maximum of the `c` candidates `cstride` bytes apart from `src`, of type K:
@@ -588,30 +628,15 @@ uint64_t argmax_at(const uint8_t* src, uint64_t c, int64_t cstride) {
 void reduce_host(const StridedView& g, const ReduceDesc& r, uint8_t* dst) {
   namespace gc = gather::cast;
   const uint64_t ss = r.src_bits / 8u, ds = r.idx_bits / 8u, n = g.row / ss;
-  uint64_t (*one)(const uint8_t*, uint64_t, int64_t) = nullptr;
-  switch (gc::src_kind(r.src_code, r.src_bits)) {
-    case gc::kU8: one = argmax_at<gc::kU8>; break;
-    case gc::kI8: one = argmax_at<gc::kI8>; break;
-    case gc::kU16: one = argmax_at<gc::kU16>; break;
-    case gc::kI16: one = argmax_at<gc::kI16>; break;
-    case gc::kF16: one = argmax_at<gc::kF16>; break;
-    case gc::kBF16: one = argmax_at<gc::kBF16>; break;
-    default: one = argmax_at<gc::kF32>; break;
-  }
-  int64_t idx[kMaxTensorDims] = {0};
-  int64_t off = 0;
-  for (uint64_t done = 0; done < r.count; done += n) {
-    for (uint64_t i = 0; i < n; ++i) {
-      const uint64_t w = one(g.src + off + static_cast<int64_t>(i * ss), r.c, r.cstride);
-      std::memcpy(dst + (done + i) * ds, &w, ds);  // (little-endian)
-    }
-    for (int k = g.nd - 1; k >= 0; --k) {
-      off += g.stride[k];
-      if (++idx[k] < g.shape[k]) break;
-      off -= g.stride[k] * g.shape[k];
-      idx[k] = 0;
-    }
-  }
+  with_src_kind(gc::src_kind(r.src_code, r.src_bits), [&](auto K) {
+    walk_rows(g, r.count, n, [&](int64_t off, uint64_t done) {
+      for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t w = argmax_at<decltype(K)::value>(
+            g.src + off + static_cast<int64_t>(i * ss), r.c, r.cstride);
+        std::memcpy(dst + (done + i) * ds, &w, ds);  // (little-endian)
+      }
+    });
+  });
 }
 
 // What reduces `t` (dora_gpu_plan_tensor_reduce, `r.op` != 0): the entry's and the tensor's
@@ -628,10 +653,7 @@ int describe_reduce(const dora_tensor& t, const dora_tensor_reduce& r, ArrowDevi
   if (!ib)
     return fail(DORA_ERR_UNSUPPORTED, "argmax index dtype %s is not supported: uint8, uint16, "
                 "int32 and int64 are", dtype_name(r.dtype_code, r.dtype_bits, 1).c_str());
-  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
-    return fail(DORA_ERR_UNSUPPORTED, "argmax source dtype %s is not supported: uint8, int8, "
-                "uint16, int16, float16, bfloat16 and float32 are",
-                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  if (const int rc = check_source_dtype(t, "argmax"); rc != DORA_OK) return rc;
   if (t.ndim < 2)
     return fail(DORA_ERR_INVALID, "argmax of a tensor of %d dimensions (at least 2: the reduced "
                 "axis and one that is kept)", t.ndim);
@@ -666,19 +688,13 @@ int describe_reduce(const dora_tensor& t, const dora_tensor_reduce& r, ArrowDevi
     kshape.push_back(t.shape[i]);
     kstrides.push_back(strides[size_t(i)]);
   }
-  // the view of the kept dimensions: any accepted dtype of the source's width describes it
-  dora_tensor kept = t;
-  kept.dtype_code = DL_UINT;
+  dora_tensor kept = t;  // the kept dimensions
   kept.ndim = t.ndim - 1;
   kept.shape = kshape.data();
   kept.strides = kstrides.data();
-  const int rc = describe_tensor(&kept, dev, v);
+  int rc = describe_source(kept, "argmax", dev, v);
   if (rc != DORA_OK) return rc;
   const int64_t ss = t.dtype_bits / 8;
-  if (v.bytes && (reinterpret_cast<uintptr_t>(v.gd.view.src) & static_cast<uintptr_t>(ss - 1)))
-    return fail(DORA_ERR_INVALID, "argmax source data %p (data + byte_offset) is not a multiple "
-                "of its %lld-byte elements", static_cast<const void*>(v.gd.view.src),
-                static_cast<long long>(ss));
   rd.on = true;
   rd.src_code = t.dtype_code;
   rd.src_bits = t.dtype_bits;
@@ -688,16 +704,10 @@ int describe_reduce(const dora_tensor& t, const dora_tensor_reduce& r, ArrowDevi
   rd.count = v.bytes / static_cast<uint64_t>(ss);
   if (__builtin_mul_overflow(strides[size_t(r.axis)], ss, &rd.cstride))
     return fail(DORA_ERR_INVALID, "tensor stride %d overflows 64 bits", r.axis);
-  if (v.bytes && dev == ARROW_DEVICE_ROCM) {  // all C steps, held against the allocation later
-    int64_t span, width;
-    GatherDesc& g = v.gd;
-    if (__builtin_mul_overflow(c - 1, rd.cstride, &span) ||
-        __builtin_add_overflow(span < 0 ? g.lo : g.hi, span, span < 0 ? &g.lo : &g.hi) ||
-        __builtin_sub_overflow(g.hi, g.lo, &width))
-      return fail(DORA_ERR_INVALID, "tensor view's reach overflows 64 bits (extent - 1 times "
-                  "stride, summed over its dimensions)");
-  }
-  v.leaf = ib == 1 ? "C" : ib == 2 ? "S" : ib == 4 ? "i" : "l";
+  // all C steps, held against the allocation later
+  if (v.bytes && dev == ARROW_DEVICE_ROCM) rc = extend_reach(v.gd, c - 1, rd.cstride);
+  if (rc != DORA_OK) return rc;
+  v.leaf = leaf_of(r.dtype_code, r.dtype_bits);
   if (__builtin_mul_overflow(rd.count, static_cast<uint64_t>(ib), &v.bytes) || v.bytes >> 63)
     return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
   return DORA_OK;
@@ -733,17 +743,9 @@ void resize_all(const gather::resize::Args& a, uint8_t* dst) {
 }
 
 void resize_host(const GatherDesc& g, const ResizeDesc& r, uint8_t* dst) {
-  namespace gc = gather::cast;
   const gather::resize::Args a = gather::resize::make_args(g, r, dst);
-  switch (a.src) {
-    case gc::kU8: resize_all<gc::kU8>(a, dst); break;
-    case gc::kI8: resize_all<gc::kI8>(a, dst); break;
-    case gc::kU16: resize_all<gc::kU16>(a, dst); break;
-    case gc::kI16: resize_all<gc::kI16>(a, dst); break;
-    case gc::kF16: resize_all<gc::kF16>(a, dst); break;
-    case gc::kBF16: resize_all<gc::kBF16>(a, dst); break;
-    default: resize_all<gc::kF32>(a, dst); break;
-  }
+  with_src_kind(static_cast<int>(a.src),
+                [&](auto K) { resize_all<decltype(K)::value>(a, dst); });
 }
 
 // What resizes `t` (dora_gpu_plan_tensor_resize, `r.mode` != 0): the entry's and the tensor's
@@ -757,10 +759,7 @@ int describe_resize(const dora_tensor& t, const dora_tensor_resize& r, ArrowDevi
     return fail(DORA_ERR_UNSUPPORTED, "resize mode %u is not supported: DORA_RESIZE_NEAREST (%u) "
                 "and DORA_RESIZE_BILINEAR (%u) are", r.mode, DORA_RESIZE_NEAREST,
                 DORA_RESIZE_BILINEAR);
-  if (t.dtype_lanes != 1 || gather::cast::src_kind(t.dtype_code, t.dtype_bits) < 0)
-    return fail(DORA_ERR_UNSUPPORTED, "resize source dtype %s is not supported: uint8, int8, "
-                "uint16, int16, float16, bfloat16 and float32 are",
-                dtype_name(t.dtype_code, t.dtype_bits, t.dtype_lanes).c_str());
+  if (const int rc = check_source_dtype(t, "resize"); rc != DORA_OK) return rc;
   const unsigned dcode = r.dtype_bits ? r.dtype_code : t.dtype_code;
   const unsigned dbits = r.dtype_bits ? r.dtype_bits : t.dtype_bits;
   if (!r.dtype_bits && t.dtype_code == DL_BFLOAT)
@@ -795,16 +794,9 @@ int describe_resize(const dora_tensor& t, const dora_tensor_resize& r, ArrowDevi
       return fail(DORA_ERR_INVALID, "resize along axis %d to extent %lld: 1 to %lld are offered",
                   r.axis[j], static_cast<long long>(r.size[j]), static_cast<long long>(kMax));
   }
-  // the view of the whole source: any accepted dtype of the source's width describes it
-  dora_tensor src = t;
-  src.dtype_code = DL_UINT;
-  const int rc = describe_tensor(&src, dev, v);
+  const int rc = describe_source(t, "resize", dev, v);  // the whole source
   if (rc != DORA_OK) return rc;
   const int64_t ss = t.dtype_bits / 8;
-  if (v.bytes && (reinterpret_cast<uintptr_t>(v.gd.view.src) & static_cast<uintptr_t>(ss - 1)))
-    return fail(DORA_ERR_INVALID, "resize source data %p (data + byte_offset) is not a multiple "
-                "of its %lld-byte elements", static_cast<const void*>(v.gd.view.src),
-                static_cast<long long>(ss));
   rs.on = true;
   rs.mode = static_cast<uint8_t>(r.mode);
   rs.src_code = t.dtype_code;
@@ -837,8 +829,7 @@ int describe_resize(const dora_tensor& t, const dora_tensor_resize& r, ArrowDevi
     return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
   rs.count = count;
   for (int i = 0; i < t.ndim; ++i) rs.shape[i] = oshape[size_t(i)];
-  v.leaf = dst_float ? (dbits == 16 ? "e" : "f")
-           : dcode == DL_UINT ? (dbits == 8 ? "C" : "S") : (dbits == 8 ? "c" : "s");
+  v.leaf = leaf_of(dcode, dbits);
   return DORA_OK;
 }
 
@@ -905,42 +896,100 @@ int build_tensor_plan(const dora_tensor* t, ArrowDeviceType dev, dora_plan** out
 
 namespace {
 
+// The entries of a message's fields, an optional array per op (n entries each, or NULL); none
+// given: every field is sent as it is.  Never with a take; a field has one op at most, affine
+// steps (describe_affine) going with a conversion (describe_convert).
+struct FieldOps {
+  const dora_tensor_cast* casts = nullptr;
+  const dora_tensor_quant* quants = nullptr;
+  const dora_tensor_affine* affines = nullptr;
+  const dora_tensor_reduce* reduces = nullptr;  // describe_reduce
+  const dora_tensor_resize* resizes = nullptr;  // describe_resize
+};
+
+// One field of a message, whatever is done to it on the way.  `v`: the view of what is read (a
+// converted, reduced or resized field's in source bytes, with its reach) under the leaf and the
+// byte count of what is sent.  As sent: `shape[0..ndim)` (in `own` where it is not the tensor's)
+// and `elem`, the element size that pads the field's offset.  `launch`: what a device plan needs
+// to fill the field, kFields when a gather will do.
+struct FieldDesc {
+  TensorView v;
+  std::vector<int64_t> own;
+  const int64_t* shape = nullptr;
+  int ndim = 0;
+  uint64_t elem = 0;
+  PlanLaunch launch = PlanLaunch::kFields;
+};
+
+// Field `k` of a message with the entries `ops`, of `taken` rows when that is >= 0: the refusals
+// of its entry and of the tensor, else `d` and the descriptors of `pf`.  A new op is one more
+// array of FieldOps, one more branch here, and its own PlanLaunch.
+int describe_field(const dora_tensor& t, size_t k, const FieldOps& ops, ArrowDeviceType dev,
+                   int64_t taken, FieldDesc& d, PlanField& pf) {
+  const bool affine = ops.affines && affine_on(ops.affines[k]);
+  CastDesc& cd = pf.cast;
+  int rc = describe_convert(t, ops.casts ? &ops.casts[k] : nullptr,
+                            ops.quants ? &ops.quants[k] : nullptr, cd, affine);
+  if (rc != DORA_OK) return rc;
+  if (affine && !cd.on) {  // refused: the tensor's own refusals first, then the entry's
+    rc = describe_tensor(&t, dev, d.v);
+    return rc != DORA_OK ? rc : describe_affine(t, dev, ops.affines[k], cd);
+  }
+  d.ndim = t.ndim;
+  d.elem = t.dtype_bits / 8u;
+  if (ops.resizes && ops.resizes[k].mode) {
+    rc = describe_resize(t, ops.resizes[k], dev, pf.resize, d.v, d.own);
+    d.launch = PlanLaunch::kResize;
+    d.elem = pf.resize.dst_bits / 8u;
+  } else if (ops.reduces && ops.reduces[k].op) {
+    rc = describe_reduce(t, ops.reduces[k], dev, pf.reduce, d.v, d.own);
+    d.launch = PlanLaunch::kReduce;
+    d.elem = pf.reduce.idx_bits / 8u;
+    d.ndim = t.ndim - 1;
+  } else if (cd.on) {
+    rc = describe_source(t, "cast", dev, d.v);
+    if (rc == DORA_OK && affine) rc = describe_affine(t, dev, ops.affines[k], cd);
+    if (rc != DORA_OK) return rc;
+    cd.count = d.v.bytes / (cd.src_bits / 8u);
+    d.v.leaf = leaf_of(cd.dst_code, cd.dst_bits);
+    d.v.bytes = cd.count * (cd.dst_bits / 8u);  // (at most twice the source's, which is < 2^63)
+    if (d.v.bytes >> 63) return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
+    d.launch = PlanLaunch::kCast;
+    d.elem = cd.dst_bits / 8u;
+  } else if (taken >= 0) {
+    rc = describe_taken(t, dev, static_cast<uint64_t>(taken), d.v, &pf.stride0);
+    if (rc != DORA_OK) return rc;
+    d.own.assign(t.shape, t.shape + t.ndim);
+    d.own[0] = taken;
+  } else {
+    rc = describe_tensor(&t, dev, d.v);
+  }
+  d.shape = d.own.empty() ? t.shape : d.own.data();
+  return rc;
+}
+
 // The fields of a record laid out from sample offset `off`: the schemas and what the loop over
 // them found, for the struct plan and the ragged-batch plan alike.
 struct FieldLayout {
   std::vector<std::unique_ptr<TypeChain>> chains;
   std::vector<ArrowSchema*> kids;
   uint64_t off = 0;     // in: where the first leaf may start; out: the end of the last
+  int64_t taken = -1;   // in, >= 0: the fields of a take of that many rows (describe_taken)
   uint64_t staged = 0;  // bytes of host fields that are gathered or copied now
   bool strided = false;
-  bool cast = false;    // any field is converted (layout_fields with `casts`)
-  bool reduce = false;  // any field is reduced (layout_fields with `reduces`)
-  bool resize = false;  // any field is resized (layout_fields with `resizes`)
+  PlanLaunch launch = PlanLaunch::kFields;  // raised to what any field asks of a device plan
   uint64_t lead = 0;    // out: the leading extent the fields share, as sent
 };
 
-// Validation, view and type info of every field of `f[0..n)`, each leaf at the running offset
-// padded to its element size: PlanFields into `p`, type info into nodes[k].  `bare`: the one
-// field is a tensor of its own (no name; its chain's head is called `head`).
-// `taken` >= 0: the fields of a take of that many rows (describe_taken): every leaf, type and
-// byte count has the leading extent `taken` where the field's own is N.
-// `casts`, `quants` (n entries each or NULL, never with `taken`): field k converted by casts[k]
-// or quantised by quants[k] (describe_convert) is
-// validated and viewed as its source — the view and its reach in source bytes — while its leaf,
-// byte count and padding are the destination dtype's.
-// `reduces` (n entries or NULL, never with `taken` or a conversion): field k with an op is viewed
-// over its kept dimensions (describe_reduce) while its shape, leaf, byte count and padding are the
-// index tensor's; the fields then share the leading extent of the shapes they are sent with.
-// `resizes` (n entries or NULL, never with any of the others): field k with a mode is viewed as
-// its whole source (describe_resize) while its shape, leaf, byte count and padding are the resized
-// tensor's; the leading extents shared are again those of the shapes as sent.
-int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
-                  const char* head, dora_plan& p, std::vector<TypeInfoNode>& nodes,
-                  FieldLayout& lay, int64_t taken = -1, const dora_tensor_cast* casts = nullptr,
-                  const dora_tensor_quant* quants = nullptr,
-                  const dora_tensor_affine* affines = nullptr,
-                  const dora_tensor_reduce* reduces = nullptr,
-                  const dora_tensor_resize* resizes = nullptr) {
+// Validation, view and type info of every field of `f[0..n)` with the entries `ops`
+// (describe_field), each leaf at the running offset padded to its element size: PlanFields into
+// `p`, type info into nodes[k].  `head` given: the one field is a bare tensor of its own (no
+// name; its chain's head is called `head`).  With `lay.taken` every leaf, type and byte count
+// has the leading extent `taken` where the field's own is N.
+int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, const char* head,
+                  dora_plan& p, std::vector<TypeInfoNode>& nodes, FieldLayout& lay,
+                  const FieldOps& ops = FieldOps()) {
+  const bool bare = head != nullptr;
   p.fields.resize(n);
   lay.chains.resize(n);
   lay.kids.resize(n);
@@ -955,61 +1004,13 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
         if (std::strcmp(f[j].name, name) == 0)
           return fail(DORA_ERR_INVALID, "field %zu `%s` repeats the name of field %zu", k, name, j);
     }
-    const dora_tensor& t = f[k].tensor;
-    TensorView v;
-    int64_t stride0 = 0;
-    CastDesc cd;
-    const bool affine = affines && affine_on(affines[k]);
-    int rc = describe_convert(t, casts ? &casts[k] : nullptr, quants ? &quants[k] : nullptr, cd,
-                              affine);
+    FieldDesc d;
+    PlanField& pf = p.fields[k];
+    const int rc = describe_field(f[k].tensor, k, ops, dev, lay.taken, d, pf);
     if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
-    if (affine && !cd.on) {
-      rc = describe_tensor(&t, dev, v);  // (the tensor's own refusals first)
-      if (rc == DORA_OK) rc = describe_affine(t, dev, affines[k], cd);
-      return bare ? rc : field_fail(rc, k, name);
-    }
-    ReduceDesc rd;
-    ResizeDesc rs;
-    std::vector<int64_t> rshape;  // a reduced or resized field's shape as sent
-    if (resizes && resizes[k].mode) {
-      rc = describe_resize(t, resizes[k], dev, rs, v, rshape);
-      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
-      lay.resize = true;
-    } else if (reduces && reduces[k].op) {
-      rc = describe_reduce(t, reduces[k], dev, rd, v, rshape);
-      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
-      lay.reduce = true;
-    } else if (cd.on) {
-      // the view of the source: any accepted dtype of its width describes it (Arrow has no
-      // bfloat16, and the leaf is the destination's anyway)
-      dora_tensor src = t;
-      src.dtype_code = DL_UINT;
-      rc = describe_tensor(&src, dev, v);
-      if (rc == DORA_OK && v.bytes &&
-          (reinterpret_cast<uintptr_t>(v.gd.view.src) & (cd.src_bits / 8u - 1)))
-        rc = fail(DORA_ERR_INVALID, "cast source data %p (data + byte_offset) is not a multiple "
-                  "of its %u-byte elements", static_cast<const void*>(v.gd.view.src),
-                  cd.src_bits / 8u);
-      if (rc == DORA_OK && affine) rc = describe_affine(t, dev, affines[k], cd);
-      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
-      cd.count = v.bytes / (cd.src_bits / 8u);
-      if (cd.quant())
-        v.leaf = cd.dst_code == DL_UINT ? (cd.dst_bits == 8 ? "C" : "S")
-                                        : (cd.dst_bits == 8 ? "c" : "s");
-      else
-        v.leaf = cd.dst_bits == 16 ? "e" : "f";
-      v.bytes = cd.count * (cd.dst_bits / 8u);  // (at most twice the source's, which is < 2^63)
-      if (v.bytes >> 63) {
-        rc = fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
-        return bare ? rc : field_fail(rc, k, name);
-      }
-      lay.cast = true;
-    } else {
-      rc = taken < 0 ? describe_tensor(&t, dev, v)
-                     : describe_taken(t, dev, static_cast<uint64_t>(taken), v, &stride0);
-      if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, name);
-    }
-    const int64_t lead = rd.on || rs.on ? rshape[0] : t.shape[0];
+    if (d.launch > lay.launch) lay.launch = d.launch;
+    // (a taken field's leading extent is that of its N source rows)
+    const int64_t lead = lay.taken >= 0 ? f[k].tensor.shape[0] : d.shape[0];
     if (k == 0) lay.lead = static_cast<uint64_t>(lead);
     if (static_cast<uint64_t>(lead) != lay.lead)
       return fail(DORA_ERR_INVALID, "field %zu `%s` has leading extent %lld, field 0 `%s` has "
@@ -1017,46 +1018,25 @@ int layout_fields(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, boo
                   "a leading extent of 1)", k, name, static_cast<long long>(lead),
                   f[0].name, static_cast<long long>(lay.lead));
     // the running offset padded to the leaf's element size (a power of two)
-    const uint64_t elem = rs.on   ? rs.dst_bits / 8u
-                          : rd.on ? rd.idx_bits / 8u
-                          : cd.on ? cd.dst_bits / 8u
-                                  : t.dtype_bits / 8u;
     uint64_t padded, end;
-    if (__builtin_add_overflow(off, elem - 1, &padded) ||
-        __builtin_add_overflow(padded & ~(elem - 1), v.bytes, &end) || end >> 63)
+    if (__builtin_add_overflow(off, d.elem - 1, &padded) ||
+        __builtin_add_overflow(padded & ~(d.elem - 1), d.v.bytes, &end) || end >> 63)
       return fail(DORA_ERR_INVALID, "field %zu `%s`: the message's size overflows 64 bits", k,
                   bare ? "" : name);
-    off = padded & ~(elem - 1);
-    PlanField& pf = p.fields[k];
+    off = padded & ~(d.elem - 1);
     pf.name = bare ? "" : name;
-    pf.gd = v.gd;
+    pf.gd = d.v.gd;
     pf.dst_off = off;
-    pf.bytes = v.bytes;
-    pf.stride0 = stride0;
-    pf.cast = cd;
-    pf.reduce = rd;
-    pf.resize = rs;
-    const int64_t* shape = t.shape;  // as sent
-    int ndim = t.ndim;
-    std::vector<int64_t> kshape;
-    if (taken >= 0) {
-      kshape.assign(t.shape, t.shape + t.ndim);
-      kshape[0] = taken;
-      shape = kshape.data();
-    }
-    if (rd.on) {
-      shape = rshape.data();
-      ndim = t.ndim - 1;
-    }
-    if (rs.on) shape = rshape.data();
-    lay.chains[k].reset(new TypeChain(v.leaf, shape, ndim, name));
+    pf.bytes = d.v.bytes;
+    lay.chains[k].reset(new TypeChain(d.v.leaf, d.shape, d.ndim, name));
     lay.kids[k] = &lay.chains[k]->sch[0];
-    tensor_type_info(*lay.chains[k], shape, ndim, off, v.bytes, nodes[k]);
+    tensor_type_info(*lay.chains[k], d.shape, d.ndim, off, d.v.bytes, nodes[k]);
     off = end;
-    const bool stage = taken >= 0 || cd.on || rd.on || rs.on || dev == ARROW_DEVICE_ROCM_HOST ||
-                       (dev == ARROW_DEVICE_CPU && v.gd.view.nd);
-    if (stage) lay.staged += v.bytes;  // (<= off)
-    lay.strided |= v.gd.view.nd != 0;
+    const bool stage = lay.taken >= 0 || d.launch != PlanLaunch::kFields ||
+                       dev == ARROW_DEVICE_ROCM_HOST ||
+                       (dev == ARROW_DEVICE_CPU && d.v.gd.view.nd);
+    if (stage) lay.staged += d.v.bytes;  // (<= off)
+    lay.strided |= d.v.gd.view.nd != 0;
   }
   lay.off = off;
   return DORA_OK;
@@ -1219,22 +1199,18 @@ void place_masked_host(dora_plan& p, const MaskIn& mk, uint64_t staged) {
   p.fields.clear();
 }
 
-// A tensor (`bare`: one field without a name) or a record of tensors as one message; with `tk`
-// the rows of it that the index takes.
+// A tensor (`bare`: one field without a name) or a record of tensors as one message, its fields
+// with the entries `ops`; with `tk` the rows of it that the index takes.
 int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool bare,
-                 const TakeIn* tk, dora_plan** out, const dora_tensor_cast* casts = nullptr,
-                 const dora_tensor_quant* quants = nullptr,
-                 const dora_tensor_affine* affines = nullptr,
-                 const dora_tensor_reduce* reduces = nullptr,
-                 const dora_tensor_resize* resizes = nullptr) {
+                 const TakeIn* tk, dora_plan** out, const FieldOps& ops = FieldOps()) {
   DORA_GUARD_BEGIN
   std::unique_ptr<dora_plan> p(new dora_plan());
   p->dev = dev == ARROW_DEVICE_ROCM ? ARROW_DEVICE_ROCM : ARROW_DEVICE_CPU;
   FieldLayout lay;
+  if (tk) lay.taken = static_cast<int64_t>(tk->ix.count);
   std::vector<TypeInfoNode> solo;
-  int rc = layout_fields(f, n, dev, bare, "", *p, bare ? solo : p->root.children, lay,
-                               tk ? static_cast<int64_t>(tk->ix.count) : -1, casts, quants,
-                               affines, reduces, resizes);
+  int rc = layout_fields(f, n, dev, bare ? "" : nullptr, *p, bare ? solo : p->root.children, lay,
+                         ops);
   if (rc != DORA_OK) return rc;
   const uint64_t off = lay.off;
   if (bare) {
@@ -1253,20 +1229,32 @@ int build_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, bool
   const uint64_t rows = static_cast<uint64_t>(f[0].tensor.shape[0]);
   if (tk) note_take(*p, *tk, rows);
   // what fills the sample: nothing (d0 == 0, an empty message); the taken rows; device fields as
-  // segments, a gather when any is strided, a cast launch when any is converted or a reduce
-  // launch when any is reduced, a resize launch when any is resized; host fields
+  // segments when all are dense and sent as they are, else the one launch the fields ask for;
+  // host fields
   if (off == 0) p->fields.clear();
   else if (tk) rc = place_taken(*p, *tk, rows, lay.staged);
   else if (dev == ARROW_DEVICE_ROCM)
-    place_device_fields(*p, !lay.strided && !lay.cast && !lay.reduce && !lay.resize,
-                        lay.resize   ? PlanLaunch::kResize
-                        : lay.reduce ? PlanLaunch::kReduce
-                                   : lay.cast ? PlanLaunch::kCast : PlanLaunch::kFields);
+    place_device_fields(*p, !lay.strided && lay.launch == PlanLaunch::kFields, lay.launch);
   else stage_host_fields(*p, dev, lay.staged);
   if (rc != DORA_OK) return rc;
   *out = p.release();
   return DORA_OK;
   DORA_GUARD_END
+}
+
+// What the builders of a message with entries do before they look at one: `out` and the device,
+// then at least one field (`noun` is refused by name) and no more than a launch carries; between
+// those two `missing`, when given: the refusal of an array of entries that is NULL.  `*bare`: the
+// one field is a tensor of its own.
+int begin_record(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, dora_plan** out,
+                 const char* noun, bool* bare, const char* missing = nullptr) {
+  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
+  if (missing && n && f) return fail(DORA_ERR_INVALID, "%s", missing);
+  const int rc = check_fields(f, n, noun);
+  *bare = rc == DORA_OK && n == 1 && !f[0].name;
+  return rc;
 }
 
 }  // namespace
@@ -1280,17 +1268,23 @@ int build_tensor_struct_plan(const dora_tensor_field* f, size_t n, ArrowDeviceTy
   return rc != DORA_OK ? rc : build_record(f, n, dev, false, nullptr, out);
 }
 
+namespace {
+
+// No entry does anything: the plain plan, whatever it is, refusals included.
+int build_plain(const dora_tensor_field* f, size_t n, ArrowDeviceType dev, dora_plan** out) {
+  if (f && n == 1 && !f[0].name) return build_tensor_plan(&f[0].tensor, dev, out);
+  return build_tensor_struct_plan(f, n, dev, out);
+}
+
+}  // namespace
+
 int build_tensor_cast_plan(const dora_tensor_field* f, size_t n, const dora_tensor_cast* casts,
                            ArrowDeviceType dev, dora_plan** out) {
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  // (ranked behind "no field" and ahead of "too many")
-  if (n && f && !casts) return fail(DORA_ERR_INVALID, "casts is NULL (one entry per field)");
-  const int rf = check_fields(f, n, "a cast");
+  bool bare = false;
+  const int rf = begin_record(f, n, dev, out, "a cast", &bare,
+                              casts ? nullptr : "casts is NULL (one entry per field)");
   if (rf != DORA_OK) return rf;
-  const bool bare = n == 1 && !f[0].name;
-  // no field converted at all (after every cast's own refusals): the plain plan, whatever it is
+  // no field converted at all (after every cast's own refusals): the plain plan
   bool any = false;
   for (size_t k = 0; k < n; ++k) {
     CastDesc cd;
@@ -1298,21 +1292,16 @@ int build_tensor_cast_plan(const dora_tensor_field* f, size_t n, const dora_tens
     if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, f[k].name);
     any |= cd.on;
   }
-  if (!any)
-    return bare ? build_tensor_plan(&f[0].tensor, dev, out)
-                : build_tensor_struct_plan(f, n, dev, out);
-  return build_record(f, n, dev, bare, nullptr, out, casts);
+  if (!any) return build_plain(f, n, dev, out);
+  return build_record(f, n, dev, bare, nullptr, out, FieldOps{casts});
 }
 
 int build_tensor_convert_plan(const dora_tensor_field* f, size_t n, const dora_tensor_cast* casts,
                               const dora_tensor_quant* quants, ArrowDeviceType dev,
                               dora_plan** out) {
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  const int rf = check_fields(f, n, "a conversion");
+  bool bare = false;
+  const int rf = begin_record(f, n, dev, out, "a conversion", &bare);
   if (rf != DORA_OK) return rf;
-  const bool bare = n == 1 && !f[0].name;
   // every entry's own refusals first; no field quantised: what the cast plan is, whatever it is
   bool quantised = false;
   for (size_t k = 0; k < n; ++k) {
@@ -1322,67 +1311,50 @@ int build_tensor_convert_plan(const dora_tensor_field* f, size_t n, const dora_t
     if (rc != DORA_OK) return bare ? rc : field_fail(rc, k, f[k].name);
     quantised |= cd.quant();
   }
-  if (!quantised) {
-    if (casts) return build_tensor_cast_plan(f, n, casts, dev, out);
-    return bare ? build_tensor_plan(&f[0].tensor, dev, out)
-                : build_tensor_struct_plan(f, n, dev, out);
-  }
-  return build_record(f, n, dev, bare, nullptr, out, casts, quants);
+  if (!quantised)
+    return casts ? build_tensor_cast_plan(f, n, casts, dev, out) : build_plain(f, n, dev, out);
+  return build_record(f, n, dev, bare, nullptr, out, FieldOps{casts, quants});
 }
 
 int build_tensor_affine_plan(const dora_tensor_field* f, size_t n, const dora_tensor_cast* casts,
                              const dora_tensor_quant* quants, const dora_tensor_affine* affines,
                              ArrowDeviceType dev, dora_plan** out) {
-  bool any = false;
+  bool any = false, bare = false;
   for (size_t k = 0; affines && f && k < n; ++k) any |= affine_on(affines[k]);
   // no affine step at all: the conversion's plan, whatever it is, refusals included
   if (!any) return build_tensor_convert_plan(f, n, casts, quants, dev, out);
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  const int rf = check_fields(f, n, "a conversion");
+  const int rf = begin_record(f, n, dev, out, "a conversion", &bare);
   if (rf != DORA_OK) return rf;
   // every field's own refusals, then its affine entry's, as the fields are laid out
-  return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, casts, quants, affines);
+  return build_record(f, n, dev, bare, nullptr, out, FieldOps{casts, quants, affines});
 }
 
 int build_tensor_reduce_plan(const dora_tensor_field* f, size_t n,
                              const dora_tensor_reduce* reduces, ArrowDeviceType dev,
                              dora_plan** out) {
-  bool any = false;
+  bool any = false, bare = false;
   for (size_t k = 0; reduces && f && k < n; ++k) any |= reduces[k].op != 0;
-  // no reduction at all: the plain plan, whatever it is, refusals included
-  if (!any) {
-    if (f && n == 1 && !f[0].name) return build_tensor_plan(&f[0].tensor, dev, out);
-    return build_tensor_struct_plan(f, n, dev, out);
-  }
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  const int rf = check_fields(f, n, "a reduction");
+  if (!any) return build_plain(f, n, dev, out);
+  const int rf = begin_record(f, n, dev, out, "a reduction", &bare);
   if (rf != DORA_OK) return rf;
-  return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, nullptr, nullptr, nullptr,
-                      reduces);
+  FieldOps ops;
+  ops.reduces = reduces;
+  return build_record(f, n, dev, bare, nullptr, out, ops);
 }
 
 int build_tensor_resize_plan(const dora_tensor_field* f, size_t n,
                              const dora_tensor_resize* resizes, ArrowDeviceType dev,
                              dora_plan** out) {
-  bool any = false;
+  bool any = false, bare = false;
   for (size_t k = 0; resizes && f && k < n; ++k) any |= resizes[k].mode != 0;
-  // no resize at all: the plain plan, whatever it is, refusals included
-  if (!any) {
-    if (f && n == 1 && !f[0].name) return build_tensor_plan(&f[0].tensor, dev, out);
-    return build_tensor_struct_plan(f, n, dev, out);
-  }
-  if (!out) return fail(DORA_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  if (!known_device(dev)) return fail(DORA_ERR_INVALID, "unsupported device_type %d", dev);
-  const int rf = check_fields(f, n, "a resize");
+  if (!any) return build_plain(f, n, dev, out);
+  const int rf = begin_record(f, n, dev, out, "a resize", &bare);
   if (rf != DORA_OK) return rf;
-  return build_record(f, n, dev, n == 1 && !f[0].name, nullptr, out, nullptr, nullptr, nullptr,
-                      nullptr, resizes);
+  FieldOps ops;
+  ops.resizes = resizes;
+  return build_record(f, n, dev, bare, nullptr, out, ops);
 }
+
 
 namespace {
 
@@ -1529,8 +1501,8 @@ int build_list(const dora_tensor_list* l, ArrowDeviceType dev, const TakeIn* tk,
   // no shape[0] to read is refused by the layout whatever N is taken to be)
   const dora_tensor& t0 = f[0].tensor;
   const int64_t mask_rows = mk && t0.shape && t0.ndim >= 1 && t0.shape[0] > 0 ? t0.shape[0] : 0;
-  rc = layout_fields(f, n, dev, bare, "item", *p, bare ? solo : child.children, lay,
-                     tk ? static_cast<int64_t>(tk->ix.count) : mk ? mask_rows : -1);
+  lay.taken = tk ? static_cast<int64_t>(tk->ix.count) : mk ? mask_rows : -1;
+  rc = layout_fields(f, n, dev, bare ? "item" : nullptr, *p, bare ? solo : child.children, lay);
   if (rc != DORA_OK) return rc;
   if (mk) {
     p->about.masked = true;

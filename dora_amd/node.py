@@ -353,29 +353,62 @@ class Node:
             return rc
         return _fast.send_tensor(self.handle, output_id, caps[0], dev, metadata, flags)
 
+    def _entries_of(self, data, wrappers) -> tuple:
+        """(items, kind, tensors, names, entries) of `data`, a tensor or a dict of tensors of
+        which some are wrapped in one of `wrappers`: `items` the values as given, under their
+        names (None: the one tensor), `kind`, `tensors` and `names` what `_values_kind` finds of
+        the tensors inside, `entries` each wrapped value's `_entry()` and None for the others
+        (without `wrappers`: None, no value has one)."""
+        record = isinstance(data, dict)
+        items = data if record else {None: data}
+        if not wrappers:
+            return (items, *self._values_kind(data), None)
+        plain = {k: (v.values if isinstance(v, wrappers) else v) for k, v in items.items()}
+        kind, tensors, names = self._values_kind(plain if record else plain[None])
+        entries = tuple(v._entry() if isinstance(v, wrappers) else None for v in items.values())
+        return items, kind, tensors, names, entries
+
+    def _send_entries(self, output_id: str, data, wrappers, fast, entry, metadata, flags: int,
+                      pre=None) -> int:
+        """Every send of a tensor or a dict of tensors whose fields may carry an entry each, done
+        once: `wrappers` the classes whose entries this send takes, `fast` the extension's
+        function — (handle, output_id, names, capsules, entries, device_type, metadata, flags),
+        without `entries` when there are no wrappers — and `entry` the library's C entry, which
+        takes one array per class of `wrappers` behind the fields (`pre`: `_entries_of` the two,
+        when the caller has it).
+
+        Host tensors have been read — converted, reduced, resized by the CPU — on return.
+        Tensors on this node's GPU do the handshake of `_device_caps` each and are read by one
+        kernel launch; an asynchronous send holds them until `sync()`.  Host tensors that numpy
+        refuses to export (`_host_caps`) are described through their array interface and go
+        through ctypes."""
+        items, kind, tensors, names, entries = pre or self._entries_of(data, wrappers)
+        mid = () if entries is None else (entries,)
+        if kind == "device":
+            caps, _, done = self._device_caps(flags, tensors)
+            return done(fast(self.handle, output_id, names, caps, *mid, ARROW_DEVICE_ROCM,
+                             metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is not None:
+            return fast(self.handle, output_id, names, caps, *mid, dev, metadata, flags)
+        from ._lib import Tensor
+        from .tensor import _describe_array, _describe_entries, _describe_list
+        described = [_describe_array(v) for v in tensors]
+        lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0, ARROW_DEVICE_CPU)
+        arrays = [_describe_entries(list(items.values()), cls) for cls in wrappers]
+        params = encode_parameters(metadata)
+        rc = entry(self.handle, output_id.encode(), lst.fields, len(tensors), *arrays, dev, params,
+                   len(params), flags)
+        del keep, described
+        return rc
+
     def _send_tensor_struct(self, output_id: str, data: dict, metadata, flags: int) -> int:
         """A dict of DLPack producers as one Struct message with a field per entry, in the dict's
         order (dora_node_send_output_tensor_struct; dora_amd.tensor): every tensor shares
-        shape[0], and all are host tensors or all are on this node's GPU.  Host fields have been
-        read on return.  Device fields do the handshake each and are read by one kernel launch;
-        an asynchronous send holds every one of them until the next `sync()`, as `_send_tensor`
-        holds its one."""
-        kind, tensors, names = self._values_kind(data)
-        if kind == "device":
-            caps, _, done = self._device_caps(flags, tensors)
-            return done(_fast.send_tensor_struct(self.handle, output_id, names, caps,
-                                                 ARROW_DEVICE_ROCM, metadata, flags))
-        dev, caps = self._host_caps(tensors)
-        if caps is None:
-            from .tensor import _describe_array, _describe_fields
-            described = [_describe_array(v) for v in tensors]
-            fields, keep = _describe_fields(names, [t for t, _ in described])
-            params = encode_parameters(metadata)
-            rc = self._lib.dora_node_send_output_tensor_struct(
-                self.handle, output_id.encode(), fields, len(names), dev, params, len(params), flags)
-            del keep, described
-            return rc
-        return _fast.send_tensor_struct(self.handle, output_id, names, caps, dev, metadata, flags)
+        shape[0], and all are host tensors or all are on this node's GPU (`_send_entries`, no
+        field with an entry)."""
+        return self._send_entries(output_id, data, (), _fast.send_tensor_struct,
+                                  self._lib.dora_node_send_output_tensor_struct, metadata, flags)
 
     def _tensor_kind(self, v, what: str) -> str:
         """"host" or "device" of a DLPack producer `v` (`what` names it in a refusal)."""
@@ -448,47 +481,20 @@ class Node:
         """A tensor quantised on send (dora_amd.tensor.quantize), or a dict of tensors of which
         some are quantised, some perhaps cast and the rest plain, as the tensor or Struct message
         of the converted values (dora_node_send_output_tensor_convert; without `quantise`, no
-        entry is a quantise entry and the call is dora_node_send_output_tensor_cast).  Host
-        tensors are converted by the CPU inside the call and have been read on return.  Tensors
-        on this node's GPU do the handshake each and are read, converted and written by one
-        kernel launch; an asynchronous send holds them until `sync()`."""
-        record = isinstance(data, dict)
-        items = data if record else {None: data}
+        entry is a quantise entry and the call is dora_node_send_output_tensor_cast), by
+        `_send_entries` (a cast entry has three items, a quantise entry four) — or, when a field
+        has a bias or a per-channel table, by `_send_tensor_affine`."""
         conv = (_Cast, _Quantized)
-        plain = {k: (v.values if isinstance(v, conv) else v) for k, v in items.items()}
-        kind, tensors, names = self._values_kind(plain if record else plain[None])
-        # (a cast entry has three items, a quantise entry four)
-        entries = tuple(v._entry() if isinstance(v, conv) else None for v in items.values())
-        affines = [v._affine() if isinstance(v, conv) else None for v in items.values()]
+        pre = self._entries_of(data, conv)
+        affines = [v._affine() if isinstance(v, conv) else None for v in pre[0].values()]
         if any(a is not None for a in affines):
-            return self._send_tensor_affine(output_id, items, kind, tensors, names, entries,
-                                            affines, metadata, flags)
-        fast = _fast.send_tensor_convert if quantise else _fast.send_tensor_cast
-        if kind == "device":
-            caps, _, done = self._device_caps(flags, tensors)
-            return done(fast(self.handle, output_id, names, caps, entries, ARROW_DEVICE_ROCM,
-                             metadata, flags))
-        dev, caps = self._host_caps(tensors)
-        if caps is None:
-            from ._lib import Tensor
-            from .tensor import (_describe_array, _describe_casts, _describe_list,
-                                 _describe_quants)
-            described = [_describe_array(v) for v in tensors]
-            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
-                                       ARROW_DEVICE_CPU)
-            carr = _describe_casts([v if isinstance(v, _Cast) else None for v in items.values()])
-            params = encode_parameters(metadata)
-            head = (self.handle, output_id.encode(), lst.fields, len(tensors), carr)
-            tail = (dev, params, len(params), flags)
-            if quantise:
-                qarr = _describe_quants([v if isinstance(v, _Quantized) else None
-                                         for v in items.values()])
-                rc = self._lib.dora_node_send_output_tensor_convert(*head, qarr, *tail)
-            else:
-                rc = self._lib.dora_node_send_output_tensor_cast(*head, *tail)
-            del keep, described
-            return rc
-        return fast(self.handle, output_id, names, caps, entries, dev, metadata, flags)
+            return self._send_tensor_affine(output_id, *pre, affines, metadata, flags)
+        if quantise:
+            return self._send_entries(output_id, data, conv, _fast.send_tensor_convert,
+                                      self._lib.dora_node_send_output_tensor_convert, metadata,
+                                      flags, pre)
+        return self._send_entries(output_id, data, (_Cast,), _fast.send_tensor_cast,
+                                  self._lib.dora_node_send_output_tensor_cast, metadata, flags, pre)
 
     def _send_tensor_affine(self, output_id: str, items, kind, tensors, names, entries, affines,
                             metadata, flags: int) -> int:
@@ -528,15 +534,14 @@ class Node:
         dev, caps = self._host_caps(tensors)
         if caps is None:
             from ._lib import Tensor
-            from .tensor import (_describe_affines, _describe_array, _describe_casts,
-                                 _describe_list, _describe_quants)
+            from .tensor import (_describe_affines, _describe_array, _describe_entries,
+                                 _describe_list)
             described = [_describe_array(v) for v in tensors]
             tdesc = {k: _describe_array(a) for k, a in host.items()}
             lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
                                        ARROW_DEVICE_CPU)
-            carr = _describe_casts([v if isinstance(v, _Cast) else None for v in items.values()])
-            qarr = _describe_quants([v if isinstance(v, _Quantized) else None
-                                     for v in items.values()])
+            carr = _describe_entries(list(items.values()), _Cast)
+            qarr = _describe_entries(list(items.values()), _Quantized)
             aarr, akeep = _describe_affines([
                 None if a is None else (None if a[0] is None else tdesc[id(a[0])][0],
                                         None if a[1] is None else tdesc[id(a[1])][0], a[2], a[3])
@@ -557,82 +562,28 @@ class Node:
     def _send_tensor_reduce(self, output_id: str, data, metadata, flags: int) -> int:
         """A tensor reduced on send (dora_amd.tensor.argmax), or a dict of tensors of which some
         are reduced and the rest plain, as the tensor or Struct message of the index tensors and
-        the plain values (dora_node_send_output_tensor_reduce).  Host tensors are reduced by the
-        CPU inside the call and have been read on return.  Tensors on this node's GPU do the
-        handshake each and are read, reduced and written by one kernel launch; an asynchronous
-        send holds them until `sync()`.  A dict that also holds a cast or a quantised field is not
-        offered: nothing is sent."""
-        record = isinstance(data, dict)
-        items = data if record else {None: data}
-        for name, v in items.items():
+        the plain values (dora_node_send_output_tensor_reduce; `_send_entries`).  A dict that
+        also holds a cast or a quantised field is not offered: nothing is sent."""
+        for name, v in (data.items() if isinstance(data, dict) else ()):
             if isinstance(v, (_Cast, _Quantized)):
                 raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion beside an argmax in "
                                                "one message is not offered (send the converted "
                                                "field in a message of its own)")
-        plain = {k: (v.values if isinstance(v, _Argmax) else v) for k, v in items.items()}
-        kind, tensors, names = self._values_kind(plain if record else plain[None])
-        entries = tuple(v._entry() if isinstance(v, _Argmax) else None for v in items.values())
-        if kind == "device":
-            caps, _, done = self._device_caps(flags, tensors)
-            return done(_fast.send_tensor_reduce(self.handle, output_id, names, caps, entries,
-                                                 ARROW_DEVICE_ROCM, metadata, flags))
-        dev, caps = self._host_caps(tensors)
-        if caps is None:
-            from ._lib import Tensor
-            from .tensor import _describe_array, _describe_list, _describe_reduces
-            described = [_describe_array(v) for v in tensors]
-            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
-                                       ARROW_DEVICE_CPU)
-            rarr = _describe_reduces([v if isinstance(v, _Argmax) else None
-                                      for v in items.values()])
-            params = encode_parameters(metadata)
-            rc = self._lib.dora_node_send_output_tensor_reduce(
-                self.handle, output_id.encode(), lst.fields, len(tensors), rarr, dev, params,
-                len(params), flags)
-            del keep, described
-            return rc
-        return _fast.send_tensor_reduce(self.handle, output_id, names, caps, entries, dev, metadata,
-                                        flags)
+        return self._send_entries(output_id, data, (_Argmax,), _fast.send_tensor_reduce,
+                                  self._lib.dora_node_send_output_tensor_reduce, metadata, flags)
 
     def _send_tensor_resize(self, output_id: str, data, metadata, flags: int) -> int:
         """A tensor resized on send (dora_amd.tensor.resize), or a dict of tensors of which some
         are resized and the rest plain, as the tensor or Struct message of the resized tensors and
-        the plain values (dora_node_send_output_tensor_resize).  Host tensors are resized by the
-        CPU inside the call and have been read on return.  Tensors on this node's GPU do the
-        handshake each and are read, resized and written by one kernel launch; an asynchronous
-        send holds them until `sync()`.  A dict that also holds a cast, a quantised or an argmax
-        field is not offered: nothing is sent."""
-        record = isinstance(data, dict)
-        items = data if record else {None: data}
-        for name, v in items.items():
+        the plain values (dora_node_send_output_tensor_resize; `_send_entries`).  A dict that
+        also holds a cast, a quantised or an argmax field is not offered: nothing is sent."""
+        for name, v in (data.items() if isinstance(data, dict) else ()):
             if isinstance(v, (_Cast, _Quantized, _Argmax)):
                 raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion or an argmax beside "
                                                "a resize in one message is not offered (send the "
                                                "field in a message of its own)")
-        plain = {k: (v.values if isinstance(v, _Resized) else v) for k, v in items.items()}
-        kind, tensors, names = self._values_kind(plain if record else plain[None])
-        entries = tuple(v._entry() if isinstance(v, _Resized) else None for v in items.values())
-        if kind == "device":
-            caps, _, done = self._device_caps(flags, tensors)
-            return done(_fast.send_tensor_resize(self.handle, output_id, names, caps, entries,
-                                                 ARROW_DEVICE_ROCM, metadata, flags))
-        dev, caps = self._host_caps(tensors)
-        if caps is None:
-            from ._lib import Tensor
-            from .tensor import _describe_array, _describe_list, _describe_resizes
-            described = [_describe_array(v) for v in tensors]
-            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
-                                       ARROW_DEVICE_CPU)
-            rarr = _describe_resizes([v if isinstance(v, _Resized) else None
-                                      for v in items.values()])
-            params = encode_parameters(metadata)
-            rc = self._lib.dora_node_send_output_tensor_resize(
-                self.handle, output_id.encode(), lst.fields, len(tensors), rarr, dev, params,
-                len(params), flags)
-            del keep, described
-            return rc
-        return _fast.send_tensor_resize(self.handle, output_id, names, caps, entries, dev, metadata,
-                                        flags)
+        return self._send_entries(output_id, data, (_Resized,), _fast.send_tensor_resize,
+                                  self._lib.dora_node_send_output_tensor_resize, metadata, flags)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
         """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with

@@ -423,6 +423,11 @@ class _Affine:
             return None
         return (self.scale_table, self.bias_table, self.axis or 0, self.bias)
 
+    def _fill(self, a):
+        a.dtype_code, a.dtype_bits = self._code, self._bits
+        a.has_scale = 0 if self.scale is None else 1
+        a.scale = 0.0 if self.scale is None else self.scale
+
     def _affine_repr(self):
         by = " * table" if self.scale_table is not None else \
             "" if self.scale is None else f" * {self.scale!r}"
@@ -439,6 +444,7 @@ class Cast(_Affine):
 
     __slots__ = ("values", "dtype", "scale", "bias", "scale_table", "bias_table", "axis", "_code",
                  "_bits")
+    _STRUCT = TensorCast
 
     def __init__(self, values, dtype, scale=None, bias=None, axis=None):
         self.values = values
@@ -525,6 +531,7 @@ class Quantized(_Affine):
 
     __slots__ = ("values", "dtype", "scale", "bias", "scale_table", "bias_table", "axis",
                  "zero_point", "_code", "_bits")
+    _STRUCT = TensorQuant
 
     def __init__(self, values, dtype, scale=None, zero_point=0, bias=None, axis=None):
         import operator
@@ -542,6 +549,10 @@ class Quantized(_Affine):
 
     def _entry(self):
         return (self._code, self._bits, self.scale, self.zero_point)
+
+    def _fill(self, a):
+        super()._fill(a)
+        a.zero_point = self.zero_point
 
     def __repr__(self):
         zp = "" if not self.zero_point else f" + {self.zero_point}"
@@ -594,6 +605,7 @@ class Argmax:
     one with `argmax`."""
 
     __slots__ = ("values", "axis", "dtype", "_code", "_bits")
+    _STRUCT = TensorReduce
 
     def __init__(self, values, axis, dtype="int64"):
         import operator
@@ -609,6 +621,9 @@ class Argmax:
 
     def _entry(self):
         return (REDUCE_ARGMAX, self.axis, self._code, self._bits)
+
+    def _fill(self, a):
+        a.op, a.axis, a.dtype_code, a.dtype_bits = self._entry()
 
     def __repr__(self):
         return f"Argmax({self.values!r} along axis {self.axis} -> {self.dtype})"
@@ -656,6 +671,7 @@ class Resized:
     own).  It reads and resizes nothing itself.  Build one with `resize`."""
 
     __slots__ = ("values", "size", "axes", "mode", "dtype", "_mode", "_code", "_bits")
+    _STRUCT = TensorResize
 
     def __init__(self, values, size, axes=(-2, -1), mode="nearest", dtype=None):
         import operator
@@ -687,6 +703,10 @@ class Resized:
     def _entry(self):
         return (self._mode, self.axes[0], self.axes[1], self.size[0], self.size[1], self._code,
                 self._bits)
+
+    def _fill(self, a):
+        (a.mode, a.axis[0], a.axis[1], a.size[0], a.size[1], a.dtype_code,
+         a.dtype_bits) = self._entry()
 
     def __repr__(self):
         return (f"Resized({self.values!r} axes {self.axes} -> {self.size}, {self.mode}"
@@ -1045,30 +1065,14 @@ def _describe_fields(names, tensors) -> tuple:
     return arr, (enc, tensors)
 
 
-def _describe_casts(casts) -> "ctypes.Array":
-    """The `dora_tensor_cast` array of `casts`, each a `Cast` or None (the field is sent as it
-    is)."""
-    arr = (TensorCast * len(casts))()
-    for k, c in enumerate(casts):
-        if c is None:
-            continue
-        arr[k].dtype_code, arr[k].dtype_bits = c._code, c._bits
-        arr[k].has_scale = 0 if c.scale is None else 1
-        arr[k].scale = 0.0 if c.scale is None else c.scale
-    return arr
-
-
-def _describe_quants(quants) -> "ctypes.Array":
-    """The `dora_tensor_quant` array of `quants`, each a `Quantized` or None (the field is not
-    quantised)."""
-    arr = (TensorQuant * len(quants))()
-    for k, q in enumerate(quants):
-        if q is None:
-            continue
-        arr[k].dtype_code, arr[k].dtype_bits = q._code, q._bits
-        arr[k].has_scale = 0 if q.scale is None else 1
-        arr[k].scale = 0.0 if q.scale is None else q.scale
-        arr[k].zero_point = q.zero_point
+def _describe_entries(values, cls) -> "ctypes.Array":
+    """The array of `cls._STRUCT` (dora_tensor_cast, _quant, _reduce or _resize) over `values`:
+    entry k is filled by values[k] where that is a `cls` (`Cast`, `Quantized`, `Argmax`,
+    `Resized`) and left zero — the field is sent as it is — where it is anything else."""
+    arr = (cls._STRUCT * len(values))()
+    for k, v in enumerate(values):
+        if isinstance(v, cls):
+            v._fill(arr[k])
     return arr
 
 
@@ -1092,29 +1096,6 @@ def _describe_affines(entries) -> tuple:
         arr[k].bias_value = 0.0 if bias is None else bias
         keep.append((s, b))
     return arr, keep
-
-
-def _describe_reduces(reduces) -> "ctypes.Array":
-    """The `dora_tensor_reduce` array of `reduces`, each an `Argmax` or None (the field is sent as
-    it is)."""
-    arr = (TensorReduce * len(reduces))()
-    for k, r in enumerate(reduces):
-        if r is None:
-            continue
-        arr[k].op, arr[k].axis, arr[k].dtype_code, arr[k].dtype_bits = r._entry()
-    return arr
-
-
-def _describe_resizes(resizes) -> "ctypes.Array":
-    """The `dora_tensor_resize` array of `resizes`, each a `Resized` or None (the field is sent as
-    it is)."""
-    arr = (TensorResize * len(resizes))()
-    for k, r in enumerate(resizes):
-        if r is None:
-            continue
-        (arr[k].mode, arr[k].axis[0], arr[k].axis[1], arr[k].size[0], arr[k].size[1],
-         arr[k].dtype_code, arr[k].dtype_bits) = r._entry()
-    return arr
 
 
 def _describe_list(names, tensors, partition, form, partition_device) -> tuple:

@@ -61,7 +61,8 @@ def resize_plan(x, size, axes, mode, dtype):
     np_dtype = {1: np.uint8, 2: np.float16, 4: np.float32}[x.element_size()]
     t, keep = tensor._describe(x.data_ptr(), tuple(x.shape), list(x.stride()), np_dtype)
     lst, keep2 = tensor._describe_list(None, [t], t, 0, 0)
-    arr = tensor._describe_resizes([tensor.resize(x, size, axes=axes, mode=mode, dtype=dtype)])
+    arr = tensor._describe_entries([tensor.resize(x, size, axes=axes, mode=mode, dtype=dtype)],
+                                    tensor.Resized)
     h = c_void_p()
     _lib.call("dora_gpu_plan_tensor_resize", lst.fields, 1, arr, ARROW_DEVICE_ROCM, byref(h))
     return Plan(h.value, (lst, keep, keep2, arr, x))
