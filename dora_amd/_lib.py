@@ -122,6 +122,13 @@ RESIZE_NEAREST = 1
 RESIZE_BILINEAR = 2
 
 
+class TensorCrop(ctypes.Structure):
+    """dora_tensor_crop of include/dora_gpu.h: the crops of one field (mode 0: none), a resize
+    entry's members and the [K, 4] int32 boxes."""
+    _fields_ = [("mode", c_uint32), ("axis", c_int32 * 2), ("size", ctypes.c_int64 * 2),
+                ("dtype_code", c_uint8), ("dtype_bits", c_uint8), ("boxes", POINTER(Tensor))]
+
+
 class TensorMask(ctypes.Structure):
     """dora_tensor_mask of include/dora_gpu.h: the fields rows are selected from, the mask that
     selects them and, for more than one list, the partition of the N source rows (else NULL)."""
@@ -203,6 +210,11 @@ _SIGS = {
     "dora_node_send_output_tensor_resize": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
                                                     c_void_p, c_int32, c_char_p, c_size_t,
                                                     c_uint32]),
+    "dora_gpu_plan_tensor_crop": (c_int, [c_void_p, c_size_t, c_void_p, c_int32,
+                                          POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_crop": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
+                                                  c_void_p, c_int32, c_char_p, c_size_t,
+                                                  c_uint32]),
     "dora_gpu_plan_tensor_mask": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_mask": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                                   c_size_t, c_uint32]),
@@ -362,6 +374,10 @@ _TEST_SIGS = {
                                           POINTER(c_uint64), POINTER(c_int), POINTER(c_int),
                                           POINTER(c_uint64), POINTER(c_uint64)]),
     "dora_gpu_test_reduce_body": (c_int, [c_int]),
+    "dora_gpu_test_plan_crop": (c_int, [c_void_p, c_size_t, c_void_p, POINTER(c_int),
+                                        POINTER(c_uint64), POINTER(c_void_p), POINTER(c_int),
+                                        POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
+                                        POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "dora_gpu_test_plan_resize": (c_int, [c_void_p, c_size_t, c_void_p, POINTER(c_int),
                                           POINTER(c_uint64), POINTER(c_int),
                                           POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),

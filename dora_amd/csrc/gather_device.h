@@ -958,6 +958,25 @@ struct Args {
 
 }  // namespace resize
 
+// ------------------------------------------------------------------------------------------
+// A field of crops (one more field kind, run by gather_crop_kernel only): K boxes read from HBM,
+// each cut from one frame and resized to the same extents.  Only the arguments live here, where
+// multi::Field needs them; the body is crop_device.h.
+// ------------------------------------------------------------------------------------------
+namespace crop {
+
+struct Args {
+  // a resized field's arguments over all K crops: the output's odometer with K as one more leading
+  // dimension of stride 0 at shape[kax], in[] the frame's extents along the two cropped
+  // dimensions (what a box is clamped to), [lo, hi] the reach of the whole frame
+  resize::Args r;
+  const uint8_t* boxes;  // K rows of four int32 words: a_lo, b_lo, a_hi, b_hi; 4-byte aligned
+  uint8_t kax;           // K's place in shape[]
+  uint8_t pad[7];
+};
+
+}  // namespace crop
+
 namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
@@ -965,10 +984,10 @@ constexpr int kMaxFields = static_cast<int>(kMaxStructFields);
 // (kRowsCast fields are run by gather_cast_kernel / gather_quant_kernel / gather_affine_kernel
 // only: gather_struct_kernel's launches hold none)
 // (kReduceLane and kReduceWave fields are run by gather_reduce_kernel only, kResize fields by
-// gather_resize_kernel only)
+// gather_resize_kernel only, kCrop fields by gather_crop_kernel only)
 enum Kind : uint32_t {
   kRows = 0, kTile = 1, kScan = 2, kRowsTaken = 3, kRowsCast = 4, kReduceLane = 5, kReduceWave = 6,
-  kResize = 7
+  kResize = 7, kCrop = 8
 };
 
 struct Field {
@@ -981,12 +1000,14 @@ struct Field {
     cast::Args cast;
     reduce::Args reduce;
     resize::Args resize;
+    crop::Args crop;
   };
 };
 static_assert(sizeof(take::Args) <= sizeof(tile::Args), "a taken field does not grow Field");
 static_assert(sizeof(cast::Args) <= sizeof(tile::Args), "a cast field does not grow Field");
 static_assert(sizeof(reduce::Args) <= sizeof(tile::Args), "a reduced field does not grow Field");
 static_assert(sizeof(resize::Args) <= sizeof(tile::Args), "a resized field does not grow Field");
+static_assert(sizeof(crop::Args) <= sizeof(tile::Args), "a field of crops does not grow Field");
 
 struct Args {
   uint32_t n;

@@ -19,6 +19,7 @@
 #include "cast_device.h"
 #include "reduce_device.h"
 #include "resize_device.h"
+#include "crop_device.h"
 #include "gather_device.h"
 #include "pack_device.h"
 #include "plan.h"
@@ -669,6 +670,54 @@ __global__ __launch_bounds__(gather::kThreads) void gather_resize_kernel(gather:
   resize_share(a, lds);
 }
 
+// The crop body's memory and arithmetic (crop_device.h): the resize body's policy plus a word of
+// the boxes, a plain cached load of an aligned dword — the lanes of a wave read the same few rows,
+// and a lane reads a row again for every unit it owns.
+struct CropMem : ResizeMem {
+  const uint8_t* boxes;
+  __device__ __forceinline__ int32_t load_box(int64_t at) const {
+    return *reinterpret_cast<const int32_t*>(boxes + at);
+  }
+};
+
+// What a workgroup of gather_crop_kernel does: struct_share's walk to its field, then the field's
+// body over the field's share of the grid: the rows or the tile body of a plain field, the crop
+// body of a field of crops (a branch uniform over the workgroup).  No scan, taken, cast, reduce or
+// resize share.
+__device__ __forceinline__ void crop_share(const gather::multi::Args& a, uint64_t* lds) {
+  const uint32_t w = blockIdx.x;
+  const int k = gather::multi::field_of(a, w);
+  const gather::multi::Field& f = a.f[k];
+  const uint64_t local = w - a.wg_begin[k], share = a.wg_begin[k + 1] - a.wg_begin[k];
+  const uint64_t lane = local * gather::kThreads + threadIdx.x, lanes = share * gather::kThreads;
+  if (f.kind == gather::multi::kRows) {
+    GatherMem m{f.rows.src, f.rows.dst};
+    gather::gather_lane(f.rows, lane, lanes, m);
+    return;
+  }
+  if (f.kind == gather::multi::kCrop) {
+    // (a copy of its own, as the cast body's arguments are)
+    const gather::crop::Args c = f.crop;
+    CropMem m{{{c.r.g.src, c.r.g.dst}}, c.boxes};
+    gather::crop::crop_lane(c, lane, lanes, m);
+    return;
+  }
+  switch (f.tile.elem) {
+    case 1: tile_loop(f.tile, local, share, reinterpret_cast<uint8_t*>(lds)); break;
+    case 2: tile_loop(f.tile, local, share, reinterpret_cast<uint16_t*>(lds)); break;
+    case 4: tile_loop(f.tile, local, share, reinterpret_cast<uint32_t*>(lds)); break;
+    default: tile_loop(f.tile, local, share, lds); break;
+  }
+}
+
+// gather_crop_kernel: the fields of a crop plan in one launch: fields of crops through the crop
+// body (crop_device.h), plain ones through their usual rows or tile body.  Chosen per plan, so the
+// other kernels hold no line of it.
+__global__ __launch_bounds__(gather::kThreads) void gather_crop_kernel(gather::multi::Args a) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  crop_share(a, lds);
+}
+
 // The mask kernels' memory (gather_device.h mask::): the mask with one aligned 16-byte
 // non-temporal load per thread (each byte is read once by each kernel) or byte by byte at its
 // head and tail; the thread counts in LDS; the workspace's index, counts and totals with plain
@@ -1009,6 +1058,11 @@ int check_plan_range(const dora_plan& plan, int device) {
       rc = check_device_range(table_reach(c.bias_tab, c.channels), device);
       what = "bias table: ";
     }
+    // a crops field's boxes in HBM: their 16 * K bytes like a take's index
+    if (rc == DORA_OK && kind == PlanLaunch::kCrop && plan.fields[k].crop.on) {
+      rc = check_device_range(crop_reach(plan.fields[k].crop), device);
+      what = "boxes: ";
+    }
     if (rc == DORA_OK) continue;
     const std::string why = dora_gpu_last_error();
     return fail(rc, "field %zu `%s`: %s%s", k, plan.fields[k].name.c_str(), what, why.c_str());
@@ -1086,7 +1140,7 @@ namespace {
 // What a launch of `kind` does to field `k`, `f`, held against what the kernel's body takes for
 // granted — its loads whole source elements, its stores whole destination elements, every extent
 // within its arithmetic.  Returns the size of the elements stored, with `*noun` what the field
-// then is ("converted", "reduced", "resized"); 0 with `*noun` NULL for a field that goes as it is;
+// then is ("converted", "reduced", "resized", "cropped"); 0 with `*noun` NULL for a field that goes as it is;
 // -1 after recording that this is not an op the kernel runs.  A new op is one more branch here.
 int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** noun) {
   namespace gc = gather::cast;
@@ -1095,10 +1149,12 @@ int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** no
   unsigned ds = 0;
   bool ok = true;
   *noun = nullptr;
-  if (kind == PlanLaunch::kResize && f.resize.on) {
-    const ResizeDesc& r = f.resize;
-    op = "a resize";
-    *noun = "resized";
+  if ((kind == PlanLaunch::kResize && f.resize.on) || (kind == PlanLaunch::kCrop && f.crop.on)) {
+    // (a field of crops: the same held against the output's dimensions, and its boxes)
+    const bool crop = kind == PlanLaunch::kCrop;
+    const ResizeDesc& r = crop ? f.crop.rs : f.resize;
+    op = crop ? "a crop" : "a resize";
+    *noun = crop ? "cropped" : "resized";
     ds = r.dst_bits / 8u;
     const bool dst_ok = r.dst_code == 2 ? ds == 2 || ds == 4
                                         : gc::dst_kind(r.dst_code, r.dst_bits) >= 0;
@@ -1110,6 +1166,10 @@ int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** no
            r.in[j] <= int64_t(gather::resize::kMaxExtent) && r.shape[r.ax[j]] >= 1 &&
            r.shape[r.ax[j]] <= int64_t(gather::resize::kMaxExtent);
     for (int i = 0; ok && i < r.nd; ++i) ok = !(static_cast<uintptr_t>(r.stride[i]) & elem_mask);
+    if (crop)
+      ok = ok && f.crop.k >= 1 && f.crop.k <= kMaxCropBoxes && r.shape[0] == int64_t(f.crop.k) &&
+           r.stride[0] == 0 && r.ax[0] >= 1 && r.ax[1] >= 1 && f.crop.boxes &&
+           !(reinterpret_cast<uintptr_t>(f.crop.boxes) & 3);
   } else if (kind == PlanLaunch::kReduce && f.reduce.on) {
     const ReduceDesc& r = f.reduce;
     op = "a reduction";
@@ -1140,7 +1200,8 @@ int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** no
 //   kReduce: the same, a reduced field through the lane or the wave body (select_reduce_wave);
 //     gather_reduce_kernel.
 //   kResize: the same, a resized field through the resize body; gather_resize_kernel.
-//   (these three: DORA_ERR_INVALID, nothing launched, when a field with an op, field_op_size,
+//   kCrop: the same, a field of crops through the crop body; gather_crop_kernel.
+//   (these four: DORA_ERR_INVALID, nothing launched, when a field with an op, field_op_size,
 //   would not start on a multiple of the size of the elements stored)
 //   kTaken (`take` given): every field through the taken body, never a tile: row i0 of its bytes
 //     is row take->src[i0] of the field, or zeros where that word is not in [0, take->n).
@@ -1171,6 +1232,7 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
   ReduceDesc rd[gather::multi::kMaxFields];
   bool wave[gather::multi::kMaxFields];
   ResizeDesc rs[gather::multi::kMaxFields];
+  CropDesc cr[gather::multi::kMaxFields];
   bool quant = false, affine = false;
   for (size_t k = 0; k < n; ++k) {
     const PlanField& f = fields[k];
@@ -1181,6 +1243,7 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
     c[k] = kind == PlanLaunch::kCast ? f.cast : CastDesc{};
     rd[k] = kind == PlanLaunch::kReduce ? f.reduce : ReduceDesc{};
     rs[k] = kind == PlanLaunch::kResize ? f.resize : ResizeDesc{};
+    cr[k] = kind == PlanLaunch::kCrop ? f.crop : CropDesc{};
     quant |= c[k].quant();
     const char* noun = nullptr;
     const int ds = field_op_size(kind, f, k, &noun);
@@ -1207,8 +1270,13 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
                    ? gm::make_reduce_args(g, rd, wave, off, tile_c, nf, dst)
                : kind == PlanLaunch::kResize
                    ? gm::make_resize_args(g, rs, off, tile_c, nf, dst)
+               : kind == PlanLaunch::kCrop
+                   ? gm::make_crop_args(g, cr, off, tile_c, nf, dst)
                    : gm::make_args(g, off, tile_c, nf, dst, scan);
   a.lookup = lookup;
+  if (kind == PlanLaunch::kCrop)
+    return launch_timed(gather_crop_kernel, gm::grid_for(a), gather::kThreads, stream, ev_start,
+                        ev_stop, a);
   if (kind == PlanLaunch::kResize)
     return launch_timed(gather_resize_kernel, gm::grid_for(a), gather::kThreads, stream, ev_start,
                         ev_stop, a);
@@ -1280,6 +1348,7 @@ int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
     case PlanLaunch::kCast:
     case PlanLaunch::kReduce:
     case PlanLaunch::kResize:
+    case PlanLaunch::kCrop:
     case PlanLaunch::kTaken:
       return launch_fields(plan.launch, plan.fields.data(), plan.fields.size(), dst, stream,
                            ev_start, ev_stop, scan,

@@ -155,6 +155,22 @@ struct ResizeDesc {
   uint64_t count = 0;
 };
 
+// A field of crops (dora_gpu_plan_tensor_crop): `k` boxes cut from one frame, each brought to one
+// size by resize's taps over the box's own clamped extents (crop_device.h).  `rs` describes the
+// output as a resize would: `rs.nd` is the frame's dimensions plus the leading one of the K crops
+// (shape[0] = K, stride[0] = 0), `rs.ax[]` the two cropped dimensions counted with it, `rs.in[]`
+// the frame's extents along them — what a box is clamped to — and `rs.count` all K crops'
+// elements.  `boxes`: K dense rows of four int32 words (a_lo, b_lo, a_hi, b_hi) where the values
+// live: read by the CPU while a host plan is built, read by the launch of a device plan and never
+// on the host (crop_reach).  `on` false: the field is sent as it is.
+constexpr uint64_t kMaxCropBoxes = 1u << 20;
+struct CropDesc {
+  bool on = false;
+  ResizeDesc rs;
+  const uint8_t* boxes = nullptr;
+  uint64_t k = 0;
+};
+
 // One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
 // own tensor plan would describe it (dense: nd == 0), where its row-major values start in the
 // sample and how many bytes they are.  Fields follow one another in destination order.
@@ -180,6 +196,9 @@ struct PlanField {
   // source bytes — any element of it may be a tap, so its [lo, hi] is the field's reach — and
   // `resize` the dimensions as given; `bytes` the resized bytes
   ResizeDesc resize;
+  // a crop plan (dora_gpu_plan_tensor_crop), `crop.on`: `gd` is the whole frame in source bytes,
+  // its [lo, hi] the field's reach as a resized field's is; `bytes` all K crops' bytes
+  CropDesc crop;
 };
 
 // `bytes` dense bytes of `elem`-byte elements from `src` as a view: what a plan reads of an
@@ -200,6 +219,10 @@ inline GatherDesc dense_reach(const uint8_t* src, uint64_t bytes, uint32_t elem)
 inline GatherDesc table_reach(const uint8_t* tab, uint64_t channels) {
   return dense_reach(tab, 4 * channels, 4);
 }
+
+// The boxes of a crops field in HBM: what check_plan_range holds against the allocation of
+// `c.boxes`.
+inline GatherDesc crop_reach(const CropDesc& c) { return dense_reach(c.boxes, 16 * c.k, 4); }
 
 // The index of a take plan when it lives in HBM: `count` (K) dense words of 4 or 8 bytes at `src`,
 // never read on the host; a word outside [0, n) yields a row of zero bytes (gather_device.h
@@ -302,11 +325,11 @@ int launch_plan_prefix(const dora_plan& plan, uint8_t* dst, hipStream_t stream);
 // launch_gather of its view; one launch over its fields — gather_struct_kernel, with the scan of a
 // ragged batch's device partition and by the index of a take, or gather_cast_kernel /
 // gather_quant_kernel / gather_affine_kernel for converted fields, gather_reduce_kernel for
-// reduced ones or gather_resize_kernel for resized ones — each field's bytes as launch_gather would write
+// reduced ones, gather_resize_kernel for resized ones or gather_crop_kernel for crops — each field's bytes as launch_gather would write
 // them, nothing between fields and nothing at or past the last field's end; for a mask plan the
 // two compaction launches and then the fields by the index they wrote, `dst` then holding the
 // sample and plan_workspace bytes behind it.  DORA_ERR_INVALID, nothing launched, when a
-// converted, reduced or resized field would not start on a multiple of its destination element
+// converted, reduced, resized or cropped field would not start on a multiple of its destination element
 // size.
 int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
@@ -391,6 +414,13 @@ int build_tensor_reduce_plan(const dora_tensor_field* fields, size_t n,
 int build_tensor_resize_plan(const dora_tensor_field* fields, size_t n,
                              const dora_tensor_resize* resizes, ArrowDeviceType dev,
                              dora_plan** out);
+// Crops on send, bare or as a record (dora_gpu_plan_tensor_crop): a field with a crop entry is
+// the tensor of its K boxes, each cut from the field's frame and brought to one size.  Host
+// values: cropped in the plan's staging buffer by the CPU, which reads the boxes; device values: a
+// gather plan whose one launch reads the boxes and crops (gather_crop_kernel).  `crops` NULL or
+// every mode 0: build_tensor_plan's (bare) or build_tensor_struct_plan's plan.
+int build_tensor_crop_plan(const dora_tensor_field* fields, size_t n,
+                           const dora_tensor_crop* crops, ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -404,7 +434,8 @@ enum class PlanLaunch : uint8_t {
   kTaken,     // the taken body over `fields` by `take` (+ scan share when scan_on)
   kMasked,    // count, compact, then the taken body by the workspace's index
   kReduce,    // gather_reduce_kernel over `fields`
-  kResize     // gather_resize_kernel over `fields`
+  kResize,    // gather_resize_kernel over `fields`
+  kCrop       // gather_crop_kernel over `fields`
 };
 
 // What kind of message a tensor plan is, whichever way its bytes move: reported by the test probes

@@ -20,6 +20,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -700,6 +701,66 @@ PyObject* py_send_tensor_resize(PyObject*, PyObject* const* args, Py_ssize_t nar
   return PyLong_FromLong(rc);
 }
 
+// send_tensor_crops(handle, output_id, names, capsules, crops, device_type, metadata, flags)
+// -> status: crops cut and resized on send as dora_node_send_output_tensor_crop.  `names` /
+// `capsules` as send_tensor_cast takes them; `crops` a tuple as long, each entry None (the field is
+// sent as it is) or (mode, axis0, axis1, size0, size1, dtype_code, dtype_bits, boxes), `boxes` a
+// "dltensor" capsule of the [K, 4] int32 boxes, which joins the fields' capsules: every capsule is
+// consumed as send_tensor_struct consumes its own.
+PyObject* py_send_tensor_crops(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  const char* usage =
+      "send_tensor_crops(handle, output_id, names, capsules, crops, device_type, metadata, "
+      "flags): names is None over one capsule or a tuple as long as the tuple of capsules; "
+      "crops a tuple as long, of None or (mode, axis0, axis1, size0, size1, code, bits, boxes)";
+  if (nargs != 8 || !as_long(args[4], args[3])) {
+    PyErr_SetString(PyExc_TypeError, usage);
+    return nullptr;
+  }
+  Capsules caps;
+  if (!caps.take(args[2], args[3], usage, true, false)) return nullptr;
+  const size_t n = caps.fields.size();
+  std::vector<dora_tensor_crop> crops(n);
+  std::vector<dora_tensor> boxes(n);
+  for (size_t k = 0; k < n; ++k) {
+    PyObject* entry = PyTuple_GET_ITEM(args[4], Py_ssize_t(k));
+    if (entry == Py_None) continue;
+    if (!PyTuple_Check(entry) || PyTuple_GET_SIZE(entry) != 8) {
+      PyErr_SetString(PyExc_TypeError, usage);
+      return nullptr;
+    }
+    long long w[7];
+    for (int j = 0; j < 7; ++j) w[j] = PyLong_AsLongLong(PyTuple_GET_ITEM(entry, j));
+    if (PyErr_Occurred()) return nullptr;
+    if (w[0] < 1 || w[0] > INT32_MAX || w[1] < INT32_MIN || w[1] > INT32_MAX ||
+        w[2] < INT32_MIN || w[2] > INT32_MAX || w[5] < 0 || w[5] > 255 || w[6] < 0 ||
+        w[6] > 255) {
+      PyErr_Format(PyExc_TypeError, "field %zu: crops entry (mode %lld, axes %lld and %lld, "
+                                    "code %lld, %lld bits)", k, w[0], w[1], w[2], w[5], w[6]);
+      return nullptr;
+    }
+    char what[48];
+    std::snprintf(what, sizeof(what), "field %zu: the boxes", k);
+    if (!caps.also(PyTuple_GET_ITEM(entry, 7), &boxes[k], what)) return nullptr;
+    dora_tensor_crop& c = crops[k];
+    c.mode = static_cast<uint32_t>(w[0]);
+    c.axis[0] = static_cast<int32_t>(w[1]);
+    c.axis[1] = static_cast<int32_t>(w[2]);
+    c.size[0] = static_cast<int64_t>(w[3]);
+    c.size[1] = static_cast<int64_t>(w[4]);
+    c.dtype_code = static_cast<uint8_t>(w[5]);
+    c.dtype_bits = static_cast<uint8_t>(w[6]);
+    c.boxes = &boxes[k];
+  }
+  Frame f;
+  if (!f.take(args[0], args[1], args[5], args[6], args[7]) || !caps.consume()) return nullptr;
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor_crop(f.node, f.oid, caps.fields.data(), n, crops.data(),
+                                         f.dev, f.params, f.params_len, f.flags);
+  Py_END_ALLOW_THREADS
+  return PyLong_FromLong(rc);
+}
+
 // send_tensor_list(handle, output_id, names, capsules, partition, form, partition_device,
 // device_type, metadata, flags) -> status: a ragged batch as dora_node_send_output_tensor_list.
 // `names` is a tuple of str over the tuple `capsules`, or None over a tuple of one capsule (a bare
@@ -1275,6 +1336,9 @@ PyMethodDef methods[] = {
     {"send_tensor_reduce",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_reduce)),
      METH_FASTCALL, "dora_node_send_output_tensor_reduce of DLPack capsules, which it consumes."},
+    {"send_tensor_crops",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_crops)),
+     METH_FASTCALL, "dora_node_send_output_tensor_crop of DLPack capsules, which it consumes."},
     {"send_tensor_resize",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_resize)),
      METH_FASTCALL, "dora_node_send_output_tensor_resize of DLPack capsules, which it consumes."},

@@ -43,6 +43,12 @@
 // field is validated and viewed as its whole source, whose reach is the field's since any element
 // may be a tap, its dimensions kept as given beside it — resized by the CPU here for host values,
 // by the plan's one launch for device values (resize_device.h).
+//
+// Crops (dora_gpu_plan_tensor_crop) are a tensor or a record in which a field with a crop entry is
+// laid out as K tensors of its two new extents under one more leading dimension: the field is
+// validated and viewed as a resized frame would be, the boxes as K dense rows of four int32 words
+// beside it — read and cropped by the CPU here for host values; for device values never read, their
+// 16 * K bytes kept for check_plan_range and the plan's one launch (crop_device.h).
 #include <cstring>
 #include <memory>
 #include <string>
@@ -54,6 +60,7 @@
 #include "cast_device.h"
 #include "reduce_device.h"
 #include "resize_device.h"
+#include "crop_device.h"
 #include "common.h"
 #include "plan.h"
 
@@ -833,6 +840,101 @@ int describe_resize(const dora_tensor& t, const dora_tensor_resize& r, ArrowDevi
   return DORA_OK;
 }
 
+// The CPU's crops of a crops field: resize_all with crop_device.h's walk, which reads the boxes.
+struct CropHostMem : ResizeHostMem {
+  const uint8_t* boxes;
+  int32_t load_box(int64_t at) const {
+    int32_t v;
+    std::memcpy(&v, boxes + at, 4);
+    return v;
+  }
+};
+
+template <uint32_t K>
+void crop_all(const gather::crop::Args& a, uint8_t* dst) {
+  namespace cr = gather::crop;
+  CropHostMem m{{{}, a.r.g.src}, a.boxes};
+  cr::Walk w;
+  cr::walk_start(a, 0, w, m);
+  for (uint64_t e = 0; e < a.r.g.total; ++e) {
+    const uint32_t q = a.r.dsize == 1   ? cr::elem_at<K, 1>(a, w, m)
+                       : a.r.dsize == 2 ? cr::elem_at<K, 2>(a, w, m)
+                                        : cr::elem_at<K, 4>(a, w, m);
+    std::memcpy(dst + e * a.r.dsize, &q, a.r.dsize);  // (little-endian)
+    if (e + 1 < a.r.g.total) cr::walk_next(a, w, m);
+  }
+}
+
+void crop_host(const GatherDesc& g, const CropDesc& c, uint8_t* dst) {
+  const gather::crop::Args a = gather::crop::make_args(g, c, dst);
+  with_src_kind(static_cast<int>(a.r.src), [&](auto K) { crop_all<decltype(K)::value>(a, dst); });
+}
+
+// What crops `t` (dora_gpu_plan_tensor_crop, `c.mode` != 0): the frame's dimension count, then
+// everything describe_resize refuses of the same frame, axes, size, mode and dtype, then the
+// boxes' refusals; else `cd`, the view `v` of the whole frame — its leaf and byte count those of
+// all K crops — and `oshape`, the shape of the message: K in front of the resized frame's.
+int describe_crop(const dora_tensor& t, const dora_tensor_crop& c, ArrowDeviceType dev,
+                  CropDesc& cd, TensorView& v, std::vector<int64_t>& oshape) {
+  cd = CropDesc{};
+  if (t.ndim < 2 || t.ndim > kMaxTensorDims - 1)
+    return fail(DORA_ERR_INVALID, "crops of a frame of %d dimensions (2 to %d: the two cropped "
+                "axes, and the message has one more)", t.ndim, kMaxTensorDims - 1);
+  dora_tensor_resize r{};
+  r.mode = c.mode;
+  r.dtype_code = c.dtype_code;
+  r.dtype_bits = c.dtype_bits;
+  for (int j = 0; j < 2; ++j) {
+    r.axis[j] = c.axis[j];
+    r.size[j] = c.size[j];
+  }
+  ResizeDesc one;
+  int rc = describe_resize(t, r, dev, one, v, oshape);
+  if (rc != DORA_OK) return rc;
+  if (!v.bytes)
+    return fail(DORA_ERR_INVALID, "crops of a frame of extent 0 in dimension 0 (a fixed-size list "
+                "of 0 values has no length to recover)");
+  if (!c.boxes) return fail(DORA_ERR_INVALID, "boxes is NULL (K rows of four int32 words)");
+  const dora_tensor& b = *c.boxes;
+  if (b.dtype_code != DL_INT || b.dtype_bits != 32 || b.dtype_lanes != 1)
+    return fail(DORA_ERR_INVALID, "boxes dtype %s is not int32",
+                dtype_name(b.dtype_code, b.dtype_bits, b.dtype_lanes).c_str());
+  if (b.ndim != 2 || !b.shape || b.shape[1] != 4)
+    return fail(DORA_ERR_INVALID, "boxes are not of shape [K, 4] (%d dimensions%s): a row is "
+                "(a_lo, b_lo, a_hi, b_hi)", b.ndim,
+                b.ndim == 2 && b.shape ? ", rows of another length" : "");
+  const int64_t k = b.shape[0];
+  if (k < 0 || k > static_cast<int64_t>(kMaxCropBoxes))
+    return fail(DORA_ERR_INVALID, "boxes hold %lld rows: 0 to %llu are cropped",
+                static_cast<long long>(k), static_cast<unsigned long long>(kMaxCropBoxes));
+  if (b.strides && k && (b.strides[1] != 1 || (k > 1 && b.strides[0] != 4)))
+    return fail(DORA_ERR_INVALID, "boxes strides (%lld, %lld): the boxes are dense",
+                static_cast<long long>(b.strides[0]), static_cast<long long>(b.strides[1]));
+  if (!b.data && k) return fail(DORA_ERR_INVALID, "boxes data is NULL");
+  cd.boxes = static_cast<const uint8_t*>(b.data) + b.byte_offset;
+  if (k && (reinterpret_cast<uintptr_t>(cd.boxes) & 3u))
+    return fail(DORA_ERR_INVALID, "boxes data %p is not aligned to its 4-byte words",
+                static_cast<const void*>(cd.boxes));
+  cd.on = true;
+  cd.k = static_cast<uint64_t>(k);
+  // the output's dimensions: K in front, never stepping through the frame
+  ResizeDesc& rs = cd.rs;
+  rs = one;
+  rs.nd = one.nd + 1;
+  rs.shape[0] = k;
+  rs.stride[0] = 0;
+  for (int i = 0; i < one.nd; ++i) {
+    rs.shape[i + 1] = one.shape[i];
+    rs.stride[i + 1] = one.stride[i];
+  }
+  for (int j = 0; j < 2; ++j) rs.ax[j] = one.ax[j] + 1;
+  if (__builtin_mul_overflow(one.count, cd.k, &rs.count) ||
+      __builtin_mul_overflow(v.bytes, cd.k, &v.bytes) || v.bytes >> 63)
+    return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
+  oshape.insert(oshape.begin(), k);
+  return DORA_OK;
+}
+
 bool known_device(ArrowDeviceType dev) {
   return dev == ARROW_DEVICE_CPU || dev == ARROW_DEVICE_ROCM_HOST || dev == ARROW_DEVICE_ROCM;
 }
@@ -905,6 +1007,7 @@ struct FieldOps {
   const dora_tensor_affine* affines = nullptr;
   const dora_tensor_reduce* reduces = nullptr;  // describe_reduce
   const dora_tensor_resize* resizes = nullptr;  // describe_resize
+  const dora_tensor_crop* crops = nullptr;      // describe_crop
 };
 
 // One field of a message, whatever is done to it on the way.  `v`: the view of what is read (a
@@ -937,7 +1040,12 @@ int describe_field(const dora_tensor& t, size_t k, const FieldOps& ops, ArrowDev
   }
   d.ndim = t.ndim;
   d.elem = t.dtype_bits / 8u;
-  if (ops.resizes && ops.resizes[k].mode) {
+  if (ops.crops && ops.crops[k].mode) {
+    rc = describe_crop(t, ops.crops[k], dev, pf.crop, d.v, d.own);
+    d.launch = PlanLaunch::kCrop;
+    d.elem = pf.crop.rs.dst_bits / 8u;
+    d.ndim = t.ndim + 1;
+  } else if (ops.resizes && ops.resizes[k].mode) {
     rc = describe_resize(t, ops.resizes[k], dev, pf.resize, d.v, d.own);
     d.launch = PlanLaunch::kResize;
     d.elem = pf.resize.dst_bits / 8u;
@@ -1049,11 +1157,12 @@ void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
   uint64_t at = 0;
   for (const PlanField& pf : p.fields) {
     if (dev == ARROW_DEVICE_CPU && pf.gd.view.nd == 0 && !pf.cast.on && !pf.reduce.on &&
-        !pf.resize.on) {
+        !pf.resize.on && !pf.crop.on) {
       p.segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
       continue;
     }
-    if (pf.resize.on) resize_host(pf.gd, pf.resize, p.staged.data() + at);
+    if (pf.crop.on) crop_host(pf.gd, pf.crop, p.staged.data() + at);
+    else if (pf.resize.on) resize_host(pf.gd, pf.resize, p.staged.data() + at);
     else if (pf.reduce.on) reduce_host(pf.gd.view, pf.reduce, p.staged.data() + at);
     else if (pf.cast.on) cast_host(pf.gd.view, pf.cast, p.staged.data() + at);
     else gather_host(pf.gd.view, p.staged.data() + at);
@@ -1355,6 +1464,17 @@ int build_tensor_resize_plan(const dora_tensor_field* f, size_t n,
   return build_record(f, n, dev, bare, nullptr, out, ops);
 }
 
+int build_tensor_crop_plan(const dora_tensor_field* f, size_t n, const dora_tensor_crop* crops,
+                           ArrowDeviceType dev, dora_plan** out) {
+  bool any = false, bare = false;
+  for (size_t k = 0; crops && f && k < n; ++k) any |= crops[k].mode != 0;
+  if (!any) return build_plain(f, n, dev, out);
+  const int rf = begin_record(f, n, dev, out, "crops", &bare);
+  if (rf != DORA_OK) return rf;
+  FieldOps ops;
+  ops.crops = crops;
+  return build_record(f, n, dev, bare, nullptr, out, ops);
+}
 
 namespace {
 
@@ -1757,6 +1877,12 @@ int dora_gpu_plan_tensor_reduce(const dora_tensor_field* fields, size_t n,
                                 const dora_tensor_reduce* reduces, ArrowDeviceType device_type,
                                 dora_plan** out) {
   return dora::build_tensor_reduce_plan(fields, n, reduces, device_type, out);
+}
+
+int dora_gpu_plan_tensor_crop(const dora_tensor_field* fields, size_t n,
+                              const dora_tensor_crop* crops, ArrowDeviceType device_type,
+                              dora_plan** out) {
+  return dora::build_tensor_crop_plan(fields, n, crops, device_type, out);
 }
 
 int dora_gpu_plan_tensor_resize(const dora_tensor_field* fields, size_t n,

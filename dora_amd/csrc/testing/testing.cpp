@@ -27,6 +27,7 @@
 #include "gather_device.h"
 #include "reduce_device.h"
 #include "resize_device.h"
+#include "crop_device.h"
 #include "plan.h"
 #include "shm.h"
 
@@ -532,6 +533,37 @@ int dora_gpu_test_plan_resize(const dora_plan* plan, size_t i, const void* dst, 
     head = a.g.head;
     nunits = a.g.nunits;
     tail = a.g.total - head - (16u / a.dsize) * nunits;
+  }
+  if (head_elements) *head_elements = head;
+  if (units) *units = nunits;
+  if (tail_elements) *tail_elements = tail;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_crop(const dora_plan* plan, size_t i, const void* dst, int* mode,
+                            uint64_t* k, const void** boxes, int* boxes_device, int64_t* lo,
+                            int64_t* hi, uint64_t* head_elements, uint64_t* units,
+                            uint64_t* tail_elements) {
+  if (!plan || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a plan that keeps a field %zu", i);
+  const dora::PlanField& f = plan->fields[i];
+  const dora::CropDesc& c = f.crop;
+  const bool on = plan->launch == dora::PlanLaunch::kCrop && c.on;
+  if (mode) *mode = on ? int(c.rs.mode) : 0;
+  if (k) *k = on ? c.k : 0;
+  if (boxes) *boxes = on ? c.boxes : nullptr;
+  if (boxes_device) *boxes_device = on && plan->dev_tensor;
+  const dora::GatherDesc reach = on ? dora::crop_reach(c) : dora::GatherDesc{};
+  if (lo) *lo = reach.lo;
+  if (hi) *hi = reach.hi;
+  uint64_t head = 0, nunits = 0, tail = 0;
+  if (on) {
+    // the body's division of a sample at `dst`: single elements, whole units, single elements
+    const dora::gather::crop::Args a = dora::gather::crop::make_args(
+        f.gd, c, const_cast<uint8_t*>(static_cast<const uint8_t*>(dst)) + f.dst_off);
+    head = a.r.g.head;
+    nunits = a.r.g.nunits;
+    tail = a.r.g.total - head - (16u / a.r.dsize) * nunits;
   }
   if (head_elements) *head_elements = head;
   if (units) *units = nunits;

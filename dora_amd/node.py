@@ -34,6 +34,7 @@ _DL_HOST = (1, 3, 11)  # kDLCPU, kDLCUDAHost, kDLROCMHost (the latter two: pinne
 from .device import DeviceArray, DeviceBuffer
 from .tensor import Argmax as _Argmax
 from .tensor import Cast as _Cast
+from .tensor import Crops as _Crops
 from .tensor import Quantized as _Quantized
 from .tensor import Ragged as _Ragged
 from .tensor import Resized as _Resized
@@ -239,6 +240,9 @@ class Node:
                                       ctypes.addressof(c.schema), ARROW_DEVICE_CPU, metadata)
         elif hasattr(data, "__dlpack__") and hasattr(data, "__dlpack_device__"):
             rc = self._send_tensor(output_id, data, metadata, f)
+        elif isinstance(data, _Crops) or (isinstance(data, dict) and any(
+                isinstance(v, _Crops) for v in data.values())):
+            rc = self._send_tensor_crops(output_id, data, metadata, f)
         elif isinstance(data, _Resized) or (isinstance(data, dict) and any(
                 isinstance(v, _Resized) for v in data.values())):
             rc = self._send_tensor_resize(output_id, data, metadata, f)
@@ -265,9 +269,10 @@ class Node:
                             "a dict of such tensors, rows of either taken by an index "
                             "(dora_amd.tensor.take) or selected by a mask "
                             "(dora_amd.tensor.masked), a ragged batch of any of these "
-                            "(dora_amd.tensor.ragged) or tensors converted, reduced or resized "
-                            "on send (dora_amd.tensor.cast, dora_amd.tensor.quantize, "
-                            "dora_amd.tensor.argmax, dora_amd.tensor.resize)")
+                            "(dora_amd.tensor.ragged) or tensors converted, reduced, resized "
+                            "or cropped on send (dora_amd.tensor.cast, dora_amd.tensor.quantize, "
+                            "dora_amd.tensor.argmax, dora_amd.tensor.resize, "
+                            "dora_amd.tensor.crops)")
         if rc:
             _lib.check(rc)
 
@@ -584,6 +589,81 @@ class Node:
                                                "field in a message of its own)")
         return self._send_entries(output_id, data, (_Resized,), _fast.send_tensor_resize,
                                   self._lib.dora_node_send_output_tensor_resize, metadata, flags)
+
+    def _send_tensor_crops(self, output_id: str, data, metadata, flags: int) -> int:
+        """Boxes cut from a frame and resized on send (dora_amd.tensor.crops), or a dict of
+        tensors of which some are crops and the rest plain, as the tensor or Struct message of the
+        crops and the plain values (dora_node_send_output_tensor_crop).  A dict that also holds a
+        cast, a quantised, an argmax or a resized field is not offered: nothing is sent.  It keeps
+        a dispatch of its own, as `_send_tensor_affine` does: every field of crops brings one more
+        tensor, its boxes.
+
+        Boxes live where the frame lives.  With host values they are a sequence, a numpy array or
+        a CPU tensor, read inside the call.  With values on this node's GPU they are an int32
+        tensor there: they do the `__dlpack__(stream=<the node stream>)` handshake like every
+        field, are never read on the host, and an asynchronous send holds them with the values
+        until `sync()`."""
+        import numpy as np
+        for name, v in (data.items() if isinstance(data, dict) else ()):
+            if isinstance(v, (_Cast, _Quantized, _Argmax, _Resized)):
+                raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion, an argmax or a "
+                                               "resize beside crops in one message is not offered "
+                                               "(send the field in a message of its own)")
+        items, kind, tensors, names, entries = self._entries_of(data, (_Crops,))
+        boxes = []
+        for name, v in items.items():
+            if not isinstance(v, _Crops):
+                continue
+            what = "the boxes" if name is None else f"field `{name}`: the boxes"
+            b = v.boxes
+            on_device = hasattr(b, "__dlpack_device__") and \
+                int(b.__dlpack_device__()[0]) not in _DL_HOST
+            if on_device:
+                self._tensor_kind(b, what)
+            if kind == "device" and not on_device:
+                raise TypeError(f"{what} are in host memory and the frame on this node's GPU: "
+                                "boxes live where the frame lives (make them an int32 tensor on "
+                                "the device)")
+            if kind != "device" and on_device:
+                raise TypeError(f"{what} are in device memory and the frame in host memory: "
+                                "boxes live where the frame lives (move them to the host once)")
+            if kind != "device":
+                if not hasattr(b, "dtype"):  # a sequence
+                    b = np.asarray(b, dtype=np.int32)
+                    b = b.reshape(0, 4) if b.size == 0 else b
+                elif isinstance(b, np.ndarray) and not b.flags.writeable:
+                    b = np.array(b)  # (numpy exports no read-only array)
+            boxes.append(b)
+        if kind == "device":
+            caps, bcaps, done = self._device_caps(flags, tensors, boxes, len(tensors) + len(boxes))
+            bcaps = iter(bcaps)
+            ent = tuple(None if e is None else (*e[:7], next(bcaps)) for e in entries)
+            return done(_fast.send_tensor_crops(self.handle, output_id, names, caps, ent,
+                                                ARROW_DEVICE_ROCM, metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
+            from ctypes import pointer
+            from ._lib import Tensor, TensorCrop
+            from .tensor import _describe_array, _describe_list
+            described = [_describe_array(v) for v in tensors]
+            bdesc = iter([_describe_array(np.asarray(b)) for b in boxes])
+            lst, keep = _describe_list(names, [t for t, _ in described], Tensor(), 0,
+                                       ARROW_DEVICE_CPU)
+            arr, bkeep = (TensorCrop * len(tensors))(), []
+            for k, v in enumerate(items.values()):
+                if isinstance(v, _Crops):
+                    bkeep.append(next(bdesc))
+                    v._fill(arr[k], pointer(bkeep[-1][0]))
+            params = encode_parameters(metadata)
+            rc = self._lib.dora_node_send_output_tensor_crop(
+                self.handle, output_id.encode(), lst.fields, len(tensors), arr, dev, params,
+                len(params), flags)
+            del keep, described, bkeep
+            return rc
+        bcaps = iter([b.__dlpack__() for b in boxes])
+        ent = tuple(None if e is None else (*e[:7], next(bcaps)) for e in entries)
+        return _fast.send_tensor_crops(self.handle, output_id, names, caps, ent, dev, metadata,
+                                       flags)
 
     def _send_take(self, output_id: str, taken, batch, metadata, flags: int) -> int:
         """Rows taken by an index (dora_amd.tensor.take) as the tensor, Struct or — with

@@ -197,6 +197,26 @@ is copied once, so every source has been read when `send_output` returns.  A ten
 memory is read by a kernel: in place when dense, gathered by the gfx950 gather kernel when it is a
 strided view (one read and one write of HBM, no `.contiguous()` first).  The producer must share
 the HIP runtime of this library: import torch before dora_amd (Node._send_tensor).
+
+The hand-off from a detector to a second-stage model — K boxes cut out of one frame and brought to
+one size — is done inside the send: `crops(frame, boxes, size, axes=(-2, -1), mode="bilinear",
+dtype=None)` stands for the tensor of shape `(K,) + frame.shape` with the two extents at `axes`
+replaced by `size`.  `boxes` is a dense `[K, 4]` int32 tensor next to the frame (host with host,
+this node's HBM with HBM, where it is never read on the host), row k `(a_lo, b_lo, a_hi, b_hi)`:
+half-open ranges along `axes[0]` and `axes[1]`.  Every coordinate is clamped to the frame on its
+own; an empty or inverted box gives a crop of zeros; every other crop equals
+`from_numpy_resize(frame[.., a0:a1, .., b0:b1, ..], size, ..)` bit for bit.  `mode` and `dtype` are
+`resize`'s.  It is sent bare or as a value of a dict next to plain fields and other `crops`, which
+share the leading extent K:
+
+    node.send_output("rois", tensor.crops(frame, boxes, (128, 64), axes=(0, 1)))
+    node.send_output("out", {"crop": tensor.crops(frame, boxes, (128, 64), axes=(0, 1)),
+                             "box": boxes, "cls": cls})
+
+`from_numpy_crops` is the statement of record.  Not offered: fractional boxes (ROI-align), rotated
+boxes, a size per box, a batch index per box, int64 or float boxes, crops beside a `cast`,
+`quantize`, `argmax` or `resize` in one dict, crops of or under `cast`, `quantize`, `argmax`,
+`resize`, `ragged`, `take` or `masked`.
 """
 from __future__ import annotations
 
@@ -204,7 +224,7 @@ from ctypes import c_int64
 
 from ._lib import (REDUCE_ARGMAX, RESIZE_BILINEAR, RESIZE_NEAREST, Tensor, TensorAffine,
                    TensorCast, TensorField, TensorList, TensorMask, TensorQuant, TensorReduce,
-                   TensorResize, TensorTake)
+                   TensorCrop, TensorResize, TensorTake)
 
 _DL_CODES = {"i": 0, "u": 1, "f": 2, "b": 6, "c": 5}  # numpy dtype kind -> DLPack type code
 
@@ -347,6 +367,12 @@ def _has_argmax(values):
     return isinstance(values, Argmax)
 
 
+def _has_crops(values):
+    if isinstance(values, dict):
+        return any(isinstance(v, Crops) for v in values.values())
+    return isinstance(values, Crops)
+
+
 def _has_resized(values):
     if isinstance(values, dict):
         return any(isinstance(v, Resized) for v in values.values())
@@ -474,6 +500,8 @@ def cast(values, dtype, scale=None, *, bias=None, axis=None):
         raise TypeError("cast of an argmax is not offered: give argmax the index dtype to send")
     if isinstance(values, Resized):
         raise TypeError("cast of a resize is not offered: give resize the dtype to send")
+    if isinstance(values, Crops):
+        raise TypeError("cast of crops is not offered: give crops the dtype to send")
     if isinstance(values, (Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("cast converts one tensor: give a dict's fields a cast each; a cast under "
                         "ragged or take is not offered")
@@ -572,6 +600,8 @@ def quantize(values, dtype, scale=None, zero_point=0, *, bias=None, axis=None):
                         "send")
     if isinstance(values, Resized):
         raise TypeError("quantize of a resize is not offered: give resize the dtype to send")
+    if isinstance(values, Crops):
+        raise TypeError("quantize of crops is not offered: give crops the dtype to send")
     if isinstance(values, (Quantized, Cast, Taken, Masked, Ragged, dict)):
         raise TypeError("quantize converts one tensor: give a dict's fields a quantize each; a "
                         "quantise of a cast, or under ragged, take or masked, is not offered")
@@ -639,6 +669,9 @@ def argmax(values, axis, dtype="int64"):
     if isinstance(values, Resized):
         raise TypeError("argmax of a resize is not offered: reduce the resized tensor yourself, or "
                         "send the two in messages of their own")
+    if isinstance(values, Crops):
+        raise TypeError("argmax of crops is not offered: reduce the crops yourself, or send the "
+                        "two in messages of their own")
     if isinstance(values, (Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
         raise TypeError("argmax reduces one tensor: give a dict's fields an argmax each; an argmax "
                         "of a cast, a quantise, a take, a mask or a ragged batch is not offered")
@@ -721,6 +754,8 @@ def resize(values, size, *, axes=(-2, -1), mode="nearest", dtype=None):
     (half-pixel centres, no antialiasing), `dtype` "float16", "float32", "uint8", "int8", "uint16"
     or "int16" (or the numpy or torch dtype; None: the source's own).  `send_output` sends it, on
     its own or as a value of a dict of tensors, as what `from_numpy_resize` states."""
+    if isinstance(values, Crops):
+        raise TypeError("resize of crops is not offered: give crops the size to send")
     if isinstance(values, (Resized, Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
         raise TypeError("resize resizes one tensor: give a dict's fields a resize each; a resize "
                         "of a cast, a quantise, an argmax, a take, a mask or a ragged batch is not "
@@ -807,6 +842,98 @@ def _numpy_resize(x, size, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=F
         return r.astype(np.int32).astype(dt)
 
 
+class Crops:
+    """Boxes cut from a frame and resized on send: `values`, the frame, `boxes`, the `[K, 4]`
+    int32 tensor next to it, and what a `Resized` holds: the two `axes` cropped (counted from the
+    front), the extents `size` of every crop, the `mode` and the destination `dtype` (None: the
+    frame's own).  It reads, cuts and resizes nothing itself.  Build one with `crops`."""
+
+    __slots__ = ("values", "boxes", "size", "axes", "mode", "dtype", "_resized")
+    _STRUCT = TensorCrop
+
+    def __init__(self, values, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None):
+        try:
+            r = Resized(values, size, axes, mode, dtype)
+        except (TypeError, ValueError) as e:
+            raise type(e)(str(e).replace("resize:", "crops:", 1)) from None
+        if not hasattr(boxes, "shape") and not isinstance(boxes, (list, tuple)):
+            raise TypeError("crops: the boxes are a [K, 4] int32 tensor next to the frame")
+        self._resized = r
+        self.values, self.boxes = values, boxes
+        self.size, self.axes, self.mode, self.dtype = r.size, r.axes, r.mode, r.dtype
+
+    def _entry(self):
+        """`Resized._entry()` and the boxes, which the node replaces by what it hands on."""
+        return (*self._resized._entry(), self.boxes)
+
+    def _fill(self, a, boxes=None):
+        """Entry `a` (dora_tensor_crop); `boxes` a ctypes pointer to the boxes' `Tensor`, which
+        the caller keeps alive."""
+        self._resized._fill(a)
+        if boxes is not None:
+            a.boxes = boxes
+
+    def __repr__(self):
+        return (f"Crops({self.values!r} by {self.boxes!r} axes {self.axes} -> {self.size}, "
+                f"{self.mode}{'' if self.dtype is None else ' -> ' + self.dtype})")
+
+
+def crops(frame, boxes, size, *, axes=(-2, -1), mode="bilinear", dtype=None):
+    """The K `boxes` of `frame`, each cut out and brought to the extents `size`, as a message:
+    `frame` a tensor of uint8, int8, uint16, int16, float16, bfloat16 or float32 with 2 to 7
+    dimensions (host memory or this node's HBM, any strided view), `boxes` a dense `[K, 4]` int32
+    tensor where the frame lives (never read on the host when that is HBM), row k
+    `(a_lo, b_lo, a_hi, b_hi)`, half-open ranges along `axes[0]` and `axes[1]`; `size`, `axes`,
+    `mode` and `dtype` as `resize` takes them.  Coordinates are clamped to the frame, a box that is
+    then empty gives zeros.  `send_output` sends it, on its own or as a value of a dict of tensors,
+    as what `from_numpy_crops` states: a tensor of shape `(K,) + frame.shape` with the two extents
+    replaced."""
+    if isinstance(frame, (Crops, Resized, Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
+        raise TypeError("crops cuts boxes from one tensor: give a dict's fields their crops each; "
+                        "crops of a cast, a quantise, an argmax, a resize, a take, a mask or a "
+                        "ragged batch are not offered")
+    return Crops(frame, boxes, size, axes, mode, dtype)
+
+
+def from_numpy_crops(x, boxes, size, *, axes=(-2, -1), mode="bilinear", dtype=None,
+                     bfloat16=False):
+    """The nested pyarrow array of the crops of `x`, the statement of record of `crops`: what
+    `send_output(output_id, crops(x, boxes, size, axes=axes, mode=mode, dtype=dtype))` puts on the
+    wire.  With Ia, Ib the extents of `x` along `axes`, row k of `boxes` is clamped word by word,
+    `a0 = min(max(a_lo, 0), Ia)`, `a1 = min(max(a_hi, 0), Ia)`, the same for b; crop k is all
+    zeros where `a1 <= a0` or `b1 <= b0`, and else `from_numpy_resize` of
+    `x[.., a0:a1, .., b0:b1, ..]`.  `bfloat16` as `from_numpy_resize` takes it."""
+    return from_numpy(_numpy_crops(x, boxes, size, axes, mode, dtype, bfloat16))
+
+
+def _numpy_crops(x, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None, bfloat16=False):
+    """`from_numpy_crops`' values as a numpy array."""
+    import numpy as np
+    x = np.asarray(x)
+    boxes = np.asarray(boxes)
+    if boxes.size == 0:  # (an empty list is an array of float64)
+        boxes = boxes.reshape(0, 4).astype(np.int32)
+    if boxes.ndim != 2 or boxes.shape[1] != 4 or boxes.dtype.kind not in "iu":
+        raise ValueError("boxes are [K, 4] integers")
+    if not 2 <= x.ndim <= 7:
+        raise ValueError("a crops message cuts a frame of 2 to 7 dimensions")
+    a, b = (ax + x.ndim if ax < 0 else ax for ax in axes)
+    if a == b or not (0 <= a < x.ndim and 0 <= b < x.ndim):
+        raise ValueError(f"axes {tuple(axes)} of {x.ndim} dimensions")
+    whole = _numpy_resize(x, size, axes, mode, dtype, bfloat16)  # (the refusals, shape and dtype)
+    out = np.zeros((boxes.shape[0],) + whole.shape, whole.dtype)
+    ia, ib = x.shape[a], x.shape[b]
+    for k, (alo, blo, ahi, bhi) in enumerate(boxes.tolist()):
+        a0, a1 = min(max(alo, 0), ia), min(max(ahi, 0), ia)
+        b0, b1 = min(max(blo, 0), ib), min(max(bhi, 0), ib)
+        if a1 <= a0 or b1 <= b0:
+            continue
+        cut = [slice(None)] * x.ndim
+        cut[a], cut[b] = slice(a0, a1), slice(b0, b1)
+        out[k] = _numpy_resize(x[tuple(cut)], size, axes, mode, dtype, bfloat16)
+    return out
+
+
 def take(values, index):
     """`values[index]` along dimension 0 as a message: `values` a tensor or a dict of at most 8
     tensors sharing their leading extent N, `index` a 1-D sequence or tensor of K int32 or int64
@@ -823,6 +950,9 @@ def take(values, index):
     if _has_argmax(values):
         raise TypeError("argmax under take is not offered: reduce the taken rows yourself, or "
                         "send the argmax without the take")
+    if _has_crops(values):
+        raise TypeError("crops under take are not offered: crop the taken rows yourself, or send "
+                        "the crops without the take")
     if _has_resized(values):
         raise TypeError("resize under take is not offered: resize the taken rows yourself, or "
                         "send the resize without the take")
@@ -846,6 +976,9 @@ def masked(values, mask):
     if _has_argmax(values):
         raise TypeError("argmax under a mask is not offered: reduce the values yourself, or send "
                         "the argmax without the mask")
+    if _has_crops(values):
+        raise TypeError("crops under a mask are not offered: crop the values yourself, or send "
+                        "the crops without the mask")
     if _has_resized(values):
         raise TypeError("resize under a mask is not offered: resize the values yourself, or send "
                         "the resize without the mask")
@@ -867,6 +1000,9 @@ def ragged(values, *, lengths=None, offsets=None):
     if _has_argmax(values):
         raise TypeError("argmax under ragged is not offered: reduce the values yourself, or send "
                         "the argmax without the partition")
+    if _has_crops(values):
+        raise TypeError("crops under ragged are not offered: crop the values yourself, or send "
+                        "the crops without the partition")
     if _has_resized(values):
         raise TypeError("resize under ragged is not offered: resize the values yourself, or send "
                         "the resize without the partition")
@@ -1165,4 +1301,5 @@ __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_nump
            "from_numpy_ragged", "from_numpy_take", "from_numpy_masked", "to_numpy", "to_torch",
            "Ragged", "ragged", "Taken", "take", "Masked", "masked", "Cast", "cast",
            "from_numpy_cast", "Quantized", "quantize", "from_numpy_quantize", "Argmax", "argmax",
-           "from_numpy_argmax", "Resized", "resize", "from_numpy_resize"]
+           "from_numpy_argmax", "Resized", "resize", "from_numpy_resize", "Crops", "crops",
+           "from_numpy_crops"]

@@ -672,6 +672,65 @@ typedef struct dora_tensor_resize { /* mode == 0: this field is sent as it is */
 int dora_gpu_plan_tensor_resize(const dora_tensor_field* fields, size_t n,
                                 const dora_tensor_resize* resizes /* NULL or n entries */,
                                 ArrowDeviceType device_type, dora_plan** out);
+/*
+ * Crops as one message: a field with a crop entry is sent as K boxes cut out of one frame, each
+ * brought to the same two extents — the detections of a 1080x1920x3 frame as the K x 128 x 64 x 3
+ * a second-stage model reads — boxes and taps read where they live, so the boxes never come to
+ * the host and only the small tensor is written.  `fields` as dora_gpu_plan_tensor_struct takes
+ * them (one field with a NULL name: a bare tensor); `crops` is NULL or n entries, and an entry
+ * with mode 0 leaves its field as it is.  With `crops` NULL or every mode 0 the call plans exactly
+ * as dora_gpu_plan_tensor (bare) or dora_gpu_plan_tensor_struct does, refusals included.
+ *
+ * A field of crops is a frame — a tensor of one of the seven cast sources, any strided view of 2
+ * to 7 dimensions — with `mode`, `axis`, `size`, `dtype_code` and `dtype_bits` exactly as
+ * dora_tensor_resize has them, and `boxes`: a dense [K, 4] int32 tensor, 0 <= K <= 2^20, its
+ * data + byte_offset a multiple of 4, living where the values live (`device_type`).  Row k is
+ * (a_lo, b_lo, a_hi, b_hi): the half-open ranges [a_lo, a_hi) along axis[0] and [b_lo, b_hi)
+ * along axis[1], in elements of the frame as given.  The wire form — type info, size, leaf offset
+ * and padding — is that of the tensor of the destination dtype whose shape is (K,) followed by the
+ * frame's with the two extents replaced by `size`; the fields of a record share the leading
+ * extent, which for a field of crops is K.
+ *
+ * The statement.  The frame's extents along the two axes are Ia and Ib.  For box k:
+ *   clamp:  a0 = min(max(a_lo, 0), Ia), a1 = min(max(a_hi, 0), Ia), the same for b — every word
+ *           on its own, before any difference is taken, so no value of an int32 overflows;
+ *   empty:  if a1 <= a0 or b1 <= b0 every byte of crop k is zero;
+ *   else:   crop k is dora_gpu_plan_tensor_resize's statement with the source extents a1 - a0 and
+ *           b1 - b0 and the taps a0 + i, b0 + i: the resize of frame[.., a0:a1, .., b0:b1, ..],
+ *           bit for bit but for the payload of a NaN in a float destination.
+ * Clamping and zeros are the meaning, not error handling: detectors emit boxes that overhang the
+ * frame's edge, and outputs of a fixed capacity pad with boxes of zeros.
+ *
+ * Host values are cropped by the CPU inside this call, which reads the boxes (a host plan like any
+ * other, ROCM_HOST sources too).  Device values and device boxes are never read on the host: the
+ * frame's reach is that of its whole view, the boxes' their 16 * K bytes, each held against its
+ * own allocation before anything is launched (a refusal says which), and the plan is one launch of
+ * gather_crop_kernel (gfx950), plain fields through their usual bodies.  K == 0 is the empty
+ * message and nothing is launched.
+ *
+ * Refusals, each naming the field in a record.  DORA_ERR_INVALID: a frame of fewer than 2 or more
+ * than 7 dimensions, or of extent 0; an axis outside them, the two axes equal, a frame extent or
+ * a size outside [1, 32768]; boxes that are NULL, not int32, not of shape [K, 4], not dense or not
+ * on a multiple of 4; K above 2^20; device boxes outside device memory (boxes on the other side
+ * from the values; the Python node refuses the pair before it plans); a record whose leading
+ * extents differ.  DORA_ERR_UNSUPPORTED, naming it: a source that is not one of the seven, a
+ * destination that is not one of the six, a bfloat16 source without a destination, a mode other
+ * than the two.
+ * Not provided: fractional boxes / ROI-align, rotated boxes, per-box sizes, a batch index per box,
+ * int64 or float boxes, crops beside a conversion, a reduction or a resize in one record, crops
+ * under a ragged batch, a take or a mask.
+ */
+typedef struct dora_tensor_crop { /* mode == 0: this field is sent as it is */
+  uint32_t mode;      /* DORA_RESIZE_NEAREST or DORA_RESIZE_BILINEAR */
+  int32_t axis[2];    /* 0 <= axis < ndim of the frame as given, different */
+  int64_t size[2];    /* the extents of every crop, in the order of axis */
+  uint8_t dtype_code; /* the destination (DLPack); dtype_bits 0: the source's own dtype */
+  uint8_t dtype_bits;
+  const dora_tensor* boxes; /* [K, 4] int32, dense, where the values live */
+} dora_tensor_crop;
+int dora_gpu_plan_tensor_crop(const dora_tensor_field* fields, size_t n,
+                              const dora_tensor_crop* crops /* NULL or n entries */,
+                              ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -948,6 +1007,16 @@ int dora_node_send_output_tensor_resize(dora_node* node, const char* output_id,
                                         const dora_tensor_resize* resizes,
                                         ArrowDeviceType device_type, const uint8_t* params,
                                         size_t params_len, uint32_t flags);
+/* Send crops (dora_gpu_plan_tensor_crop: the statement, where the boxes live, refusals), with the
+ * contract of dora_node_send_output_tensor_resize: host values and host boxes are read and cropped
+ * on return, device values and device boxes are read by one launch on a fill stream, and the
+ * synchronous send waits for the read; with DORA_SEND_ASYNC the caller keeps the boxes alive and
+ * unwritten with the fields until dora_node_sync. */
+int dora_node_send_output_tensor_crop(dora_node* node, const char* output_id,
+                                      const dora_tensor_field* fields, size_t n,
+                                      const dora_tensor_crop* crops,
+                                      ArrowDeviceType device_type, const uint8_t* params,
+                                      size_t params_len, uint32_t flags);
 /* Send rows selected by a mask (dora_gpu_plan_tensor_mask: wire form, where the mask lives,
  * refusals), with the contract of the take send: host values with a host mask take every path of
  * a host plan and everything has been read on return; device values with a device mask go where

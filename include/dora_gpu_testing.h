@@ -161,6 +161,18 @@ int dora_gpu_test_plan_resize(const dora_plan* plan, size_t i, const void* dst, 
                               uint64_t* outputs, int* dst_bits, int64_t* in_extent,
                               int64_t* out_extent, int64_t* axis_stride, uint64_t* head_elements,
                               uint64_t* units, uint64_t* tail_elements);
+/* Test tool (host only): whether field `i` of a device plan of dora_gpu_plan_tensor_crop is a
+ * field of crops (*mode DORA_RESIZE_NEAREST or DORA_RESIZE_BILINEAR; 0 for a field sent as it is
+ * and for any other plan that keeps its fields; a host plan keeps none): then *k the K boxes,
+ * *boxes their first byte, *boxes_device 1 if the launch reads them in HBM, [*lo, *hi] the bytes
+ * from *boxes that are checked against their allocation, and the unit paths the body takes into a
+ * sample at address `dst`: *head_elements and *tail_elements the elements written singly before
+ * the first and after the last whole 16-byte unit, *units the whole units.
+ * dora_gpu_test_plan_field keeps reporting the view of the whole frame and its reach. */
+int dora_gpu_test_plan_crop(const dora_plan* plan, size_t i, const void* dst, int* mode,
+                            uint64_t* k, const void** boxes, int* boxes_device, int64_t* lo,
+                            int64_t* hi, uint64_t* head_elements, uint64_t* units,
+                            uint64_t* tail_elements);
 /* Test tool: counts[4], the launches of this process so far over the fields of a plan, by kernel:
  * gather_struct_kernel, gather_cast_kernel, gather_quant_kernel, gather_affine_kernel. */
 int dora_gpu_test_fields_launches(uint64_t* counts);
@@ -180,7 +192,7 @@ int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mas
  * host plan, dense device plans, empty plans), 1 the gather of its one strided view, 2
  * gather_struct_kernel over its fields, 3 gather_cast_kernel / gather_quant_kernel, 4 the taken
  * body by an index in HBM, 5 a mask's count, compact and taken launches, 6 gather_reduce_kernel,
- * 7 gather_resize_kernel; *scan 1 if that launch
+ * 7 gather_resize_kernel, 8 gather_crop_kernel; *scan 1 if that launch
  * also scans a partition in HBM; *checked 1 if the plan reads HBM whose range is checked before
  * anything is launched. */
 int dora_gpu_test_plan_launch(const dora_plan* plan, int* launch, int* scan, int* checked);

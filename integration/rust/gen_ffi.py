@@ -22,7 +22,7 @@ SIZED = {"dora_fill_ticket"}
 STRUCTS = {"dora_tensor", "dora_tensor_cast", "dora_tensor_quant", "dora_tensor_field",
            "dora_tensor_list",
            "dora_tensor_take", "dora_tensor_mask", "dora_tensor_affine", "dora_tensor_reduce",
-           "dora_tensor_resize"}
+           "dora_tensor_resize", "dora_tensor_crop"}
 SCALAR = {"uint16_t": "u16", "int": "c_int", "int64_t": "i64", "uint64_t": "u64", "uint32_t": "u32",
           "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64",
           "uint8_t": "u8", "char": "c_char", "void": "c_void", "ArrowDeviceType": "ArrowDeviceType",
