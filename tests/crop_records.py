@@ -264,6 +264,30 @@ def cases():
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def limit_cases():
+    """[(label, record, destination offsets mod 16)] at the edge of the contract, beside `cases()`:
+    a frame with an axis of 32768 steps cut by boxes over all of it, its last row, all but its
+    first and last row, and the int32 extremes, to crops of 32768 x 1 and of 7 x 2.  None has more
+    than 100 000 output elements."""
+    n = rr.LIMIT
+    b = cr.source("uint8", (n, 3), seed=71)
+    inside = [(0, 0, n, 3), (n - 1, 0, n, 3), (1, 0, n - 1, 2)]
+    extremes = [(I32_MIN, I32_MIN, I32_MAX, I32_MAX), (I32_MAX, I32_MAX, I32_MIN, I32_MIN),
+                (I32_MIN, 1, n - 1, I32_MAX)]
+    out = []
+    for label, rows in (("boxes over the long axis", inside), ("int32 extremes", extremes)):
+        out.append((f"{label} -> ({n}, 1) bilinear",
+                    [(None, b, b, crop("uint8", (0, 1), (n, 1), rows, "bilinear"))], (0,)))
+    out.append((f"boxes over the long axis -> ({n}, 1) nearest to float16",
+                [(None, b, b, crop("uint8", (0, 1), (n, 1), inside, "nearest", "float16"))], (2,)))
+    for mode in MODES:
+        out.append((f"all six boxes -> (7, 2) {mode}",
+                    [(None, b, b, crop("uint8", (0, 1), (7, 2), inside + extremes, mode, mis=4))],
+                    (0, 5)))
+    return out
+
+
 def many():
     """[(label, record)]: K = 40 crops of 32 x 32 x 3 uint8 — 7680 units, 30 workgroups — from a
     (70, 90, 3) view cut from a wider base, both modes, by seeded boxes of which 30 overhang the

@@ -253,6 +253,64 @@ def cases():
     return out
 
 
+LIMIT = 32768  # the largest I and O of the statement
+# output extents at which the weights are read directly: small odd ones, either side of 2^8 and
+# 2^12, 2^16 / 3, and the limit and the one below it
+WEIGHT_EXTENTS = (3, 5, 7, 255, 256, 257, 4095, 4097, 21845, LIMIT - 1, LIMIT)
+# float32 frames of one column whose bilinear resize along axis 0 is a weight of every output
+# coordinate: w1, w0, and with I = 3 the other residues
+WEIGHT_FRAMES = (("w1", [[0], [1]]), ("w0", [[1], [0]]), ("I = 3", [[0], [0], [1]]))
+
+
+@functools.lru_cache(maxsize=None)
+def limit_cases():
+    """[(label, record, destination offsets mod 16)] at the edge of the contract, beside `cases()`:
+    axes of 32768 source or output steps over small frames, where (2 * o + 1) * I reaches
+    2^31 - 32768 and d = 2 * O is 65536, and the weights of WEIGHT_EXTENTS read directly.  None
+    has more than 100 000 output elements."""
+    out = []
+    u = cr.source("uint8", (LIMIT, 3), seed=71)
+    for mode in MODES:
+        for size in ((LIMIT - 1, 2), (LIMIT, 3)):
+            out.append((f"({LIMIT}, 3) uint8 -> {size} {mode}",
+                        [(None, u, u, rs("uint8", (0, 1), size, mode))], (0,)))
+    w = cr.source("int16", (3, LIMIT), seed=72)
+    out.append((f"(3, {LIMIT}) int16 -> (5, {LIMIT - 1}) float16",
+                [(None, w, w, rs("int16", (0, 1), (5, LIMIT - 1), "bilinear", "float16"))], (0,)))
+    f = cr.source("float32", (2, 3), seed=73)
+    out.append((f"(2, 3) float32 -> ({LIMIT}, 2)",
+                [(None, f, f, rs("float32", (0, 1), (LIMIT, 2), "bilinear"))], (4,)))
+    for mode in MODES:
+        out.append((f"({LIMIT}, 1) -> (1, 1) {mode}",
+                    [(None, u, u[:, 1:2], rs("uint8", (0, 1), (1, 1), mode, "float32"))], (0,)))
+    wide = cr.source("uint8", (2 * LIMIT, 3), seed=74)
+    out.append((f"({LIMIT}, 3) cut with step 2 -> ({LIMIT - 1}, 2)",
+                [(None, wide, wide[::2], rs("uint8", (0, 1), (LIMIT - 1, 2), "bilinear"))], (3,)))
+    out.append((f"({LIMIT}, 3) cut with step -2 -> ({LIMIT - 1}, 2)",
+                [(None, wide, wide[::-2], rs("uint8", (0, 1), (LIMIT - 1, 2), "bilinear"))], (0,)))
+    for label, rows in WEIGHT_FRAMES:
+        x = np.array(rows, np.float32)
+        for o in WEIGHT_EXTENTS:
+            out.append((f"{label} O={o}", [(None, x, x, rs("float32", (0, 1), (o, 1), "bilinear"))],
+                        (0,)))
+    return out
+
+
+def weights_in_float64(n_in, n_out):
+    """(w0, w1, where the last source element stands alone) of every output coordinate of a
+    bilinear axis by the statement's integer formula,
+    the division in float64 and rounded to float32 once.  That is the correctly rounded float32
+    quotient: float64's 53 bits are at least 2 * 24 + 2, so rounding a quotient twice is
+    innocuous."""
+    o = np.arange(n_out, dtype=np.int64)
+    d = 2 * n_out
+    n = np.maximum((2 * o + 1) * n_in - n_out, 0)
+    last = n // d >= n_in - 1
+    r = np.where(last, 0, n % d)
+    return (((d - r).astype(np.float64) / d).astype(np.float32),
+            (r.astype(np.float64) / d).astype(np.float32), last)
+
+
 def record(d0=2):
     """A resized batch of HWC thumbnails between a plain int64 field and a strided plain float32
     field, then a second resized field to float16 whose leading extent is a resized one."""

@@ -142,6 +142,19 @@ def test_more_than_one_workgroup_through_the_emulated_body(lib, emulator, tmp_pa
     assert counts["grid"] == 4 * 30 and counts["units"] >= 4 * 7679, counts
 
 
+def test_the_limit_of_the_contract_through_the_emulated_body(lib, emulator, tmp_path):
+    """A frame axis of 32768 steps under boxes over all of it, its last row alone and the int32
+    extremes, to crops of 32768 x 1 and 7 x 2."""
+    batch = Batch(tmp_path)
+    for label, rec, offsets in kr.limit_cases():
+        expect = kr.want(rec[0][2], rec[0][3])
+        assert expect.size <= 100000 and sum(bool(e.any()) for e in expect) >= 2, label
+        for mis in offsets:
+            batch.add(f"{label} dst%16={mis}", rec, DST + mis)
+    counts = batch.run(emulator)
+    assert counts["units"] > 6 * 32768 // 16, counts
+
+
 def test_units_straddle_crops(lib):
     """The crops of 15 uint8 elements: at each destination offset some whole unit holds the last
     elements of one crop and the first of the next, into the empty second crop and out of it."""

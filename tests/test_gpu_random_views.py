@@ -10,14 +10,27 @@ garbage.  Every view was first checked to lie inside its base, and every base li
 one source buffer a test allocates: nothing here hands the GPU an address it could fault on.  A
 cast whose source is off its element size is refused with nothing launched.
 
+The five op kernels (quantise, affine, argmax, resize, crops) run the first 200 seeds of their host
+ranges through `run_op`: the bytes of every field equal the op's `want` through its `same`.  Affine
+tables go to the words buffer at 4, 8, 12 and 0 mod 16 in turn; a crop's boxes are bases like its
+frame, and garbage lives only in their words, which the kernel clamps by contract.  Argmax packs
+every seed under the body the library chooses and, wherever the wave body applies, under the other
+one.  20 seeds per op put the op on a source off its element size: refused by the field's name,
+the destination keeps its poison.
+
 Each test allocates its buffers once, for its largest case, and poisons the destination anew for
 every pack.  A failure prints `seed=`: tests/random_views.py reproduces the case from it."""
 import numpy as np
 import pytest
 
+from tests import affine_records as ar
+from tests import argmax_records as am
 from tests import cast_records as cr
+from tests import crop_records as kr
 from tests import mask_records as mr
+from tests import quant_records as qr
 from tests import random_views as rv
+from tests import resize_records as rr
 from tests import struct_records as sr
 from tests import take_records as tr
 from tests import test_random_views_host as host
@@ -33,6 +46,11 @@ RECORD_SEEDS = host.RECORD_SEEDS[:150]
 TAKE_SEEDS = host.TAKE_SEEDS[:200]
 CAST_SEEDS = host.CAST_SEEDS[:200]
 MASK_SEEDS = host.MASK_SEEDS[:150]
+QUANT_SEEDS = host.QUANT_SEEDS[:200]
+AFFINE_SEEDS = host.AFFINE_SEEDS[:200]
+ARGMAX_SEEDS = host.ARGMAX_SEEDS[:200]
+RESIZE_SEEDS = host.RESIZE_SEEDS[:200]
+CROP_SEEDS = host.CROP_SEEDS[:200]
 
 
 @pytest.fixture(scope="module")
@@ -249,6 +267,164 @@ def test_casts(dev):
         assert bufs.untouched(bufs.dst.size)
     finally:
         bufs.free()
+
+
+# ---------------------------------------------------------------------------------------------
+# The op bodies: quantise, affine, argmax, resize, crops
+# ---------------------------------------------------------------------------------------------
+class Op:
+    """What the sweep of one op kernel needs of its tests/*_records.py: the record's (name, base,
+    view) triples (a crop's boxes and nothing else are bases too), its oracle, its plan over the
+    buffers, the wanted array of a field and the comparison."""
+
+    def __init__(self, name, triples, oracle, plan, want, same):
+        self.name, self.triples, self.oracle, self.plan = name, triples, oracle, plan
+        self.want, self.same = want, same
+
+
+def first_three(rec):
+    return [x[:3] for x in rec]
+
+
+def upload_tables(bufs, rec):
+    """The tables of an affine record in the words buffer, each at 4, 8, 12 or 0 mod 16 in turn;
+    {id(table): device pointer}."""
+    ptrs, at = {}, 0
+    for k, t in enumerate(ar.tables_of(rec)):
+        at = (at + 15) // 16 * 16 + 4 * ((k + 1) % 4)
+        ptrs[id(t)] = bufs.upload(t, at)
+        at += t.nbytes
+    return ptrs
+
+
+def plan_affine(rec, bufs):
+    from dora_amd._lib import ARROW_DEVICE_ROCM
+    ptrs = upload_tables(bufs, rec)
+    return ar.plan_affine(rec, bufs.ptr_of, ARROW_DEVICE_ROCM, lambda t: ptrs[id(t)])
+
+
+def device_plan(plan):
+    from dora_amd._lib import ARROW_DEVICE_ROCM
+    return lambda rec, bufs: plan(rec, bufs.ptr_of, ARROW_DEVICE_ROCM)
+
+
+OPS = {
+    "quant": Op("quant", first_three, qr.oracle, device_plan(qr.plan_convert),
+                lambda x: qr.want(x[2], x[3]), qr.same),
+    "affine": Op("affine", first_three, ar.oracle, plan_affine,
+                 lambda x: ar.want(x[2], x[3], x[4]), ar.same),
+    "argmax": Op("argmax", first_three, am.oracle, device_plan(am.plan_reduce),
+                 lambda x: am.want(x[2], x[3]), am.same),
+    "resize": Op("resize", first_three, rr.oracle, device_plan(rr.plan_resize),
+                 lambda x: rr.want(x[2], x[3]), rr.same),
+    "crop": Op("crop", kr.triples, kr.oracle, device_plan(kr.plan_crop),
+               lambda x: kr.want(x[2], x[3]), kr.same),
+}
+
+
+def table_room(recs):
+    return max([sum(t.nbytes + 32 for t in ar.tables_of(rec)) for rec in recs if len(rec[0]) == 5]
+               + [64])
+
+
+def check_fields(op, got, rec, ranges, what):
+    """Every field's bytes are the op's `want`, every byte outside the fields keeps the poison."""
+    pad = bytearray(got)
+    for (off, ln), x in zip(ranges, rec):
+        op.same(got[off:off + ln], op.want(x), what)
+        pad[off:off + ln] = bytes([POISON]) * ln
+    assert bytes(pad) == bytes([POISON]) * len(got), "padding written, " + what
+
+
+def run_op(dev, op, seeds, cases, refused_seeds, other_bodies=None):
+    """The sweep of one op kernel: every case of `cases` ((record, destination mod 16, ..) of
+    `seeds`) packed and compared, then the misaligned records of `refused_seeds` refused by name
+    with nothing launched.  `other_bodies(plan, rec, mis)` yields what to pack once more."""
+    from dora_amd._lib import DoraGpuError
+    refused = [rv.misaligned_op(rv.rng(seed), op.name) for seed in refused_seeds]
+    recs = [c[0] for c in cases]
+    oracles = [op.oracle(rec) for rec in recs]
+    bufs = Buffers(dev, source_room([op.triples(rec) for rec in recs + refused]),
+                   max(len(o[0]) for o in oracles) + 64, table_room(recs + refused))
+    try:
+        for seed, case, (sample, info, ranges) in zip(seeds, cases, oracles):
+            rec, mis = case[0], case[1]
+            what = f"seed={seed} dst%16={mis}"
+            assert all(rv.inside(b, v) for _, b, v in op.triples(rec)), what
+            bufs.place(sr.bases_of(op.triples(rec)))
+            with op.plan(rec, bufs) as p:
+                assert p.size == len(sample) and p.type_info().to_json() == info.to_json(), what
+                assert p.segments() == [], what
+                got, intact = bufs.pack(p, mis)
+                assert intact, "guard bands overwritten, " + what
+                check_fields(op, got, rec, ranges, what)
+            for label in (other_bodies(rec, mis, bufs) if other_bodies else ()):
+                with op.plan(rec, bufs) as p:
+                    got, intact = bufs.pack(p, mis)
+                assert intact, f"guard bands overwritten, {what} {label}"
+                check_fields(op, got, rec, ranges, f"{what} {label}")
+        # an op on a source off its element size: refused by name, nothing launched
+        bufs.dst.fill(POISON, dev)
+        for seed, rec in zip(refused_seeds, refused):
+            bufs.place(sr.bases_of(op.triples(rec)))
+            assert bufs.ptr_of(rec[1][1]) % rec[1][1].itemsize in (1, 3)
+            with pytest.raises(DoraGpuError) as e:
+                with op.plan(rec, bufs) as p:
+                    p.pack(bufs.dst.ptr + GUARD, p.size, dev)
+            assert e.value.code == -1 and "field 1 `f1`" in str(e.value), (f"seed={seed}", str(e.value))
+        assert bufs.untouched(bufs.dst.size)
+    finally:
+        bufs.free()
+
+
+def test_quants(dev):
+    run_op(dev, OPS["quant"], QUANT_SEEDS, [host.quant_case(s) for s in QUANT_SEEDS],
+           host.MISALIGNED_QUANT_SEEDS)
+
+
+def test_affines(dev):
+    run_op(dev, OPS["affine"], AFFINE_SEEDS, [host.affine_case(s) for s in AFFINE_SEEDS],
+           host.MISALIGNED_AFFINE_SEEDS)
+
+
+def test_argmaxes(dev):
+    """Every seed under the body the library chooses, and wherever the wave body applies under
+    the one it did not choose."""
+    from dora_amd import _lib
+    from dora_amd._lib import ARROW_DEVICE_ROCM
+    others = [0]
+
+    def bodies(rec, bufs, mis):
+        with am.plan_reduce(rec, bufs.ptr_of, ARROW_DEVICE_ROCM) as p:
+            return [k["body"] for k in am.plan_reduces(p, len(rec), bufs.dst.ptr + GUARD + mis)]
+
+    def other_bodies(rec, mis, bufs):
+        chosen = bodies(rec, bufs, mis)
+        for mode in (1, 2):
+            _lib.call("dora_gpu_test_reduce_body", mode)
+            if bodies(rec, bufs, mis) != chosen:
+                others[0] += 1
+                yield f"body {mode}"
+        _lib.call("dora_gpu_test_reduce_body", 0)
+
+    try:
+        run_op(dev, OPS["argmax"], ARGMAX_SEEDS, [host.argmax_case(s) for s in ARGMAX_SEEDS],
+               host.MISALIGNED_ARGMAX_SEEDS, other_bodies)
+    finally:
+        _lib.call("dora_gpu_test_reduce_body", 0)
+    assert others[0] >= 20, others
+
+
+def test_resizes(dev):
+    run_op(dev, OPS["resize"], RESIZE_SEEDS, [host.resize_case(s) for s in RESIZE_SEEDS],
+           host.MISALIGNED_RESIZE_SEEDS)
+
+
+def test_crops(dev):
+    """Garbage lives only in the words of the boxes, which the kernel clamps by contract."""
+    cases = [host.crop_case(s) for s in CROP_SEEDS]
+    assert any(not len(rec[0][3]["boxes"]) for rec, _ in cases if rec[0][3])  # K = 0 among them
+    run_op(dev, OPS["crop"], CROP_SEEDS, cases, host.MISALIGNED_CROP_SEEDS)
 
 
 def test_masks(dev):

@@ -80,6 +80,14 @@ def test_more_than_one_workgroup(dev):
         run_record(rec, dev, (0, 7), label)
 
 
+def test_the_limit_of_the_contract(dev):
+    """crop_records.limit_cases(): a frame axis of 32768 steps under boxes over all of it, its
+    last row and the int32 extremes, each after it passed the emulation in
+    test_crop_index_host.py."""
+    for label, rec, offsets in kr.limit_cases():
+        run_record(rec, dev, offsets, label)
+
+
 def test_refused_with_nothing_launched(dev):
     """Boxes that end one byte past their allocation, named; a frame whose view does; a destination
     that is odd for int16: DORA_ERR_INVALID, the destination keeps its poison.  Moved back inside

@@ -88,6 +88,14 @@ def test_more_than_one_workgroup(dev):
     run_record(rec, dev, (4,), "planes")
 
 
+def test_the_limit_of_the_contract(dev):
+    """resize_records.limit_cases(): axes of 32768 source and output steps and the weights read
+    directly, each after it passed the emulation in test_resize_index_host.py.  The device's
+    weights are its own float32 divisions: these cases hold them to the statement's bit for bit."""
+    for label, rec, offsets in rr.limit_cases():
+        run_record(rec, dev, offsets, label)
+
+
 def test_refused_with_nothing_launched(dev):
     """A resized field whose view reaches one byte past its allocation, named; a destination that
     is odd for int16: DORA_ERR_INVALID, the destination keeps its poison.  Moved back inside and

@@ -119,6 +119,30 @@ def test_every_case_through_the_emulated_body(lib, emulator, tmp_path):
     assert counts["head_elements"] and counts["units"] and counts["tail_elements"], counts
 
 
+def test_the_limit_of_the_contract_through_the_emulated_body(lib, emulator, tmp_path):
+    """Axes of 32768 source and output steps, where the statement's integers come closest to 2^31
+    and d = 2 * O is 65536, and the weights read directly: a column [0, 1] resized along axis 0
+    is w1 of every output coordinate, [1, 0] is w0.  The statement of record's own weights are
+    first held against the integer formula divided in float64 and rounded once."""
+    import numpy as np
+    for label, rec, _ in rr.limit_cases():
+        if label.startswith(("w1 ", "w0 ")):
+            (_, _, v, r), = rec
+            w0, w1, last = rr.weights_in_float64(2, r["size"][0])
+            want = rr.want(v, r)
+            # (where the last element stands alone the output is that element: 1 or 0)
+            expect = np.where(last, v[1, 0], w1 if label.startswith("w1 ") else w0)
+            assert want.tobytes() == expect.astype(np.float32).tobytes(), label
+            assert len(np.unique(want)) > r["size"][0] // 2, label  # (weights, not a constant)
+    batch = Batch(tmp_path)
+    for label, rec, offsets in rr.limit_cases():
+        assert rr.want(rec[0][2], rec[0][3]).size <= 5 * rr.LIMIT, label
+        for mis in offsets:
+            batch.add(f"{label} dst%16={mis}", rec, DST + mis)
+    counts = batch.run(emulator)
+    assert counts["units"] > 10 * rr.LIMIT // 16, counts
+
+
 def test_the_record_fields_meet_heads_and_tails(lib):
     starts = set()
     for mis in (0, 2, 8):
