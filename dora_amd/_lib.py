@@ -415,6 +415,12 @@ _TEST_SIGS = {
                                                 c_size_t, POINTER(c_size_t)]),
     "dora_gpu_test_ide_decode": (c_int, [c_void_p, c_size_t, c_char_p, c_size_t,
                                          POINTER(c_size_t)]),
+    "dora_gpu_test_pack_segments": (c_int, [c_int, c_size_t, POINTER(c_size_t), POINTER(c_uint64),
+                                            POINTER(c_uint64), POINTER(c_uint64), c_uint32,
+                                            c_uint32, c_void_p, POINTER(ctypes.c_uint32)]),
+    "dora_gpu_test_pack_args": (c_int, [c_int, c_size_t, POINTER(c_size_t), POINTER(c_uint64),
+                                        POINTER(c_uint64), POINTER(c_uint64), c_uint32, c_uint32,
+                                        c_void_p, c_size_t, POINTER(c_size_t)]),
     "dora_gpu_test_batch_args": (c_int, [c_size_t, POINTER(c_size_t), POINTER(c_uint64),
                                          POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64),
                                          POINTER(c_uint64), c_void_p, c_size_t,

@@ -110,7 +110,8 @@ def build(verbose: bool = False) -> str:
     return out
 
 
-TESTING_SOURCES = ["testing/testing.cpp", "testing/publish_kernel.hip", "testing/fence_probes.hip"]
+TESTING_SOURCES = ["testing/testing.cpp", "testing/publish_kernel.hip", "testing/fence_probes.hip",
+                   "testing/pack_probe.hip"]
 TESTING_NAME = "libdora_gpu_testing.so"
 
 

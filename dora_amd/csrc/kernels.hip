@@ -825,12 +825,28 @@ uint64_t edge_mask(const Segment* segs, size_t n, const uint8_t* dst, uint64_t c
     if (segs[k].dst_off < segs[k - 1].dst_off + segs[k - 1].len) return 0;
   const uint64_t base = reinterpret_cast<uintptr_t>(dst);
   auto inside = [&](uint64_t unit) { return unit >= base && unit + 16 <= base + cap; };
+  // The kernel leaves a stitched head unit to the lowest segment holding a byte of it
+  // (pack_chunk own_head), and that segment takes the unit only if seg[j - 1] ends before it.  An
+  // empty seg[j - 1] that starts inside the unit hides the owner from that rule: nobody would
+  // write the unit, so no head in it is stitched (its bytes are stored one by one).  Plans drop
+  // empty segments or are empty altogether; raw segment lists need not.
+  auto hidden = [&](size_t k, uint64_t unit) {
+    size_t j = k;  // the lowest non-empty segment holding a byte of the unit
+    for (size_t p = k; p-- > 0;) {
+      if (!segs[p].len) continue;
+      if (base + segs[p].dst_off + segs[p].len <= unit) break;
+      j = p;
+    }
+    // a segment that starts before the unit (or on it) writes it as its tail or body
+    return base + segs[j].dst_off > unit && j > 0 && segs[j - 1].len == 0 &&
+           base + segs[j - 1].dst_off > unit;
+  };
   uint64_t mask = 0;
   for (size_t k = 0; k < n; ++k) {
     const uint64_t d0 = base + segs[k].dst_off, d1 = d0 + segs[k].len;
     if (d1 == d0) continue;
     const uint64_t A0 = (d0 + 15) & ~uint64_t(15);
-    if (A0 > d0 && inside(A0 - 16)) mask |= uint64_t(1) << (2 * k);
+    if (A0 > d0 && inside(A0 - 16) && !hidden(k, A0 - 16)) mask |= uint64_t(1) << (2 * k);
     if (A0 < d1 && (d1 & 15) && inside(d1 & ~uint64_t(15))) mask |= uint64_t(2) << (2 * k);
   }
   return mask;
@@ -884,6 +900,29 @@ int finish_args(A& a, uint8_t* dst, const FillSignal& sig, size_t nseg, uint32_t
   a.grid = pack_grid(a.n_chunks, how, single);
   return DORA_OK;
 }
+
+}  // namespace
+
+// finish_args by argument type, for the pack probe of the testing library
+// (testing/pack_probe.hip): `signals` selects the in-kernel signal's grid, else one workgroup per
+// chunk.
+int finish_pack_args(PackArgs& a, uint8_t* dst, const FillSignal& sig, size_t nseg,
+                     uint32_t chunk_bytes, uint64_t edge, bool signals) {
+  return finish_args(a, dst, sig, nseg, chunk_bytes, edge,
+                     signals ? Signal::kInKernel : Signal::kNone, nseg == 1);
+}
+int finish_aql_args(AqlPackArgs& a, uint8_t* dst, const FillSignal& sig, size_t nseg,
+                    uint32_t chunk_bytes, uint64_t edge, bool signals) {
+  return finish_args(a, dst, sig, nseg, chunk_bytes, edge,
+                     signals ? Signal::kInKernel : Signal::kNone, false);
+}
+int finish_batch_args(AqlBatchArgs& a, uint8_t* dst, const FillSignal& sig, size_t nseg,
+                      uint32_t chunk_bytes, uint64_t edge, bool signals) {
+  return finish_args(a, dst, sig, nseg, chunk_bytes, edge,
+                     signals ? Signal::kInKernel : Signal::kNone, false);
+}
+
+namespace {
 
 // One kernel launch on `stream`, timed or not: with an event it is the extended launch, whose
 // dispatch packet stamps the kernel's begin into `ev_start` and its end into `ev_stop` (either

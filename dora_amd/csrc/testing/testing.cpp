@@ -25,6 +25,7 @@
 #include "dora_gpu_testing.h"
 #include "fence_probes.h"
 #include "gather_device.h"
+#include "pack_probe.h"
 #include "reduce_device.h"
 #include "resize_device.h"
 #include "crop_device.h"
@@ -105,6 +106,30 @@ int dora_gpu_test_batch_args(size_t n_msgs, const size_t* seg_counts, const uint
                 dst_caps[m]};
   }
   return dora::build_aql_batch_args(items, n_msgs, out, cap, grid);
+}
+
+int dora_gpu_test_pack_segments(int body, size_t n_msgs, const size_t* seg_counts,
+                                const uint64_t* segs, const uint64_t* dsts,
+                                const uint64_t* dst_caps, uint32_t chunk_bytes, uint32_t grid,
+                                dora_stream_t stream, uint32_t* flags_ok) {
+  if (!seg_counts || !segs || !dsts || !dst_caps)
+    return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  return dora::pack_probe(body, n_msgs, seg_counts, segs, dsts, dst_caps, chunk_bytes, grid,
+                          static_cast<hipStream_t>(stream), flags_ok, nullptr, 0, nullptr);
+  DORA_GUARD_END
+}
+
+int dora_gpu_test_pack_args(int body, size_t n_msgs, const size_t* seg_counts,
+                            const uint64_t* segs, const uint64_t* dsts, const uint64_t* dst_caps,
+                            uint32_t chunk_bytes, uint32_t grid, uint8_t* out, size_t cap,
+                            size_t* out_len) {
+  if (!seg_counts || !segs || !dsts || !dst_caps || !out)
+    return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  DORA_GUARD_BEGIN
+  return dora::pack_probe(body, n_msgs, seg_counts, segs, dsts, dst_caps, chunk_bytes, grid,
+                          nullptr, nullptr, out, cap, out_len);
+  DORA_GUARD_END
 }
 
 int dora_gpu_test_l2_touch(const void* data, size_t len, dora_stream_t stream) {

@@ -65,6 +65,33 @@ int dora_gpu_test_batch_args(size_t n_msgs, const size_t* seg_counts, const uint
                              const uint64_t* dsts, const uint64_t* dst_caps,
                              const uint64_t* flags, const uint64_t* epochs, uint8_t* out,
                              size_t cap, uint32_t* grid);
+/* Test hook of the pack bodies (dora_amd/csrc/pack_device.h): one pack of caller-given segments
+ * through body `body`, then a synchronise of `stream`.  Messages as dora_gpu_test_batch_args gives
+ * them: message m has seg_counts[m] segments, (src, dst_off, len) triples in `segs`, sorted and
+ * disjoint, its destination at dsts[m] with dst_caps[m] writable bytes (0: unknown).  Bodies:
+ * 0 the product's launch_pack, unsignalled (any segment count: launches of 32, none stitched
+ * when there is more than one); 1 pack_body<4, 2> over PackArgs (<= 32 segments, write-through
+ * stores); 2 pack_body<4, kCoherent> over AqlPackArgs (<= 8 segments); 3 pack_body<4, 2> over the
+ * AqlBatchArgs that build_aql_batch_args makes of 1-8 messages (<= 16 segments), each with its
+ * own flag and epoch.  Bodies 0-2 take one message.  Bodies 1-3 fill their arguments with the
+ * product's finish_args / edge_mask / chunk_layout and signal pinned host flags and done words
+ * of the hook's own; *flags_ok (may be NULL) gets bit m set if message m's flag holds exactly its
+ * epoch after the synchronise.  `chunk_bytes` 0: the product's choice, else a multiple of 8192 up
+ * to 4 MiB (what choose_chunk_bytes can return); `grid` 0: the product's choice, else a value in
+ * [1, n_chunks]; body 0 takes neither.  Every source and destination range is checked against the
+ * device allocation that holds it before anything is launched.  The kernels are compiled from
+ * the same header as the AQL code object but without its kernarg-preload flag. */
+int dora_gpu_test_pack_segments(int body, size_t n_msgs, const size_t* seg_counts,
+                                const uint64_t* segs, const uint64_t* dsts,
+                                const uint64_t* dst_caps, uint32_t chunk_bytes, uint32_t grid,
+                                dora_stream_t stream, uint32_t* flags_ok);
+/* Test tool (host only): the argument block dora_gpu_test_pack_segments would launch with, nothing
+ * launched: PackArgs (bodies 0 and 1; of body 0 the first launch), AqlPackArgs (2) or AqlBatchArgs
+ * (3), its size in *out_len.  The flags are placeholders. */
+int dora_gpu_test_pack_args(int body, size_t n_msgs, const size_t* seg_counts,
+                            const uint64_t* segs, const uint64_t* dsts, const uint64_t* dst_caps,
+                            uint32_t chunk_bytes, uint32_t grid, uint8_t* out, size_t cap,
+                            size_t* out_len);
 /* Test tool (host only): what a device tensor plan (dora_gpu_plan_tensor with ARROW_DEVICE_ROCM)
  * reads.  *gather 1 if a gather kernel reads it (the plan then has no segments), 0 if it is
  * dense; *src element (0, .., 0); the canonical view as *nd (<= 8) extents and byte strides in

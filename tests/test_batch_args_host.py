@@ -2,48 +2,18 @@
 640-byte argument block of `dora_aql_packb_u4` for several messages — segments sorted by
 absolute destination, chunk bounds, each message's stitched-edge bits carried to its segments'
 sorted positions, one fill flag / epoch per message — against a Python statement of the same
-rules (pack_device.h `segment_chunks`, kernels.hip `edge_mask`)."""
+rules (pack_device.h `segment_chunks`, kernels.hip `edge_mask`; tests/random_packs.py states
+them)."""
 import ctypes
 import struct
 
 import pytest
 
 from dora_amd import _lib
+from tests.random_packs import edge_mask, segment_chunks
 
 ARGS_BYTES = 640
 MAX_SEGS = 16
-LINE = 128
-
-
-def segment_chunks(d0, length, chunk):
-    a0 = (d0 + 15) & ~15
-    a1 = (d0 + length) & ~15
-    if a1 <= a0:
-        return 1
-    o = a0 & ~(LINE - 1)
-    return (a1 - o + chunk - 1) // chunk
-
-
-def edge_mask(segs, dst, cap):
-    if not cap:
-        return 0
-    for k in range(1, len(segs)):
-        if segs[k][1] < segs[k - 1][1] + segs[k - 1][2]:
-            return 0
-
-    def inside(u):
-        return u >= dst and u + 16 <= dst + cap
-    m = 0
-    for k, (_, off, n) in enumerate(segs):
-        d0, d1 = dst + off, dst + off + n
-        if d1 == d0:
-            continue
-        a0 = (d0 + 15) & ~15
-        if a0 > d0 and inside(a0 - 16):
-            m |= 1 << (2 * k)
-        if a0 < d1 and (d1 & 15) and inside(d1 & ~15):
-            m |= 2 << (2 * k)
-    return m
 
 
 def build(msgs):
