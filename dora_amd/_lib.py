@@ -129,6 +129,16 @@ class TensorCrop(ctypes.Structure):
                 ("dtype_code", c_uint8), ("dtype_bits", c_uint8), ("boxes", POINTER(Tensor))]
 
 
+class TensorPrep(ctypes.Structure):
+    """dora_tensor_prep of include/dora_gpu.h: what a model input adds to the resize or crops of
+    one field (all zero: nothing): the per-channel scale and bias tables (NULL: none), the axis
+    they run along, the scalar terms, and the placement of the resized image inside the output."""
+    _fields_ = [("scale", POINTER(Tensor)), ("bias", POINTER(Tensor)), ("axis", c_int32),
+                ("has_scale", ctypes.c_uint16), ("has_bias", ctypes.c_uint16),
+                ("scale_value", c_float), ("bias_value", c_float),
+                ("inner", ctypes.c_int64 * 2), ("lead", ctypes.c_int64 * 2), ("fill", c_float)]
+
+
 class TensorMask(ctypes.Structure):
     """dora_tensor_mask of include/dora_gpu.h: the fields rows are selected from, the mask that
     selects them and, for more than one list, the partition of the N source rows (else NULL)."""
@@ -215,6 +225,11 @@ _SIGS = {
     "dora_node_send_output_tensor_crop": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
                                                   c_void_p, c_int32, c_char_p, c_size_t,
                                                   c_uint32]),
+    "dora_gpu_plan_tensor_prep": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                          c_int32, POINTER(c_void_p)]),
+    "dora_node_send_output_tensor_prep": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t,
+                                                  c_void_p, c_void_p, c_void_p, c_int32,
+                                                  c_char_p, c_size_t, c_uint32]),
     "dora_gpu_plan_tensor_mask": (c_int, [c_void_p, c_int32, POINTER(c_void_p)]),
     "dora_node_send_output_tensor_mask": (c_int, [c_void_p, c_char_p, c_void_p, c_int32, c_char_p,
                                                   c_size_t, c_uint32]),
@@ -378,6 +393,11 @@ _TEST_SIGS = {
                                         POINTER(c_uint64), POINTER(c_void_p), POINTER(c_int),
                                         POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
                                         POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "dora_gpu_test_plan_prep": (c_int, [c_void_p, c_size_t, POINTER(c_int), POINTER(c_void_p),
+                                        POINTER(c_void_p), POINTER(c_uint64), POINTER(c_int),
+                                        POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),
+                                        POINTER(c_float), POINTER(ctypes.c_int64),
+                                        POINTER(ctypes.c_int64)]),
     "dora_gpu_test_plan_resize": (c_int, [c_void_p, c_size_t, c_void_p, POINTER(c_int),
                                           POINTER(c_uint64), POINTER(c_int),
                                           POINTER(ctypes.c_int64), POINTER(ctypes.c_int64),

@@ -18,6 +18,11 @@
 // zero and reads no tap.  Everything else — units on absolute 16-byte boundaries of the
 // destination, heads and tails element by element, a policy object `M` for all memory and
 // arithmetic, compiled for host and device alike — is as resize_device.h says.
+//
+// Model inputs (gather_crop_prep_kernel): resize_device.h's step type is passed through; the
+// tables' axis is counted with K in front like the two cropped axes, the affine step is applied to
+// every element of a non-empty box, and an empty box's element is zero before any of it.
+// Placement is not provided for crops.
 #pragma once
 
 #include <cstdint>
@@ -40,13 +45,18 @@ DORA_HD Args make_args(const GatherDesc& g, const CropDesc& c, uint8_t* dst) {
 
 DORA_HD uint64_t grid_for(const Args& a) { return resize::grid_for(a.r); }
 
-// Where a lane is: resize's walk, the crop its box was read for (-1: none yet), and the box
-// clamped: its first steps along the two axes and its extents, both 0 for an empty box.
-struct Walk {
-  resize::Walk w;
+// Where a lane is: resize's walk (RW: resize::Walk, or resize::PrepWalk under the model-input
+// step), the crop its box was read for (-1: none yet), and the box clamped: its first steps along
+// the two axes and its extents, both 0 for an empty box.
+template <class RW>
+struct WalkT {
+  RW w;
   int64_t ok;
   uint32_t a0, b0, ia, ib;
 };
+using Walk = WalkT<resize::Walk>;
+template <class PA>
+using WalkFor = WalkT<typename resize::WalkFor<PA>::type>;
 
 // `v` clamped to [0, n], n <= 32768.
 DORA_HDI uint32_t clamp_to(int32_t v, uint32_t n) {
@@ -55,9 +65,10 @@ DORA_HDI uint32_t clamp_to(int32_t v, uint32_t n) {
 }
 
 // The box and the taps of the element the odometer stands on: the box again only where the crop
-// differs from the one it was read for, an axis' taps where the box or its coordinate does.
-template <class M>
-DORA_HDI void refresh(const Args& a, Walk& c, M& m) {
+// differs from the one it was read for, an axis' taps where the box or its coordinate does.  With
+// the step (`pa` a prep::Args) the terms of a non-empty box's element as resize fetches them.
+template <class CW, class PA, class M>
+DORA_HDI void refresh(const Args& a, CW& c, M& m, const PA& pa) {
   const int64_t k = resize::coord(c.w.p, a.kax);
   if (k != c.ok) {
     c.ok = k;
@@ -89,93 +100,117 @@ DORA_HDI void refresh(const Args& a, Walk& c, M& m) {
     c.w.tb.s0 += first;
     c.w.tb.s1 += first;
   }
+  if constexpr (PA::on) resize::refresh_terms(c.w.p, c.w, m, pa);
+}
+
+template <class CW, class PA, class M>
+DORA_HDI void walk_start(const Args& a, uint64_t e, CW& c, M& m, const PA& pa) {
+  row_pos(a.r.g, e, c.w.p);
+  c.ok = -1;
+  c.ia = c.ib = c.a0 = c.b0 = 0;
+  if constexpr (PA::on) resize::start_terms(c.w, pa);
+  refresh(a, c, m, pa);
+}
+
+template <class CW, class PA, class M>
+DORA_HDI void walk_next(const Args& a, CW& c, M& m, const PA& pa) {
+  next_row(a.r.g, c.w.p);
+  refresh(a, c, m, pa);
+}
+
+// The element the walk stands on as a destination element of D bytes, zero-extended; its source
+// of type K.  An empty box's element is zero before anything else, the step included.
+template <uint32_t K, int D, class CW, class PA, class M>
+DORA_HDI uint32_t elem_at(const Args& a, const CW& c, M& m, const PA& pa) {
+  if (!c.ia) return 0u;
+  if constexpr (PA::on)
+    return resize::to_dst<D>(a.r, resize::step(resize::value_at<K>(a.r, c.w, m), c.w, m, pa), m);
+  else
+    return resize::to_dst<D>(a.r, resize::value_at<K>(a.r, c.w, m), m);
 }
 
 template <class M>
 DORA_HDI void walk_start(const Args& a, uint64_t e, Walk& c, M& m) {
-  row_pos(a.r.g, e, c.w.p);
-  c.ok = -1;
-  c.ia = c.ib = c.a0 = c.b0 = 0;
-  refresh(a, c, m);
+  walk_start(a, e, c, m, prep::None{});
 }
-
 template <class M>
 DORA_HDI void walk_next(const Args& a, Walk& c, M& m) {
-  next_row(a.r.g, c.w.p);
-  refresh(a, c, m);
+  walk_next(a, c, m, prep::None{});
 }
-
-// The element the walk stands on as a destination element of D bytes, zero-extended; its source
-// of type K.
 template <uint32_t K, int D, class M>
 DORA_HDI uint32_t elem_at(const Args& a, const Walk& c, M& m) {
-  if (!c.ia) return 0u;
-  return resize::to_dst<D>(a.r, resize::value_at<K>(a.r, c.w, m), m);
+  return elem_at<K, D>(a, c, m, prep::None{});
 }
 
 // Whole unit `u` of the output.
-template <uint32_t K, int D, class M>
-DORA_HDI void crop_unit(const Args& a, uint64_t u, M& m) {
+template <uint32_t K, int D, class PA, class M>
+DORA_HDI void crop_unit(const Args& a, uint64_t u, M& m, const PA& pa) {
   constexpr int E = 16 / D;
   const uint64_t e = a.r.g.head + static_cast<uint64_t>(E) * u;
-  Walk c;
-  walk_start(a, e, c, m);
+  WalkFor<PA> c;
+  walk_start(a, e, c, m, pa);
   U16 out = {{0, 0, 0, 0}};
 #pragma unroll
   for (int j = 0; j < E; ++j) {
-    const uint32_t q = elem_at<K, D>(a, c, m);
+    const uint32_t q = elem_at<K, D>(a, c, m, pa);
     if constexpr (D == 1) out.w[j / 4] |= q << (8 * (j % 4));
     else if constexpr (D == 2) out.w[j / 2] |= q << (16 * (j % 2));
     else out.w[j] = q;
-    if (j + 1 < E) walk_next(a, c, m);
+    if (j + 1 < E) walk_next(a, c, m, pa);
   }
   m.store16(e * D, out);
 }
 
 // Output element `e` on its own (before the first and after the last whole unit).
-template <uint32_t K, int D, class M>
-DORA_HDI void crop_elem(const Args& a, uint64_t e, M& m) {
-  Walk c;
-  walk_start(a, e, c, m);
-  m.template store_elem<D>(e, elem_at<K, D>(a, c, m));
+template <uint32_t K, int D, class PA, class M>
+DORA_HDI void crop_elem(const Args& a, uint64_t e, M& m, const PA& pa) {
+  WalkFor<PA> c;
+  walk_start(a, e, c, m, pa);
+  m.template store_elem<D>(e, elem_at<K, D>(a, c, m, pa));
 }
 
 // resize::lane_as' division of the work: lanes 0..15 a head element each, lanes 16..31 a tail
 // element each, and every lane the whole units lane, lane + lanes, ..
-template <uint32_t K, int D, class M>
-DORA_HDI void lane_as(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+template <uint32_t K, int D, class PA, class M>
+DORA_HDI void lane_as(const Args& a, uint64_t lane, uint64_t lanes, M& m, const PA& pa) {
   constexpr int E = 16 / D;
   static_assert(E - 1 <= 15, "16 lanes each for the head's and the tail's elements");
   if (lane < 16) {
-    if (lane < a.r.g.head) crop_elem<K, D>(a, lane, m);
+    if (lane < a.r.g.head) crop_elem<K, D>(a, lane, m, pa);
   } else if (lane < 32) {
     const uint64_t t0 = a.r.g.head + static_cast<uint64_t>(E) * a.r.g.nunits;  // <= total
-    if (lane - 16 < a.r.g.total - t0) crop_elem<K, D>(a, t0 + (lane - 16), m);
+    if (lane - 16 < a.r.g.total - t0) crop_elem<K, D>(a, t0 + (lane - 16), m, pa);
   }
-  for (uint64_t u = lane; u < a.r.g.nunits; u += lanes) crop_unit<K, D>(a, u, m);
+  for (uint64_t u = lane; u < a.r.g.nunits; u += lanes) crop_unit<K, D>(a, u, m, pa);
 }
 
-template <uint32_t K, class M>
-DORA_HDI void lane_of(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+template <uint32_t K, class PA, class M>
+DORA_HDI void lane_of(const Args& a, uint64_t lane, uint64_t lanes, M& m, const PA& pa) {
   switch (a.r.dsize) {
-    case 1: lane_as<K, 1>(a, lane, lanes, m); break;
-    case 2: lane_as<K, 2>(a, lane, lanes, m); break;
-    default: lane_as<K, 4>(a, lane, lanes, m); break;
+    case 1: lane_as<K, 1>(a, lane, lanes, m, pa); break;
+    case 2: lane_as<K, 2>(a, lane, lanes, m, pa); break;
+    default: lane_as<K, 4>(a, lane, lanes, m, pa); break;
   }
 }
 
-// Everything lane `lane` of `lanes` does for a field of crops.
+// Everything lane `lane` of `lanes` does for a field of crops; with `pa` a prep::Args
+// (gather_crop_prep_kernel) every element of a non-empty box goes through the affine step.
+template <class PA, class M>
+DORA_HDI void crop_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m, const PA& pa) {
+  switch (a.r.src) {
+    case cast::kU8: lane_of<cast::kU8>(a, lane, lanes, m, pa); break;
+    case cast::kI8: lane_of<cast::kI8>(a, lane, lanes, m, pa); break;
+    case cast::kU16: lane_of<cast::kU16>(a, lane, lanes, m, pa); break;
+    case cast::kI16: lane_of<cast::kI16>(a, lane, lanes, m, pa); break;
+    case cast::kF16: lane_of<cast::kF16>(a, lane, lanes, m, pa); break;
+    case cast::kBF16: lane_of<cast::kBF16>(a, lane, lanes, m, pa); break;
+    default: lane_of<cast::kF32>(a, lane, lanes, m, pa); break;
+  }
+}
+
 template <class M>
 DORA_HDI void crop_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
-  switch (a.r.src) {
-    case cast::kU8: lane_of<cast::kU8>(a, lane, lanes, m); break;
-    case cast::kI8: lane_of<cast::kI8>(a, lane, lanes, m); break;
-    case cast::kU16: lane_of<cast::kU16>(a, lane, lanes, m); break;
-    case cast::kI16: lane_of<cast::kI16>(a, lane, lanes, m); break;
-    case cast::kF16: lane_of<cast::kF16>(a, lane, lanes, m); break;
-    case cast::kBF16: lane_of<cast::kBF16>(a, lane, lanes, m); break;
-    default: lane_of<cast::kF32>(a, lane, lanes, m); break;
-  }
+  crop_lane(a, lane, lanes, m, prep::None{});
 }
 
 }  // namespace crop
@@ -196,6 +231,21 @@ DORA_HD Args make_crop_args(const GatherDesc* g, const CropDesc* c, const uint64
 }
 
 }  // namespace multi
+
+namespace prep {
+
+// resize's make_resize_launch for a launch of gather_crop_prep_kernel: a crops field's step is
+// held against its output with K in front (c[k].rs).
+DORA_HD Launch make_crop_launch(const GatherDesc* g, const CropDesc* c, const PrepDesc* d,
+                                const uint64_t* off, const int* tile_c, int n, uint8_t* dst) {
+  Launch l{};
+  l.a = multi::make_crop_args(g, c, off, tile_c, n, dst);
+  for (int k = 0; k < n; ++k)
+    if (c[k].on) l.p[k] = make_args(d[k], c[k].rs);
+  return l;
+}
+
+}  // namespace prep
 
 }  // namespace gather
 }  // namespace dora

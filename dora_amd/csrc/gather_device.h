@@ -977,6 +977,37 @@ struct Args {
 
 }  // namespace crop
 
+// ------------------------------------------------------------------------------------------
+// What a model-input field adds to its resize or crops (run by gather_resize_prep_kernel and
+// gather_crop_prep_kernel only): the resized image placed inside a filled output, and the affine
+// step y = r * S[c] + B[c] before the conversion.  The arguments travel beside multi::Args
+// (prep::Launch, resize_device.h), so resize::Args, crop::Args and multi::Args keep their sizes;
+// the bodies are resize_device.h and crop_device.h under their flag.
+// ------------------------------------------------------------------------------------------
+namespace prep {
+
+// The bodies' flag: with None no line of the step is compiled.
+struct None {
+  static constexpr bool on = false;
+};
+
+struct Args {
+  static constexpr bool on = true;
+  const uint8_t* stab;   // per-channel float32 tables along shape[cax], 4-byte aligned; null: the
+  const uint8_t* btab;   // scalar below (or no term at all)
+  float scale, bias;     // the scalar terms
+  float fill;            // the value of an element outside the placed image, before the step
+  uint16_t inner[2];     // the extents of the resized image, 1 .. out[j] (out[j]: it fills the axis)
+  uint16_t lead[2];      // where it starts in the output, lead[j] + inner[j] <= out[j]
+  uint8_t cax;           // the tables' place in shape[]; read only with a table
+  uint8_t has_scale;     // a product is applied: by stab[c], else by `scale`
+  uint8_t has_bias;      // a sum is applied: with btab[c], else with `bias`
+  uint8_t pad;
+};
+static_assert(sizeof(Args) == 40, "eight of them travel beside multi::Args");
+
+}  // namespace prep
+
 namespace multi {
 
 constexpr int kMaxFields = static_cast<int>(kMaxStructFields);

@@ -718,6 +718,67 @@ __global__ __launch_bounds__(gather::kThreads) void gather_crop_kernel(gather::m
   crop_share(a, lds);
 }
 
+// What a workgroup of gather_resize_prep_kernel (kCrops false) or gather_crop_prep_kernel does:
+// resize_share's or crop_share's walk, a resized field or a field of crops through its body with
+// the model-input step of the field (l.p[k], beside the fields' own arguments), every such field
+// of the launch, those whose entry adds nothing included.
+template <bool kCrops>
+__device__ __forceinline__ void prep_share(const gather::prep::Launch& l, uint64_t* lds) {
+  const gather::multi::Args& a = l.a;
+  const uint32_t w = blockIdx.x;
+  const int k = gather::multi::field_of(a, w);
+  const gather::multi::Field& f = a.f[k];
+  const uint64_t local = w - a.wg_begin[k], share = a.wg_begin[k + 1] - a.wg_begin[k];
+  const uint64_t lane = local * gather::kThreads + threadIdx.x, lanes = share * gather::kThreads;
+  if (f.kind == gather::multi::kRows) {
+    GatherMem m{f.rows.src, f.rows.dst};
+    gather::gather_lane(f.rows, lane, lanes, m);
+    return;
+  }
+  if constexpr (kCrops) {
+    if (f.kind == gather::multi::kCrop) {
+      // (copies of their own, as the cast body's arguments are)
+      const gather::crop::Args c = f.crop;
+      const gather::prep::Args pa = l.p[k];
+      CropMem m{{{c.r.g.src, c.r.g.dst}}, c.boxes};
+      gather::crop::crop_lane(c, lane, lanes, m, pa);
+      return;
+    }
+  } else {
+    if (f.kind == gather::multi::kResize) {
+      const gather::resize::Args r = f.resize;
+      const gather::prep::Args pa = l.p[k];
+      ResizeMem m{{r.g.src, r.g.dst}};
+      gather::resize::resize_lane(r, lane, lanes, m, pa);
+      return;
+    }
+  }
+  switch (f.tile.elem) {
+    case 1: tile_loop(f.tile, local, share, reinterpret_cast<uint8_t*>(lds)); break;
+    case 2: tile_loop(f.tile, local, share, reinterpret_cast<uint16_t*>(lds)); break;
+    case 4: tile_loop(f.tile, local, share, reinterpret_cast<uint32_t*>(lds)); break;
+    default: tile_loop(f.tile, local, share, lds); break;
+  }
+}
+
+// gather_resize_prep_kernel: the fields of a prep plan over resizes in one launch: resized fields
+// through the resize body with placement and the affine step (resize_device.h under its flag),
+// plain ones through their usual rows or tile body.  Chosen per plan when any field has a prep
+// entry, so gather_resize_kernel holds no line of the step and keeps its code.
+__global__ __launch_bounds__(gather::kThreads) void gather_resize_prep_kernel(
+    gather::prep::Launch l) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  prep_share<false>(l, lds);
+}
+
+// gather_crop_prep_kernel: the same over crops (crop_device.h under its flag): the affine step on
+// every element of a non-empty box; gather_crop_kernel keeps its code.
+__global__ __launch_bounds__(gather::kThreads) void gather_crop_prep_kernel(
+    gather::prep::Launch l) {
+  __shared__ uint64_t lds[gather::tile::kLds];
+  prep_share<true>(l, lds);
+}
+
 // The mask kernels' memory (gather_device.h mask::): the mask with one aligned 16-byte
 // non-temporal load per thread (each byte is read once by each kernel) or byte by byte at its
 // head and tail; the thread counts in LDS; the workspace's index, counts and totals with plain
@@ -1097,8 +1158,19 @@ int check_plan_range(const dora_plan& plan, int device) {
       rc = check_device_range(table_reach(c.bias_tab, c.channels), device);
       what = "bias table: ";
     }
+    // a model-input field's tables in HBM, the same
+    const PrepDesc& pd = plan.fields[k].prep;
+    const bool prepped = kind == PlanLaunch::kResizePrep || kind == PlanLaunch::kCropPrep;
+    if (rc == DORA_OK && prepped && pd.on && pd.scale_tab) {
+      rc = check_device_range(table_reach(pd.scale_tab, pd.channels), device);
+      what = "scale table: ";
+    }
+    if (rc == DORA_OK && prepped && pd.on && pd.bias_tab) {
+      rc = check_device_range(table_reach(pd.bias_tab, pd.channels), device);
+      what = "bias table: ";
+    }
     // a crops field's boxes in HBM: their 16 * K bytes like a take's index
-    if (rc == DORA_OK && kind == PlanLaunch::kCrop && plan.fields[k].crop.on) {
+    if (rc == DORA_OK && crops(kind) && plan.fields[k].crop.on) {
       rc = check_device_range(crop_reach(plan.fields[k].crop), device);
       what = "boxes: ";
     }
@@ -1188,9 +1260,9 @@ int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** no
   unsigned ds = 0;
   bool ok = true;
   *noun = nullptr;
-  if ((kind == PlanLaunch::kResize && f.resize.on) || (kind == PlanLaunch::kCrop && f.crop.on)) {
+  if ((resizes(kind) && f.resize.on) || (crops(kind) && f.crop.on)) {
     // (a field of crops: the same held against the output's dimensions, and its boxes)
-    const bool crop = kind == PlanLaunch::kCrop;
+    const bool crop = crops(kind);
     const ResizeDesc& r = crop ? f.crop.rs : f.resize;
     op = crop ? "a crop" : "a resize";
     *noun = crop ? "cropped" : "resized";
@@ -1209,6 +1281,18 @@ int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** no
       ok = ok && f.crop.k >= 1 && f.crop.k <= kMaxCropBoxes && r.shape[0] == int64_t(f.crop.k) &&
            r.stride[0] == 0 && r.ax[0] >= 1 && r.ax[1] >= 1 && f.crop.boxes &&
            !(reinterpret_cast<uintptr_t>(f.crop.boxes) & 3);
+    // (the model-input step: the image inside the output, the tables' axis a kept dimension of
+    // as many steps as the tables have words, the tables whole dwords)
+    const PrepDesc& d = f.prep;
+    if (ok && d.on && d.placed) {
+      ok = !crop;
+      for (int j = 0; ok && j < 2; ++j)
+        ok = d.inner[j] >= 1 && d.lead[j] >= 0 && d.inner[j] + d.lead[j] <= r.shape[r.ax[j]];
+    }
+    if (ok && d.on && (d.scale_tab || d.bias_tab))
+      ok = d.axis >= 0 && d.axis < r.nd && d.axis != r.ax[0] && d.axis != r.ax[1] &&
+           r.shape[d.axis] == int64_t(d.channels) &&
+           !((reinterpret_cast<uintptr_t>(d.scale_tab) | reinterpret_cast<uintptr_t>(d.bias_tab)) & 3);
   } else if (kind == PlanLaunch::kReduce && f.reduce.on) {
     const ReduceDesc& r = f.reduce;
     op = "a reduction";
@@ -1240,6 +1324,8 @@ int field_op_size(PlanLaunch kind, const PlanField& f, size_t k, const char** no
 //     gather_reduce_kernel.
 //   kResize: the same, a resized field through the resize body; gather_resize_kernel.
 //   kCrop: the same, a field of crops through the crop body; gather_crop_kernel.
+//   kResizePrep, kCropPrep: kResize and kCrop with the model-input step of every field beside the
+//     fields (prep::Launch); gather_resize_prep_kernel, gather_crop_prep_kernel.
 //   (these four: DORA_ERR_INVALID, nothing launched, when a field with an op, field_op_size,
 //   would not start on a multiple of the size of the elements stored)
 //   kTaken (`take` given): every field through the taken body, never a tile: row i0 of its bytes
@@ -1272,6 +1358,7 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
   bool wave[gather::multi::kMaxFields];
   ResizeDesc rs[gather::multi::kMaxFields];
   CropDesc cr[gather::multi::kMaxFields];
+  PrepDesc pd[gather::multi::kMaxFields];
   bool quant = false, affine = false;
   for (size_t k = 0; k < n; ++k) {
     const PlanField& f = fields[k];
@@ -1281,8 +1368,9 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
     stride0[k] = f.stride0;
     c[k] = kind == PlanLaunch::kCast ? f.cast : CastDesc{};
     rd[k] = kind == PlanLaunch::kReduce ? f.reduce : ReduceDesc{};
-    rs[k] = kind == PlanLaunch::kResize ? f.resize : ResizeDesc{};
-    cr[k] = kind == PlanLaunch::kCrop ? f.crop : CropDesc{};
+    rs[k] = resizes(kind) ? f.resize : ResizeDesc{};
+    cr[k] = crops(kind) ? f.crop : CropDesc{};
+    pd[k] = f.prep;
     quant |= c[k].quant();
     const char* noun = nullptr;
     const int ds = field_op_size(kind, f, k, &noun);
@@ -1303,6 +1391,16 @@ int launch_fields(PlanLaunch kind, const PlanField* fields, size_t n, uint8_t* d
   }
   namespace gm = gather::multi;
   const int nf = static_cast<int>(n);
+  if (kind == PlanLaunch::kResizePrep) {
+    const gather::prep::Launch l = gather::prep::make_resize_launch(g, rs, pd, off, tile_c, nf, dst);
+    return launch_timed(gather_resize_prep_kernel, gm::grid_for(l.a), gather::kThreads, stream,
+                        ev_start, ev_stop, l);
+  }
+  if (kind == PlanLaunch::kCropPrep) {
+    const gather::prep::Launch l = gather::prep::make_crop_launch(g, cr, pd, off, tile_c, nf, dst);
+    return launch_timed(gather_crop_prep_kernel, gm::grid_for(l.a), gather::kThreads, stream,
+                        ev_start, ev_stop, l);
+  }
   gm::Args a = take                        ? gm::make_taken_args(g, stride0, off, nf, dst, *take, scan)
                : kind == PlanLaunch::kCast ? gm::make_cast_args(g, c, off, tile_c, nf, dst)
                : kind == PlanLaunch::kReduce
@@ -1388,6 +1486,8 @@ int launch_plan_gather(const dora_plan& plan, uint8_t* dst, hipStream_t stream,
     case PlanLaunch::kReduce:
     case PlanLaunch::kResize:
     case PlanLaunch::kCrop:
+    case PlanLaunch::kResizePrep:
+    case PlanLaunch::kCropPrep:
     case PlanLaunch::kTaken:
       return launch_fields(plan.launch, plan.fields.data(), plan.fields.size(), dst, stream,
                            ev_start, ev_stop, scan,

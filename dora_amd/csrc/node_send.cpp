@@ -1105,6 +1105,18 @@ int dora_node_send_output_tensor_crop(dora_node* n, const char* output_id,
   });
 }
 
+int dora_node_send_output_tensor_prep(dora_node* n, const char* output_id,
+                                      const dora_tensor_field* fields, size_t count,
+                                      const dora_tensor_resize* resizes,
+                                      const dora_tensor_crop* crops, const dora_tensor_prep* preps,
+                                      ArrowDeviceType device_type, const uint8_t* params,
+                                      size_t params_len, uint32_t flags) {
+  if (!n || !output_id) return dora::fail(DORA_ERR_INVALID, "NULL argument");
+  return dora::send_plan(n, output_id, params, params_len, flags, [&](dora_plan** plan) {
+    return dora::build_tensor_prep_plan(fields, count, resizes, crops, preps, device_type, plan);
+  });
+}
+
 int dora_node_send_output_tensor_list(dora_node* n, const char* output_id,
                                       const dora_tensor_list* list, ArrowDeviceType device_type,
                                       const uint8_t* params, size_t params_len, uint32_t flags) {

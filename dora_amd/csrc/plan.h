@@ -171,6 +171,28 @@ struct CropDesc {
   uint64_t k = 0;
 };
 
+// What a model-input field adds to its resize or crops (dora_gpu_plan_tensor_prep): the resized
+// image of extents `inner` placed at `lead` inside an output filled with `fill` (`placed`; resize
+// only), and y = r * S + B before the conversion, S = scale_tab[c] or the scalar scale or absent,
+// B = bias_tab[c] or the scalar bias or absent, c the output coordinate along `axis` — a dimension
+// of the output as ResizeDesc counts them (a crops field's: with K in front).  A table is
+// `channels` dense float32 words where the values live: read by the CPU while a host plan is
+// built, read by the launch of a device plan and never on the host (table_reach).  `on` false:
+// the field's resize or crops is as dora_gpu_plan_tensor_resize / _crop plans it.
+struct PrepDesc {
+  bool on = false;
+  const uint8_t* scale_tab = nullptr;
+  const uint8_t* bias_tab = nullptr;
+  uint64_t channels = 0;
+  int axis = 0;
+  uint32_t has_scale = 0, has_bias = 0;
+  float scale = 1.0f, bias = 0.0f;
+  bool placed = false;
+  int64_t inner[2] = {0, 0};
+  int64_t lead[2] = {0, 0};
+  float fill = 0.0f;
+};
+
 // One field of a struct-of-tensors plan (dora_gpu_plan_tensor_struct): the field's view as its
 // own tensor plan would describe it (dense: nd == 0), where its row-major values start in the
 // sample and how many bytes they are.  Fields follow one another in destination order.
@@ -199,6 +221,8 @@ struct PlanField {
   // a crop plan (dora_gpu_plan_tensor_crop), `crop.on`: `gd` is the whole frame in source bytes,
   // its [lo, hi] the field's reach as a resized field's is; `bytes` all K crops' bytes
   CropDesc crop;
+  // a prep plan (dora_gpu_plan_tensor_prep), `prep.on`: what is added to `resize` or `crop`
+  PrepDesc prep;
 };
 
 // `bytes` dense bytes of `elem`-byte elements from `src` as a view: what a plan reads of an
@@ -421,6 +445,15 @@ int build_tensor_resize_plan(const dora_tensor_field* fields, size_t n,
 // every mode 0: build_tensor_plan's (bare) or build_tensor_struct_plan's plan.
 int build_tensor_crop_plan(const dora_tensor_field* fields, size_t n,
                            const dora_tensor_crop* crops, ArrowDeviceType dev, dora_plan** out);
+// Model inputs on send, bare or as a record (dora_gpu_plan_tensor_prep): a resize plan or a crop
+// plan whose fields may carry a prep entry each — the image placed inside a filled output (resize
+// only) and a per-channel or scalar affine step before the conversion.  Host values: by the CPU in
+// the plan's staging buffer; device values: one launch of gather_resize_prep_kernel or
+// gather_crop_prep_kernel.  `preps` NULL or all zero: build_tensor_resize_plan's (`crops` NULL)
+// or build_tensor_crop_plan's plan.
+int build_tensor_prep_plan(const dora_tensor_field* fields, size_t n,
+                           const dora_tensor_resize* resizes, const dora_tensor_crop* crops,
+                           const dora_tensor_prep* preps, ArrowDeviceType dev, dora_plan** out);
 int build_plan_compact(const ArrowArray* array, const ArrowSchema* schema, ArrowDeviceType dev,
                        dora_plan** out);
 
@@ -435,8 +468,15 @@ enum class PlanLaunch : uint8_t {
   kMasked,    // count, compact, then the taken body by the workspace's index
   kReduce,    // gather_reduce_kernel over `fields`
   kResize,    // gather_resize_kernel over `fields`
-  kCrop       // gather_crop_kernel over `fields`
+  kCrop,      // gather_crop_kernel over `fields`
+  kResizePrep,  // gather_resize_prep_kernel over `fields`: kResize with a model-input step
+  kCropPrep     // gather_crop_prep_kernel over `fields`: kCrop with a model-input step
 };
+
+// Whether a launch of `k` resizes its fields (`resize.on`) or crops them (`crop.on`), with the
+// model-input step or without.
+inline bool resizes(PlanLaunch k) { return k == PlanLaunch::kResize || k == PlanLaunch::kResizePrep; }
+inline bool crops(PlanLaunch k) { return k == PlanLaunch::kCrop || k == PlanLaunch::kCropPrep; }
 
 // What kind of message a tensor plan is, whichever way its bytes move: reported by the test probes
 // (testing.cpp) and read by nothing on the send path.

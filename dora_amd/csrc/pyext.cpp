@@ -761,6 +761,122 @@ PyObject* py_send_tensor_crops(PyObject*, PyObject* const* args, Py_ssize_t narg
   return PyLong_FromLong(rc);
 }
 
+// send_tensor_prep(handle, output_id, names, capsules, entries, preps, device_type, metadata,
+// flags) -> status: model inputs as dora_node_send_output_tensor_prep.  `names` / `capsules` as
+// send_tensor_cast takes them; `entries` a tuple as long, each entry None, a resize entry (7
+// items, send_tensor_resize) or a crops entry (8 items, send_tensor_crops); `preps` a tuple as
+// long, each entry None or (scale table or None, bias table or None, axis, scalar scale or None,
+// scalar bias or None, inner0, inner1, lead0, lead1, fill), a table a "dltensor" capsule.  Every
+// capsule, the boxes' and the tables' included, is consumed as send_tensor_struct consumes its
+// own.
+PyObject* py_send_tensor_prep(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
+  const char* usage =
+      "send_tensor_prep(handle, output_id, names, capsules, entries, preps, device_type, "
+      "metadata, flags): names is None over one capsule or a tuple as long as the tuple of "
+      "capsules; entries a tuple as long, of None, (mode, axis0, axis1, size0, size1, code, bits) "
+      "or the same with boxes; preps a tuple as long, of None or (scale table, bias table, axis, "
+      "scale, bias, inner0, inner1, lead0, lead1, fill)";
+  if (nargs != 9 || !as_long(args[4], args[3]) || !as_long(args[5], args[3])) {
+    PyErr_SetString(PyExc_TypeError, usage);
+    return nullptr;
+  }
+  Capsules caps;
+  if (!caps.take(args[2], args[3], usage, true, false)) return nullptr;
+  const size_t n = caps.fields.size();
+  std::vector<dora_tensor_resize> resizes(n);
+  std::vector<dora_tensor_crop> crops(n);
+  std::vector<dora_tensor_prep> preps(n);
+  std::vector<dora_tensor> boxes(n), tables(2 * n);  // field k's scale table, then its bias
+  for (size_t k = 0; k < n; ++k) {
+    PyObject* entry = PyTuple_GET_ITEM(args[4], Py_ssize_t(k));
+    if (entry != Py_None) {
+      if (!PyTuple_Check(entry) || (PyTuple_GET_SIZE(entry) != 7 && PyTuple_GET_SIZE(entry) != 8)) {
+        PyErr_SetString(PyExc_TypeError, usage);
+        return nullptr;
+      }
+      long long w[7];
+      for (int j = 0; j < 7; ++j) w[j] = PyLong_AsLongLong(PyTuple_GET_ITEM(entry, j));
+      if (PyErr_Occurred()) return nullptr;
+      if (w[0] < 1 || w[0] > INT32_MAX || w[1] < INT32_MIN || w[1] > INT32_MAX ||
+          w[2] < INT32_MIN || w[2] > INT32_MAX || w[5] < 0 || w[5] > 255 || w[6] < 0 ||
+          w[6] > 255) {
+        PyErr_Format(PyExc_TypeError, "field %zu: entry (mode %lld, axes %lld and %lld, code "
+                                      "%lld, %lld bits)", k, w[0], w[1], w[2], w[5], w[6]);
+        return nullptr;
+      }
+      if (PyTuple_GET_SIZE(entry) == 8) {
+        char what[48];
+        std::snprintf(what, sizeof(what), "field %zu: the boxes", k);
+        if (!caps.also(PyTuple_GET_ITEM(entry, 7), &boxes[k], what)) return nullptr;
+        dora_tensor_crop& c = crops[k];
+        c.mode = static_cast<uint32_t>(w[0]);
+        c.axis[0] = static_cast<int32_t>(w[1]);
+        c.axis[1] = static_cast<int32_t>(w[2]);
+        c.size[0] = static_cast<int64_t>(w[3]);
+        c.size[1] = static_cast<int64_t>(w[4]);
+        c.dtype_code = static_cast<uint8_t>(w[5]);
+        c.dtype_bits = static_cast<uint8_t>(w[6]);
+        c.boxes = &boxes[k];
+      } else {
+        dora_tensor_resize& r = resizes[k];
+        r.mode = static_cast<uint32_t>(w[0]);
+        r.axis[0] = static_cast<int32_t>(w[1]);
+        r.axis[1] = static_cast<int32_t>(w[2]);
+        r.size[0] = static_cast<int64_t>(w[3]);
+        r.size[1] = static_cast<int64_t>(w[4]);
+        r.dtype_code = static_cast<uint8_t>(w[5]);
+        r.dtype_bits = static_cast<uint8_t>(w[6]);
+      }
+    }
+    PyObject* prep = PyTuple_GET_ITEM(args[5], Py_ssize_t(k));
+    if (prep == Py_None) continue;
+    if (!PyTuple_Check(prep) || PyTuple_GET_SIZE(prep) != 10) {
+      PyErr_Format(PyExc_TypeError, "field %zu: a prep entry is None or (scale table, bias table, "
+                                    "axis, scale, bias, inner0, inner1, lead0, lead1, fill)", k);
+      return nullptr;
+    }
+    dora_tensor_prep& p = preps[k];
+    for (size_t t = 0; t < 2; ++t) {
+      PyObject* cap = PyTuple_GET_ITEM(prep, Py_ssize_t(t));
+      if (cap == Py_None) continue;
+      if (!caps.table(cap, &tables[2 * k + t], Py_ssize_t(k))) return nullptr;
+      (t ? p.bias : p.scale) = &tables[2 * k + t];
+    }
+    const long axis = PyLong_AsLong(PyTuple_GET_ITEM(prep, 2));
+    if (axis == -1 && PyErr_Occurred()) return nullptr;
+    if (axis < INT32_MIN || axis > INT32_MAX) {
+      PyErr_Format(PyExc_TypeError, "field %zu: axis %ld", k, axis);
+      return nullptr;
+    }
+    p.axis = static_cast<int32_t>(axis);
+    for (int t = 0; t < 2; ++t) {
+      PyObject* v = PyTuple_GET_ITEM(prep, 3 + t);
+      if (v == Py_None) continue;
+      const double x = PyFloat_AsDouble(v);
+      if (x == -1.0 && PyErr_Occurred()) return nullptr;
+      (t ? p.has_bias : p.has_scale) = 1;
+      (t ? p.bias_value : p.scale_value) = static_cast<float>(x);
+    }
+    for (int j = 0; j < 4; ++j) {
+      const long long v = PyLong_AsLongLong(PyTuple_GET_ITEM(prep, 5 + j));
+      if (v == -1 && PyErr_Occurred()) return nullptr;
+      (j < 2 ? p.inner[j] : p.lead[j - 2]) = static_cast<int64_t>(v);
+    }
+    const double fill = PyFloat_AsDouble(PyTuple_GET_ITEM(prep, 9));
+    if (fill == -1.0 && PyErr_Occurred()) return nullptr;
+    p.fill = static_cast<float>(fill);
+  }
+  Frame f;
+  if (!f.take(args[0], args[1], args[6], args[7], args[8]) || !caps.consume()) return nullptr;
+  int rc;
+  Py_BEGIN_ALLOW_THREADS
+  rc = dora_node_send_output_tensor_prep(f.node, f.oid, caps.fields.data(), n, resizes.data(),
+                                         crops.data(), preps.data(), f.dev, f.params,
+                                         f.params_len, f.flags);
+  Py_END_ALLOW_THREADS
+  return PyLong_FromLong(rc);
+}
+
 // send_tensor_list(handle, output_id, names, capsules, partition, form, partition_device,
 // device_type, metadata, flags) -> status: a ragged batch as dora_node_send_output_tensor_list.
 // `names` is a tuple of str over the tuple `capsules`, or None over a tuple of one capsule (a bare
@@ -1336,6 +1452,9 @@ PyMethodDef methods[] = {
     {"send_tensor_reduce",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_reduce)),
      METH_FASTCALL, "dora_node_send_output_tensor_reduce of DLPack capsules, which it consumes."},
+    {"send_tensor_prep",
+     reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_prep)),
+     METH_FASTCALL, "dora_node_send_output_tensor_prep of DLPack capsules, which it consumes."},
     {"send_tensor_crops",
      reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(py_send_tensor_crops)),
      METH_FASTCALL, "dora_node_send_output_tensor_crop of DLPack capsules, which it consumes."},

@@ -34,6 +34,15 @@
 // axes, computed again only when a coordinate changes — the C channels of an HWC pixel share
 // both axes' taps, the elements of a CHW unit those of the first axis.  Taps are naturally
 // aligned element loads at off + ia * sa + ib * sb.  One 16-byte store a unit.
+//
+// Model inputs (gather_resize_prep_kernel, a prep plan of tensor_plan.cpp): the body takes the step
+// as a type, prep::None or prep::Args, as cast_device.h's body takes its flag A — with None no line
+// of the step is compiled.  With prep::Args three things are added.  Placement: an axis' taps are
+// those of o - lead over `inner` output steps, and an element whose o is not in
+// [lead, lead + inner) on either axis reads no tap and has the value `fill`.  Channel: the
+// tables' index is the odometer's coordinate along their axis, so nothing is divided per element,
+// and their words are fetched again only when that coordinate changes.  Step: y = r * S + B, the
+// policy's product and then its sum, before to_dst.
 #pragma once
 
 #include <cstdint>
@@ -126,6 +135,22 @@ struct Walk {
   Tap ta, tb;
 };
 
+// The same under the model-input step (prep::Args): whether the element lies outside the placed
+// image along either axis, the channel the terms were fetched for (-1: none yet) and the terms.
+struct PrepWalk : Walk {
+  int64_t oc;
+  float s, b;
+  bool outa, outb;
+};
+template <class PA>
+struct WalkFor {
+  using type = Walk;
+};
+template <>
+struct WalkFor<prep::Args> {
+  using type = PrepWalk;
+};
+
 // Index `ax` of the odometer, as a chain of selects: no register array is indexed by a variable.
 DORA_HDI int64_t coord(const RowPos& p, uint32_t ax) {
   int64_t c = 0;
@@ -134,32 +159,85 @@ DORA_HDI int64_t coord(const RowPos& p, uint32_t ax) {
   return c;
 }
 
+// The terms of the element the odometer stands on: the tables' words again only where the
+// coordinate along their axis differs from the one they were fetched for (CHW: rarely; HWC: every
+// element, the same few words a wave shares).  The channel is a coordinate, never a division.
+template <class W, class M>
+DORA_HDI void refresh_terms(const RowPos& p, W& w, M& m, const prep::Args& pa) {
+  if (!pa.stab && !pa.btab) return;
+  const int64_t c = coord(p, pa.cax);
+  if (c == w.oc) return;
+  w.oc = c;  // < shape[cax], the tables' length
+  if (pa.stab) w.s = m.load_table(pa.stab, static_cast<uint64_t>(c));
+  if (pa.btab) w.b = m.load_table(pa.btab, static_cast<uint64_t>(c));
+}
+
+// The walk's terms before any element: the scalars, and no channel fetched.
+template <class W>
+DORA_HDI void start_terms(W& w, const prep::Args& pa) {
+  w.oc = -1;
+  w.s = pa.scale;
+  w.b = pa.bias;
+  w.outa = w.outb = false;
+}
+
 // The taps of the element the odometer stands on: an axis' taps again only where its coordinate
-// differs from the one they were computed for.
-template <class M>
-DORA_HDI void refresh(const Args& a, Walk& w, M& m) {
+// differs from the one they were computed for.  With the step (`pa` a prep::Args) an axis' taps
+// are those of o - lead over `inner` output steps, and the axis is marked outside where o is not
+// in [lead, lead + inner): no tap is computed for it.
+template <class W, class PA, class M>
+DORA_HDI void refresh(const Args& a, W& w, M& m, const PA& pa) {
   const int64_t oa = coord(w.p, a.ax[0]), ob = coord(w.p, a.ax[1]);
   if (oa != w.oa) {
     w.oa = oa;
-    tap_of(a.mode, a.in[0], a.out[0], static_cast<uint32_t>(oa), a.sa[0], w.ta, m);
+    if constexpr (PA::on) {
+      const int64_t o = oa - pa.lead[0];
+      w.outa = o < 0 || o >= pa.inner[0];
+      if (!w.outa)
+        tap_of(a.mode, a.in[0], pa.inner[0], static_cast<uint32_t>(o), a.sa[0], w.ta, m);
+    } else {
+      tap_of(a.mode, a.in[0], a.out[0], static_cast<uint32_t>(oa), a.sa[0], w.ta, m);
+    }
   }
   if (ob != w.ob) {
     w.ob = ob;
-    tap_of(a.mode, a.in[1], a.out[1], static_cast<uint32_t>(ob), a.sa[1], w.tb, m);
+    if constexpr (PA::on) {
+      const int64_t o = ob - pa.lead[1];
+      w.outb = o < 0 || o >= pa.inner[1];
+      if (!w.outb)
+        tap_of(a.mode, a.in[1], pa.inner[1], static_cast<uint32_t>(o), a.sa[1], w.tb, m);
+    } else {
+      tap_of(a.mode, a.in[1], a.out[1], static_cast<uint32_t>(ob), a.sa[1], w.tb, m);
+    }
   }
+  if constexpr (PA::on) refresh_terms(w.p, w, m, pa);
 }
 
-template <class M>
-DORA_HDI void walk_start(const Args& a, uint64_t e, Walk& w, M& m) {
+template <class W, class PA, class M>
+DORA_HDI void walk_start(const Args& a, uint64_t e, W& w, M& m, const PA& pa) {
   row_pos(a.g, e, w.p);
   w.oa = w.ob = -1;
-  refresh(a, w, m);
+  if constexpr (PA::on) start_terms(w, pa);
+  refresh(a, w, m, pa);
+}
+
+template <class W, class PA, class M>
+DORA_HDI void walk_next(const Args& a, W& w, M& m, const PA& pa) {
+  next_row(a.g, w.p);
+  refresh(a, w, m, pa);
 }
 
 template <class M>
+DORA_HDI void refresh(const Args& a, Walk& w, M& m) {
+  refresh(a, w, m, prep::None{});
+}
+template <class M>
+DORA_HDI void walk_start(const Args& a, uint64_t e, Walk& w, M& m) {
+  walk_start(a, e, w, m, prep::None{});
+}
+template <class M>
 DORA_HDI void walk_next(const Args& a, Walk& w, M& m) {
-  next_row(a.g, w.p);
-  refresh(a, w, m);
+  walk_next(a, w, m, prep::None{});
 }
 
 // The value of the element the walk stands on, its source of type K.
@@ -192,70 +270,100 @@ DORA_HDI uint32_t to_dst(const Args& a, float y, M& m) {
   }
 }
 
+// The affine step of the model-input fields: the product rounded, then the sum, each applied only
+// where its term is present (a zero product keeps its sign).
+template <class W, class M>
+DORA_HDI float step(float y, const W& w, M& m, const prep::Args& pa) {
+  if (pa.has_scale) y = m.mul(y, w.s);
+  if (pa.has_bias) y = m.add(y, w.b);
+  return y;
+}
+
+// The value of the element the walk stands on before its conversion: value_at, or with the step
+// the fill where the element lies outside the placed image (no tap is read), then the step.
+template <uint32_t K, class W, class PA, class M>
+DORA_HDI float prepped_at(const Args& a, const W& w, M& m, const PA& pa) {
+  if constexpr (PA::on) {
+    float r;
+    if (w.outa || w.outb) r = pa.fill;
+    else r = value_at<K>(a, w, m);
+    return step(r, w, m, pa);
+  } else {
+    return value_at<K>(a, w, m);
+  }
+}
+
 // Whole unit `u` of the output.
-template <uint32_t K, int D, class M>
-DORA_HDI void resize_unit(const Args& a, uint64_t u, M& m) {
+template <uint32_t K, int D, class PA, class M>
+DORA_HDI void resize_unit(const Args& a, uint64_t u, M& m, const PA& pa) {
   constexpr int E = 16 / D;
   const uint64_t e = a.g.head + static_cast<uint64_t>(E) * u;
-  Walk w;
-  walk_start(a, e, w, m);
+  typename WalkFor<PA>::type w;
+  walk_start(a, e, w, m, pa);
   U16 out = {{0, 0, 0, 0}};
 #pragma unroll
   for (int j = 0; j < E; ++j) {
-    const uint32_t q = to_dst<D>(a, value_at<K>(a, w, m), m);
+    const uint32_t q = to_dst<D>(a, prepped_at<K>(a, w, m, pa), m);
     if constexpr (D == 1) out.w[j / 4] |= q << (8 * (j % 4));
     else if constexpr (D == 2) out.w[j / 2] |= q << (16 * (j % 2));
     else out.w[j] = q;
-    if (j + 1 < E) walk_next(a, w, m);
+    if (j + 1 < E) walk_next(a, w, m, pa);
   }
   m.store16(e * D, out);
 }
 
 // Output element `e` on its own (before the first and after the last whole unit).
-template <uint32_t K, int D, class M>
-DORA_HDI void resize_elem(const Args& a, uint64_t e, M& m) {
-  Walk w;
-  walk_start(a, e, w, m);
-  m.template store_elem<D>(e, to_dst<D>(a, value_at<K>(a, w, m), m));
+template <uint32_t K, int D, class PA, class M>
+DORA_HDI void resize_elem(const Args& a, uint64_t e, M& m, const PA& pa) {
+  typename WalkFor<PA>::type w;
+  walk_start(a, e, w, m, pa);
+  m.template store_elem<D>(e, to_dst<D>(a, prepped_at<K>(a, w, m, pa), m));
 }
 
 // cast_lane_as' division of the work: lanes 0..15 a head element each, lanes 16..31 a tail
 // element each (at most E - 1 <= 15 of either), and every lane the whole units lane,
 // lane + lanes, ..
-template <uint32_t K, int D, class M>
-DORA_HDI void lane_as(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+template <uint32_t K, int D, class PA, class M>
+DORA_HDI void lane_as(const Args& a, uint64_t lane, uint64_t lanes, M& m, const PA& pa) {
   constexpr int E = 16 / D;
   static_assert(E - 1 <= 15, "16 lanes each for the head's and the tail's elements");
   if (lane < 16) {
-    if (lane < a.g.head) resize_elem<K, D>(a, lane, m);
+    if (lane < a.g.head) resize_elem<K, D>(a, lane, m, pa);
   } else if (lane < 32) {
     const uint64_t t0 = a.g.head + static_cast<uint64_t>(E) * a.g.nunits;  // <= total
-    if (lane - 16 < a.g.total - t0) resize_elem<K, D>(a, t0 + (lane - 16), m);
+    if (lane - 16 < a.g.total - t0) resize_elem<K, D>(a, t0 + (lane - 16), m, pa);
   }
-  for (uint64_t u = lane; u < a.g.nunits; u += lanes) resize_unit<K, D>(a, u, m);
+  for (uint64_t u = lane; u < a.g.nunits; u += lanes) resize_unit<K, D>(a, u, m, pa);
 }
 
-template <uint32_t K, class M>
-DORA_HDI void lane_of(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
+template <uint32_t K, class PA, class M>
+DORA_HDI void lane_of(const Args& a, uint64_t lane, uint64_t lanes, M& m, const PA& pa) {
   switch (a.dsize) {
-    case 1: lane_as<K, 1>(a, lane, lanes, m); break;
-    case 2: lane_as<K, 2>(a, lane, lanes, m); break;
-    default: lane_as<K, 4>(a, lane, lanes, m); break;
+    case 1: lane_as<K, 1>(a, lane, lanes, m, pa); break;
+    case 2: lane_as<K, 2>(a, lane, lanes, m, pa); break;
+    default: lane_as<K, 4>(a, lane, lanes, m, pa); break;
   }
 }
 
-// Everything lane `lane` of `lanes` does for a resized field.
+// Everything lane `lane` of `lanes` does for a resized field; with `pa` a prep::Args
+// (gather_resize_prep_kernel) every element goes through placement and the affine step, without
+// it (prep::None) no line of either is compiled.
+template <class PA, class M>
+DORA_HDI void resize_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m, const PA& pa) {
+  switch (a.src) {
+    case cast::kU8: lane_of<cast::kU8>(a, lane, lanes, m, pa); break;
+    case cast::kI8: lane_of<cast::kI8>(a, lane, lanes, m, pa); break;
+    case cast::kU16: lane_of<cast::kU16>(a, lane, lanes, m, pa); break;
+    case cast::kI16: lane_of<cast::kI16>(a, lane, lanes, m, pa); break;
+    case cast::kF16: lane_of<cast::kF16>(a, lane, lanes, m, pa); break;
+    case cast::kBF16: lane_of<cast::kBF16>(a, lane, lanes, m, pa); break;
+    default: lane_of<cast::kF32>(a, lane, lanes, m, pa); break;
+  }
+}
+
 template <class M>
 DORA_HDI void resize_lane(const Args& a, uint64_t lane, uint64_t lanes, M& m) {
-  switch (a.src) {
-    case cast::kU8: lane_of<cast::kU8>(a, lane, lanes, m); break;
-    case cast::kI8: lane_of<cast::kI8>(a, lane, lanes, m); break;
-    case cast::kU16: lane_of<cast::kU16>(a, lane, lanes, m); break;
-    case cast::kI16: lane_of<cast::kI16>(a, lane, lanes, m); break;
-    case cast::kF16: lane_of<cast::kF16>(a, lane, lanes, m); break;
-    case cast::kBF16: lane_of<cast::kBF16>(a, lane, lanes, m); break;
-    default: lane_of<cast::kF32>(a, lane, lanes, m); break;
-  }
+  resize_lane(a, lane, lanes, m, prep::None{});
 }
 
 // The conversions and arithmetic of a policy without the hardware's (host plans, the emulation):
@@ -295,6 +403,47 @@ DORA_HD Args make_resize_args(const GatherDesc* g, const ResizeDesc* r, const ui
 }
 
 }  // namespace multi
+
+namespace prep {
+
+// The step's arguments of a field whose output `r` describes (a crops field's with K in front,
+// `d.axis` counted with it): the image fills the output unless `d` places it.
+DORA_HD Args make_args(const PrepDesc& d, const ResizeDesc& r) {
+  Args a{};
+  a.stab = d.scale_tab;
+  a.btab = d.bias_tab;
+  a.scale = d.scale;
+  a.bias = d.bias;
+  a.fill = d.fill;
+  for (int j = 0; j < 2; ++j) {
+    a.inner[j] = static_cast<uint16_t>(d.placed ? d.inner[j] : r.shape[r.ax[j]]);
+    a.lead[j] = static_cast<uint16_t>(d.placed ? d.lead[j] : 0);
+  }
+  a.cax = static_cast<uint8_t>(d.axis + (kDims - r.nd));
+  a.has_scale = d.scale_tab || d.has_scale;
+  a.has_bias = d.bias_tab || d.has_bias;
+  return a;
+}
+
+// Arguments of a launch of gather_resize_prep_kernel or gather_crop_prep_kernel: the launch as
+// the plain kernels take it and, beside f[], the step of every field (all zero but `inner` for a
+// field without one), read by these two kernels alone.
+struct Launch {
+  multi::Args a;
+  Args p[multi::kMaxFields];
+};
+static_assert(sizeof(Launch) <= 4096, "prep::Launch is passed by value: the kernel-argument limit");
+
+DORA_HD Launch make_resize_launch(const GatherDesc* g, const ResizeDesc* r, const PrepDesc* d,
+                                  const uint64_t* off, const int* tile_c, int n, uint8_t* dst) {
+  Launch l{};
+  l.a = multi::make_resize_args(g, r, off, tile_c, n, dst);
+  for (int k = 0; k < n; ++k)
+    if (r[k].on) l.p[k] = make_args(d[k], r[k]);
+  return l;
+}
+
+}  // namespace prep
 
 }  // namespace gather
 }  // namespace dora

@@ -49,6 +49,13 @@
 // validated and viewed as a resized frame would be, the boxes as K dense rows of four int32 words
 // beside it — read and cropped by the CPU here for host values; for device values never read, their
 // 16 * K bytes kept for check_plan_range and the plan's one launch (crop_device.h).
+//
+// Model inputs (dora_gpu_plan_tensor_prep) are a resize plan or a crop plan whose fields may carry
+// a prep entry each: the resized image placed inside a filled output (resize only) and a
+// per-channel or scalar affine step before the conversion, the tables validated like an affine
+// field's — by the CPU here for host values, by the plan's one launch of
+// gather_resize_prep_kernel or gather_crop_prep_kernel for device values.  The wire form never
+// depends on the entry.
 #include <cstring>
 #include <memory>
 #include <string>
@@ -731,28 +738,37 @@ struct ResizeHostMem : gather::resize::HostArith {
     std::memcpy(&raw, src + s, S);  // (little-endian)
     return raw;
   }
+  // (word `c` of a host table of the model-input step, any alignment)
+  float load_table(const uint8_t* tab, uint64_t c) const {
+    float v;
+    std::memcpy(&v, tab + 4 * c, 4);
+    return v;
+  }
 };
 
-template <uint32_t K>
-void resize_all(const gather::resize::Args& a, uint8_t* dst) {
+// (`pa`: gather::prep::None, or the model-input step's arguments)
+template <uint32_t K, class PA>
+void resize_all(const gather::resize::Args& a, uint8_t* dst, const PA& pa) {
   namespace rs = gather::resize;
   ResizeHostMem m{{}, a.g.src};
-  rs::Walk w;
-  rs::walk_start(a, 0, w, m);
+  typename rs::WalkFor<PA>::type w;
+  rs::walk_start(a, 0, w, m, pa);
   for (uint64_t e = 0; e < a.g.total; ++e) {
-    const float y = rs::value_at<K>(a, w, m);
+    const float y = rs::prepped_at<K>(a, w, m, pa);
     const uint32_t q = a.dsize == 1   ? rs::to_dst<1>(a, y, m)
                        : a.dsize == 2 ? rs::to_dst<2>(a, y, m)
                                       : rs::to_dst<4>(a, y, m);
     std::memcpy(dst + e * a.dsize, &q, a.dsize);  // (little-endian)
-    if (e + 1 < a.g.total) rs::walk_next(a, w, m);
+    if (e + 1 < a.g.total) rs::walk_next(a, w, m, pa);
   }
 }
 
-void resize_host(const GatherDesc& g, const ResizeDesc& r, uint8_t* dst) {
+void resize_host(const GatherDesc& g, const ResizeDesc& r, const PrepDesc& d, uint8_t* dst) {
   const gather::resize::Args a = gather::resize::make_args(g, r, dst);
-  with_src_kind(static_cast<int>(a.src),
-                [&](auto K) { resize_all<decltype(K)::value>(a, dst); });
+  with_src_kind(static_cast<int>(a.src), [&](auto K) {
+    if (d.on) resize_all<decltype(K)::value>(a, dst, gather::prep::make_args(d, r));
+    else resize_all<decltype(K)::value>(a, dst, gather::prep::None{});
+  });
 }
 
 // What resizes `t` (dora_gpu_plan_tensor_resize, `r.mode` != 0): the entry's and the tensor's
@@ -850,24 +866,27 @@ struct CropHostMem : ResizeHostMem {
   }
 };
 
-template <uint32_t K>
-void crop_all(const gather::crop::Args& a, uint8_t* dst) {
+template <uint32_t K, class PA>
+void crop_all(const gather::crop::Args& a, uint8_t* dst, const PA& pa) {
   namespace cr = gather::crop;
   CropHostMem m{{{}, a.r.g.src}, a.boxes};
-  cr::Walk w;
-  cr::walk_start(a, 0, w, m);
+  cr::WalkFor<PA> w;
+  cr::walk_start(a, 0, w, m, pa);
   for (uint64_t e = 0; e < a.r.g.total; ++e) {
-    const uint32_t q = a.r.dsize == 1   ? cr::elem_at<K, 1>(a, w, m)
-                       : a.r.dsize == 2 ? cr::elem_at<K, 2>(a, w, m)
-                                        : cr::elem_at<K, 4>(a, w, m);
+    const uint32_t q = a.r.dsize == 1   ? cr::elem_at<K, 1>(a, w, m, pa)
+                       : a.r.dsize == 2 ? cr::elem_at<K, 2>(a, w, m, pa)
+                                        : cr::elem_at<K, 4>(a, w, m, pa);
     std::memcpy(dst + e * a.r.dsize, &q, a.r.dsize);  // (little-endian)
-    if (e + 1 < a.r.g.total) cr::walk_next(a, w, m);
+    if (e + 1 < a.r.g.total) cr::walk_next(a, w, m, pa);
   }
 }
 
-void crop_host(const GatherDesc& g, const CropDesc& c, uint8_t* dst) {
+void crop_host(const GatherDesc& g, const CropDesc& c, const PrepDesc& d, uint8_t* dst) {
   const gather::crop::Args a = gather::crop::make_args(g, c, dst);
-  with_src_kind(static_cast<int>(a.r.src), [&](auto K) { crop_all<decltype(K)::value>(a, dst); });
+  with_src_kind(static_cast<int>(a.r.src), [&](auto K) {
+    if (d.on) crop_all<decltype(K)::value>(a, dst, gather::prep::make_args(d, c.rs));
+    else crop_all<decltype(K)::value>(a, dst, gather::prep::None{});
+  });
 }
 
 // What crops `t` (dora_gpu_plan_tensor_crop, `c.mode` != 0): the frame's dimension count, then
@@ -932,6 +951,79 @@ int describe_crop(const dora_tensor& t, const dora_tensor_crop& c, ArrowDeviceTy
       __builtin_mul_overflow(v.bytes, cd.k, &v.bytes) || v.bytes >> 63)
     return fail(DORA_ERR_INVALID, "tensor byte count overflows 64 bits");
   oshape.insert(oshape.begin(), k);
+  return DORA_OK;
+}
+
+// Whether a prep entry adds anything to its field (all zero: it does not; `fill` alone is not
+// read).
+bool prep_on(const dora_tensor_prep& p) {
+  return p.scale || p.bias || p.has_scale || p.has_bias || p.inner[0] || p.inner[1] ||
+         p.lead[0] || p.lead[1];
+}
+
+// The model-input step of a field `t` (validated) whose resize — or, `crop`, whose crops with K in
+// front — `rs` describes, by the entry `pr` (prep_on): its refusals, else `out`.
+int describe_prep(const dora_tensor& t, const dora_tensor_prep& pr, const ResizeDesc& rs, bool crop,
+                  ArrowDeviceType dev, PrepDesc& out) {
+  out = PrepDesc{};
+  const int shift = crop ? 1 : 0;  // (K in front of the frame's dimensions)
+  if (pr.scale && pr.has_scale)
+    return fail(DORA_ERR_INVALID, "a scale table together with a scalar scale (has_scale): one "
+                "scale a field");
+  if (pr.bias && pr.has_bias)
+    return fail(DORA_ERR_INVALID, "a bias table together with a scalar bias (has_bias): one bias "
+                "a field");
+  if (pr.scale || pr.bias) {
+    if (pr.axis < 0 || pr.axis >= t.ndim)
+      return fail(DORA_ERR_INVALID, "prep axis %d is outside the tensor's %d dimensions", pr.axis,
+                  t.ndim);
+    if (pr.axis + shift == rs.ax[0] || pr.axis + shift == rs.ax[1])
+      return fail(DORA_ERR_INVALID, "prep axis %d is one of the two resized axes (%d and %d): the "
+                  "tables run along a dimension that is kept", pr.axis, rs.ax[0] - shift,
+                  rs.ax[1] - shift);
+    int rc = pr.scale ? describe_table(*pr.scale, "scale", t, pr.axis, dev, &out.scale_tab)
+                      : DORA_OK;
+    if (rc == DORA_OK && pr.bias)
+      rc = describe_table(*pr.bias, "bias", t, pr.axis, dev, &out.bias_tab);
+    if (rc != DORA_OK) return rc;
+    out.channels = static_cast<uint64_t>(t.shape[pr.axis]);
+    out.axis = pr.axis + shift;
+  }
+  if (pr.has_scale && !std::isfinite(pr.scale_value))
+    return fail(DORA_ERR_INVALID, "prep scale %f is not finite",
+                static_cast<double>(pr.scale_value));
+  if (pr.has_bias && !std::isfinite(pr.bias_value))
+    return fail(DORA_ERR_INVALID, "prep bias %f is not finite",
+                static_cast<double>(pr.bias_value));
+  if (pr.inner[0] || pr.inner[1] || pr.lead[0] || pr.lead[1]) {
+    if (crop)
+      return fail(DORA_ERR_INVALID, "inner / lead on a field of crops: placement for crops is not "
+                  "provided (per-box aspect would put a division per box on the device)");
+    for (int j = 0; j < 2; ++j) {
+      const int64_t size = rs.shape[rs.ax[j]];
+      if (pr.inner[j] < 1 || pr.inner[j] > size)
+        return fail(DORA_ERR_INVALID, "prep inner[%d] %lld is outside [1, %lld], the output's "
+                    "extent along axis %d", j, static_cast<long long>(pr.inner[j]),
+                    static_cast<long long>(size), rs.ax[j]);
+      if (pr.lead[j] < 0 || pr.lead[j] > size - pr.inner[j])
+        return fail(DORA_ERR_INVALID, "prep lead[%d] %lld is outside [0, %lld]: the image of "
+                    "extent %lld lies inside the output's %lld along axis %d", j,
+                    static_cast<long long>(pr.lead[j]),
+                    static_cast<long long>(size - pr.inner[j]),
+                    static_cast<long long>(pr.inner[j]), static_cast<long long>(size), rs.ax[j]);
+      out.inner[j] = pr.inner[j];
+      out.lead[j] = pr.lead[j];
+    }
+    if (!std::isfinite(pr.fill))
+      return fail(DORA_ERR_INVALID, "prep fill %f is not finite", static_cast<double>(pr.fill));
+    out.placed = true;
+    out.fill = pr.fill;
+  }
+  out.on = true;
+  out.has_scale = pr.has_scale ? 1 : 0;
+  out.scale = pr.has_scale ? pr.scale_value : 1.0f;
+  out.has_bias = pr.has_bias ? 1 : 0;
+  out.bias = pr.has_bias ? pr.bias_value : 0.0f;
   return DORA_OK;
 }
 
@@ -1008,6 +1100,7 @@ struct FieldOps {
   const dora_tensor_reduce* reduces = nullptr;  // describe_reduce
   const dora_tensor_resize* resizes = nullptr;  // describe_resize
   const dora_tensor_crop* crops = nullptr;      // describe_crop
+  const dora_tensor_prep* preps = nullptr;      // describe_prep, with a resize or crops
 };
 
 // One field of a message, whatever is done to it on the way.  `v`: the view of what is read (a
@@ -1040,15 +1133,22 @@ int describe_field(const dora_tensor& t, size_t k, const FieldOps& ops, ArrowDev
   }
   d.ndim = t.ndim;
   d.elem = t.dtype_bits / 8u;
+  const bool prep = ops.preps && prep_on(ops.preps[k]);
   if (ops.crops && ops.crops[k].mode) {
     rc = describe_crop(t, ops.crops[k], dev, pf.crop, d.v, d.own);
-    d.launch = PlanLaunch::kCrop;
+    if (rc == DORA_OK && prep) rc = describe_prep(t, ops.preps[k], pf.crop.rs, true, dev, pf.prep);
+    d.launch = prep ? PlanLaunch::kCropPrep : PlanLaunch::kCrop;
     d.elem = pf.crop.rs.dst_bits / 8u;
     d.ndim = t.ndim + 1;
   } else if (ops.resizes && ops.resizes[k].mode) {
     rc = describe_resize(t, ops.resizes[k], dev, pf.resize, d.v, d.own);
-    d.launch = PlanLaunch::kResize;
+    if (rc == DORA_OK && prep) rc = describe_prep(t, ops.preps[k], pf.resize, false, dev, pf.prep);
+    d.launch = prep ? PlanLaunch::kResizePrep : PlanLaunch::kResize;
     d.elem = pf.resize.dst_bits / 8u;
+  } else if (prep) {  // refused: the tensor's own refusals first, then the entry's
+    rc = describe_tensor(&t, dev, d.v);
+    if (rc == DORA_OK)
+      rc = fail(DORA_ERR_INVALID, "a prep entry on a field that is neither resized nor crops");
   } else if (ops.reduces && ops.reduces[k].op) {
     rc = describe_reduce(t, ops.reduces[k], dev, pf.reduce, d.v, d.own);
     d.launch = PlanLaunch::kReduce;
@@ -1161,8 +1261,8 @@ void stage_host_fields(dora_plan& p, ArrowDeviceType dev, uint64_t staged) {
       p.segs.push_back({pf.gd.view.src, pf.dst_off, pf.bytes});
       continue;
     }
-    if (pf.crop.on) crop_host(pf.gd, pf.crop, p.staged.data() + at);
-    else if (pf.resize.on) resize_host(pf.gd, pf.resize, p.staged.data() + at);
+    if (pf.crop.on) crop_host(pf.gd, pf.crop, pf.prep, p.staged.data() + at);
+    else if (pf.resize.on) resize_host(pf.gd, pf.resize, pf.prep, p.staged.data() + at);
     else if (pf.reduce.on) reduce_host(pf.gd.view, pf.reduce, p.staged.data() + at);
     else if (pf.cast.on) cast_host(pf.gd.view, pf.cast, p.staged.data() + at);
     else gather_host(pf.gd.view, p.staged.data() + at);
@@ -1473,6 +1573,33 @@ int build_tensor_crop_plan(const dora_tensor_field* f, size_t n, const dora_tens
   if (rf != DORA_OK) return rf;
   FieldOps ops;
   ops.crops = crops;
+  return build_record(f, n, dev, bare, nullptr, out, ops);
+}
+
+int build_tensor_prep_plan(const dora_tensor_field* f, size_t n, const dora_tensor_resize* resizes,
+                           const dora_tensor_crop* crops, const dora_tensor_prep* preps,
+                           ArrowDeviceType dev, dora_plan** out) {
+  bool any = false, any_r = false, any_c = false, bare = false;
+  for (size_t k = 0; f && k < n; ++k) {
+    any |= preps && prep_on(preps[k]);
+    any_r |= resizes && resizes[k].mode != 0;
+    any_c |= crops && crops[k].mode != 0;
+  }
+  if (any_r && any_c) {
+    if (out) *out = nullptr;
+    return fail(DORA_ERR_INVALID, "resize entries and crops entries are both active in one call: "
+                "resize and crops in one record are not provided");
+  }
+  // no prep entry at all: the resize's or the crops' plan, whatever it is, refusals included
+  if (!any)
+    return any_c ? build_tensor_crop_plan(f, n, crops, dev, out)
+                 : build_tensor_resize_plan(f, n, resizes, dev, out);
+  const int rf = begin_record(f, n, dev, out, "a model input", &bare);
+  if (rf != DORA_OK) return rf;
+  FieldOps ops;
+  ops.resizes = any_r ? resizes : nullptr;
+  ops.crops = any_c ? crops : nullptr;
+  ops.preps = preps;
   return build_record(f, n, dev, bare, nullptr, out, ops);
 }
 
@@ -1883,6 +2010,13 @@ int dora_gpu_plan_tensor_crop(const dora_tensor_field* fields, size_t n,
                               const dora_tensor_crop* crops, ArrowDeviceType device_type,
                               dora_plan** out) {
   return dora::build_tensor_crop_plan(fields, n, crops, device_type, out);
+}
+
+int dora_gpu_plan_tensor_prep(const dora_tensor_field* fields, size_t n,
+                              const dora_tensor_resize* resizes, const dora_tensor_crop* crops,
+                              const dora_tensor_prep* preps, ArrowDeviceType device_type,
+                              dora_plan** out) {
+  return dora::build_tensor_prep_plan(fields, n, resizes, crops, preps, device_type, out);
 }
 
 int dora_gpu_plan_tensor_resize(const dora_tensor_field* fields, size_t n,

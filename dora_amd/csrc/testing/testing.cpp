@@ -541,7 +541,7 @@ int dora_gpu_test_plan_resize(const dora_plan* plan, size_t i, const void* dst, 
   namespace rs = dora::gather::resize;
   const dora::PlanField& f = plan->fields[i];
   const dora::ResizeDesc& r = f.resize;
-  const bool on = plan->launch == dora::PlanLaunch::kResize && r.on;
+  const bool on = dora::resizes(plan->launch) && r.on;
   if (mode) *mode = on ? int(r.mode) : 0;
   if (outputs) *outputs = on ? r.count : 0;
   if (dst_bits) *dst_bits = on ? r.dst_bits : 0;
@@ -573,7 +573,7 @@ int dora_gpu_test_plan_crop(const dora_plan* plan, size_t i, const void* dst, in
     return dora::fail(DORA_ERR_INVALID, "not a plan that keeps a field %zu", i);
   const dora::PlanField& f = plan->fields[i];
   const dora::CropDesc& c = f.crop;
-  const bool on = plan->launch == dora::PlanLaunch::kCrop && c.on;
+  const bool on = dora::crops(plan->launch) && c.on;
   if (mode) *mode = on ? int(c.rs.mode) : 0;
   if (k) *k = on ? c.k : 0;
   if (boxes) *boxes = on ? c.boxes : nullptr;
@@ -623,6 +623,30 @@ int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mas
   }
   for (size_t i = 0; stride0 && i < dora::kMaxStructFields; ++i)
     stride0[i] = dev && i < plan->fields.size() ? plan->fields[i].stride0 : 0;
+  return DORA_OK;
+}
+
+int dora_gpu_test_plan_prep(const dora_plan* plan, size_t i, int* on, const void** scale_table,
+                            const void** bias_table, uint64_t* channels, int* axis,
+                            int64_t* inner, int64_t* lead, float* fill, int64_t* lo, int64_t* hi) {
+  if (!plan || !plan->dev_tensor || i >= plan->fields.size())
+    return dora::fail(DORA_ERR_INVALID, "not a device plan with a field %zu", i);
+  const dora::PrepDesc& d = plan->fields[i].prep;
+  const bool is = (plan->launch == dora::PlanLaunch::kResizePrep ||
+                   plan->launch == dora::PlanLaunch::kCropPrep) && d.on;
+  const bool tables = is && (d.scale_tab || d.bias_tab);
+  if (on) *on = is;
+  if (scale_table) *scale_table = is ? d.scale_tab : nullptr;
+  if (bias_table) *bias_table = is ? d.bias_tab : nullptr;
+  if (channels) *channels = tables ? d.channels : 0;
+  if (axis) *axis = tables ? d.axis : -1;
+  for (int j = 0; j < 2; ++j) {
+    if (inner) inner[j] = is && d.placed ? d.inner[j] : 0;
+    if (lead) lead[j] = is && d.placed ? d.lead[j] : 0;
+  }
+  if (fill) *fill = is && d.placed ? d.fill : 0.0f;
+  if (lo) *lo = 0;
+  if (hi) *hi = tables ? dora::table_reach(d.scale_tab, d.channels).hi : -1;
   return DORA_OK;
 }
 

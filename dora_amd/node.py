@@ -587,29 +587,16 @@ class Node:
                 raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion or an argmax beside "
                                                "a resize in one message is not offered (send the "
                                                "field in a message of its own)")
+        if any(isinstance(v, _Resized) and v._prep() is not None
+               for v in (data.values() if isinstance(data, dict) else (data,))):
+            return self._send_tensor_prep(output_id, data, _Resized, metadata, flags)
         return self._send_entries(output_id, data, (_Resized,), _fast.send_tensor_resize,
                                   self._lib.dora_node_send_output_tensor_resize, metadata, flags)
 
-    def _send_tensor_crops(self, output_id: str, data, metadata, flags: int) -> int:
-        """Boxes cut from a frame and resized on send (dora_amd.tensor.crops), or a dict of
-        tensors of which some are crops and the rest plain, as the tensor or Struct message of the
-        crops and the plain values (dora_node_send_output_tensor_crop).  A dict that also holds a
-        cast, a quantised, an argmax or a resized field is not offered: nothing is sent.  It keeps
-        a dispatch of its own, as `_send_tensor_affine` does: every field of crops brings one more
-        tensor, its boxes.
-
-        Boxes live where the frame lives.  With host values they are a sequence, a numpy array or
-        a CPU tensor, read inside the call.  With values on this node's GPU they are an int32
-        tensor there: they do the `__dlpack__(stream=<the node stream>)` handshake like every
-        field, are never read on the host, and an asynchronous send holds them with the values
-        until `sync()`."""
+    def _boxes_of(self, items, kind: str) -> list:
+        """The boxes of every crops field of `items`, in order, as the send hands them on: held
+        against where the frame lives (`kind`), host boxes as something numpy exports."""
         import numpy as np
-        for name, v in (data.items() if isinstance(data, dict) else ()):
-            if isinstance(v, (_Cast, _Quantized, _Argmax, _Resized)):
-                raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion, an argmax or a "
-                                               "resize beside crops in one message is not offered "
-                                               "(send the field in a message of its own)")
-        items, kind, tensors, names, entries = self._entries_of(data, (_Crops,))
         boxes = []
         for name, v in items.items():
             if not isinstance(v, _Crops):
@@ -634,6 +621,86 @@ class Node:
                 elif isinstance(b, np.ndarray) and not b.flags.writeable:
                     b = np.array(b)  # (numpy exports no read-only array)
             boxes.append(b)
+        return boxes
+
+    def _send_tensor_prep(self, output_id: str, data, cls, metadata, flags: int) -> int:
+        """`_send_tensor_resize` (`cls` `_Resized`) or `_send_tensor_crops` (`_Crops`) when a field
+        is a model input — it has a scale, a bias or a placement
+        (dora_node_send_output_tensor_prep).  It keeps a dispatch of its own, as
+        `_send_tensor_affine` does: a field brings up to two more tensors, its tables, and a
+        crops field its boxes.
+
+        Tables live where the values live, as `_send_tensor_affine` has it: with host values a
+        sequence, a numpy array or a CPU tensor, converted to float32 here and checked inside the
+        call; with values on this node's GPU a float32 tensor there, which does the
+        `__dlpack__(stream=<the node stream>)` handshake like every field, is never read on the
+        host, and is held with the values by an asynchronous send until `sync()`."""
+        import numpy as np
+        items, kind, tensors, names, entries = self._entries_of(data, (cls,))
+        preps = [v._prep() if isinstance(v, cls) else None for v in items.values()]
+        tabs = [t for p in preps if p is not None for t in p[:2] if t is not None]
+        for t in tabs:
+            on_device = hasattr(t, "__dlpack_device__") and \
+                int(t.__dlpack_device__()[0]) not in _DL_HOST
+            if on_device:
+                self._tensor_kind(t, "a per-channel table")
+            if kind == "device" and not on_device:
+                raise TypeError("a per-channel table in host memory over values on this node's "
+                                "GPU: make the table once on the device (a float32 tensor) and "
+                                "send with that")
+            if kind != "device" and on_device:
+                raise TypeError("a per-channel table in device memory over host values: move the "
+                                "table next to the values (.tolist())")
+        boxes = self._boxes_of(items, kind)
+
+        def described(bcaps, tcaps):
+            """(entries, preps) with the boxes' and the tables' capsules in their places."""
+            bcaps, tcaps = iter(bcaps), iter(tcaps)
+            ent = tuple(e if e is None or len(e) == 7 else (*e[:7], next(bcaps)) for e in entries)
+            pre = tuple(None if p is None else
+                        (None if p[0] is None else next(tcaps),
+                         None if p[1] is None else next(tcaps), *p[2:]) for p in preps)
+            return ent, pre
+        if kind == "device":
+            also = boxes + tabs
+            caps, acaps, done = self._device_caps(flags, tensors, also, len(tensors) + len(also))
+            ent, pre = described(acaps[:len(boxes)], acaps[len(boxes):])
+            return done(_fast.send_tensor_prep(self.handle, output_id, names, caps, ent, pre,
+                                               ARROW_DEVICE_ROCM, metadata, flags))
+        dev, caps = self._host_caps(tensors)
+        if caps is None:
+            # (numpy exports no read-only array: the call reads a copy of each and drops it)
+            dev, caps = self._host_caps([np.array(v) if isinstance(v, np.ndarray) and
+                                         not v.flags.writeable else v for v in tensors])
+        host = [np.ascontiguousarray(np.asarray(t, dtype=np.float32)) for t in tabs]
+        ent, pre = described([b.__dlpack__() for b in boxes], [t.__dlpack__() for t in host])
+        return _fast.send_tensor_prep(self.handle, output_id, names, caps, ent, pre, dev, metadata,
+                                      flags)
+
+    def _send_tensor_crops(self, output_id: str, data, metadata, flags: int) -> int:
+        """Boxes cut from a frame and resized on send (dora_amd.tensor.crops), or a dict of
+        tensors of which some are crops and the rest plain, as the tensor or Struct message of the
+        crops and the plain values (dora_node_send_output_tensor_crop).  A dict that also holds a
+        cast, a quantised, an argmax or a resized field is not offered: nothing is sent.  It keeps
+        a dispatch of its own, as `_send_tensor_affine` does: every field of crops brings one more
+        tensor, its boxes.
+
+        Boxes live where the frame lives.  With host values they are a sequence, a numpy array or
+        a CPU tensor, read inside the call.  With values on this node's GPU they are an int32
+        tensor there: they do the `__dlpack__(stream=<the node stream>)` handshake like every
+        field, are never read on the host, and an asynchronous send holds them with the values
+        until `sync()`."""
+        import numpy as np
+        for name, v in (data.items() if isinstance(data, dict) else ()):
+            if isinstance(v, (_Cast, _Quantized, _Argmax, _Resized)):
+                raise _lib.UnsupportedType(-4, f"field `{name}`: a conversion, an argmax or a "
+                                               "resize beside crops in one message is not offered "
+                                               "(send the field in a message of its own)")
+        if any(isinstance(v, _Crops) and v._prep() is not None
+               for v in (data.values() if isinstance(data, dict) else (data,))):
+            return self._send_tensor_prep(output_id, data, _Crops, metadata, flags)
+        items, kind, tensors, names, entries = self._entries_of(data, (_Crops,))
+        boxes = self._boxes_of(items, kind)
         if kind == "device":
             caps, bcaps, done = self._device_caps(flags, tensors, boxes, len(tensors) + len(boxes))
             bcaps = iter(bcaps)

@@ -698,15 +698,75 @@ def from_numpy_argmax(x, axis, dtype="int64", *, bfloat16=False):
 _RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR}
 
 
-class Resized:
+def letterbox(in_extents, size, anchor="center"):
+    """`(inner, lead)` of the aspect-preserving fit of a source of extents `in_extents`
+    `(Ia, Ib)` into an output of extents `size` `(Oa, Ob)`, in integer arithmetic only: the
+    resized image has extents `inner = (Ra, Rb)` and starts at `lead = (pa, pb)` inside the
+    output.  If `Oa * Ib <= Ob * Ia` the first axis is filled, `Ra = Oa` and
+    `Rb = min(max((2 * Ib * Oa + Ia) // (2 * Ia), 1), Ob)` (the quotient rounded half up); else
+    `Rb = Ob` and `Ra = min(max((2 * Ia * Ob + Ib) // (2 * Ib), 1), Oa)`.  `lead` is
+    `((Oa - Ra) // 2, (Ob - Rb) // 2)` for `anchor="center"` and `(0, 0)` for `"start"`.
+    (1080, 1920) into (640, 640) gives inner (360, 640), lead (140, 0).
+
+    `resize(.., fit="letterbox")` places the image by this function, and a receiver uses the same
+    function with the same arguments to map boxes found in the output back into the source:
+    output coordinate `o` along an axis is source coordinate `(o - lead) * I / R`."""
+    import operator
+    try:
+        (ia, ib), (oa, ob) = (tuple(operator.index(v) for v in p) for p in (in_extents, size))
+    except (TypeError, ValueError):
+        raise TypeError("letterbox: in_extents and size are two integers each") from None
+    if min(ia, ib, oa, ob) < 1:
+        raise ValueError(f"letterbox: extents {(ia, ib)} into {(oa, ob)}: every extent is at "
+                         "least 1")
+    if anchor not in ("center", "start"):
+        raise ValueError(f"letterbox: anchor {anchor!r} is not offered: 'center' and 'start' are")
+    if oa * ib <= ob * ia:
+        ra, rb = oa, min(max((2 * ib * oa + ia) // (2 * ia), 1), ob)
+    else:
+        ra, rb = min(max((2 * ia * ob + ib) // (2 * ib), 1), oa), ob
+    lead = ((oa - ra) // 2, (ob - rb) // 2) if anchor == "center" else (0, 0)
+    return (ra, rb), lead
+
+
+class _Prep(_Affine):
+    """What `Resized` and `Crops` share of a model input's step: `_Affine`'s members — the terms
+    of `r * S + B` before the conversion — and, for a resize, the placement: `inner` and `lead`
+    (None: the image fills the output) and `fill`."""
+
+    __slots__ = ()
+
+    def _prep(self):
+        """None (nothing is added), or the send's prep entry before its tables are described:
+        (scale table or None, bias table or None, axis, scalar scale or None, scalar bias or
+        None, inner0, inner1, lead0, lead1, fill)."""
+        inner = getattr(self, "inner", None)
+        if self.scale is None and self.bias is None and self.scale_table is None and \
+                self.bias_table is None and inner is None:
+            return None
+        lead = (0, 0) if inner is None else self.lead
+        return (self.scale_table, self.bias_table, self.axis or 0, self.scale, self.bias, *(inner or (0, 0)), *lead,
+                float(getattr(self, "fill", 0.0)))
+
+    def _prep_repr(self):
+        inner = getattr(self, "inner", None)
+        at = "" if inner is None else f", {inner} at {self.lead} in {self.fill!r}"
+        return at + self._affine_repr()
+
+
+class Resized(_Prep):
     """A tensor resized on send: `values`, a tensor, the two `axes` resized (counted from the
     front), their new extents `size`, the `mode` and the destination `dtype` (None: the source's
-    own).  It reads and resizes nothing itself.  Build one with `resize`."""
+    own); for a model input also the terms of the affine step (`_Affine`'s members) and the
+    placement `inner`, `lead` (None: the image fills the output) and `fill`.  It reads and resizes
+    nothing itself.  Build one with `resize`."""
 
-    __slots__ = ("values", "size", "axes", "mode", "dtype", "_mode", "_code", "_bits")
+    __slots__ = ("values", "size", "axes", "mode", "dtype", "_mode", "_code", "_bits", "scale",
+                 "bias", "scale_table", "bias_table", "axis", "inner", "lead", "fill")
     _STRUCT = TensorResize
 
-    def __init__(self, values, size, axes=(-2, -1), mode="nearest", dtype=None):
+    def __init__(self, values, size, axes=(-2, -1), mode="nearest", dtype=None, scale=None,
+                 bias=None, axis=None, inner=None, lead=None, fill=0.0, what="resize"):
         import operator
         self.values = values
         shape = getattr(values, "shape", None)
@@ -732,6 +792,25 @@ class Resized:
             self._code, self._bits, self.dtype = 0, 0, None
         else:
             self._code, self._bits, self.dtype = _cast_dtype(dtype)
+        self._set_affine(what, scale, bias, axis)
+        self.inner = self.lead = None
+        try:
+            self.fill = float(fill)
+        except (TypeError, ValueError):
+            raise TypeError(f"{what}: the fill is one number") from None
+        if inner is not None:
+            try:
+                self.inner = tuple(operator.index(v) for v in inner)
+                self.lead = tuple(operator.index(v) for v in ((0, 0) if lead is None else lead))
+            except TypeError:
+                raise TypeError(f"{what}: inner and lead are two integers each") from None
+            if len(self.inner) != 2 or len(self.lead) != 2:
+                raise TypeError(f"{what}: inner and lead are two integers each")
+            # (out of range: the send refuses them)
+            if not all(-2 ** 63 <= v < 2 ** 63 for v in self.inner + self.lead):
+                raise ValueError(f"{what}: inner {self.inner}, lead {self.lead}")
+        elif lead is not None:
+            raise TypeError(f"{what}: lead= places an image of the extents inner=; give both")
 
     def _entry(self):
         return (self._mode, self.axes[0], self.axes[1], self.size[0], self.size[1], self._code,
@@ -743,24 +822,48 @@ class Resized:
 
     def __repr__(self):
         return (f"Resized({self.values!r} axes {self.axes} -> {self.size}, {self.mode}"
-                f"{'' if self.dtype is None else ' -> ' + self.dtype})")
+                f"{self._prep_repr()}{'' if self.dtype is None else ' -> ' + self.dtype})")
 
 
-def resize(values, size, *, axes=(-2, -1), mode="nearest", dtype=None):
+def resize(values, size, *, axes=(-2, -1), mode="nearest", dtype=None, scale=None, bias=None,
+           axis=None, fit="stretch", anchor="center", fill=0.0, inner=None, lead=None):
     """`values` with its two dimensions `axes` at the new extents `size` as a message: `values` a
     tensor of uint8, int8, uint16, int16, float16, bfloat16 or float32 with 2 to 8 dimensions (host
     memory or this node's HBM, any strided view), `axes` two of its dimensions as given (negative:
     from the back), `size` their new extents in that order, `mode` "nearest" or "bilinear"
     (half-pixel centres, no antialiasing), `dtype` "float16", "float32", "uint8", "int8", "uint16"
-    or "int16" (or the numpy or torch dtype; None: the source's own).  `send_output` sends it, on
-    its own or as a value of a dict of tensors, as what `from_numpy_resize` states."""
+    or "int16" (or the numpy or torch dtype; None: the source's own).
+
+    A model input in the same message: `scale` and `bias` are the terms of `r * S + B`, applied in
+    float32 to the resized value before its conversion, each a finite number or a 1-D table of one
+    value per channel along `axis` — a dimension of `values` as given that is not one of `axes` —
+    living next to the values as `cast`'s tables do.  `fit="letterbox"` keeps the aspect: the
+    image is resized to the `inner` extents that `letterbox(in_extents, size, anchor)` gives and
+    placed at its `lead` inside an output of extents `size` whose other elements are `fill` (114
+    for the usual grey), taken through the same `scale` and `bias`.  `inner=` and `lead=` give
+    the placement directly (not together with `fit="letterbox"`).  `send_output` sends it, on its
+    own or as a value of a dict of tensors, as what `from_numpy_resize` states."""
+    if fit not in ("stretch", "letterbox"):
+        raise ValueError(f"resize: fit {fit!r} is not offered: 'stretch' and 'letterbox' are")
+    if fit == "letterbox":
+        if inner is not None or lead is not None:
+            raise TypeError("resize: fit='letterbox' computes inner and lead itself; give either "
+                            "the fit or the placement")
+        shape = getattr(values, "shape", None)
+        if shape is None:
+            raise TypeError("resize: the values have no shape to count axes in")
+        try:
+            src = tuple(shape[a] for a in axes)
+        except (IndexError, TypeError):
+            raise ValueError(f"resize: axes {tuple(axes)} of {len(shape)} dimensions") from None
+        inner, lead = letterbox(src, size, anchor)
     if isinstance(values, Crops):
         raise TypeError("resize of crops is not offered: give crops the size to send")
     if isinstance(values, (Resized, Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
         raise TypeError("resize resizes one tensor: give a dict's fields a resize each; a resize "
                         "of a cast, a quantise, an argmax, a take, a mask or a ragged batch is not "
                         "offered")
-    return Resized(values, size, axes, mode, dtype)
+    return Resized(values, size, axes, mode, dtype, scale, bias, axis, inner, lead, fill)
 
 
 def _resize_taps(n_in, n_out, mode):
@@ -783,7 +886,8 @@ def _resize_taps(n_in, n_out, mode):
     return i0, i1, w0, w1
 
 
-def from_numpy_resize(x, size, *, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=False):
+def from_numpy_resize(x, size, *, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=False,
+                      scale=None, bias=None, axis=None, inner=None, lead=(0, 0), fill=0.0):
     """The nested pyarrow array of `x` resized, the statement of record of `resize`: what
     `send_output(output_id, resize(x, size, axes=axes, mode=mode, dtype=dtype))` puts on the wire.
     Every element is widened to float32; an axis of I source and O output steps reads at o the tap
@@ -792,11 +896,23 @@ def from_numpy_resize(x, size, *, axes=(-2, -1), mode="nearest", dtype=None, bfl
     last element alone where `q >= I - 1`), along the second of `axes` first, every product
     rounded to float32 and then every sum; the result goes to `dtype` as `from_numpy_cast` or
     `from_numpy_quantize` (no scale, zero point 0) takes it.  `bfloat16`: `x` holds the bits of
-    bfloat16 values as uint16 (numpy has no such dtype) and `dtype` must be given."""
-    return from_numpy(_numpy_resize(x, size, axes, mode, dtype, bfloat16))
+    bfloat16 values as uint16 (numpy has no such dtype) and `dtype` must be given.
+
+    A model input (all absent by default).  Placement, `inner = (Ra, Rb)` with `1 <= R <= size`
+    at `lead = (pa, pb)` with `0 <= p <= size - R`: the float32 value `r` of an output element at
+    `(oa, ob)` along `axes` is the statement above with output extents `(Ra, Rb)` at
+    `(oa - pa, ob - pb)` where `pa <= oa < pa + Ra` and `pb <= ob < pb + Rb`, and `float32(fill)`
+    (finite) everywhere else.  Normalise, `scale`, `bias` and `axis` as `from_numpy_cast` takes
+    them: `y = r * S[c] + B[c]` in float32, `c` the coordinate along `axis` (not one of `axes`),
+    the product rounded and then the sum, an absent term not applied; padding goes through it like
+    every other element.  Then the conversion of `y` as above, into the source's own integer dtype
+    included."""
+    return from_numpy(_numpy_resize(x, size, axes, mode, dtype, bfloat16, scale, bias, axis, inner,
+                                    lead, fill))
 
 
-def _numpy_resize(x, size, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=False):
+def _numpy_resize(x, size, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=False, scale=None,
+                  bias=None, axis=None, inner=None, lead=(0, 0), fill=0.0):
     """`from_numpy_resize`'s values as a numpy array."""
     import numpy as np
     x = np.asarray(x)
@@ -815,6 +931,19 @@ def _numpy_resize(x, size, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=F
         if not 1 <= n <= 32768:
             raise ValueError(f"extent {n}: 1 to 32768 are resized")
     dt = x.dtype if dtype is None else np.dtype(_cast_dtype(dtype)[2])
+    if axis is not None:
+        axis = axis + x.ndim if axis < 0 else axis
+        if not 0 <= axis < x.ndim or axis in (a, b):
+            raise ValueError(f"axis {axis}: a dimension of the values that is not resized")
+    full = tuple(size)
+    if inner is not None:
+        if not np.isfinite(np.float32(fill)):
+            raise ValueError(f"fill {fill!r} is not finite")
+        for r, p, n in zip(inner, lead, size):
+            if not (1 <= r <= n and 0 <= p <= n - r):
+                raise ValueError(f"inner {tuple(inner)} at lead {tuple(lead)} does not lie inside "
+                                 f"size {tuple(size)}")
+        size = tuple(inner)
     v = x.astype(np.float32)
     a0, a1, wa0, wa1 = _resize_taps(x.shape[a], size[0], mode)
     b0, b1, wb0, wb1 = _resize_taps(x.shape[b], size[1], mode)
@@ -834,6 +963,17 @@ def _numpy_resize(x, size, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=F
             bot = np.take(va1, b0, axis=b) * wb0 + np.take(va1, b1, axis=b) * wb1
             y = top * wa0 + bot * wa1
         assert y.dtype == np.float32
+        if inner is not None:
+            shape = list(y.shape)
+            shape[a], shape[b] = full
+            placed = np.full(shape, np.float32(fill), np.float32)
+            at = [slice(None)] * x.ndim
+            at[a] = slice(lead[0], lead[0] + inner[0])
+            at[b] = slice(lead[1], lead[1] + inner[1])
+            placed[tuple(at)] = y
+            y = placed
+        y = _numpy_affine(y, scale, bias, axis)
+        assert y.dtype == np.float32
         if dt.kind == "f":
             return y.astype(dt)
         info = np.iinfo(dt)
@@ -842,20 +982,24 @@ def _numpy_resize(x, size, axes=(-2, -1), mode="nearest", dtype=None, bfloat16=F
         return r.astype(np.int32).astype(dt)
 
 
-class Crops:
+class Crops(_Prep):
     """Boxes cut from a frame and resized on send: `values`, the frame, `boxes`, the `[K, 4]`
     int32 tensor next to it, and what a `Resized` holds: the two `axes` cropped (counted from the
     front), the extents `size` of every crop, the `mode` and the destination `dtype` (None: the
     frame's own).  It reads, cuts and resizes nothing itself.  Build one with `crops`."""
 
-    __slots__ = ("values", "boxes", "size", "axes", "mode", "dtype", "_resized")
+    __slots__ = ("values", "boxes", "size", "axes", "mode", "dtype", "_resized", "scale", "bias",
+                 "scale_table", "bias_table", "axis")
     _STRUCT = TensorCrop
 
-    def __init__(self, values, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None):
+    def __init__(self, values, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None,
+                 scale=None, bias=None, axis=None):
         try:
-            r = Resized(values, size, axes, mode, dtype)
+            r = Resized(values, size, axes, mode, dtype, scale, bias, axis, what="crops")
         except (TypeError, ValueError) as e:
             raise type(e)(str(e).replace("resize:", "crops:", 1)) from None
+        for name in ("scale", "bias", "scale_table", "bias_table", "axis"):
+            setattr(self, name, getattr(r, name))
         if not hasattr(boxes, "shape") and not isinstance(boxes, (list, tuple)):
             raise TypeError("crops: the boxes are a [K, 4] int32 tensor next to the frame")
         self._resized = r
@@ -875,38 +1019,57 @@ class Crops:
 
     def __repr__(self):
         return (f"Crops({self.values!r} by {self.boxes!r} axes {self.axes} -> {self.size}, "
-                f"{self.mode}{'' if self.dtype is None else ' -> ' + self.dtype})")
+                f"{self.mode}{self._prep_repr()}"
+                f"{'' if self.dtype is None else ' -> ' + self.dtype})")
 
 
-def crops(frame, boxes, size, *, axes=(-2, -1), mode="bilinear", dtype=None):
+def _no_crops_placement(kw):
+    if kw:
+        raise TypeError(f"crops: {', '.join(sorted(kw))}: placement for crops is not provided "
+                        "(inner=, lead=, fit=, anchor= and fill= belong to resize: per-box aspect "
+                        "would put a division per box on the device)"
+                        if set(kw) <= {"inner", "lead", "fit", "anchor", "fill"} else
+                        f"crops: unexpected keyword {sorted(kw)[0]!r}")
+
+
+def crops(frame, boxes, size, *, axes=(-2, -1), mode="bilinear", dtype=None, scale=None,
+          bias=None, axis=None, **placement):
     """The K `boxes` of `frame`, each cut out and brought to the extents `size`, as a message:
     `frame` a tensor of uint8, int8, uint16, int16, float16, bfloat16 or float32 with 2 to 7
     dimensions (host memory or this node's HBM, any strided view), `boxes` a dense `[K, 4]` int32
     tensor where the frame lives (never read on the host when that is HBM), row k
     `(a_lo, b_lo, a_hi, b_hi)`, half-open ranges along `axes[0]` and `axes[1]`; `size`, `axes`,
     `mode` and `dtype` as `resize` takes them.  Coordinates are clamped to the frame, a box that is
-    then empty gives zeros.  `send_output` sends it, on its own or as a value of a dict of tensors,
-    as what `from_numpy_crops` states: a tensor of shape `(K,) + frame.shape` with the two extents
-    replaced."""
+    then empty gives zeros.  `scale`, `bias` and `axis` normalise every crop as `resize` takes
+    them, `axis` a dimension of `frame` as given (not counting K); an empty box stays zeros.
+    Placement (`inner=`, `lead=`, `fit=`, `fill=`) is not provided for crops.  `send_output` sends
+    it, on its own or as a value of a dict of tensors, as what `from_numpy_crops` states: a tensor
+    of shape `(K,) + frame.shape` with the two extents replaced."""
+    _no_crops_placement(placement)
     if isinstance(frame, (Crops, Resized, Argmax, Cast, Quantized, Taken, Masked, Ragged, dict)):
         raise TypeError("crops cuts boxes from one tensor: give a dict's fields their crops each; "
                         "crops of a cast, a quantise, an argmax, a resize, a take, a mask or a "
                         "ragged batch are not offered")
-    return Crops(frame, boxes, size, axes, mode, dtype)
+    return Crops(frame, boxes, size, axes, mode, dtype, scale, bias, axis)
 
 
 def from_numpy_crops(x, boxes, size, *, axes=(-2, -1), mode="bilinear", dtype=None,
-                     bfloat16=False):
+                     bfloat16=False, scale=None, bias=None, axis=None, **placement):
     """The nested pyarrow array of the crops of `x`, the statement of record of `crops`: what
     `send_output(output_id, crops(x, boxes, size, axes=axes, mode=mode, dtype=dtype))` puts on the
     wire.  With Ia, Ib the extents of `x` along `axes`, row k of `boxes` is clamped word by word,
     `a0 = min(max(a_lo, 0), Ia)`, `a1 = min(max(a_hi, 0), Ia)`, the same for b; crop k is all
     zeros where `a1 <= a0` or `b1 <= b0`, and else `from_numpy_resize` of
-    `x[.., a0:a1, .., b0:b1, ..]`.  `bfloat16` as `from_numpy_resize` takes it."""
-    return from_numpy(_numpy_crops(x, boxes, size, axes, mode, dtype, bfloat16))
+    `x[.., a0:a1, .., b0:b1, ..]`.  `bfloat16` as `from_numpy_resize` takes it.  `scale`, `bias`
+    and `axis` (a dimension of `x`, not counting K) normalise every non-empty crop as
+    `from_numpy_resize` states; every byte of an empty box's crop is zero whatever they are.
+    Placement is not provided for crops."""
+    _no_crops_placement(placement)
+    return from_numpy(_numpy_crops(x, boxes, size, axes, mode, dtype, bfloat16, scale, bias, axis))
 
 
-def _numpy_crops(x, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None, bfloat16=False):
+def _numpy_crops(x, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None, bfloat16=False,
+                 scale=None, bias=None, axis=None, **placement):
     """`from_numpy_crops`' values as a numpy array."""
     import numpy as np
     x = np.asarray(x)
@@ -920,7 +1083,10 @@ def _numpy_crops(x, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None, bfl
     a, b = (ax + x.ndim if ax < 0 else ax for ax in axes)
     if a == b or not (0 <= a < x.ndim and 0 <= b < x.ndim):
         raise ValueError(f"axes {tuple(axes)} of {x.ndim} dimensions")
-    whole = _numpy_resize(x, size, axes, mode, dtype, bfloat16)  # (the refusals, shape and dtype)
+    _no_crops_placement(placement)
+    norm = dict(scale=scale, bias=bias, axis=axis)
+    # (the refusals, shape and dtype)
+    whole = _numpy_resize(x, size, axes, mode, dtype, bfloat16, **norm)
     out = np.zeros((boxes.shape[0],) + whole.shape, whole.dtype)
     ia, ib = x.shape[a], x.shape[b]
     for k, (alo, blo, ahi, bhi) in enumerate(boxes.tolist()):
@@ -930,7 +1096,7 @@ def _numpy_crops(x, boxes, size, axes=(-2, -1), mode="bilinear", dtype=None, bfl
             continue
         cut = [slice(None)] * x.ndim
         cut[a], cut[b] = slice(a0, a1), slice(b0, b1)
-        out[k] = _numpy_resize(x[tuple(cut)], size, axes, mode, dtype, bfloat16)
+        out[k] = _numpy_resize(x[tuple(cut)], size, axes, mode, dtype, bfloat16, **norm)
     return out
 
 
@@ -1302,4 +1468,4 @@ __all__ = ["tensor_type", "struct_type", "ragged_type", "from_numpy", "from_nump
            "Ragged", "ragged", "Taken", "take", "Masked", "masked", "Cast", "cast",
            "from_numpy_cast", "Quantized", "quantize", "from_numpy_quantize", "Argmax", "argmax",
            "from_numpy_argmax", "Resized", "resize", "from_numpy_resize", "Crops", "crops",
-           "from_numpy_crops"]
+           "from_numpy_crops", "letterbox"]

@@ -731,6 +731,78 @@ typedef struct dora_tensor_crop { /* mode == 0: this field is sent as it is */
 int dora_gpu_plan_tensor_crop(const dora_tensor_field* fields, size_t n,
                               const dora_tensor_crop* crops /* NULL or n entries */,
                               ArrowDeviceType device_type, dora_plan** out);
+/*
+ * Model inputs as one message: a resized field or a field of crops with what a model's input
+ * still needs — the image placed inside a filled output (a letterbox) and a per-channel
+ * normalisation — done in the same read of the source.  A 1080x1920x3 uint8 frame goes out as the
+ * 3x640x640 float16 a detector reads: aspect kept, padded with grey 114, (x / 255 - mean[c]) /
+ * std[c].  `fields` as dora_gpu_plan_tensor_struct takes them; `resizes` and `crops` as
+ * dora_gpu_plan_tensor_resize and dora_gpu_plan_tensor_crop take them, one of the two NULL (or
+ * without an active entry); `preps` is NULL or n entries, and an all-zero entry adds nothing to
+ * its field.  With `preps` NULL or all zero the call plans exactly as
+ * dora_gpu_plan_tensor_resize (`crops` NULL) or dora_gpu_plan_tensor_crop (`resizes` NULL) does,
+ * refusals included.  The wire form — type info, sample size, leaf offsets, padding — never
+ * depends on a prep entry: it is that of the field's resize or crops.
+ *
+ * The statement.  For every output element, r is a float32:
+ *   placement (resize only; inner != {0, 0}): the resized image has extents inner = (Ra, Rb),
+ *     1 <= R <= size, and starts at lead = (pa, pb), 0 <= p <= size - R, inside the output of
+ *     extents `size`.  At output coordinates (oa, ob) along axis[0], axis[1]: if pa <= oa < pa + Ra
+ *     and pb <= ob < pb + Rb, r is dora_gpu_plan_tensor_resize's value before its conversion with
+ *     the output extents (Ra, Rb) at the coordinates (oa - pa, ob - pb); otherwise r = fill and no
+ *     source element is read.  inner == {0, 0}: the image fills the output, r is the resize's (the
+ *     crop's) value before its conversion.
+ *   normalise: y = r * S + B, two IEEE float32 operations, the product rounded, then the sum,
+ *     never one fused multiply-add.  S = scale[c] (a table), or scale_value (has_scale), or absent:
+ *     no multiplication.  B = bias[c], or bias_value (has_bias), or absent: no addition, a zero
+ *     product keeps its sign.  c is the output coordinate along `axis`, a dimension of the field
+ *     (for crops: of the frame, not counting K) as given that is not one of the two resized ones.
+ *     Padding goes through the same step: fill 114 under (x / 255 - mean) / std is what padding
+ *     before normalising gives.
+ *   conversion: y to the field's destination exactly as the resize or crops converts — float16 /
+ *     float32 as dora_gpu_plan_tensor_cast, integers as dora_gpu_plan_tensor_convert without a
+ *     scale and with zero point 0 (a normalise into the source's own integer dtype included).
+ *   crops: every byte of an empty box's crop stays zero, the normalise step is not applied to it.
+ * The statement of record is dora_amd.tensor.from_numpy_resize / from_numpy_crops with the same
+ * arguments; results are bit-exact against it, from host and from device values, but for the
+ * payload of a NaN in a float destination.  dora_amd.tensor.letterbox gives the integer geometry
+ * (inner, lead) of an aspect-preserving fit, which a receiver uses to map boxes back.
+ *
+ * Tables live where the values live, as dora_gpu_plan_tensor_affine's do.  Host values: C float32
+ * words in host memory, read inside this call, every value finite; the CPU resizes, places and
+ * normalises inside this call.  Device values: C float32 words in HBM, never read on the host;
+ * each table's 4 * C bytes are held against its own allocation before anything is launched, like
+ * the frame's reach and the boxes (a refusal says which), and since c < C always no word outside
+ * a table is read.  Any field with a non-zero prep entry makes a device plan one launch of
+ * gather_resize_prep_kernel or gather_crop_prep_kernel (gfx950), plain fields through their
+ * usual bodies.
+ *
+ * DORA_ERR_INVALID naming the field, on top of the resize's or the crops' own refusals: a prep
+ * entry on a field that is neither resized nor crops; `axis` (with a table) outside the field's
+ * dimensions or equal to a resized axis; a table together with its scalar (has_scale, has_bias);
+ * a table that is not 1-D, not of shape[axis] elements, not dense or not on a multiple of 4; a
+ * scalar or `fill` that is not finite; a host table's value that is not finite; inner[j] outside
+ * [1, size[j]] or lead[j] outside [0, size[j] - inner[j]] (one of inner's two 0 included); `inner`
+ * on a crops field; resize entries and crops entries both active in one call.  A table that is
+ * not float32 is DORA_ERR_UNSUPPORTED, naming the dtype.
+ * Not provided: zero points, placement for crops (per-box aspect would put a division per box on
+ * the device), per-box fill, bfloat16 destinations, resize and crops in one record.
+ */
+typedef struct dora_tensor_prep { /* all zero: nothing is added to the field's resize or crops */
+  const dora_tensor* scale; /* NULL, or C float32 values along `axis` */
+  const dora_tensor* bias;  /* NULL, or C float32 values along `axis` */
+  int32_t axis;             /* a dimension of the field (the frame) as given, not a resized one; read only with a table */
+  uint16_t has_scale, has_bias;
+  float scale_value, bias_value;
+  int64_t inner[2];         /* 0, 0: the image fills the output; else 1 <= inner[j] <= size[j] */
+  int64_t lead[2];          /* 0 <= lead[j] <= size[j] - inner[j] */
+  float fill;               /* finite; read only with inner */
+} dora_tensor_prep;
+int dora_gpu_plan_tensor_prep(const dora_tensor_field* fields, size_t n,
+                              const dora_tensor_resize* resizes /* NULL or n entries */,
+                              const dora_tensor_crop* crops /* NULL or n entries */,
+                              const dora_tensor_prep* preps /* NULL or n entries */,
+                              ArrowDeviceType device_type, dora_plan** out);
 void dora_gpu_plan_free(dora_plan* plan);
 /* required_data_size (arrow_utils.rs:4-8). */
 size_t dora_gpu_plan_size(const dora_plan* plan);
@@ -1015,6 +1087,18 @@ int dora_node_send_output_tensor_resize(dora_node* node, const char* output_id,
 int dora_node_send_output_tensor_crop(dora_node* node, const char* output_id,
                                       const dora_tensor_field* fields, size_t n,
                                       const dora_tensor_crop* crops,
+                                      ArrowDeviceType device_type, const uint8_t* params,
+                                      size_t params_len, uint32_t flags);
+/* Send model inputs (dora_gpu_plan_tensor_prep: the statement, where the tables live, refusals),
+ * with the contract of dora_node_send_output_tensor_resize / _crop: host values, host tables and
+ * host boxes are read on return, device values, tables and boxes are read by one launch on a fill
+ * stream, and the synchronous send waits for the read; with DORA_SEND_ASYNC the caller keeps the
+ * tables and the boxes alive and unwritten with the fields until dora_node_sync. */
+int dora_node_send_output_tensor_prep(dora_node* node, const char* output_id,
+                                      const dora_tensor_field* fields, size_t n,
+                                      const dora_tensor_resize* resizes,
+                                      const dora_tensor_crop* crops,
+                                      const dora_tensor_prep* preps,
                                       ArrowDeviceType device_type, const uint8_t* params,
                                       size_t params_len, uint32_t flags);
 /* Send rows selected by a mask (dora_gpu_plan_tensor_mask: wire form, where the mask lives,

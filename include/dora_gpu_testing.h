@@ -200,6 +200,16 @@ int dora_gpu_test_plan_crop(const dora_plan* plan, size_t i, const void* dst, in
                             uint64_t* k, const void** boxes, int* boxes_device, int64_t* lo,
                             int64_t* hi, uint64_t* head_elements, uint64_t* units,
                             uint64_t* tail_elements);
+/* Test tool (host only): whether field `i` of a device plan of dora_gpu_plan_tensor_prep has a
+ * model-input step (*on 1: its launch is gather_resize_prep_kernel or gather_crop_prep_kernel):
+ * then *scale_table / *bias_table the tables in HBM (NULL: none), *channels their words and *axis
+ * the dimension of the output they run along (a crops field's counted with K in front; 0 and -1
+ * without a table), [*lo, *hi] the bytes from either table that are checked against its
+ * allocation (0, -1 without one), and inner[2], lead[2] and *fill the placement (all 0: the image
+ * fills the output).  dora_gpu_test_plan_resize and dora_gpu_test_plan_crop report the rest. */
+int dora_gpu_test_plan_prep(const dora_plan* plan, size_t i, int* on, const void** scale_table,
+                            const void** bias_table, uint64_t* channels, int* axis,
+                            int64_t* inner, int64_t* lead, float* fill, int64_t* lo, int64_t* hi);
 /* Test tool: counts[4], the launches of this process so far over the fields of a plan, by kernel:
  * gather_struct_kernel, gather_cast_kernel, gather_quant_kernel, gather_affine_kernel. */
 int dora_gpu_test_fields_launches(uint64_t* counts);
@@ -219,7 +229,8 @@ int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mas
  * host plan, dense device plans, empty plans), 1 the gather of its one strided view, 2
  * gather_struct_kernel over its fields, 3 gather_cast_kernel / gather_quant_kernel, 4 the taken
  * body by an index in HBM, 5 a mask's count, compact and taken launches, 6 gather_reduce_kernel,
- * 7 gather_resize_kernel, 8 gather_crop_kernel; *scan 1 if that launch
+ * 7 gather_resize_kernel, 8 gather_crop_kernel, 9 gather_resize_prep_kernel, 10
+ * gather_crop_prep_kernel; *scan 1 if that launch
  * also scans a partition in HBM; *checked 1 if the plan reads HBM whose range is checked before
  * anything is launched. */
 int dora_gpu_test_plan_launch(const dora_plan* plan, int* launch, int* scan, int* checked);

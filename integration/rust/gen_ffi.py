@@ -22,7 +22,7 @@ SIZED = {"dora_fill_ticket"}
 STRUCTS = {"dora_tensor", "dora_tensor_cast", "dora_tensor_quant", "dora_tensor_field",
            "dora_tensor_list",
            "dora_tensor_take", "dora_tensor_mask", "dora_tensor_affine", "dora_tensor_reduce",
-           "dora_tensor_resize", "dora_tensor_crop"}
+           "dora_tensor_resize", "dora_tensor_crop", "dora_tensor_prep"}
 SCALAR = {"uint16_t": "u16", "int": "c_int", "int64_t": "i64", "uint64_t": "u64", "uint32_t": "u32",
           "int32_t": "i32", "size_t": "usize", "float": "f32", "double": "f64",
           "uint8_t": "u8", "char": "c_char", "void": "c_void", "ArrowDeviceType": "ArrowDeviceType",
@@ -117,11 +117,13 @@ def struct_decl(name, text):
         decl = " ".join(decl.split())
         if not decl:
             continue
-        fm = re.match(r"(.*?)(\b\w+)(?:\[(\d+)\])?$", decl)
+        first, *more = [d.strip() for d in decl.split(",")]  # (`float a, b`: members of one type)
+        fm = re.match(r"(.*?)(\b\w+)(?:\[(\d+)\])?$", first)
         t = rust_type(fm.group(1))
-        if fm.group(3):  # a fixed array member
-            t = f"[{t}; {fm.group(3)}]"
-        out.append(f"    pub {fm.group(2)}: {t},")
+        for member in [fm.group(2) + (f"[{fm.group(3)}]" if fm.group(3) else ""), *more]:
+            mm = re.match(r"(\w+)(?:\[(\d+)\])?$", member)
+            # (a fixed array member)
+            out.append(f"    pub {mm.group(1)}: {f'[{t}; {mm.group(2)}]' if mm.group(2) else t},")
     out.append("}")
     return out
 
