@@ -17,7 +17,9 @@ deals along its seeds and hands in (`narrow`: 8-bit destinations only, so that a
 addresses; `dense` for argmax); left out, the same things are drawn.  Values are shaped where the
 plain ones would test little: quantised sources are brought to about the destination's span, float
 sources that go to integers are grown, argmax sources are sprinkled with NaN, infinities, zeros of
-both signs and repeats.  To reproduce a case of a sweep call its `*_case(seed)` in
+both signs and repeats.  The two model-input bodies (gather_resize_prep_kernel,
+gather_crop_prep_kernel) get `prep_resize_record` and `prep_crop_record`: the resize's and the
+crops' records with a step of `prep_step` on their op fields.  To reproduce a case of a sweep call its `*_case(seed)` in
 tests/test_random_views_host.py."""
 import numpy as np
 
@@ -26,6 +28,7 @@ from tests import argmax_records as am
 from tests import cast_records as cr
 from tests import crop_records as kr
 from tests import mask_records as mr
+from tests import prep_records as pr
 from tests import quant_records as qr
 from tests import resize_records as rr
 from tests import take_records as tr
@@ -584,10 +587,123 @@ def crop_record(r, n_fields=None, max_elems=MAX_ELEMS, narrow=None):
     return with_planes(r, names(rec), k)
 
 
+PREP_FILLS = (114.0, 0.0, -0.0, -2.5, 300.0, -1e6)
+PLACEMENTS = ("none", "letterbox", "free")
+
+
+def prep_reach(v, op):
+    """(the largest finite magnitude among the view's values, the magnitude the destination
+    holds): their ratio is the scale that brings the one to the other.  A float destination is
+    given the source's own reach, held well inside float16."""
+    x = np.abs(cr.to_f32(v, op["src"]))
+    x = x[np.isfinite(x)]
+    most = float(x.max()) if x.size and x.max() > 0 else 1.0
+    dst = rr.dst_name(op)
+    if dst[0] in "ui":
+        return most, float(np.iinfo(np.dtype(dst)).max)
+    return most, min(most, 20000.0)
+
+
+def prep_term(r, form, n, about, unsigned, lead):
+    """A scale or a bias of `form`: None, a number of magnitude about `about`, or a table of `n`
+    such numbers that starts `lead` words into its base — mostly positive for an unsigned
+    destination, now and then with an exact 0.0, -0.0 or 1.0 in one entry."""
+    if form == "none":
+        return None
+    vals = about * r.uniform(0.2, 0.9, n if form == "table" else 1)
+    vals = np.where(r.random(len(vals)) < (0.1 if unsigned else 0.5), -vals, vals).astype(np.float32)
+    if form == "scalar":
+        return float(vals[0])
+    if r.random() < 0.3:
+        vals[int(r.integers(0, n))] = [0.0, -0.0, 1.0][int(r.integers(0, 3))]
+    return pr.table(vals, lead)
+
+
+def prep_step(r, v, op, crops):
+    """The model-input step of `op` (a resize, or with `crops` a crop) over view `v`, never an
+    empty one.  Scale and bias are each absent, a number or a table; a table where the view has a
+    dimension that is not resized, both along one axis — a broadcast or a reversed dimension more
+    often than its turn, negative a third of the time — and 0 to 3 words into their bases.  Their
+    magnitudes come from the ratio of the destination's reach to the source's, so that an integer
+    destination is filled and not overrun; the bias of an unsigned destination lies inside it.  A
+    resize is placed by nothing, by `tensor.letterbox` or by a free `inner` of at least three
+    quarters of the output at any `lead`, over a `fill` of PREP_FILLS."""
+    from dora_amd import tensor
+    nd = v.ndim
+    taken = {a % nd for a in op["axes"]}
+    free = [k for k in range(nd) if k not in taken]
+    still = [k for k in free if v.strides[k] == 0 and v.shape[k] > 1]
+    back = [k for k in free if v.strides[k] < 0]
+    forms = AFFINE_TERMS if free else AFFINE_TERMS[:2]
+    st, bt = (forms[int(r.integers(0, len(forms)))] for _ in range(2))
+    if (still or back) and "table" not in (st, bt) and r.random() < 0.8:
+        # (a table along a broadcast or a reversed dimension, which few views have)
+        st, bt = [("table", bt), (st, "table"), ("table", "table")][int(r.integers(0, 3))]
+    place = "none" if crops else PLACEMENTS[int(r.choice(3, p=[0.3, 0.3, 0.4]))]
+    if (st, bt, place) == ("none", "none", "none"):
+        st = "scalar"  # (an empty step would plan as the plain kernel)
+    axis = None
+    if "table" in (st, bt):
+        if still and r.random() < 0.8:
+            axis = int(r.choice(still))
+        elif back and r.random() < 0.5:
+            axis = int(r.choice(back))
+        else:
+            axis = int(r.choice([free[0], free[-1], free[int(r.integers(0, len(free)))]]))
+    n = v.shape[axis] if axis is not None else 1
+    most, reach = prep_reach(v, op)
+    unsigned = rr.dst_name(op)[0] == "u"
+    signed_src = op["src"] not in ("uint8", "uint16")
+    # an unsigned destination of a signed source: half the span each way, the bias in the middle
+    half = unsigned and signed_src and st != "none"
+    scale = prep_term(r, st, n, reach / most / (2 if half else 1), unsigned, int(r.integers(0, 4)))
+    bias = prep_term(r, bt, n, reach * (0.7 if half else 0.4), unsigned, int(r.integers(0, 4)))
+    step = pr.prep(scale, bias, None if axis is None else axis - nd if r.random() < 1 / 3 else axis)
+    if place != "none":
+        size = op["size"]
+        if place == "letterbox":
+            inner, lead = tensor.letterbox(tuple(v.shape[a % nd] for a in op["axes"]), size)
+        else:
+            inner = tuple(int(r.integers(-(-3 * s // 4), s + 1)) for s in size)
+            lead = tuple(int(r.integers(0, s - i + 1)) for s, i in zip(size, inner))
+        fill = PREP_FILLS[int(r.integers(0, len(PREP_FILLS)))]
+        if rr.dst_name(op)[0] == "f" and r.random() < 0.5:
+            fill = -0.0  # (few destinations are floats: the zero whose sign the product keeps)
+        step.update(inner=tuple(inner), lead=tuple(lead), fill=fill)
+    return step
+
+
+def with_steps(r, rec, crops):
+    """`rec` with a model-input step on its first op field and on about 0.6 of the others."""
+    first = True
+    for _, _, v, op in rec:
+        if op is None:
+            continue
+        op["prep"] = prep_step(r, v, op, crops) if first or r.random() < 0.6 else None
+        first = False
+    return rec
+
+
+def prep_resize_record(r, n_fields=None, max_elems=MAX_ELEMS, narrow=None):
+    """`resize_record`'s record as tests/prep_records.py takes it: every resize with one more key,
+    "prep", the first one's a step, the others' a step or None."""
+    return with_steps(r, resize_record(r, n_fields, max_elems, narrow), False)
+
+
+def prep_crop_record(r, n_fields=None, max_elems=MAX_ELEMS, narrow=None):
+    """`crop_record`'s record with steps in the same way (no placement: crops have none)."""
+    return with_steps(r, crop_record(r, n_fields, max_elems, narrow), True)
+
+
 def misaligned_op(r, op):
-    """The record of `op` ("quant", "affine", "argmax", "resize", "crop"): an aligned plain field
-    in front of an op field whose 2- or 4-byte source starts 1 or 3 bytes past a multiple of its
-    element size: no kernel runs it."""
+    """The record of `op` ("quant", "affine", "argmax", "resize", "crop", "prep_resize",
+    "prep_crop"): an aligned plain field in front of an op field whose 2- or 4-byte source starts 1
+    or 3 bytes past a multiple of its element size: no kernel runs it.  The last two are the
+    resize's and the crops' record with a scalar scale and bias on `f1`."""
+    if op.startswith("prep_"):
+        rec = misaligned_op(r, op[len("prep_"):])
+        rec[1][3]["prep"] = pr.prep(scale=0.5, bias=1.0)
+        return rec
     d0 = int(r.choice(EXTENTS[:8]))
     src = ["uint16", "int16", "float16", "bfloat16", "float32"][int(r.integers(0, 5))]
     a, va = view(r, np.uint8, d0=d0, max_elems=2000)

@@ -10,7 +10,8 @@ garbage.  Every view was first checked to lie inside its base, and every base li
 one source buffer a test allocates: nothing here hands the GPU an address it could fault on.  A
 cast whose source is off its element size is refused with nothing launched.
 
-The five op kernels (quantise, affine, argmax, resize, crops) run the first 200 seeds of their host
+The op kernels (quantise, affine, argmax, resize, crops, and the model-input forms of the last two,
+gather_resize_prep_kernel and gather_crop_prep_kernel) run the first 200 seeds of their host
 ranges through `run_op`: the bytes of every field equal the op's `want` through its `same`.  Affine
 tables go to the words buffer at 4, 8, 12 and 0 mod 16 in turn; a crop's boxes are bases like its
 frame, and garbage lives only in their words, which the kernel clamps by contract.  Argmax packs
@@ -28,6 +29,7 @@ from tests import argmax_records as am
 from tests import cast_records as cr
 from tests import crop_records as kr
 from tests import mask_records as mr
+from tests import prep_records as pr
 from tests import quant_records as qr
 from tests import random_views as rv
 from tests import resize_records as rr
@@ -51,6 +53,8 @@ AFFINE_SEEDS = host.AFFINE_SEEDS[:200]
 ARGMAX_SEEDS = host.ARGMAX_SEEDS[:200]
 RESIZE_SEEDS = host.RESIZE_SEEDS[:200]
 CROP_SEEDS = host.CROP_SEEDS[:200]
+PREP_RESIZE_SEEDS = host.PREP_RESIZE_SEEDS[:200]
+PREP_CROP_SEEDS = host.PREP_CROP_SEEDS[:200]
 
 
 @pytest.fixture(scope="module")
@@ -319,6 +323,11 @@ OPS = {
                  lambda x: rr.want(x[2], x[3]), rr.same),
     "crop": Op("crop", kr.triples, kr.oracle, device_plan(kr.plan_crop),
                lambda x: kr.want(x[2], x[3]), kr.same),
+    # (tables and boxes are bases of the record: placed in the source buffer like the frames)
+    "prep_resize": Op("prep_resize", pr.triples, pr.oracle, device_plan(pr.plan_prep),
+                      lambda x: pr.want(x[2], x[3]), pr.same),
+    "prep_crop": Op("prep_crop", pr.triples, pr.oracle, device_plan(pr.plan_prep),
+                    lambda x: pr.want(x[2], x[3]), pr.same),
 }
 
 
@@ -425,6 +434,20 @@ def test_crops(dev):
     cases = [host.crop_case(s) for s in CROP_SEEDS]
     assert any(not len(rec[0][3]["boxes"]) for rec, _ in cases if rec[0][3])  # K = 0 among them
     run_op(dev, OPS["crop"], CROP_SEEDS, cases, host.MISALIGNED_CROP_SEEDS)
+
+
+def test_prep_resizes(dev):
+    """gather_resize_prep_kernel: placement, fill, per-channel tables at 0, 4, 8 and 12 mod 16 and
+    the affine step of every field that has one, at the seeds' shapes and residues."""
+    run_op(dev, OPS["prep_resize"], PREP_RESIZE_SEEDS, [host.prep_resize_case(s) for s in PREP_RESIZE_SEEDS],
+           host.MISALIGNED_PREP_RESIZE_SEEDS)
+
+
+def test_prep_crops(dev):
+    """gather_crop_prep_kernel: the channel coordinate behind K, empty boxes beside a bias."""
+    cases = [host.prep_crop_case(s) for s in PREP_CROP_SEEDS]
+    assert any(not len(rec[0][3]["boxes"]) for rec, _ in cases if rec[0][3])  # K = 0 among them
+    run_op(dev, OPS["prep_crop"], PREP_CROP_SEEDS, cases, host.MISALIGNED_PREP_CROP_SEEDS)
 
 
 def test_masks(dev):

@@ -35,6 +35,26 @@ occurs, 0 among them.  One test per op alters a word of what the emulator is giv
 that the comparison fails; one per op asserts that a source off its element size is refused by
 name.
 
+The two model-input bodies (gather_resize_prep_kernel, gather_crop_prep_kernel: resize_device.h and
+crop_device.h under their step) run `prep_resize_case(seed)` and `prep_crop_case(seed)` through
+prep_emulate and the `Batch` of test_prep_index_host.py, bit for bit against `pr.want`, and once
+more as host plans, whose staged segments are tensor_plan.cpp's own statement of the same values.
+`PrepStats` counts what the seeds hold and `check` asserts it: every source, destination, mode and
+residue and both plain shares 10 times; each of the eight combinations of an absent, a scalar and
+a table scale and bias 10 times; no placement, a letterbox, a free one and a placement without
+any term 10 times each; 20 records with two steps, 10 with a resized field without one beside a
+step, 10 whose first step is not in field 0; the tables' axis first, in the middle, innermost,
+broadcast, reversed and given negative 10 times each, of extent 1 once, under five dimensions or
+more 20 times; tables at 0, 4, 8 and 12 mod 16; units in which the channel coordinate changes and
+units in which it stays in 20 seeds each; a unit with elements inside and outside the image in 20
+seeds, `lead == 0` and `lead + inner == size` on each axis, a fill of -0.0 to a float and a
+saturating one to an integer destination; for crops a unit across two crops, a box outside int16
+and an empty box beside a full one under a bias in 20 seeds each, and every K.  Four shares of the
+reference cap what a pass may mean: at most half of the integer outputs on a bound, at most half
+of the placed elements outside the image, at most a tenth of the steps without effect on the
+statement, at most a twentieth of the float outputs not finite.  Tests alter `lead` and `inner`,
+a table's word and a box's word and assert that the comparison fails.
+
 tests/test_gpu_random_views.py runs the same seeds on the kernels."""
 import collections
 import subprocess
@@ -49,6 +69,7 @@ from tests import argmax_records as am
 from tests import cast_records as cr
 from tests import crop_records as kr
 from tests import mask_records as mr
+from tests import prep_records as pr
 from tests import quant_records as qr
 from tests import random_views as rv
 from tests import resize_records as rr
@@ -60,6 +81,7 @@ from tests.test_cast_index_host import Batch as CastBatch
 from tests.test_crop_index_host import Batch as CropBatch
 from tests.test_quant_index_host import Batch as QuantBatch
 from tests.test_resize_index_host import Batch as ResizeBatch
+from tests.test_prep_index_host import Batch as PrepBatch
 from tests.test_gather_index_host import gather_desc
 from tests.test_gather_index_host import run as run_gather
 from tests.test_gather_struct_index_host import run as run_struct
@@ -90,6 +112,10 @@ MISALIGNED_AFFINE_SEEDS = range(5200, 5220)
 MISALIGNED_ARGMAX_SEEDS = range(5300, 5320)
 MISALIGNED_RESIZE_SEEDS = range(5400, 5420)
 MISALIGNED_CROP_SEEDS = range(5500, 5520)
+PREP_RESIZE_SEEDS = range(11000, 11300)
+PREP_CROP_SEEDS = range(12000, 12300)
+MISALIGNED_PREP_RESIZE_SEEDS = range(5600, 5620)
+MISALIGNED_PREP_CROP_SEEDS = range(5700, 5720)
 MASK_ROWS = rv.EXTENTS + (255, 257, mr.TILE - 1, mr.TILE + 1)
 
 
@@ -994,4 +1020,370 @@ def test_crops_of_an_element_misaligned_source_are_refused(lib):
     for seed in MISALIGNED_CROP_SEEDS:
         rec = rv.misaligned_op(rv.rng(seed), "crop")
         ok, text = refused_by_name(kr.plan_crop, rec, kr.bases_of(rec))
+        assert ok, (seed, text)
+
+
+# ---------------------------------------------------------------------------------------------
+# Model inputs: gather_resize_prep_kernel and gather_crop_prep_kernel.  A case is (record of
+# tests/prep_records.py, destination mod 16); what the sweeps must see is counted by `PrepStats`
+# from the record, the plan and `pr.want` alone.
+# ---------------------------------------------------------------------------------------------
+def prep_resize_case(seed):
+    r = rv.rng(seed)
+    rec = rv.prep_resize_record(r, narrow=narrow(seed))
+    return rec, residue(seed, [pr.DESTS[pr.dst_name(x[3])][1] // 8 for x in rec if x[3]])
+
+
+def prep_crop_case(seed):
+    r = rv.rng(seed)
+    rec = rv.prep_crop_record(r, narrow=narrow(seed))
+    return rec, residue(seed, [pr.DESTS[pr.dst_name(x[3])][1] // 8 for x in rec if x[3]])
+
+
+@pytest.fixture(scope="module")
+def prep_emulator(tmp_path_factory):
+    return build(tmp_path_factory, "prep_emulate")
+
+
+def host_ptr(b):
+    return b.__array_interface__["data"][0]
+
+
+def form(term):
+    return "none" if term is None else "table" if pr.is_table(term) else "scalar"
+
+
+def inside_of(shape, op):
+    """The elements of an output of `shape` that lie inside the image `op`'s step places."""
+    q = op["prep"]
+    inside = np.zeros(shape, bool)
+    at = [slice(None)] * len(shape)
+    for ax, n, l in zip(op["axes"], q["inner"], q["lead"]):
+        at[ax % len(shape)] = slice(l, l + n)
+    inside[tuple(at)] = True
+    return inside
+
+
+def mixed_units(inside, k, elem):
+    """Some whole 16-byte unit of a field whose plan reports head and units `k` holds elements
+    inside and outside the image."""
+    per = 16 // elem
+    flat = inside.reshape(-1)[k["head"]: k["head"] + k["units"] * per].reshape(-1, per)
+    return bool((flat.any(1) & ~flat.all(1)).any())
+
+
+def box_areas(v, c):
+    """The clamped area of every box of crop `c` over frame `v`."""
+    ia, ib = (v.shape[a] for a in c["axes"])
+    w = np.clip(c["boxes"].astype(np.int64), 0, [ia, ib, ia, ib])
+    return np.maximum(w[:, 2] - w[:, 0], 0) * np.maximum(w[:, 3] - w[:, 1], 0)
+
+
+class PrepStats:
+    """What a sweep of model-input records saw, counted per field with a step (`field`) and per
+    seed (`seed`), and the four shares of the reference that cap what a pass may mean."""
+
+    def __init__(self, crops):
+        self.crops = crops
+        names = ("srcs", "dsts", "modes", "residues", "shares", "combos", "places", "records",
+                 "axes", "tables", "units", "placed", "fills", "counts")
+        for name in names:
+            setattr(self, name, collections.Counter())
+        self.bound = self.ints = self.outside = self.placed_elems = 0
+        self.nothing = self.steps = self.nonfinite = self.floats = 0
+
+    def field(self, v, c, k, seen):
+        """Field of view `v` under op `c` with a step, `k` its head and units in the plan; `seen`
+        collects what is counted once per seed."""
+        from dora_amd import tensor
+        q, nd, up = c["prep"], v.ndim, int(self.crops)
+        self.srcs[c["src"]] += 1
+        self.dsts[c["dst"]] += 1
+        self.modes[c["mode"]] += 1
+        self.combos[form(q["scale"]), form(q["bias"])] += 1
+        out = pr.want(v, c)
+        elem = out.itemsize
+        self.steps += 1
+        self.nothing += out.tobytes() == pr.want(v, dict(c, prep=None)).tobytes()
+        if out.dtype.kind == "f":
+            self.floats += out.size
+            self.nonfinite += int((~np.isfinite(out)).sum())
+        else:
+            self.ints += out.size
+            self.bound += on_a_bound(out)
+        # the tables and their axis
+        if q["axis"] is not None:
+            ax = q["axis"] % nd
+            self.axes["first" if ax == 0 else "innermost" if ax == nd - 1 else "middle"] += 1
+            self.axes["broadcast"] += v.strides[ax] == 0 and v.shape[ax] > 1
+            self.axes["reversed"] += v.strides[ax] < 0
+            self.axes["extent 1"] += v.shape[ax] == 1
+            self.axes["negative"] += q["axis"] < 0
+            self.axes["five dimensions or more"] += nd >= 5
+            for w in ("scale", "bias"):
+                if pr.is_table(q[w]):
+                    tb, tv = q[w]
+                    self.tables[(misalignment(tb) + host_ptr(tv) - host_ptr(tb)) % 16] += 1
+                    self.tables["an exact 0.0, -0.0 or 1.0"] += bool(np.isin(tv, [0.0, 1.0]).any())
+            changes, keeps = units_of(list(out.shape), (ax + up,), k, elem)
+            seen.update(["changes"] * changes + ["keeps"] * keeps)
+        # the placement
+        if q["inner"] is None:
+            self.places["none"] += 1
+            return
+        sizes = tuple(v.shape[a % nd] for a in c["axes"])
+        boxed = (tuple(q["inner"]), tuple(q["lead"])) == tensor.letterbox(sizes, c["size"])
+        self.places["letterbox" if boxed else "free"] += 1
+        self.places["placement alone"] += q["scale"] is None and q["bias"] is None
+        inside = inside_of(out.shape, c)
+        self.placed_elems += out.size
+        self.outside += int((~inside).sum())
+        if mixed_units(inside, k, elem):
+            seen.add("mixed")
+        for j in (0, 1):
+            self.placed[f"lead[{j}] == 0"] += q["lead"][j] == 0
+            self.placed[f"lead[{j}] + inner[{j}] == size[{j}]"] += q["lead"][j] + q["inner"][j] == c["size"][j]
+        pad = out[~inside]
+        if pad.size and out.dtype.kind == "f":
+            self.fills["-0.0 to a float"] += q["fill"] == 0 and bool(np.signbit(np.float32(q["fill"])))
+        if pad.size and out.dtype.kind != "f":
+            info = np.iinfo(out.dtype)
+            self.fills["saturating to an integer"] += not info.min <= q["fill"] <= info.max and \
+                on_a_bound(pad) == pad.size
+
+    def record(self, rec, mis, plan):
+        """One seed's record under its device plan."""
+        dst = DST + mis
+        ks = kr.plan_crops(plan, len(rec), dst) if self.crops else rr.plan_resizes(plan, len(rec), dst)
+        self.residues[mis] += 1
+        plain_shares(plan, rec, mis, self.shares)
+        seen, stepped = set(), [i for i, x in enumerate(rec) if x[3] and x[3].get("prep")]
+        assert stepped and stepped[0] == next(i for i, x in enumerate(rec) if x[3])
+        for i in stepped:
+            self.field(rec[i][2], rec[i][3], ks[i], seen)
+        self.records["two fields with a step"] += len(stepped) >= 2
+        self.records["a resized field without a step"] += any(x[3] and not x[3].get("prep") for x in rec)
+        self.records["the first step not in field 0"] += stepped[0] > 0
+        if self.crops:
+            straddle = wide = False
+            for (_, _, v, c), k in zip(rec, ks):
+                if not c:
+                    continue
+                n = pr.want(v, c)
+                straddle = straddle or straddles(k, n[0].size, n.itemsize)
+                wide = wide or bool(((c["boxes"] > 32767) | (c["boxes"] < -32768)).any())
+                area = box_areas(v, c)
+                if (c.get("prep") or {}).get("bias") is not None and (area == 0).any() and area.any():
+                    seen.add("empty beside a bias")
+            seen.update(["straddle"] * straddle + ["outside int16"] * wide)
+        self.units.update(seen)
+
+    def check(self):
+        """The conditions of the sweep, every count printed (pytest -s)."""
+        at_least(self.srcs, pr.SOURCES, 10, "sources")
+        at_least(self.dsts, [None] + list(pr.DESTS), 10, "destinations")
+        at_least(self.modes, pr.MODES, 10, "modes")
+        at_least(self.residues, range(16), 10, "residues")
+        at_least(self.shares, ("tile", "rows"), 10, "plain fields")
+        terms = [(s, b) for s in rv.AFFINE_TERMS for b in rv.AFFINE_TERMS if (s, b) != ("none", "none")]
+        at_least(self.combos, terms, 10, "(scale, bias)")
+        if not self.crops:
+            at_least(self.places, ("none", "letterbox", "free", "placement alone"), 10, "placement")
+            at_least(self.placed, [f"lead[{j}] == 0" for j in (0, 1)] +
+                     [f"lead[{j}] + inner[{j}] == size[{j}]" for j in (0, 1)], 10, "placed")
+            at_least(self.fills, ("-0.0 to a float", "saturating to an integer"), 10, "fills")
+            at_least(self.units, ("mixed",), 20, "units inside and outside the image")
+        at_least(self.records, ("two fields with a step",), 20, "records")
+        at_least(self.records, ("a resized field without a step", "the first step not in field 0"), 10, "records")
+        at_least(self.axes, ("first", "middle", "innermost", "broadcast", "reversed", "negative"), 10, "channel axis")
+        at_least(self.axes, ("extent 1",), 1, "channel axis")
+        at_least(self.axes, ("five dimensions or more",), 20, "channel axis")
+        at_least(self.tables, (0, 4, 8, 12, "an exact 0.0, -0.0 or 1.0"), 10, "tables mod 16")
+        at_least(self.units, ("changes", "keeps"), 20, "units and the channel coordinate")
+        if self.crops:
+            at_least(self.units, ("straddle", "outside int16", "empty beside a bias"), 20, "crops")
+            at_least(self.counts, rv.CROP_COUNTS, 1, "K")
+        # the caps on the reference
+        print(f"shares: {self.bound} of {self.ints} integer outputs on a bound; {self.outside} of "
+              f"{self.placed_elems} placed elements outside the image; {self.nothing} of {self.steps} "
+              f"steps change nothing; {self.nonfinite} of {self.floats} float outputs not finite")
+        assert 2 * self.bound <= self.ints, (self.bound, self.ints)
+        assert 2 * self.outside <= self.placed_elems, (self.outside, self.placed_elems)
+        assert 10 * self.nothing <= self.steps, (self.nothing, self.steps)
+        assert 20 * self.nonfinite <= self.floats, (self.nonfinite, self.floats)
+
+
+def prep_sweep(seeds, case, crops, emulator, tmp_path):
+    """Every seed through the emulated body, bit for bit against `pr.want`; the conditions."""
+    batch, stats = PrepBatch(tmp_path), PrepStats(crops)
+    for seed in seeds:
+        rec, mis = case(seed)
+        what = f"seed={seed} dst%16={mis}"
+        assert all(rv.inside(b, v) for _, b, v in pr.triples(rec)), what
+        if crops:
+            k0 = len(next(x[3] for x in rec if x[3])["boxes"])
+            stats.counts[k0] += 1
+        addr = addresses(pr.bases_of(rec))
+        with pr.plan_prep(rec, lambda b: addr[id(b)], ARROW_DEVICE_ROCM) as p:
+            assert p.size == len(pr.oracle(rec)[0]) and p.segments() == [], what
+            if crops and not k0:
+                continue  # K == 0: the empty message, nothing is launched
+            assert pr.plan_launch(p) == (10 if crops else 9), what
+            stats.record(rec, mis, p)
+        batch.add(what, rec, DST + mis)
+    counts = batch.run(emulator)
+    print(f"emulator: {counts}")
+    assert batch.paths == {"head", "units", "tail"}, batch.paths
+    assert counts["head_elements"] and counts["units"] and counts["tail_elements"], counts
+    assert counts["table_loads"] and (counts["box_loads"] if crops else counts["outside"]), counts
+    stats.check()
+
+
+def test_prep_resizes(lib, prep_emulator, tmp_path):
+    prep_sweep(PREP_RESIZE_SEEDS, prep_resize_case, False, prep_emulator, tmp_path)
+
+
+def test_prep_crops(lib, prep_emulator, tmp_path):
+    prep_sweep(PREP_CROP_SEEDS, prep_crop_case, True, prep_emulator, tmp_path)
+
+
+def host_plans(seeds, case):
+    """Every seed planned over host memory: resize_host and crop_host of tensor_plan.cpp write the
+    staged segments, which laid out by their offsets hold `pr.want` of every field."""
+    import ctypes
+    for seed in seeds:
+        rec, _ = case(seed)
+        what = f"seed={seed}"
+        sample, info, ranges = pr.oracle(rec)
+        with pr.plan_prep(rec, host_ptr, ARROW_DEVICE_CPU) as p:
+            assert p.size == len(sample) and p.type_info().to_json() == info.to_json(), what
+            got = bytearray([POISON]) * p.size
+            for ptr, off, n in p.segments():
+                assert got[off:off + n] == bytes([POISON]) * n and off + n <= p.size, what
+                got[off:off + n] = ctypes.string_at(ptr, n)
+            for (off, ln), (_, _, v, c) in zip(ranges, rec):
+                pr.same(got[off:off + ln], pr.want(v, c), what)
+                got[off:off + ln] = bytes([POISON]) * ln
+            assert bytes(got) == bytes([POISON]) * p.size, "padding staged, " + what
+
+
+def test_prep_resizes_over_host_memory(lib):
+    host_plans(PREP_RESIZE_SEEDS, prep_resize_case)
+
+
+def test_prep_crops_over_host_memory(lib):
+    host_plans(PREP_CROP_SEEDS, prep_crop_case)
+
+
+def stepped_field(rec):
+    return next(i for i, x in enumerate(rec) if x[3] and x[3].get("prep"))
+
+
+def one_case(tmp_path, emulator, seed, case):
+    """The batch of one seed's case, run once."""
+    rec, mis = case(seed)
+    batch = PrepBatch(tmp_path)
+    batch.add(f"seed={seed}", rec, DST + mis)
+    batch.run(emulator)
+    return batch
+
+
+def test_the_prep_resize_sweep_notices_a_moved_image(lib, prep_emulator, tmp_path):
+    """`lead` of the first placed seed one step further along an axis and `inner` one step shorter,
+    so that the image still lies inside the output: another statement, the comparison fails."""
+    for seed in PREP_RESIZE_SEEDS:
+        rec, _ = prep_resize_case(seed)
+        i = stepped_field(rec)
+        v, c = rec[i][2], rec[i][3]
+        q = c["prep"]
+        j = next((j for j in (0, 1) if q["inner"] is not None and q["inner"][j] >= 2), None)
+        if j is None:
+            continue
+        moved = dict(q, inner=tuple(n - (k == j) for k, n in enumerate(q["inner"])),
+                     lead=tuple(n + (k == j) for k, n in enumerate(q["lead"])))
+        if pr.want(v, dict(c, prep=moved)).tobytes() != pr.want(v, c).tobytes():  # (the reference notices)
+            break
+    else:
+        raise AssertionError("no placed seed")
+    batch = one_case(tmp_path, prep_emulator, seed, prep_resize_case)
+    lines = batch.spec[-1].split("\n")
+    words = lines[1 + i].split(" ")
+    assert [int(w) for w in words[-7:-3]] == [*q["inner"], *q["lead"]]
+    words[-7 + j], words[-5 + j] = str(q["inner"][j] - 1), str(q["lead"][j] + 1)
+    lines[1 + i] = " ".join(words)
+    batch.spec[-1] = "\n".join(lines)
+    with pytest.raises(AssertionError):
+        batch.run(prep_emulator)
+
+
+def changed_table_word(tmp_path, emulator, seeds, case):
+    """One float32 word of the first table of the first seed that has one under a float destination
+    (where no saturation hides it) replaced by another number: the comparison fails."""
+    for seed in seeds:
+        rec, _ = case(seed)
+        i = stepped_field(rec)
+        v, c = rec[i][2], rec[i][3]
+        w = next((w for w in ("scale", "bias") if pr.is_table(c["prep"][w])), None)
+        if w is None or c["dst"] not in ("float16", "float32") or not v.size:
+            continue
+        tb, tv = c["prep"][w]
+        other = tv.copy()
+        other[0] = -2.0 * other[0] - 3.0
+        changed = dict(c, prep=dict(c["prep"], **{w: (other, other)}))
+        if pr.want(v, changed).tobytes() != pr.want(v, c).tobytes():  # (the reference notices)
+            break
+    else:
+        raise AssertionError("no seed with a table under a float destination")
+    batch = one_case(tmp_path, emulator, seed, case)
+    name = batch.spec[-1].split("\n")[1 + i].split(" ")[-2 if w == "scale" else -1]
+    words = np.fromfile(name, np.float32)
+    assert words.tobytes() == tv.tobytes()
+    other.tofile(name)
+    with pytest.raises(AssertionError):
+        batch.run(emulator)
+
+
+def test_the_prep_resize_sweep_notices_a_changed_table_word(lib, prep_emulator, tmp_path):
+    changed_table_word(tmp_path, prep_emulator, PREP_RESIZE_SEEDS, prep_resize_case)
+
+
+def test_the_prep_crop_sweep_notices_a_changed_table_word(lib, prep_emulator, tmp_path):
+    changed_table_word(tmp_path, prep_emulator, PREP_CROP_SEEDS, prep_crop_case)
+
+
+def test_the_prep_crop_sweep_notices_a_changed_box_word(lib, prep_emulator, tmp_path):
+    """The first box, a whole frame, two steps shorter along its second axis."""
+    for seed in PREP_CROP_SEEDS:
+        rec, _ = prep_crop_case(seed)
+        i = stepped_field(rec)
+        v, c = rec[i][2], rec[i][3]
+        if len(c["boxes"]) and v.shape[c["axes"][1]] > 3 and \
+                tuple(c["boxes"][0]) == (0, 0, v.shape[c["axes"][0]], v.shape[c["axes"][1]]):
+            rows = c["boxes"].copy()
+            rows[0, 1] += 2
+            if pr.want(v, dict(c, boxes=rows)).tobytes() != pr.want(v, c).tobytes():
+                break
+    else:
+        raise AssertionError("no seed whose first box is the whole frame")
+    batch = one_case(tmp_path, prep_emulator, seed, prep_crop_case)
+    name = batch.spec[-1].split("\n")[1 + i].split(" ")[-18]
+    words = np.fromfile(name, np.int32)
+    assert words.tobytes() == c["boxes"].tobytes()
+    words[1] += 2
+    words.tofile(name)
+    with pytest.raises(AssertionError):
+        batch.run(prep_emulator)
+
+
+def test_a_prep_resize_of_an_element_misaligned_source_is_refused(lib):
+    for seed in MISALIGNED_PREP_RESIZE_SEEDS:
+        rec = rv.misaligned_op(rv.rng(seed), "prep_resize")
+        ok, text = refused_by_name(pr.plan_prep, rec, pr.bases_of(rec))
+        assert ok, (seed, text)
+
+
+def test_prep_crops_of_an_element_misaligned_source_are_refused(lib):
+    for seed in MISALIGNED_PREP_CROP_SEEDS:
+        rec = rv.misaligned_op(rv.rng(seed), "prep_crop")
+        ok, text = refused_by_name(pr.plan_prep, rec, pr.bases_of(rec))
         assert ok, (seed, text)

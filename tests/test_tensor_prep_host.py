@@ -20,20 +20,7 @@ from tests.test_tensor_cast_host import DESC
 from tests.test_tensor_resize_host import as_values, same_arrays
 
 
-def oracle(rec):
-    """(sample bytes, ArrowTypeInfo, [(offset, length) of each field's leaf]) of the reference
-    packing of the materialised record: the nested array of a bare tensor, else the StructArray of
-    the fields."""
-    cols = [tensor.from_numpy(pr.want(v, c)) for _, _, v, c in rec]
-    bare = len(rec) == 1 and rec[0][0] is None
-    arr = cols[0] if bare else pa.StructArray.from_arrays(cols, names=[x[0] for x in rec])
-    sample, info = pack(arr)
-    ranges = []
-    for c in ([info] if bare else info.child_data):
-        while c.child_data:
-            c = c.child_data[0]
-        ranges.append((c.buffer_offsets[0].offset, c.buffer_offsets[0].len))
-    return sample, info, ranges
+oracle = pr.oracle
 
 
 def sent_as(v, c):
