@@ -413,6 +413,8 @@ _TEST_SIGS = {
                                         POINTER(c_uint64), POINTER(ctypes.c_int64)]),
     "dora_gpu_test_plan_launch": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int),
                                           POINTER(c_int)]),
+    "dora_gpu_test_plan_segment_op": (c_int, [c_void_p, c_size_t, POINTER(c_uint32),
+                                              POINTER(c_uint32), POINTER(c_uint64)]),
     "dora_gpu_test_aql_hold": (c_int, [c_int, c_int]),
     "dora_gpu_test_reduce_timeout": (c_int, [c_uint64]),
     "dora_gpu_test_d2h_copy_probe": (c_int, [c_int, c_int, c_uint64, c_uint32, c_uint64, c_void_p]),

@@ -24,11 +24,13 @@
 #include "pack_device.h"
 #include "plan.h"
 #include "splitmix_device.h"
+#include "transform_device.h"
 
 namespace dora {
 namespace {
 
 using namespace pack;
+using namespace xform;
 
 template <int U, int NT>
 __global__ __launch_bounds__(kThreads) void pack_kernel(PackArgs args) {
@@ -58,70 +60,36 @@ constexpr uint32_t kCpGridMulti = 640;
 constexpr int kUnroll = 4;
 
 // ------------------------------------------------------------------------------------------
-// Transform segments of compacting plans: bitmap slices shifted to bit 0 and offsets rebased to
-// 0.  Elementwise and tiny next to the value buffers (a bitmap is len/8 bytes, offsets
-// 4-8 B per list), so one simple grid over all transform segments.
+// transform_kernel: the transform segments of compacting plans (transform_device.h holds the
+// body and the table of a launch; this is its memory policy): plain loads and stores, whole
+// words where source and destination allow it.
 // ------------------------------------------------------------------------------------------
-struct XSeg {
-  const uint8_t* src;
-  uint64_t dst_off;
-  uint64_t len;      // output bytes
-  uint64_t src_len;  // readable source bytes (bitshift)
-  uint32_t op;
-  uint32_t aux;      // bit offset (bitshift)
-};
+static_assert(kXThreads == kThreads && kXMaxSegs == kMaxSegs, "a transform launch is cut as a pack");
 
-struct XArgs {
-  uint8_t* dst;
-  uint32_t nseg;
-  uint32_t block_end[kMaxSegs];
-  XSeg seg[kMaxSegs];
-};
-
-constexpr uint64_t kXElems = 4096;  // output elements per workgroup
-
-template <typename T>
-__device__ __forceinline__ void rebase(const uint8_t* src, uint8_t* dst, uint64_t count,
-                                       uint64_t e0, uint64_t e1) {
-  T base;
-  __builtin_memcpy(&base, src, sizeof(T));
-  const bool aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) &
-                        (sizeof(T) - 1)) == 0;
-  for (uint64_t i = e0 + threadIdx.x; i < e1 && i < count; i += kThreads) {
-    if (aligned) {
-      reinterpret_cast<T*>(dst)[i] = reinterpret_cast<const T*>(src)[i] - base;
-    } else {
-      T v;
-      __builtin_memcpy(&v, src + i * sizeof(T), sizeof(T));
-      v -= base;
-      __builtin_memcpy(dst + i * sizeof(T), &v, sizeof(T));
-    }
+struct XformMem {
+  template <typename T>
+  __device__ __forceinline__ T ld(const uint8_t* p) const {
+    return *reinterpret_cast<const T*>(p);
   }
-}
+  template <typename T>
+  __device__ __forceinline__ void st(uint8_t* p, T v) const {
+    *reinterpret_cast<T*>(p) = v;
+  }
+  template <typename T>
+  __device__ __forceinline__ T ldu(const uint8_t* p) const {
+    T v;
+    __builtin_memcpy(&v, p, sizeof(T));
+    return v;
+  }
+  template <typename T>
+  __device__ __forceinline__ void stu(uint8_t* p, T v) const {
+    __builtin_memcpy(p, &v, sizeof(T));
+  }
+};
 
 __global__ __launch_bounds__(kThreads) void transform_kernel(XArgs a) {
-  const uint32_t blk = blockIdx.x;
-  uint32_t s = 0;
-  while (s + 1 < a.nseg && blk >= a.block_end[s]) ++s;
-  const XSeg g = a.seg[s];
-  const uint64_t c = blk - (s ? a.block_end[s - 1] : 0u);
-  const uint64_t e0 = c * kXElems, e1 = e0 + kXElems;
-  uint8_t* dst = a.dst + g.dst_off;
-  if (g.op == SEG_BITSHIFT) {
-    for (uint64_t j = e0 + threadIdx.x; j < e1 && j < g.len; j += kThreads) {
-      const uint32_t lo = g.src[j];
-      const uint32_t hi = j + 1 < g.src_len ? g.src[j + 1] : 0u;
-      dst[j] = static_cast<uint8_t>(g.aux ? ((lo >> g.aux) | (hi << (8 - g.aux))) : lo);
-    }
-  } else if (g.op == SEG_REBASE32) {
-    rebase<int32_t>(g.src, dst, g.len / 4, e0, e1);
-  } else if (g.op == SEG_REBASE64) {
-    rebase<int64_t>(g.src, dst, g.len / 8, e0, e1);
-  }
-}
-
-uint64_t xseg_elems(const Segment& s) {
-  return s.op == SEG_REBASE32 ? s.len / 4 : s.op == SEG_REBASE64 ? s.len / 8 : s.len;
+  XformMem m;
+  transform_body(a, blockIdx.x, threadIdx.x, m);
 }
 
 // Loads in flight per lane: 4 at every size.  r01's isolated-pack probes preferred 8 loads over
@@ -1057,19 +1025,11 @@ int launch_pack(const Segment* segs_in, size_t n_in, ArrowDeviceType dev, uint8_
   for (size_t j = 0; j < xforms.size(); j += kMaxSegs) {
     XArgs x;
     std::memset(&x, 0, sizeof(x));
-    x.dst = dst;
     const size_t m = std::min<size_t>(kMaxSegs, xforms.size() - j);
-    uint64_t blocks = 0;
-    for (size_t k = 0; k < m; ++k) {
-      const Segment& s = xforms[j + k];
-      x.seg[k] = {static_cast<const uint8_t*>(s.src), s.dst_off, s.len, s.src_len, s.op, s.aux};
-      blocks += std::max<uint64_t>(1, (xseg_elems(s) + kXElems - 1) / kXElems);
-      if (blocks > 0x7fffffffull) return fail(DORA_ERR_INVALID, "pack: too many blocks");
-      x.block_end[k] = static_cast<uint32_t>(blocks);
-    }
-    x.nseg = static_cast<uint32_t>(m);
+    const uint32_t blocks = fill_xargs(x, dst, xforms.data() + j, m);
+    if (!blocks) return fail(DORA_ERR_INVALID, "pack: too many blocks");
     const bool first = launch == 0, last = launch + 1 == n_launch;
-    const int rl = launch_timed(transform_kernel, static_cast<unsigned>(blocks), kThreads, stream,
+    const int rl = launch_timed(transform_kernel, blocks, kThreads, stream,
                                 first ? ev_start : nullptr, last ? ev_stop : nullptr, x);
     if (rl != DORA_OK) return rl;
     ++launch;

@@ -658,6 +658,16 @@ int dora_gpu_test_plan_launch(const dora_plan* plan, int* launch, int* scan, int
   return DORA_OK;
 }
 
+int dora_gpu_test_plan_segment_op(const dora_plan* plan, size_t i, uint32_t* op, uint32_t* aux,
+                                  uint64_t* src_len) {
+  if (!plan || i >= plan->segs.size())
+    return dora::fail(DORA_ERR_INVALID, "segment index %zu out of range", i);
+  if (op) *op = plan->segs[i].op;
+  if (aux) *aux = plan->segs[i].aux;
+  if (src_len) *src_len = plan->segs[i].src_len;
+  return DORA_OK;
+}
+
 int dora_gpu_test_ide_output(const char* dataflow_id, const char* node_id,
                                         const char* output_id, const uint8_t* type_info,
                                         size_t type_info_len, const uint8_t* params,

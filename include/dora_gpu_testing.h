@@ -234,6 +234,13 @@ int dora_gpu_test_plan_mask(const dora_plan* plan, int* device, const void** mas
  * also scans a partition in HBM; *checked 1 if the plan reads HBM whose range is checked before
  * anything is launched. */
 int dora_gpu_test_plan_launch(const dora_plan* plan, int* launch, int* scan, int* checked);
+/* Test tool (host only): how segment `i` of any plan is moved (dora_gpu_plan_segment gives its
+ * source, destination offset and length).  *op 0 a verbatim copy; of a compacting plan
+ * (dora_gpu_plan_compact) also 1 a bitmap slice shifted to bit 0, starting *aux bits into the
+ * source, of which *src_len bytes are readable; 2 / 3 int32 / int64 offsets minus the first.
+ * DORA_ERR_INVALID for an index past the plan's segments. */
+int dora_gpu_test_plan_segment_op(const dora_plan* plan, size_t i, uint32_t* op, uint32_t* aux,
+                                  uint64_t* src_len);
 /* Test and probe tool: which kernel gathers strided device tensor views of this process from now
  * on: 0 the library's own selection, 1 gather_rows_kernel always, 2 gather_tile_kernel wherever
  * it applies (short contiguous extents included). */
